@@ -4,6 +4,7 @@
     python bench.py [--gpus N] [--steps K] [--warmup W]            # starts its own N ranks when no launcher did
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...
     python bench.py --train [--gpus N]                             # BASELINE cfg-3 / cfg-4: bf16 training step, B=64 per GPU, DDP
+    python bench.py ... --dump-outputs DIR                         # also write rank 0's last timed step's outputs as DIR/*.npy
 
 Without RANK/WORLD_SIZE in the environment and with --gpus N > 1 this process is only a PARENT: it parses the arguments,
 starts N child processes of this same file with RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR=127.0.0.1 / MASTER_PORT set
@@ -34,6 +35,7 @@ sys.path.insert(0, ROOT)
 CFG = dict(n_mel=80, n_blocks=16, d=512, n_heads=8, ksize=31, B=32, T=1000)
 PEAK_MFMA_F32_TFLOPS = 157.3      # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32, 64 FLOP/clk/SIMD
 PEAK_HBM_GBS = 8000.0
+DUMP_BUDGET = 60 << 20            # --dump-outputs: array bytes written at most (under 64 MB with the .npy headers)
 
 
 def log(*a):
@@ -48,6 +50,20 @@ def algorithmic_flops(B, T, d, L, K, n_mel=80):
     front = 18 * d * F1 * T1 * B + 18 * d * d * Fp * Tp * B + 2 * (Fp * d) * d * N
     block = 46 * N * d * d + 2 * P * d * d + 6 * B * Tp * Tp * d + 2 * N * d * K
     return front + L * block
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every tensor whole as <path>/<name>.npy on the host, floating point as float32 and integers (lengths)
+    as float64, which holds them exactly.  The largest dump (--train logits) is ~24 MB, well inside DUMP_BUDGET."""
+    import numpy as np
+    host = {k: v.detach().to("cpu", torch.float32 if v.is_floating_point() else torch.float64) for k, v in arrays.items()}
+    total = sum(v.numel() * v.element_size() for v in host.values())
+    if total > DUMP_BUDGET:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_BUDGET}-byte budget")
+    os.makedirs(path, exist_ok=True)
+    for k, v in host.items():
+        np.save(os.path.join(path, k + ".npy"), v.numpy())
+    log(f"[bench] outputs of the last timed step -> {path}: " + ", ".join(f"{k}{tuple(v.shape)}" for k, v in host.items()))
 
 
 def time_events(fn, iters, warm=2, inner=10):
@@ -363,11 +379,15 @@ def train_bench(args, env, dev, dist):
         loss.backward()
         opt.step()
         last["loss"] = loss
+        if args.dump_outputs:
+            last["logits"], last["len"] = logits.detach(), out_len
 
     dt = parallel.timed_steps(step, args.steps, args.warmup, torch.cuda.synchronize, dev)
     marks.append(torch.cuda.Event(enable_timing=True))
     marks[-1].record()
     torch.cuda.synchronize()
+    if args.dump_outputs and env.rank == 0:
+        dump_outputs(args.dump_outputs, {"loss": last["loss"], "logits": last["logits"], "logit_lengths": last["len"]})
     mine = [marks[i].elapsed_time(marks[i + 1]) for i in range(args.warmup, args.warmup + args.steps)]
     per_rank = parallel.gather_to_rank0(sum(mine) / len(mine))
     comms = parallel.gather_to_rank0(probe.summary(skip=args.warmup))
@@ -407,8 +427,11 @@ def main():
     ap.add_argument("--selftest-cpu", action="store_true",
                     help="plumbing test only (tests/test_parallel_cpu.py): ranks rendezvous over gloo on the CPU and time a "
                          "no-kernel step; the JSON line says so and carries value 0")
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps (>= 1); ms_per_step is their mean")
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one returned (rank 0) as DIR/<name>.npy, float32 / float64, "
+                         "at most 64 MB; inputs and weights are seeded, so runs with the same arguments are comparable")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-graph", action="store_true", help="launch the ~260 kernels eagerly instead of one hipGraph replay")
@@ -422,6 +445,10 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.selftest_cpu:
+        raise SystemExit("--dump-outputs: the plumbing self-test computes nothing to dump")
     if "RANK" not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))          # parent only: nothing below runs in this process
 
@@ -476,10 +503,12 @@ def main():
 
     def step():
         with torch.no_grad(), amp():
-            last["y"], _ = runner(x, lengths)
+            last["y"], last["len"] = runner(x, lengths)
 
     dt = parallel.timed_steps(step, args.steps, args.warmup, torch.cuda.synchronize, dev)
     y = last["y"]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"encoder_out": y, "encoder_out_lengths": last["len"]})
     if not torch.isfinite(y).all():
         raise SystemExit("non-finite encoder output")
     n0 = _lib.CALLS[0]

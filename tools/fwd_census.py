@@ -1,9 +1,9 @@
 import sys, os, collections, traceback
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
 import torch
 from torch.utils._python_dispatch import TorchDispatchMode
 from model.modules.encoder import Encoder
-ROOT = os.environ.get("GRAFT_REPO_ROOT", "/root/repo")
 class Sites(TorchDispatchMode):
     def __init__(s): super().__init__(); s.c = collections.Counter()
     def __torch_dispatch__(s, func, types, args=(), kwargs=None):

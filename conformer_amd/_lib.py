@@ -103,6 +103,8 @@ SIGNATURES = {
     "cfm_subsample_conv1_bwd_f32": (c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "cfm_adam_step_f32": (c_int, [_P, _I, _F, _F, _F, _F, _F, _F, _P]),
     "cfm_greedy_ctc_decode_f32": (c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "cfm_ctc_beam_workspace_bytes": (ctypes.c_size_t, [_I, _I, _I, _I]),
+    "cfm_ctc_beam_decode_f32": (c_int, [_P, _P, _I, _I, _I, _I, _I, _I, _F, _F, _I, _P, ctypes.c_size_t, _P, _P, _P, _P, _P]),
     "cfm_lstm_fwd_f32": (c_int, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "cfm_lstm_fwd_frag_f32": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "cfm_lstm_bwd_frag_f32": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),

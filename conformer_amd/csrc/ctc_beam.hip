@@ -1,0 +1,427 @@
+// CTC prefix beam search (Hannun et al. 2014), lexicon-free, with pyctcdecode's pruning knobs (token_min_logp, max_candidates,
+// beam_prune_logp).  The semantics are written down in INTEGRATION.md ("CTC prefix beam search"); tests/ctc_beam_restatement.py
+// restates them in float64.
+//
+// Two launches:
+//   beam_prep_kernel: one wave per (utterance, frame) row, lanes over the vocabulary: the log-softmax normaliser and the
+//     candidate list C_t (the up-to-K non-blank ids with the highest log probability >= token_min_logp, ties to the lower id).
+//   beam_search_kernel: one workgroup per utterance loops over its frames; the hypotheses live in LDS in rank order.
+// The normaliser and every score are fp64: the device then agrees with the float64 restatement to ~1e-12, far inside the
+// smallest score gaps a real search meets (~1e-6 at W = 100, T = 249), so pruning and keep-W decisions are the same.
+//
+// Merging is exact.  Every hypothesis owns a node (parent node, token) of a per-utterance prefix tree in the workspace
+// (node 0 = the empty prefix; the extension that survives frame t as rank q creates node 1 + t*W + q).  The extension of
+// hypothesis i by c can only equal a live hypothesis j whose last token is c and whose prefix is the sequence of i: j is
+// found through a hash of the token sequence (LDS open-addressing table of the live hypotheses) and then CHECKED by walking
+// both parent chains in step until they meet or a token differs (the same sequence may own several nodes: a prefix that
+// was pruned and found again gets a new node).
+// Keep-W: a most-significant-digit radix select over the 96-bit composite (order-preserving bits of the score, then the
+// complement of the origin key), 8 bits per pass, starting at the highest bit in which the surviving scores differ; the
+// composites are unique, so the selected set has exactly W members.  The kept hypotheses are then ranked by counting.
+#include <float.h>
+#include "cfm_common.h"
+
+namespace {
+
+constexpr int BEAM_MAX_W = 256;          // also the workgroup size of the search: thread i owns hypothesis i
+constexpr int BEAM_MAX_K = 32;
+constexpr int BEAM_TABLE = 512;          // hash slots (>= 2 W)
+constexpr int BEAM_MAX_V = 1 << 23;      // origin keys rank * (V + 1) + token + 1 fit in 31 bits
+
+struct BeamWs {
+    double* lse;      // (B*T) log-sum-exp of each logits row
+    int* ncand;       // (B*T) |C_t|
+    int* ctok;        // (B*T, K) candidate ids, best first
+    double* clp;      // (B*T, K) their log probabilities
+    int2* nodes;      // (B, 1 + T*W) prefix-tree nodes (parent, token)
+};
+
+inline size_t beam_align(size_t x) { return (x + 255) & ~size_t(255); }
+
+inline size_t beam_carve(int B, int T, int W, int K, char* base, BeamWs* ws) {
+    const size_t rows = (size_t)B * T;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += beam_align(bytes); return p; };
+    char* lse = take(rows * sizeof(double));
+    char* ncand = take(rows * sizeof(int));
+    char* ctok = take(rows * K * sizeof(int));
+    char* clp = take(rows * K * sizeof(double));
+    char* nodes = take((size_t)B * (1 + (size_t)T * W) * sizeof(int2));
+    if (ws) *ws = BeamWs{(double*)lse, (int*)ncand, (int*)ctok, (double*)clp, (int2*)nodes};
+    return off;
+}
+
+__device__ __forceinline__ int beam_frames(const int64_t* lengths, int b, int T) {
+    return lengths ? (int)min((int64_t)T, max((int64_t)0, lengths[b])) : T;
+}
+
+// (x, c) precedes (bx, bc) in candidate order: higher logit first, ties to the lower id; bc == INT_MAX is "none"
+__device__ __forceinline__ bool cand_before(float x, int c, float bx, int bc) {
+    return bc == INT_MAX || x > bx || (x == bx && c < bc);
+}
+
+__global__ __launch_bounds__(256) void beam_prep_kernel(const float* __restrict__ logits, const int64_t* __restrict__ lengths,
+                                                        BeamWs ws, int B, int T, int V, int blank, int K, double token_min_logp) {
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= (int64_t)B * T) return;
+    const int b = (int)(row / T), t = (int)(row % T);
+    if (t >= beam_frames(lengths, b, T)) return;                // rows the search does not consume
+    const float* r = logits + row * V;
+    float m = -INFINITY;
+    for (int c = lane; c < V; c += 64) m = fmaxf(m, r[c]);
+    m = wave_max(m);
+    double sum = 0.0;
+    for (int c = lane; c < V; c += 64) sum += exp((double)r[c] - (double)m);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+    const double lse = (double)m + log(sum);
+    // C_t by K rounds of a wave arg-max over the entries that follow the previous pick in candidate order.  lp = x - lse is
+    // monotone in x, so the order of the fp32 logits is the order of the log probabilities.
+    float px = INFINITY;
+    int pc = -1, cnt = 0;
+    for (int k = 0; k < K; ++k) {
+        float bx = -INFINITY;
+        int bc = INT_MAX;
+        for (int c = lane; c < V; c += 64) {
+            const float x = r[c];
+            if (c == blank || !((double)x - lse >= token_min_logp)) continue;          // also drops NaN
+            if (!(x < px || (x == px && c > pc))) continue;                           // already picked
+            if (cand_before(x, c, bx, bc)) { bx = x; bc = c; }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const float ox = __shfl_xor(bx, o, 64);
+            const int oc = __shfl_xor(bc, o, 64);
+            if (oc != INT_MAX && cand_before(ox, oc, bx, bc)) { bx = ox; bc = oc; }
+        }
+        if (bc == INT_MAX) break;                                  // wave-uniform after the butterfly
+        if (lane == 0) {
+            ws.ctok[row * K + k] = bc;
+            ws.clp[row * K + k] = (double)bx - lse;
+        }
+        px = bx; pc = bc; ++cnt;
+    }
+    if (lane == 0) {
+        ws.lse[row] = lse;
+        ws.ncand[row] = cnt;
+    }
+}
+
+__device__ __forceinline__ double lae(double a, double b) {            // log(exp(a) + exp(b))
+    const double m = a > b ? a : b;
+    if (m == -INFINITY) return -INFINITY;
+    return m + log1p(exp(-fabs(a - b)));
+}
+
+// order-preserving unsigned image of a double (larger double -> larger image; NaN never reaches it)
+__device__ __forceinline__ unsigned long long ord64(double x) {
+    const unsigned long long u = (unsigned long long)__double_as_longlong(x);
+    return u ^ ((u >> 63) ? ~0ull : 0x8000000000000000ull);
+}
+
+__device__ __forceinline__ unsigned long long seq_hash(unsigned long long h, int c) {
+    unsigned long long z = h + (unsigned long long)(c + 1) * 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+constexpr unsigned long long ROOT_HASH = 0x243F6A8885A308D3ull;
+
+// nodes a and b stand for sequences of the same length: are the sequences equal?
+__device__ bool same_sequence(const int2* nd, int a, int b, int len) {
+    for (int step = 0; step <= len; ++step) {
+        if (a == b) return true;
+        if (a <= 0 || b <= 0) return false;
+        const int2 na = nd[a], nb = nd[b];
+        if (na.y != nb.y) return false;
+        a = na.x; b = nb.x;
+    }
+    return false;
+}
+
+typedef unsigned __int128 u128;
+
+__global__ __launch_bounds__(BEAM_MAX_W) void beam_search_kernel(
+        const float* __restrict__ logits, const int64_t* __restrict__ lengths, BeamWs ws, int T, int V, int blank, int W,
+        int K, double prune, int N, int64_t* __restrict__ tokens, int64_t* __restrict__ counts, float* __restrict__ scores,
+        int64_t* __restrict__ num_hyps) {
+    // hypotheses in rank order, double-buffered across frames
+    __shared__ double h_pb[2][BEAM_MAX_W], h_pnb[2][BEAM_MAX_W], h_s[2][BEAM_MAX_W];
+    __shared__ unsigned long long h_hash[2][BEAM_MAX_W];
+    __shared__ int h_node[2][BEAM_MAX_W], h_par[2][BEAM_MAX_W], h_last[2][BEAM_MAX_W], h_len[2][BEAM_MAX_W];
+    __shared__ double m_val[BEAM_MAX_W];              // extension merged into hypothesis j: its value and origin key
+    __shared__ unsigned m_key[BEAM_MAX_W];
+    __shared__ int c_tok[BEAM_MAX_K];
+    __shared__ double c_lp[BEAM_MAX_K];
+    __shared__ int table[BEAM_TABLE];
+    __shared__ unsigned hist[2][256];
+    __shared__ double red_best[4];
+    __shared__ int red_cnt[4];
+    __shared__ unsigned long long red_min[4];
+    __shared__ int sel_d, sel_need, sel_done, n_kept;
+    // the kept candidates before ranking
+    __shared__ unsigned long long l_ord[BEAM_MAX_W];
+    __shared__ unsigned l_low[BEAM_MAX_W];
+    __shared__ int l_item[BEAM_MAX_W];
+    __shared__ double l_pb[BEAM_MAX_W], l_pnb[BEAM_MAX_W], l_s[BEAM_MAX_W];
+
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int n = beam_frames(lengths, b, T);
+    int2* nd = ws.nodes + (int64_t)b * (1 + (int64_t)T * W);
+    const unsigned V1 = (unsigned)V + 1u;
+
+    for (int i = tid; i < BEAM_TABLE; i += BEAM_MAX_W) table[i] = -1;
+    if (tid == 0) {
+        h_pb[0][0] = 0.0; h_pnb[0][0] = -INFINITY; h_s[0][0] = 0.0;
+        h_hash[0][0] = ROOT_HASH; h_node[0][0] = 0; h_par[0][0] = -1; h_last[0][0] = -1; h_len[0][0] = 0;
+        nd[0] = make_int2(-1, -1);
+    }
+    __syncthreads();
+    if (tid == 0) table[ROOT_HASH & (BEAM_TABLE - 1)] = 0;
+    int cur = 0, nh = 1;
+
+    for (int t = 0; t < n; ++t) {
+        const int64_t row = (int64_t)b * T + t;
+        const int nc = ws.ncand[row];
+        const double lse = ws.lse[row];
+        const float* lrow = logits + row * V;
+        // ---- A: this frame's candidates; own hypothesis; stays
+        if (tid < nc) { c_tok[tid] = ws.ctok[row * K + tid]; c_lp[tid] = ws.clp[row * K + tid]; }
+        hist[0][tid] = 0u;
+        if (tid == 0) n_kept = 0;
+        const bool own = tid < nh;
+        double pb = 0, pnb = 0, s = 0, st_pb = -INFINITY, st_pnb = -INFINITY;
+        int last = -1, len = 0, node = 0;
+        unsigned long long hash = 0;
+        if (own) {
+            pb = h_pb[cur][tid]; pnb = h_pnb[cur][tid]; s = h_s[cur][tid];
+            last = h_last[cur][tid]; len = h_len[cur][tid]; node = h_node[cur][tid]; hash = h_hash[cur][tid];
+            st_pb = s + ((double)lrow[blank] - lse);
+            st_pnb = last >= 0 ? pnb + ((double)lrow[last] - lse) : -INFINITY;
+            m_val[tid] = -INFINITY;
+            m_key[tid] = 0xFFFFFFFFu;
+        }
+        __syncthreads();
+        // ---- B: extensions that equal a live hypothesis fold into its stay
+        unsigned mask = 0;
+        if (own) {
+            for (int k = 0; k < nc; ++k) {
+                const int c = c_tok[k];
+                const unsigned long long target = seq_hash(hash, c);
+                for (int p = 0, slot = (int)(target & (BEAM_TABLE - 1)); p < BEAM_TABLE; ++p, slot = (slot + 1) & (BEAM_TABLE - 1)) {
+                    const int j = table[slot];
+                    if (j < 0) break;
+                    if (h_hash[cur][j] == target && h_last[cur][j] == c && h_len[cur][j] == len + 1 &&
+                        same_sequence(nd, h_par[cur][j], node, len)) {
+                        mask |= 1u << k;
+                        m_val[j] = (c == last ? pb : s) + c_lp[k];
+                        m_key[j] = (unsigned)tid * V1 + (unsigned)c + 1u;
+                        break;
+                    }
+                }
+            }
+        }
+        __syncthreads();
+        // ---- C: stay scores and the best candidate score
+        for (int i = tid; i < BEAM_TABLE; i += BEAM_MAX_W) table[i] = -1;
+        double st_score = -INFINITY, best = -INFINITY;
+        unsigned st_key = 0;
+        if (own) {
+            st_pnb = lae(st_pnb, m_val[tid]);
+            st_score = lae(st_pb, st_pnb);
+            st_key = min((unsigned)tid * V1, m_key[tid]);
+            best = st_score;
+            for (int k = 0; k < nc; ++k) {
+                if ((mask >> k) & 1u) continue;
+                const double e = (c_tok[k] == last ? pb : s) + c_lp[k];
+                if (e > best) best = e;
+            }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) { const double x = __shfl_xor(best, o, 64); if (x > best) best = x; }
+        if (lane == 0) red_best[wv] = best;
+        __syncthreads();
+        best = fmax(fmax(red_best[0], red_best[1]), fmax(red_best[2], red_best[3]));
+        const double thr = best + prune;
+        // ---- D: survivors (score >= best + prune): count, lowest score
+        int cnt = 0;
+        unsigned long long omin = ~0ull;
+        if (own) {
+            if (st_score >= thr) { ++cnt; omin = ord64(st_score); }
+            for (int k = 0; k < nc; ++k) {
+                if ((mask >> k) & 1u) continue;
+                const double e = (c_tok[k] == last ? pb : s) + c_lp[k];
+                if (e >= thr) { ++cnt; omin = min(omin, ord64(e)); }
+            }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            cnt += __shfl_xor(cnt, o, 64);
+            omin = min(omin, (unsigned long long)__shfl_xor(omin, o, 64));
+        }
+        if (lane == 0) { red_cnt[wv] = cnt; red_min[wv] = omin; }
+        __syncthreads();
+        const int S = red_cnt[0] + red_cnt[1] + red_cnt[2] + red_cnt[3];
+        // ---- keep-W: radix select of the W largest composites (only when more than W survive)
+        int pos = 0;
+        u128 prefix = 0;
+        if (S > W) {
+            const unsigned long long diff = ord64(best) ^ min(min(red_min[0], red_min[1]), min(red_min[2], red_min[3]));
+            const int top = diff ? 32 + 64 - __clzll((long long)diff) : 32;
+            pos = (top + 7) & ~7;
+            prefix = ((u128)ord64(best) << 32) >> pos;                  // the bits every survivor shares
+            int need = W;
+            for (int pass = 0; pos > 0; ++pass) {
+                const int buf = pass & 1;
+                hist[buf ^ 1][tid] = 0u;
+                if (own) {
+                    for (int k = -1; k < nc; ++k) {
+                        double e;
+                        unsigned key;
+                        if (k < 0) { e = st_score; key = st_key; }
+                        else {
+                            if ((mask >> k) & 1u) continue;
+                            e = (c_tok[k] == last ? pb : s) + c_lp[k];
+                            key = (unsigned)tid * V1 + (unsigned)c_tok[k] + 1u;
+                        }
+                        if (!(e >= thr)) continue;
+                        const u128 comp = ((u128)ord64(e) << 32) | (u128)(0xFFFFFFFFu - key);
+                        if ((comp >> pos) == prefix) atomicAdd(&hist[buf][(unsigned)(comp >> (pos - 8)) & 255u], 1u);
+                    }
+                }
+                __syncthreads();
+                if (wv == 0) {
+                    unsigned h[4], sum = 0;
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) { h[q] = hist[buf][4 * lane + q]; sum += h[q]; }
+                    unsigned suf = sum;                                   // bins of lanes >= lane
+#pragma unroll
+                    for (int o = 1; o < 64; o <<= 1) {
+                        const unsigned x = __shfl_down(suf, o, 64);
+                        if (lane + o < 64) suf += x;
+                    }
+                    unsigned above = suf - sum;
+#pragma unroll
+                    for (int q = 3; q >= 0; --q) {
+                        if (above < (unsigned)need && above + h[q] >= (unsigned)need) {
+                            sel_d = 4 * lane + q;
+                            sel_need = need - (int)above;
+                            sel_done = h[q] == (unsigned)(need - (int)above);
+                        }
+                        above += h[q];
+                    }
+                }
+                __syncthreads();
+                prefix = (prefix << 8) | (u128)(unsigned)sel_d;
+                pos -= 8;
+                need = sel_need;
+                if (sel_done) break;
+            }
+        }
+        // ---- E: compaction of the kept candidates
+        if (own) {
+            for (int k = -1; k < nc; ++k) {
+                double e, ipb, ipnb;
+                unsigned key;
+                if (k < 0) { e = st_score; key = st_key; ipb = st_pb; ipnb = st_pnb; }
+                else {
+                    if ((mask >> k) & 1u) continue;
+                    e = (c_tok[k] == last ? pb : s) + c_lp[k];
+                    key = (unsigned)tid * V1 + (unsigned)c_tok[k] + 1u;
+                    ipb = -INFINITY; ipnb = e;
+                }
+                if (!(e >= thr)) continue;
+                const u128 comp = ((u128)ord64(e) << 32) | (u128)(0xFFFFFFFFu - key);
+                if (S > W && (comp >> pos) < prefix) continue;
+                const int slot = atomicAdd(&n_kept, 1);
+                if (slot < W) {
+                    l_ord[slot] = ord64(e); l_low[slot] = 0xFFFFFFFFu - key; l_item[slot] = tid * 64 + (k + 1);
+                    l_pb[slot] = ipb; l_pnb[slot] = ipnb; l_s[slot] = e;
+                }
+            }
+        }
+        __syncthreads();
+        // ---- F: rank the kept hypotheses by counting, write the next frame's state, rebuild the table
+        const int M = min(n_kept, W);
+        const int nxt = cur ^ 1;
+        if (tid < M) {
+            const unsigned long long o = l_ord[tid];
+            const unsigned lo = l_low[tid];
+            int q = 0;
+            for (int j = 0; j < M; ++j) q += (l_ord[j] > o) || (l_ord[j] == o && l_low[j] > lo);
+            const int i = l_item[tid] >> 6, k = (l_item[tid] & 63) - 1;
+            h_pb[nxt][q] = l_pb[tid]; h_pnb[nxt][q] = l_pnb[tid]; h_s[nxt][q] = l_s[tid];
+            unsigned long long qh;
+            if (k < 0) {
+                qh = h_hash[cur][i];
+                h_node[nxt][q] = h_node[cur][i]; h_par[nxt][q] = h_par[cur][i]; h_last[nxt][q] = h_last[cur][i];
+                h_len[nxt][q] = h_len[cur][i];
+            } else {
+                const int c = c_tok[k], id = 1 + t * W + q;
+                nd[id] = make_int2(h_node[cur][i], c);
+                qh = seq_hash(h_hash[cur][i], c);
+                h_node[nxt][q] = id; h_par[nxt][q] = h_node[cur][i]; h_last[nxt][q] = c; h_len[nxt][q] = h_len[cur][i] + 1;
+            }
+            h_hash[nxt][q] = qh;
+            int slot = (int)(qh & (BEAM_TABLE - 1));
+            for (int p = 0; p < BEAM_TABLE && atomicCAS(&table[slot], -1, q) != -1; ++p) slot = (slot + 1) & (BEAM_TABLE - 1);
+        }
+        __syncthreads();
+        cur = nxt;
+        nh = M;
+    }
+
+    // ---- traceback: one thread per returned hypothesis
+    if (tid < N) {
+        const int64_t o = (int64_t)b * N + tid;
+        int64_t* out = tokens + o * T;
+        int len = 0;
+        if (tid < nh) {
+            len = min(h_len[cur][tid], T);
+            int x = h_node[cur][tid];
+            for (int p = len - 1; p >= 0 && x > 0; --p) {
+                const int2 e = nd[x];
+                out[p] = e.y;
+                x = e.x;
+            }
+            scores[o] = (float)h_s[cur][tid];
+        } else {
+            scores[o] = -INFINITY;
+        }
+        counts[o] = len;
+        for (int p = len; p < T; ++p) out[p] = -1;
+    }
+    if (tid == 0) num_hyps[b] = min(nh, N);
+}
+
+}  // namespace
+
+extern "C" size_t cfm_ctc_beam_workspace_bytes(int B, int T, int W, int K) {
+    if (B <= 0 || T <= 0 || W < 1 || W > BEAM_MAX_W || K < 1 || K > BEAM_MAX_K) return 0;
+    return beam_carve(B, T, W, K, nullptr, nullptr);
+}
+
+extern "C" int cfm_ctc_beam_decode_f32(const float* logits, const int64_t* lengths_or_null, int B, int T, int V, int blank_id,
+                                       int beam_width, int max_candidates, float token_min_logp, float beam_prune_logp,
+                                       int n_best, void* workspace, size_t workspace_bytes, int64_t* tokens, int64_t* counts,
+                                       float* scores, int64_t* num_hyps, cfm_stream_t stream) {
+    CFM_REQUIRE(logits && workspace && tokens && counts && scores && num_hyps, CFM_ERR_NULL);
+    CFM_REQUIRE(B > 0 && T > 0 && V >= 2, CFM_ERR_BAD_SHAPE);
+    CFM_REQUIRE(beam_width >= 1 && beam_width <= BEAM_MAX_W, CFM_ERR_UNSUPPORTED);
+    CFM_REQUIRE(max_candidates >= 1 && max_candidates <= BEAM_MAX_K, CFM_ERR_UNSUPPORTED);
+    CFM_REQUIRE(n_best >= 1 && n_best <= beam_width, CFM_ERR_BAD_SHAPE);
+    CFM_REQUIRE(blank_id >= 0 && blank_id < V, CFM_ERR_BAD_SHAPE);
+    CFM_REQUIRE(V <= BEAM_MAX_V && (int64_t)T * beam_width < INT32_MAX, CFM_ERR_UNSUPPORTED);
+    CFM_REQUIRE(!(token_min_logp != token_min_logp) && !(beam_prune_logp != beam_prune_logp), CFM_ERR_BAD_SHAPE);   // NaN
+    CFM_REQUIRE(workspace_bytes >= beam_carve(B, T, beam_width, max_candidates, nullptr, nullptr), CFM_ERR_BAD_SHAPE);
+    BeamWs ws;
+    beam_carve(B, T, beam_width, max_candidates, static_cast<char*>(workspace), &ws);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int64_t rows = (int64_t)B * T;
+    hipLaunchKernelGGL(beam_prep_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, logits, lengths_or_null, ws, B, T, V,
+                       blank_id, max_candidates, (double)token_min_logp);
+    hipLaunchKernelGGL(beam_search_kernel, dim3((unsigned)B), dim3(BEAM_MAX_W), 0, s, logits, lengths_or_null, ws, T, V, blank_id,
+                       beam_width, max_candidates, (double)beam_prune_logp, n_best, tokens, counts, scores, num_hyps);
+    return cfm_launch_status();
+}

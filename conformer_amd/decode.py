@@ -1,9 +1,15 @@
-"""Greedy CTC decoding on the device (reference: ConformerProcessor.greedy_decode /
-batch_greedy_decode, processing/processor.py:301-334): one kernel does the per-frame argmax ("CTC alignment indices")
-and the pad/unk filtering + repeat collapse, replacing the reference's per-frame `.item()` host loop (train.py:61)."""
+"""CTC decoding on the device.
+
+Greedy (reference: ConformerProcessor.greedy_decode / batch_greedy_decode, processing/processor.py:301-334):
+one kernel does the per-frame argmax ("CTC alignment indices") and the pad/unk filtering + repeat collapse, replacing the
+reference's per-frame `.item()` host loop (train.py:61).
+
+Prefix beam search (reference: KenLanguageModel, processing/lm.py:6-75, without the language model): `beam_ctc_decode` and
+`BeamCTCDecoder`, semantics in INTEGRATION.md "CTC prefix beam search".  Unlike the greedy decoder it collapses by the
+standard CTC rule: a blank separates repeats."""
 from __future__ import annotations
 
-from typing import List, Optional, Sequence, Tuple
+from typing import Callable, List, Optional, Sequence, Tuple, Union
 
 import torch
 
@@ -31,3 +37,72 @@ def tokens_to_text(tokens: torch.Tensor, counts: torch.Tensor, vocab: Sequence[s
     """Host-side join of the decoded ids (processor.py:319): ''.join(vocab[id]).replace(delim, ' ')."""
     tk, ct = tokens.cpu().tolist(), counts.cpu().tolist()
     return ["".join(vocab[i] for i in row[:n]).replace(delim_token, " ") for row, n in zip(tk, ct)]
+
+
+def beam_ctc_decode(logits: torch.Tensor, blank_id: int, lengths: Optional[torch.Tensor] = None, beam_width: int = 100,
+                    n_best: int = 1, token_min_logp: float = -5.0, beam_prune_logp: float = -10.0, max_candidates: int = 16
+                    ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """CTC prefix beam search over logits (B,T,V) on the HIP device (fp32, or bf16 / fp16 cast to fp32).
+    Returns (tokens (B,N,T) int64 padded with -1, counts (B,N) int64, scores (B,N) fp32, num_hyps (B) int64), N = n_best,
+    hypotheses best first; unused rows hold count 0, tokens -1 and score -inf.  `lengths` (B) int64 on the device: frames
+    to consume per utterance (clamped to [0,T]; None = all).  Nothing synchronises with the host."""
+    if isinstance(logits, torch.Tensor) and logits.dtype in (torch.bfloat16, torch.float16):
+        logits = logits.float()
+    x = ops._req(logits, "logits")
+    if x.dim() != 3:
+        raise ValueError(f"logits: expected (B,T,V), got {tuple(x.shape)}")
+    B, T, V = x.shape
+    if lengths is not None:
+        lengths = ops._req(lengths, "lengths", torch.int64)
+    lib = _lib.load()
+    ws_bytes = lib.cfm_ctc_beam_workspace_bytes(B, T, int(beam_width), int(max_candidates))
+    workspace = torch.empty(max(int(ws_bytes), 1), dtype=torch.uint8, device=x.device)
+    tokens = torch.empty(B, n_best, T, dtype=torch.int64, device=x.device)
+    counts = torch.empty(B, n_best, dtype=torch.int64, device=x.device)
+    scores = torch.empty(B, n_best, dtype=torch.float32, device=x.device)
+    num_hyps = torch.empty(B, dtype=torch.int64, device=x.device)
+    st = lib.cfm_ctc_beam_decode_f32(x.data_ptr(), ops._p(lengths), B, T, V, int(blank_id), int(beam_width),
+                                     int(max_candidates), float(token_min_logp), float(beam_prune_logp), int(n_best),
+                                     workspace.data_ptr(), int(ws_bytes), tokens.data_ptr(), counts.data_ptr(),
+                                     scores.data_ptr(), num_hyps.data_ptr(), ops._stream())
+    _lib.check(st, "cfm_ctc_beam_decode_f32")
+    return tokens, counts, scores, num_hyps
+
+
+class BeamCTCDecoder:
+    """Drop-in for the reference's KenLanguageModel (processing/lm.py:6-75) without the language model: the same
+    `__call__(logits, lengths=None, decode_func=None)`, a str for (T,V) logits and a list of str for (B,T,V).
+    The best hypothesis is joined as ''.join(vocab[id]) with `delim_token` read as a space (processor.py:319); ids in
+    `skip_ids` (the unk id, for example) are dropped from the text, not from the search."""
+
+    def __init__(self, vocab: Sequence[str], blank_id: int, skip_ids: Sequence[int] = (), delim_token: str = "|",
+                 beam_width: int = 190, beam_prune_logp: float = -20.0, token_min_logp: float = -5.0,
+                 max_candidates: int = 16) -> None:
+        self.vocab = list(vocab)
+        self.blank_id = int(blank_id)
+        self.skip_ids = frozenset(int(i) for i in skip_ids)
+        self.delim_token = delim_token
+        self.beam_width = beam_width
+        self.beam_prune_logp = beam_prune_logp
+        self.token_min_logp = token_min_logp
+        self.max_candidates = max_candidates
+
+    def text(self, ids: Sequence[int]) -> str:
+        joined = "".join(self.vocab[i] for i in ids if i not in self.skip_ids)
+        return " ".join(joined.replace(self.delim_token, " ").split())
+
+    def __call__(self, logits: torch.Tensor, lengths: Optional[torch.Tensor] = None,
+                 decode_func: Optional[Callable[[str], str]] = None) -> Union[str, List[str]]:
+        single = logits.dim() == 2
+        if single:
+            logits = logits.unsqueeze(0)
+        if lengths is not None and not (isinstance(lengths, torch.Tensor) and lengths.is_cuda):
+            lengths = torch.as_tensor(lengths, dtype=torch.int64).reshape(-1).to(logits.device)   # numpy lengths, as lm.py takes
+        tokens, counts, _, _ = beam_ctc_decode(logits, self.blank_id, lengths, beam_width=self.beam_width, n_best=1,
+                                               token_min_logp=self.token_min_logp, beam_prune_logp=self.beam_prune_logp,
+                                               max_candidates=self.max_candidates)
+        preds = []
+        for row, n in zip(tokens[:, 0].cpu().tolist(), counts[:, 0].cpu().tolist()):
+            text = self.text(row[:n])
+            preds.append(decode_func(text) if decode_func is not None else text)
+        return preds[0] if single else preds

@@ -475,6 +475,18 @@ int cfm_greedy_ctc_decode_f32(const float* logits, const int64_t* lengths_or_nul
                               int64_t* tokens, int64_t* counts, int B, int T, int V, int pad_id, int unk_id,
                               cfm_stream_t stream);
 
+/*      CTC prefix beam search (lexicon-free; the search half of pyctcdecode as processing/lm.py drives it), semantics in
+ *      INTEGRATION.md "CTC prefix beam search".  logits (B,T,V) fp32; lengths_or_null: frames per utterance (int64, clamped
+ *      to [0,T]); beam_width W in [1,256]; max_candidates K in [1,32]; n_best N in [1,W]; blank_id in [0,V); V >= 2.
+ *      workspace: cfm_ctc_beam_workspace_bytes(B,T,W,K) bytes (0 for arguments out of range), no initialisation needed.
+ *      Outputs: tokens (B,N,T) int64 padded with -1, counts (B,N) int64, scores (B,N) fp32 (log probability of the prefix
+ *      summed over its alignments; -inf in unused rows), num_hyps (B) int64.  Argument errors return before any HIP call. */
+size_t cfm_ctc_beam_workspace_bytes(int B, int T, int W, int K);
+int cfm_ctc_beam_decode_f32(const float* logits, const int64_t* lengths_or_null, int B, int T, int V, int blank_id,
+                            int beam_width, int max_candidates, float token_min_logp, float beam_prune_logp, int n_best,
+                            void* workspace, size_t workspace_bytes, int64_t* tokens, int64_t* counts, float* scores,
+                            int64_t* num_hyps, cfm_stream_t stream);
+
 /* N1 decoder (decoder.py:10-27): LSTM recurrence over a packed batch.  gates_x (B,T,4H) = X.W_ih^T + b_ih + b_hh from
  *      one of the GEMM entries; w_hh (4H,H), gate order i|f|g|o; lengths_or_null: frames per utterance (outputs beyond are
  *      0, as pad_packed_sequence returns); y (B,T,H) <- h_t; c_state (B,H) scratch; save_* (B,T,4H)/(B,T,H) or NULL.

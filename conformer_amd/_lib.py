@@ -105,6 +105,12 @@ SIGNATURES = {
     "cfm_greedy_ctc_decode_f32": (c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "cfm_ctc_beam_workspace_bytes": (ctypes.c_size_t, [_I, _I, _I, _I]),
     "cfm_ctc_beam_decode_f32": (c_int, [_P, _P, _I, _I, _I, _I, _I, _I, _F, _F, _I, _P, ctypes.c_size_t, _P, _P, _P, _P, _P]),
+    "cfm_ngram_lm_pack_bytes": (ctypes.c_size_t, [_I, _P, _I, _L, _I, _L]),
+    "cfm_ngram_lm_pack": (c_int, [_I, _P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, ctypes.c_size_t]),
+    "cfm_ngram_lm_score_f64": (c_int, [_P, _P, _P, _I, _I, _P, _P]),
+    "cfm_ctc_beam_lm_workspace_bytes": (ctypes.c_size_t, [_I, _I, _I, _I]),
+    "cfm_ctc_beam_lm_decode_f32": (c_int, [_P, _P, _I, _I, _I, _I, _I, _I, _F, _F, _I, _P, ctypes.c_double, ctypes.c_double,
+                                           ctypes.c_double, _I, _P, ctypes.c_size_t, _P, _P, _P, _P, _P, _P]),
     "cfm_lstm_fwd_f32": (c_int, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "cfm_lstm_fwd_frag_f32": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "cfm_lstm_bwd_frag_f32": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),

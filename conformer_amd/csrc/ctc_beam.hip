@@ -18,8 +18,19 @@
 // Keep-W: a most-significant-digit radix select over the 96-bit composite (order-preserving bits of the score, then the
 // complement of the origin key), 8 bits per pass, starting at the highest bit in which the surviving scores differ; the
 // composites are unique, so the selected set has exactly W members.  The kept hypotheses are then ranked by counting.
+//
+// Language-model fusion (beam_search_kernel<true>, INTEGRATION.md "Language-model fusion"): the same search ranked by the
+// fused score F = logaddexp(pb, pnb) + (lm + P), where lm sums the word terms of the completed words and P penalises a
+// partial word that spells no prefix of a unigram.  Each hypothesis also carries its trie node, the code-point length of its
+// partial word and its last LM_CTX word ids.  Per frame, the candidates' token kinds and code points are staged in LDS;
+// each thread walks the trie for its unmerged character candidates (LM_WALK walks advance together, one probe per round)
+// and scores the word a delimiter completes once (all n-gram probes of one lookup in flight together, ngram_lm.h).  The
+// trie node each extension reaches is kept in LDS (x_node) for the ranking passes and the next frame's state.  After the
+// last frame the hypotheses gain their end-of-utterance terms and are re-ranked by the final F.  beam_search_kernel<false>
+// is the LM-free search, unchanged.
 #include <float.h>
 #include "cfm_common.h"
+#include "ngram_lm.h"
 
 namespace {
 
@@ -27,6 +38,22 @@ constexpr int BEAM_MAX_W = 256;          // also the workgroup size of the searc
 constexpr int BEAM_MAX_K = 32;
 constexpr int BEAM_TABLE = 512;          // hash slots (>= 2 W)
 constexpr int BEAM_MAX_V = 1 << 23;      // origin keys rank * (V + 1) + token + 1 fit in 31 bits
+constexpr int LM_TOK_CP = 8;             // code points of a candidate token staged in LDS (the rest is read from the tables)
+constexpr int LM_WALK = 8;               // trie walks a thread advances together
+constexpr double LN10 = 2.302585092994045684;
+
+template <bool LM> struct LmParams {};
+template <> struct LmParams<true> {
+    const void* tables;                  // cfm_ngram_lm_pack blob on the device
+    double alpha, beta, unk_offset;
+    int score_boundary;
+    float* am_scores;
+};
+
+// P(p): 0 for an empty partial word or one that spells a prefix of some unigram (node >= 0)
+__device__ __forceinline__ double lm_pen(int node, int plen, double unk) {
+    return (plen == 0 || node >= 0) ? 0.0 : unk * fmax(1.0, (double)plen / 6.0);
+}
 
 struct BeamWs {
     double* lse;      // (B*T) log-sum-exp of each logits row
@@ -142,10 +169,11 @@ __device__ bool same_sequence(const int2* nd, int a, int b, int len) {
 
 typedef unsigned __int128 u128;
 
+template <bool LM>
 __global__ __launch_bounds__(BEAM_MAX_W) void beam_search_kernel(
         const float* __restrict__ logits, const int64_t* __restrict__ lengths, BeamWs ws, int T, int V, int blank, int W,
         int K, double prune, int N, int64_t* __restrict__ tokens, int64_t* __restrict__ counts, float* __restrict__ scores,
-        int64_t* __restrict__ num_hyps) {
+        int64_t* __restrict__ num_hyps, LmParams<LM> lp) {
     // hypotheses in rank order, double-buffered across frames
     __shared__ double h_pb[2][BEAM_MAX_W], h_pnb[2][BEAM_MAX_W], h_s[2][BEAM_MAX_W];
     __shared__ unsigned long long h_hash[2][BEAM_MAX_W];
@@ -165,17 +193,30 @@ __global__ __launch_bounds__(BEAM_MAX_W) void beam_search_kernel(
     __shared__ unsigned l_low[BEAM_MAX_W];
     __shared__ int l_item[BEAM_MAX_W];
     __shared__ double l_pb[BEAM_MAX_W], l_pnb[BEAM_MAX_W], l_s[BEAM_MAX_W];
+    // language-model state of the hypotheses (double-buffered like the rest), this frame's candidate tokens, and per
+    // thread: the word term its delimiters add, the word id they push, the trie node each candidate reaches
+    constexpr int LW = LM ? BEAM_MAX_W : 1, LK = LM ? BEAM_MAX_K : 1;
+    __shared__ double h_lm[2][LW], x_term[LW];
+    __shared__ int h_tn[2][LW], h_pl[2][LW], h_ctx[2][LM_CTX][LW], x_wid[LW], x_node[LK][LW];
+    __shared__ int c_kind[LK], c_len[LK], c_off[LK], c_cp[LK][LM_TOK_CP];
 
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int n = beam_frames(lengths, b, T);
     int2* nd = ws.nodes + (int64_t)b * (1 + (int64_t)T * W);
     const unsigned V1 = (unsigned)V + 1u;
+    [[maybe_unused]] LmView lmv;
+    if constexpr (LM) lmv = lm_view(lp.tables);
 
     for (int i = tid; i < BEAM_TABLE; i += BEAM_MAX_W) table[i] = -1;
     if (tid == 0) {
         h_pb[0][0] = 0.0; h_pnb[0][0] = -INFINITY; h_s[0][0] = 0.0;
         h_hash[0][0] = ROOT_HASH; h_node[0][0] = 0; h_par[0][0] = -1; h_last[0][0] = -1; h_len[0][0] = 0;
         nd[0] = make_int2(-1, -1);
+        if constexpr (LM) {
+            h_lm[0][0] = 0.0; h_tn[0][0] = 0; h_pl[0][0] = 0;
+            for (int i = 0; i < LM_CTX; ++i) h_ctx[0][i][0] = -1;
+            if (lp.score_boundary) h_ctx[0][LM_CTX - 1][0] = lmv.bos;
+        }
     }
     __syncthreads();
     if (tid == 0) table[ROOT_HASH & (BEAM_TABLE - 1)] = 0;
@@ -188,15 +229,34 @@ __global__ __launch_bounds__(BEAM_MAX_W) void beam_search_kernel(
         const float* lrow = logits + row * V;
         // ---- A: this frame's candidates; own hypothesis; stays
         if (tid < nc) { c_tok[tid] = ws.ctok[row * K + tid]; c_lp[tid] = ws.clp[row * K + tid]; }
+        if constexpr (LM) {
+            if (tid < nc) {
+                const int c = ws.ctok[row * K + tid];
+                int kind = LM_TOK_SKIP, o = 0, l = 0;
+                if (c < lmv.V) { kind = lmv.tok_kind[c]; o = lmv.tok_off[c]; l = lmv.tok_off[c + 1] - o; }
+                if (kind != LM_TOK_CHARS) l = 0;
+                c_kind[tid] = kind; c_off[tid] = o; c_len[tid] = l;
+                for (int q = 0; q < min(l, LM_TOK_CP); ++q) c_cp[tid][q] = lmv.tok_cp[o + q];
+            }
+        }
         hist[0][tid] = 0u;
         if (tid == 0) n_kept = 0;
         const bool own = tid < nh;
         double pb = 0, pnb = 0, s = 0, st_pb = -INFINITY, st_pnb = -INFINITY;
         int last = -1, len = 0, node = 0;
         unsigned long long hash = 0;
+        // LM state of the own hypothesis: completed-word sum, trie node, partial length, context; lm + P; the word term
+        [[maybe_unused]] double lm = 0, lmp = 0, term = 0;
+        [[maybe_unused]] int tn = 0, pl = 0;
+        [[maybe_unused]] int ctx[LM_CTX];
         if (own) {
             pb = h_pb[cur][tid]; pnb = h_pnb[cur][tid]; s = h_s[cur][tid];
             last = h_last[cur][tid]; len = h_len[cur][tid]; node = h_node[cur][tid]; hash = h_hash[cur][tid];
+            if constexpr (LM) {
+                lm = h_lm[cur][tid]; tn = h_tn[cur][tid]; pl = h_pl[cur][tid];
+                for (int i = 0; i < LM_CTX; ++i) ctx[i] = h_ctx[cur][i][tid];
+                lmp = lm + lm_pen(tn, pl, lp.unk_offset);
+            }
             st_pb = s + ((double)lrow[blank] - lse);
             st_pnb = last >= 0 ? pnb + ((double)lrow[last] - lse) : -INFINITY;
             m_val[tid] = -INFINITY;
@@ -221,20 +281,87 @@ __global__ __launch_bounds__(BEAM_MAX_W) void beam_search_kernel(
                     }
                 }
             }
+            if constexpr (LM) {
+                // the word a delimiter completes (the same for every delimiter candidate)
+                bool delim = false;
+                for (int k = 0; k < nc; ++k) delim |= !((mask >> k) & 1u) && c_kind[k] == LM_TOK_DELIM;
+                if (delim && pl > 0) {
+                    const int wd = tn >= 0 ? lmv.node_word[tn] : -1;
+                    const int w = wd >= 0 ? wd : lmv.unk;
+                    term = lp.alpha * LN10 * (lm_cond_log10(lmv, ctx, w) + (wd >= 0 ? 0.0 : lp.unk_offset)) + lp.beta;
+                    x_term[tid] = term;
+                    x_wid[tid] = w;
+                }
+                // trie walks of the character candidates, LM_WALK at a time
+                auto cp_at = [&](int k, int q) { return q < LM_TOK_CP ? c_cp[k][q] : lmv.tok_cp[c_off[k] + q]; };
+                for (int k0 = 0; k0 < nc; k0 += LM_WALK) {
+                    int wn[LM_WALK], wq[LM_WALK];
+                    unsigned wsl[LM_WALK];
+                    bool wa[LM_WALK];
+#pragma unroll
+                    for (int u = 0; u < LM_WALK; ++u) {
+                        const int k = k0 + u;
+                        wn[u] = tn; wq[u] = 0; wsl[u] = 0u;
+                        wa[u] = k < nc && tn >= 0 && !((mask >> k) & 1u) && c_len[k] > 0;
+                        if (wa[u]) wsl[u] = (unsigned)trie_hash(tn, cp_at(k, 0)) & lmv.trie_mask;
+                    }
+                    for (;;) {
+                        bool any = false;
+#pragma unroll
+                        for (int u = 0; u < LM_WALK; ++u) any |= wa[u];
+                        if (!any) break;
+                        int4 e[LM_WALK];
+#pragma unroll
+                        for (int u = 0; u < LM_WALK; ++u)
+                            if (wa[u]) e[u] = lmv.trie[wsl[u]];
+#pragma unroll
+                        for (int u = 0; u < LM_WALK; ++u) {
+                            if (!wa[u]) continue;
+                            const int k = k0 + u, cp = cp_at(k, wq[u]);
+                            if (e[u].x == -1) {                                  // no such edge: no unigram has this prefix
+                                wn[u] = -1; wa[u] = false;
+                            } else if (e[u].x == wn[u] && e[u].y == cp) {
+                                wn[u] = e[u].z;
+                                if (++wq[u] == c_len[k]) wa[u] = false;
+                                else wsl[u] = (unsigned)trie_hash(wn[u], cp_at(k, wq[u])) & lmv.trie_mask;
+                            } else {
+                                wsl[u] = (wsl[u] + 1u) & lmv.trie_mask;
+                            }
+                        }
+                    }
+#pragma unroll
+                    for (int u = 0; u < LM_WALK; ++u)
+                        if (k0 + u < nc) x_node[k0 + u][tid] = wn[u];
+                }
+            }
         }
         __syncthreads();
+        // lm + P after the own hypothesis is extended by candidate k (LM only)
+        [[maybe_unused]] auto ext_lmp = [&](int k) -> double {
+            if constexpr (LM) {
+                const int kind = c_kind[k];
+                if (kind == LM_TOK_CHARS) return lm + lm_pen(x_node[k][tid], pl + c_len[k], lp.unk_offset);
+                if (kind == LM_TOK_DELIM && pl > 0) return (lm + term) + 0.0;
+                return lmp;
+            } else {
+                return 0.0;
+            }
+        };
         // ---- C: stay scores and the best candidate score
         for (int i = tid; i < BEAM_TABLE; i += BEAM_MAX_W) table[i] = -1;
         double st_score = -INFINITY, best = -INFINITY;
+        [[maybe_unused]] double st_am = -INFINITY;
         unsigned st_key = 0;
         if (own) {
             st_pnb = lae(st_pnb, m_val[tid]);
             st_score = lae(st_pb, st_pnb);
+            if constexpr (LM) { st_am = st_score; st_score = st_am + lmp; }         // stays rank by the fused score
             st_key = min((unsigned)tid * V1, m_key[tid]);
             best = st_score;
             for (int k = 0; k < nc; ++k) {
                 if ((mask >> k) & 1u) continue;
-                const double e = (c_tok[k] == last ? pb : s) + c_lp[k];
+                double e = (c_tok[k] == last ? pb : s) + c_lp[k];
+                if constexpr (LM) e = e + ext_lmp(k);
                 if (e > best) best = e;
             }
         }
@@ -251,7 +378,8 @@ __global__ __launch_bounds__(BEAM_MAX_W) void beam_search_kernel(
             if (st_score >= thr) { ++cnt; omin = ord64(st_score); }
             for (int k = 0; k < nc; ++k) {
                 if ((mask >> k) & 1u) continue;
-                const double e = (c_tok[k] == last ? pb : s) + c_lp[k];
+                double e = (c_tok[k] == last ? pb : s) + c_lp[k];
+                if constexpr (LM) e = e + ext_lmp(k);
                 if (e >= thr) { ++cnt; omin = min(omin, ord64(e)); }
             }
         }
@@ -283,6 +411,7 @@ __global__ __launch_bounds__(BEAM_MAX_W) void beam_search_kernel(
                         else {
                             if ((mask >> k) & 1u) continue;
                             e = (c_tok[k] == last ? pb : s) + c_lp[k];
+                            if constexpr (LM) e = e + ext_lmp(k);
                             key = (unsigned)tid * V1 + (unsigned)c_tok[k] + 1u;
                         }
                         if (!(e >= thr)) continue;
@@ -323,13 +452,17 @@ __global__ __launch_bounds__(BEAM_MAX_W) void beam_search_kernel(
         if (own) {
             for (int k = -1; k < nc; ++k) {
                 double e, ipb, ipnb;
+                [[maybe_unused]] double am;                          // LM: the acoustic score beside the fused e
                 unsigned key;
-                if (k < 0) { e = st_score; key = st_key; ipb = st_pb; ipnb = st_pnb; }
-                else {
+                if (k < 0) {
+                    e = st_score; key = st_key; ipb = st_pb; ipnb = st_pnb;
+                    if constexpr (LM) am = st_am;
+                } else {
                     if ((mask >> k) & 1u) continue;
                     e = (c_tok[k] == last ? pb : s) + c_lp[k];
                     key = (unsigned)tid * V1 + (unsigned)c_tok[k] + 1u;
                     ipb = -INFINITY; ipnb = e;
+                    if constexpr (LM) { am = e; e = e + ext_lmp(k); }
                 }
                 if (!(e >= thr)) continue;
                 const u128 comp = ((u128)ord64(e) << 32) | (u128)(0xFFFFFFFFu - key);
@@ -337,7 +470,9 @@ __global__ __launch_bounds__(BEAM_MAX_W) void beam_search_kernel(
                 const int slot = atomicAdd(&n_kept, 1);
                 if (slot < W) {
                     l_ord[slot] = ord64(e); l_low[slot] = 0xFFFFFFFFu - key; l_item[slot] = tid * 64 + (k + 1);
-                    l_pb[slot] = ipb; l_pnb[slot] = ipnb; l_s[slot] = e;
+                    l_pb[slot] = ipb; l_pnb[slot] = ipnb;
+                    if constexpr (LM) l_s[slot] = am;
+                    else l_s[slot] = e;
                 }
             }
         }
@@ -364,6 +499,18 @@ __global__ __launch_bounds__(BEAM_MAX_W) void beam_search_kernel(
                 h_node[nxt][q] = id; h_par[nxt][q] = h_node[cur][i]; h_last[nxt][q] = c; h_len[nxt][q] = h_len[cur][i] + 1;
             }
             h_hash[nxt][q] = qh;
+            if constexpr (LM) {
+                double nlm = h_lm[cur][i];
+                int ntn = h_tn[cur][i], npl = h_pl[cur][i], sh = 0;
+                if (k >= 0) {
+                    const int kind = c_kind[k];
+                    if (kind == LM_TOK_CHARS) { ntn = x_node[k][i]; npl += c_len[k]; }
+                    else if (kind == LM_TOK_DELIM && npl > 0) { nlm = (nlm + x_term[i]) + 0.0; ntn = 0; npl = 0; sh = 1; }
+                }
+                h_lm[nxt][q] = nlm; h_tn[nxt][q] = ntn; h_pl[nxt][q] = npl;
+                for (int u = 0; u < LM_CTX; ++u)
+                    h_ctx[nxt][u][q] = u + sh < LM_CTX ? h_ctx[cur][u + sh][i] : x_wid[i];
+            }
             int slot = (int)(qh & (BEAM_TABLE - 1));
             for (int p = 0; p < BEAM_TABLE && atomicCAS(&table[slot], -1, q) != -1; ++p) slot = (slot + 1) & (BEAM_TABLE - 1);
         }
@@ -372,6 +519,53 @@ __global__ __launch_bounds__(BEAM_MAX_W) void beam_search_kernel(
         nh = M;
     }
 
+    if constexpr (LM) {
+        // ---- end of utterance: drop P, score the partial word and </s>; re-rank by the final F (ties to the earlier rank)
+        if (tid < nh) {
+            double lmf = h_lm[cur][tid];
+            const int tn = h_tn[cur][tid], pl = h_pl[cur][tid];
+            int ctx[LM_CTX];
+            for (int i = 0; i < LM_CTX; ++i) ctx[i] = h_ctx[cur][i][tid];
+            if (pl > 0) {
+                const int wd = tn >= 0 ? lmv.node_word[tn] : -1;
+                const int w = wd >= 0 ? wd : lmv.unk;
+                lmf = lmf + (lp.alpha * LN10 * (lm_cond_log10(lmv, ctx, w) + (wd >= 0 ? 0.0 : lp.unk_offset)) + lp.beta);
+                lm_ctx_push(ctx, w);
+            }
+            if (lp.score_boundary) lmf = lmf + lp.alpha * LN10 * lm_cond_log10(lmv, ctx, lmv.eos);
+            m_val[tid] = h_s[cur][tid] + lmf;
+        }
+        __syncthreads();
+        int r = tid;                                         // rows [nh, N) are padding
+        if (tid < nh) {
+            const double f = m_val[tid];
+            r = 0;
+            for (int j = 0; j < nh; ++j) r += m_val[j] > f || (m_val[j] == f && j < tid);
+        }
+        if (r < N) {
+            const int64_t o = (int64_t)b * N + r;
+            int64_t* out = tokens + o * T;
+            int len = 0;
+            if (tid < nh) {
+                len = min(h_len[cur][tid], T);
+                int x = h_node[cur][tid];
+                for (int p = len - 1; p >= 0 && x > 0; --p) {
+                    const int2 e = nd[x];
+                    out[p] = e.y;
+                    x = e.x;
+                }
+                scores[o] = (float)m_val[tid];
+                lp.am_scores[o] = (float)h_s[cur][tid];
+            } else {
+                scores[o] = -INFINITY;
+                lp.am_scores[o] = -INFINITY;
+            }
+            counts[o] = len;
+            for (int p = len; p < T; ++p) out[p] = -1;
+        }
+        if (tid == 0) num_hyps[b] = min(nh, N);
+        return;
+    }
     // ---- traceback: one thread per returned hypothesis
     if (tid < N) {
         const int64_t o = (int64_t)b * N + tid;
@@ -421,7 +615,42 @@ extern "C" int cfm_ctc_beam_decode_f32(const float* logits, const int64_t* lengt
     const int64_t rows = (int64_t)B * T;
     hipLaunchKernelGGL(beam_prep_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, logits, lengths_or_null, ws, B, T, V,
                        blank_id, max_candidates, (double)token_min_logp);
-    hipLaunchKernelGGL(beam_search_kernel, dim3((unsigned)B), dim3(BEAM_MAX_W), 0, s, logits, lengths_or_null, ws, T, V, blank_id,
-                       beam_width, max_candidates, (double)beam_prune_logp, n_best, tokens, counts, scores, num_hyps);
+    hipLaunchKernelGGL(beam_search_kernel<false>, dim3((unsigned)B), dim3(BEAM_MAX_W), 0, s, logits, lengths_or_null, ws, T, V,
+                       blank_id, beam_width, max_candidates, (double)beam_prune_logp, n_best, tokens, counts, scores, num_hyps,
+                       LmParams<false>{});
+    return cfm_launch_status();
+}
+
+extern "C" size_t cfm_ctc_beam_lm_workspace_bytes(int B, int T, int W, int K) {
+    if (B <= 0 || T <= 0 || W < 1 || W > BEAM_MAX_W || K < 1 || K > BEAM_MAX_K) return 0;
+    return beam_carve(B, T, W, K, nullptr, nullptr);
+}
+
+extern "C" int cfm_ctc_beam_lm_decode_f32(const float* logits, const int64_t* lengths_or_null, int B, int T, int V, int blank_id,
+                                          int beam_width, int max_candidates, float token_min_logp, float beam_prune_logp,
+                                          int n_best, const void* lm_tables, double alpha, double beta, double unk_score_offset,
+                                          int score_boundary, void* workspace, size_t workspace_bytes, int64_t* tokens,
+                                          int64_t* counts, float* scores, float* am_scores, int64_t* num_hyps,
+                                          cfm_stream_t stream) {
+    CFM_REQUIRE(logits && lm_tables && workspace && tokens && counts && scores && am_scores && num_hyps, CFM_ERR_NULL);
+    CFM_REQUIRE(B > 0 && T > 0 && V >= 2, CFM_ERR_BAD_SHAPE);
+    CFM_REQUIRE(beam_width >= 1 && beam_width <= BEAM_MAX_W, CFM_ERR_UNSUPPORTED);
+    CFM_REQUIRE(max_candidates >= 1 && max_candidates <= BEAM_MAX_K, CFM_ERR_UNSUPPORTED);
+    CFM_REQUIRE(n_best >= 1 && n_best <= beam_width, CFM_ERR_BAD_SHAPE);
+    CFM_REQUIRE(blank_id >= 0 && blank_id < V, CFM_ERR_BAD_SHAPE);
+    CFM_REQUIRE(V <= BEAM_MAX_V && (int64_t)T * beam_width < INT32_MAX, CFM_ERR_UNSUPPORTED);
+    CFM_REQUIRE(!(token_min_logp != token_min_logp) && !(beam_prune_logp != beam_prune_logp), CFM_ERR_BAD_SHAPE);   // NaN
+    CFM_REQUIRE(__builtin_isfinite(alpha) && __builtin_isfinite(beta) && __builtin_isfinite(unk_score_offset), CFM_ERR_BAD_SHAPE);
+    CFM_REQUIRE(workspace_bytes >= beam_carve(B, T, beam_width, max_candidates, nullptr, nullptr), CFM_ERR_BAD_SHAPE);
+    BeamWs ws;
+    beam_carve(B, T, beam_width, max_candidates, static_cast<char*>(workspace), &ws);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int64_t rows = (int64_t)B * T;
+    hipLaunchKernelGGL(beam_prep_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, logits, lengths_or_null, ws, B, T, V,
+                       blank_id, max_candidates, (double)token_min_logp);
+    const LmParams<true> lp{lm_tables, alpha, beta, unk_score_offset, score_boundary ? 1 : 0, am_scores};
+    hipLaunchKernelGGL(beam_search_kernel<true>, dim3((unsigned)B), dim3(BEAM_MAX_W), 0, s, logits, lengths_or_null, ws, T, V,
+                       blank_id, beam_width, max_candidates, (double)beam_prune_logp, n_best, tokens, counts, scores, num_hyps,
+                       lp);
     return cfm_launch_status();
 }

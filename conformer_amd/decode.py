@@ -6,7 +6,10 @@ reference's per-frame `.item()` host loop (train.py:61).
 
 Prefix beam search (reference: KenLanguageModel, processing/lm.py:6-75, without the language model): `beam_ctc_decode` and
 `BeamCTCDecoder`, semantics in INTEGRATION.md "CTC prefix beam search".  Unlike the greedy decoder it collapses by the
-standard CTC rule: a blank separates repeats."""
+standard CTC rule: a blank separates repeats.
+
+The same search fused with a word n-gram model (`conformer_amd.lm`, an ARPA file): `beam_ctc_lm_decode` and
+`BeamCTCDecoder(lm=...)`, semantics in INTEGRATION.md "Language-model fusion"."""
 from __future__ import annotations
 
 from typing import Callable, List, Optional, Sequence, Tuple, Union
@@ -14,6 +17,7 @@ from typing import Callable, List, Optional, Sequence, Tuple, Union
 import torch
 
 from . import _lib, ops
+from .lm import NgramLanguageModel, as_language_model
 
 
 def greedy_ctc_decode(logits: torch.Tensor, pad_id: int, unk_id: int, lengths: Optional[torch.Tensor] = None
@@ -69,15 +73,60 @@ def beam_ctc_decode(logits: torch.Tensor, blank_id: int, lengths: Optional[torch
     return tokens, counts, scores, num_hyps
 
 
+def beam_ctc_lm_decode(logits: torch.Tensor, blank_id: int, lm: Union[NgramLanguageModel, str],
+                       lengths: Optional[torch.Tensor] = None, *, vocab: Sequence[str], delim_token: str = "|",
+                       skip_ids: Sequence[int] = (), alpha: float = 2.1, beta: float = 9.2, unk_score_offset: float = -10.0,
+                       score_boundary: bool = True, beam_width: int = 100, n_best: int = 1, token_min_logp: float = -5.0,
+                       beam_prune_logp: float = -10.0, max_candidates: int = 16
+                       ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """CTC prefix beam search fused with the word n-gram model `lm` (an NgramLanguageModel or an ARPA path), on the HIP
+    device.  `vocab` (V strings) spells the tokens: a token equal to `delim_token` (or " ") ends a word, tokens in
+    `skip_ids` have no characters.  Hypotheses rank by the fused score (INTEGRATION.md "Language-model fusion").
+    Returns (tokens (B,N,T) int64 padded with -1, counts (B,N) int64, scores (B,N) fp32 fused, am_scores (B,N) fp32
+    acoustic, num_hyps (B) int64), best first by the final fused score; unused rows hold count 0, tokens -1 and scores
+    -inf.  The device tables are packed and copied once per (lm, vocab, delim_token, skip_ids); after that nothing
+    synchronises with the host."""
+    if isinstance(logits, torch.Tensor) and logits.dtype in (torch.bfloat16, torch.float16):
+        logits = logits.float()
+    x = ops._req(logits, "logits")
+    if x.dim() != 3:
+        raise ValueError(f"logits: expected (B,T,V), got {tuple(x.shape)}")
+    B, T, V = x.shape
+    if len(vocab) != V:
+        raise ValueError(f"vocab has {len(vocab)} tokens, the logits {V}")
+    if lengths is not None:
+        lengths = ops._req(lengths, "lengths", torch.int64)
+    tables = as_language_model(lm).device_tables(vocab, delim_token, skip_ids, x.device)
+    lib = _lib.load()
+    ws_bytes = lib.cfm_ctc_beam_lm_workspace_bytes(B, T, int(beam_width), int(max_candidates))
+    workspace = torch.empty(max(int(ws_bytes), 1), dtype=torch.uint8, device=x.device)
+    tokens = torch.empty(B, n_best, T, dtype=torch.int64, device=x.device)
+    counts = torch.empty(B, n_best, dtype=torch.int64, device=x.device)
+    scores = torch.empty(B, n_best, dtype=torch.float32, device=x.device)
+    am_scores = torch.empty(B, n_best, dtype=torch.float32, device=x.device)
+    num_hyps = torch.empty(B, dtype=torch.int64, device=x.device)
+    st = lib.cfm_ctc_beam_lm_decode_f32(x.data_ptr(), ops._p(lengths), B, T, V, int(blank_id), int(beam_width),
+                                        int(max_candidates), float(token_min_logp), float(beam_prune_logp), int(n_best),
+                                        tables.data_ptr(), float(alpha), float(beta), float(unk_score_offset),
+                                        1 if score_boundary else 0, workspace.data_ptr(), int(ws_bytes), tokens.data_ptr(),
+                                        counts.data_ptr(), scores.data_ptr(), am_scores.data_ptr(), num_hyps.data_ptr(),
+                                        ops._stream())
+    _lib.check(st, "cfm_ctc_beam_lm_decode_f32")
+    return tokens, counts, scores, am_scores, num_hyps
+
+
 class BeamCTCDecoder:
     """Drop-in for the reference's KenLanguageModel (processing/lm.py:6-75) without the language model: the same
     `__call__(logits, lengths=None, decode_func=None)`, a str for (T,V) logits and a list of str for (B,T,V).
     The best hypothesis is joined as ''.join(vocab[id]) with `delim_token` read as a space (processor.py:319); ids in
-    `skip_ids` (the unk id, for example) are dropped from the text, not from the search."""
+    `skip_ids` (the unk id, for example) are dropped from the text, not from the search.
+    With `lm` (an NgramLanguageModel or the path of an ARPA file) the search is fused with that word n-gram model, as
+    KenLanguageModel(lm_path, ..., alpha, beta) does: beam_ctc_lm_decode.  Without it the decoder is acoustic only."""
 
     def __init__(self, vocab: Sequence[str], blank_id: int, skip_ids: Sequence[int] = (), delim_token: str = "|",
                  beam_width: int = 190, beam_prune_logp: float = -20.0, token_min_logp: float = -5.0,
-                 max_candidates: int = 16) -> None:
+                 max_candidates: int = 16, *, lm: Union[NgramLanguageModel, str, None] = None, alpha: float = 2.1,
+                 beta: float = 9.2, unk_score_offset: float = -10.0, score_boundary: bool = True) -> None:
         self.vocab = list(vocab)
         self.blank_id = int(blank_id)
         self.skip_ids = frozenset(int(i) for i in skip_ids)
@@ -86,6 +135,11 @@ class BeamCTCDecoder:
         self.beam_prune_logp = beam_prune_logp
         self.token_min_logp = token_min_logp
         self.max_candidates = max_candidates
+        self.lm = None if lm is None else as_language_model(lm)
+        self.alpha = alpha
+        self.beta = beta
+        self.unk_score_offset = unk_score_offset
+        self.score_boundary = score_boundary
 
     def text(self, ids: Sequence[int]) -> str:
         joined = "".join(self.vocab[i] for i in ids if i not in self.skip_ids)
@@ -98,9 +152,17 @@ class BeamCTCDecoder:
             logits = logits.unsqueeze(0)
         if lengths is not None and not (isinstance(lengths, torch.Tensor) and lengths.is_cuda):
             lengths = torch.as_tensor(lengths, dtype=torch.int64).reshape(-1).to(logits.device)   # numpy lengths, as lm.py takes
-        tokens, counts, _, _ = beam_ctc_decode(logits, self.blank_id, lengths, beam_width=self.beam_width, n_best=1,
-                                               token_min_logp=self.token_min_logp, beam_prune_logp=self.beam_prune_logp,
-                                               max_candidates=self.max_candidates)
+        if self.lm is None:
+            tokens, counts, _, _ = beam_ctc_decode(logits, self.blank_id, lengths, beam_width=self.beam_width, n_best=1,
+                                                   token_min_logp=self.token_min_logp, beam_prune_logp=self.beam_prune_logp,
+                                                   max_candidates=self.max_candidates)
+        else:
+            tokens, counts, _, _, _ = beam_ctc_lm_decode(
+                logits, self.blank_id, self.lm, lengths, vocab=self.vocab, delim_token=self.delim_token,
+                skip_ids=tuple(sorted(self.skip_ids)), alpha=self.alpha, beta=self.beta,
+                unk_score_offset=self.unk_score_offset, score_boundary=self.score_boundary, beam_width=self.beam_width,
+                n_best=1, token_min_logp=self.token_min_logp, beam_prune_logp=self.beam_prune_logp,
+                max_candidates=self.max_candidates)
         preds = []
         for row, n in zip(tokens[:, 0].cpu().tolist(), counts[:, 0].cpu().tolist()):
             text = self.text(row[:n])

@@ -487,6 +487,41 @@ int cfm_ctc_beam_decode_f32(const float* logits, const int64_t* lengths_or_null,
                             void* workspace, size_t workspace_bytes, int64_t* tokens, int64_t* counts, float* scores,
                             int64_t* num_hyps, cfm_stream_t stream);
 
+/*      Word n-gram language model for the fused CTC beam search (INTEGRATION.md "Language-model fusion"; conformer_amd/lm.py
+ *      reads ARPA files and drives these).  HOST entries, no HIP call: they pack the model into one blob the caller copies to
+ *      the device once.  order in [1,6]; ngram_counts[order] (ngram_counts[0] == n_words); ngram_words: the n-grams' word
+ *      ids, order 1 first (count * n ids per order), each in [0,n_words), no n-gram twice; ngram_logp / ngram_backoff:
+ *      log10 values per n-gram in the same order (float32; backoff 0 where the file has none).  word_cp_offsets
+ *      (n_words + 1) / word_cp: CSR code points of each word's spelling; every word but bos_id, eos_id and unk_id (all three
+ *      required) enters the character trie.  tok_cp_offsets (V + 1) / tok_cp: CSR code points of each vocabulary token;
+ *      tok_kind (V int32): 0 characters, 1 word delimiter, 2 no characters.  cfm_ngram_lm_pack_bytes returns the blob size
+ *      (0 for arguments out of range), word_cp_total = word_cp_offsets[n_words], tok_cp_total = tok_cp_offsets[V]. */
+size_t cfm_ngram_lm_pack_bytes(int order, const int64_t* ngram_counts, int n_words, int64_t word_cp_total, int V,
+                               int64_t tok_cp_total);
+int cfm_ngram_lm_pack(int order, const int64_t* ngram_counts, const int32_t* ngram_words, const float* ngram_logp,
+                      const float* ngram_backoff, int n_words, const int64_t* word_cp_offsets, const int32_t* word_cp, int bos_id,
+                      int eos_id, int unk_id, int V, const int64_t* tok_cp_offsets, const int32_t* tok_cp, const int32_t* tok_kind,
+                      void* out, size_t out_bytes);
+/*      Device sentence scorer: out[s] = sum of log10 P(w | context) over the words of sentence s (fp64 sums of the float32
+ *      table values), words[offsets[s] .. offsets[s+1]) (int32 word ids; ids outside [0,n_words) are scored as <unk>); with
+ *      boundary != 0 the context starts as <s> and </s> is scored at the end.  lm_tables: the packed blob on the device;
+ *      offsets (n_sentences + 1) int64 on the device. */
+int cfm_ngram_lm_score_f64(const void* lm_tables, const int32_t* words, const int64_t* offsets, int n_sentences, int boundary,
+                           double* out, cfm_stream_t stream);
+/*      CTC prefix beam search fused with the language model: the search of cfm_ctc_beam_decode_f32 (same arguments, limits
+ *      and workspace) ranked by the fused score (INTEGRATION.md "Language-model fusion"): acoustic score + alpha ln10 log10
+ *      P(word) + beta per completed word (+ alpha ln10 unk_score_offset for a word outside the model), + unk_score_offset
+ *      max(1, len/6) while the partial word spells no prefix of a word; at the end the partial word and, with
+ *      score_boundary != 0, </s> are scored and the hypotheses re-ranked.  lm_tables: the packed blob on the device, packed
+ *      for this V.  alpha, beta, unk_score_offset finite.  Outputs as cfm_ctc_beam_decode_f32, with scores the fused score and
+ *      am_scores (B,N) fp32 the acoustic score logaddexp(pb, pnb) of each returned hypothesis (-inf in unused rows). */
+size_t cfm_ctc_beam_lm_workspace_bytes(int B, int T, int W, int K);
+int cfm_ctc_beam_lm_decode_f32(const float* logits, const int64_t* lengths_or_null, int B, int T, int V, int blank_id,
+                               int beam_width, int max_candidates, float token_min_logp, float beam_prune_logp, int n_best,
+                               const void* lm_tables, double alpha, double beta, double unk_score_offset, int score_boundary,
+                               void* workspace, size_t workspace_bytes, int64_t* tokens, int64_t* counts, float* scores,
+                               float* am_scores, int64_t* num_hyps, cfm_stream_t stream);
+
 /* N1 decoder (decoder.py:10-27): LSTM recurrence over a packed batch.  gates_x (B,T,4H) = X.W_ih^T + b_ih + b_hh from
  *      one of the GEMM entries; w_hh (4H,H), gate order i|f|g|o; lengths_or_null: frames per utterance (outputs beyond are
  *      0, as pad_packed_sequence returns); y (B,T,H) <- h_t; c_state (B,H) scratch; save_* (B,T,4H)/(B,T,H) or NULL.

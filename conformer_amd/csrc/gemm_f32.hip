@@ -549,8 +549,142 @@ extern "C" int cfm_gemm_lnfold_f32(int epi, const float* A, const float* ln_stat
     return CFM_ERR_UNSUPPORTED;
 }
 
+// ---- 8-wave tile for the stem's implicit GEMM ----------------------------------------------------------------------
+// conv2 (151392 x 512 x 4608 at B = 32, 28 % of the forward) on gemm_f32_kernel<128, 128> re-gathers h1 once per 128-column
+// tile, and per MFMA a wave issues 1/4 of a fragment read and 1/16 of a staging load + LDS store with their address
+// arithmetic.  This tile is 256 x 256 on 8 waves (2 x 4; a wave owns 128 x 64 = 4 x 2 MFMA tiles, 128 accumulator registers,
+// 226 VGPRs in all; one workgroup per CU, two waves per SIMD): half the fragment reads and a quarter of the staging
+// instructions per MFMA (288 instructions per 128 MFMAs in the K-loop against 295 per 64), and N = 512 is two column tiles,
+// back to back in dispatch order on one XCD (xcd_remap, tn fastest), so the second finds its h1 rows in L2.  Same MFMA,
+// same k order (channel-chunk-major, K-tile 16, one 16-byte LDS read feeding four MFMA steps), same epilogue arithmetic as the
+// 128 x 128 kernel: the output is bit-identical.  The entry point guarantees C % 256 == 0 (so K % 16 == 0: no K guard).
+// Every refill is unconditional (clamped to tile nkt - 1), in the prologue too: behind a branch the wait-counter pass merges
+// in the path without the newer loads and waits for ALL of them (vmcnt(0)) before the LDS stores -- one K-tile ahead
+// instead of two (the 128 x 128 kernel's loop has that vmcnt(0)).
+// Measured and dropped: a half-K-tile stagger of the LDS stores of waves 4-7 (or of the odd waves)
+// against their SIMD partners, and a 256 x 128 tile at two workgroups per CU.
+namespace {
+__global__ __launch_bounds__(512, 2) void conv2_f32_wide_kernel(const GemmArgs g) {
+    constexpr int BM = 256, BN = 256, WN = 4, TM = 4, TN = 2, BK = 16, LDSR = BK + 4;
+    constexpr int LDS_STAGE = 2 * (BM + BN) * LDSR;
+    static_assert(8 * 32 * (32 * TN + 4) <= LDS_STAGE, "the row-major epilogue scratch must fit the staging buffers");
+    __shared__ __attribute__((aligned(16))) float lds[LDS_STAGE];
+    float* As = lds;                    // [2][BM][LDSR]
+    float* Bs = lds + 2 * BM * LDSR;    // [2][BN][LDSR]
+
+    const unsigned tile = xcd_remap(blockIdx.x, g.tiles_m * g.tiles_n);
+    const unsigned tm = tile / g.tiles_n, tn = tile % g.tiles_n;
+    const int64_t m0 = (int64_t)tm * BM;
+    const int n0 = (int)tn * BN;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wr = wave / WN, wc = wave % WN;
+    const int li = lane & 31, hf = lane >> 5;
+
+    constexpr int CPR = BK / 4, RPP = 512 / CPR, PA = BM / RPP, PB = BN / RPP;   // 2 rows of A and 2 of W per thread
+    const int chunk = tid & (CPR - 1), srow = tid / CPR;
+    const float* a_ptr[PA];
+    const float* w_ptr[PB];
+#pragma unroll
+    for (int i = 0; i < PA; ++i) a_ptr[i] = a_row_ptr<1>(g, m0 + srow + RPP * i) + chunk * 4;
+#pragma unroll
+    for (int i = 0; i < PB; ++i) w_ptr[i] = w_row_ptr<EPI_RELU, BN>(g, n0, srow + RPP * i) + chunk * 4;
+
+    const int nkt = g.K / BK;
+    f32x4 ra0[PA], rb0[PB], ra1[PA], rb1[PB];   // tiles t+1 and t+2 in flight
+    auto load_tile = [&](f32x4 (&ra)[PA], f32x4 (&rb)[PB], int kt) __attribute__((always_inline)) {
+        const int c32 = kt / 18, r = kt - 18 * c32, tap = r >> 1;      // channel-chunk-major: see gemm_f32_kernel load_tile
+        const int ci = 32 * c32 + 16 * (r & 1), kf = tap / 3, ktp = tap - 3 * kf;
+        const int64_t aoff = ((int64_t)ktp * g.cF1 + kf) * g.cC + ci;
+        const int k = tap * g.cC + ci;
+#pragma unroll
+        for (int i = 0; i < PA; ++i) ra[i] = *reinterpret_cast<const f32x4*>(a_ptr[i] + aoff);
+#pragma unroll
+        for (int i = 0; i < PB; ++i) rb[i] = *reinterpret_cast<const f32x4*>(w_ptr[i] + k);
+    };
+    auto store_tile = [&](const f32x4 (&ra)[PA], const f32x4 (&rb)[PB], int buf) __attribute__((always_inline)) {
+#pragma unroll
+        for (int i = 0; i < PA; ++i)
+            *reinterpret_cast<f32x4*>(As + (buf * BM + srow + RPP * i) * LDSR + chunk * 4) = ra[i];
+#pragma unroll
+        for (int i = 0; i < PB; ++i)
+            *reinterpret_cast<f32x4*>(Bs + (buf * BN + srow + RPP * i) * LDSR + chunk * 4) = rb[i];
+    };
+
+    f32x16 acc[TM][TN];
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+
+    const int a_row = wr * (BM / 2) + li, b_row = wc * (BN / WN) + li;
+    f32x4 fa0[TM], fb0[TN], fa1[TM], fb1[TN];
+    auto read_frags = [&](f32x4 (&fa)[TM], f32x4 (&fb)[TN], int buf, int c) __attribute__((always_inline)) {
+#pragma unroll
+        for (int t = 0; t < TM; ++t)
+            fa[t] = *reinterpret_cast<const f32x4*>(As + (buf * BM + a_row + 32 * t) * LDSR + 8 * c + 4 * hf);
+#pragma unroll
+        for (int t = 0; t < TN; ++t)
+            fb[t] = *reinterpret_cast<const f32x4*>(Bs + (buf * BN + b_row + 32 * t) * LDSR + 8 * c + 4 * hf);
+    };
+
+    load_tile(ra0, rb0, 0);
+    store_tile(ra0, rb0, 0);
+    load_tile(ra1, rb1, min(1, nkt - 1));
+    load_tile(ra0, rb0, min(2, nkt - 1));
+    __syncthreads();
+    read_frags(fa0, fb0, 0, 0);
+    auto k_step = [&](int kt, f32x4 (&ra)[PA], f32x4 (&rb)[PB]) __attribute__((always_inline)) {   // (ra, rb) holds tile kt+1 on entry
+        const int cur = kt & 1;
+        const bool more = kt + 1 < nkt;
+        read_frags(fa1, fb1, cur, 1);
+        __builtin_amdgcn_sched_barrier(0);
+        GEMM_MFMA_SLICE(fa0, fb0);
+        __builtin_amdgcn_sched_barrier(0);
+        if (more) store_tile(ra, rb, cur ^ 1);
+        load_tile(ra, rb, min(kt + 3, nkt - 1));
+        __syncthreads();
+        if (more) read_frags(fa0, fb0, cur ^ 1, 0);
+        __builtin_amdgcn_sched_barrier(0);
+        GEMM_MFMA_SLICE(fa1, fb1);
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    int kt = 0;
+    for (; kt + 1 < nkt; kt += 2) {
+        k_step(kt, ra1, rb1);
+        k_step(kt + 1, ra0, rb0);
+    }
+    if (kt < nkt) k_step(kt, ra1, rb1);
+
+    __syncthreads();                                       // every wave is done reading the staging buffers
+    gemm_epilogue_rows<BM, BN, EPI_RELU, TM, TN, 2, false, EPF_INFER, WN>(g, acc, m0, n0, wr, wc, lane,
+                                                                         lds + wave * 32 * (32 * TN + 4));
+}
+
+int launch_conv2_wide(GemmArgs g, hipStream_t s) {
+    g.tiles_m = (unsigned)((g.M + 255) / 256);
+    g.tiles_n = (unsigned)(g.N / 256);
+    hipLaunchKernelGGL(conv2_f32_wide_kernel, dim3(g.tiles_m * g.tiles_n), dim3(512), 0, s, g);
+    return cfm_launch_status();
+}
+
+int device_cus() {
+    static int cus = 0;
+    if (cus == 0) {
+        int dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+            cus <= 0)
+            cus = 256;
+    }
+    return cus;
+}
+}  // namespace
+
 static int g_conv2_bk = 16;
 static int g_conv2_kperm = 1;
+static int g_conv2_tile = 0;
 // Implicit-GEMM second stem convolution (3x3, stride 2, channel-last input, packed weight).  Declared in the stem
 // section of the ABI; lives here to share the kernel templates.
 extern "C" int cfm_subsample_conv2_relu_f32(const float* h1, const float* w2p, const float* b2, float* h2, int B,
@@ -564,15 +698,43 @@ extern "C" int cfm_subsample_conv2_relu_f32(const float* h1, const float* w2p, c
     g.A = h1; g.W = w2p; g.bias = b2; g.C = h2;
     g.M = (int64_t)B * g.cT2 * g.cF2; g.N = C; g.K = 9 * C; g.lda = 0; g.ldc = C; g.alpha = 1.f;
     g.conv_kperm = g_conv2_kperm && C % 32 == 0;
-    if (g_conv2_bk == 32 && C % 32 == 0) return launch<EPI_RELU, true, EPF_INFER, 32>(g, static_cast<hipStream_t>(stream));
-    return launch<EPI_RELU, true, EPF_INFER>(g, static_cast<hipStream_t>(stream));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (g_conv2_bk == 32 && C % 32 == 0) return launch<EPI_RELU, true, EPF_INFER, 32>(g, s);
+    if (g_conv2_bk == 16 && g.conv_kperm && g_conv2_tile != 1 && C % 256 == 0) {
+        if (g_conv2_tile == 2) return launch_conv2_wide(g, s);
+        // By shape: the 256x256 tile once it fills the chip about twice (two rounds of one workgroup per CU).  A partial last
+        // round would run the largest tiles at part occupancy (B = 32: 1184 tiles = 4.6 rounds), so the tile takes the leading
+        // utterances that fill whole rounds and the 128x128 kernel the rest (its workgroups are a quarter of the size, three
+        // per CU).  Every output row is computed by one kernel or the other, the same way: the result does not change.
+        const int64_t per_b = (int64_t)g.cT2 * g.cF2, cols = C / 256, round = device_cus();
+        auto tiles = [&](int64_t b) { return (b * per_b + 255) / 256 * cols; };
+        if (tiles(B) >= 2 * round) {
+            const int64_t whole = tiles(B) / round * round;
+            int64_t b1 = B;
+            while (b1 > 0 && tiles(b1) > whole) --b1;
+            if (b1 > 0) {
+                GemmArgs gw = g;
+                gw.M = b1 * per_b;
+                int st = launch_conv2_wide(gw, s);
+                if (st || b1 == B) return st;
+                g.A = h1 + b1 * (int64_t)T1 * F1 * C;
+                g.C = h2 + b1 * per_b * C;
+                g.M = (B - b1) * per_b;
+            }
+        }
+    }
+    return launch<EPI_RELU, true, EPF_INFER>(g, s);
 }
 
-// diagnostics (tools/conv2_bk_ab.py): K-tile of the stem's implicit GEMM: 16 (default) | 32; returns the previous setting
+// diagnostics (tools/conv2_bk_ab.py, tools/conv2_f32_tile_ab.py): the stem's implicit GEMM.  16 (default) | 32: K-tile;
+// 0 / 1: K walked in storage order / channel-chunk-major (default); 100: tile chosen by shape (default) | 101: the 128x128
+// tile only | 102: the 256x256 tile for all rows wherever C % 256 == 0 (K-tile 16, channel-chunk-major).  Returns the
+// previous K-tile.
 extern "C" int cfm_debug_set_conv2_bk(int bk) {
     const int prev = g_conv2_bk;
     if (bk == 16 || bk == 32) g_conv2_bk = bk;
-    if (bk == 0 || bk == 1) g_conv2_kperm = bk;            // 0 / 1: K walked in storage order / channel-chunk-major (default)
+    if (bk == 0 || bk == 1) g_conv2_kperm = bk;
+    if (bk >= 100 && bk <= 102) g_conv2_tile = bk - 100;
     return prev;
 }
 

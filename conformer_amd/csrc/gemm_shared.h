@@ -397,14 +397,15 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, const f32x16 (&
 // CLS: the rows are transposed-conv class rows (CONV == 2) and are scattered to their dh1 positions.  A TEMPLATE flag: as a run-time
 // test of g.pA the (skipped) 64-bit divisions were still unrolled into every kernel's epilogue -- 60 % more code in the 256x256
 // kernels, which ran 12-20 % slower from instruction-cache misses alone.
-template <int BM, int BN, int EPI, int TM, int TN, int WM = 2, bool CLS = false, int F = 0>
+// WM x WN waves: a wave owns rows wr * BM / WM + [0, 32 TM) and columns wc * BN / WN + [0, 32 TN).
+template <int BM, int BN, int EPI, int TM, int TN, int WM = 2, bool CLS = false, int F = 0, int WN = 2>
 __device__ __forceinline__ void gemm_epilogue_rows(const GemmArgs& g, const f32x16 (&acc)[TM][TN], int64_t m0, int n0,
                                                    int wr, int wc, int lane, float* scratch, const float* rowstats = nullptr) {
     static_assert(EPI != EPI_GLU || TN == 2, "GLU: n-tile 0 = values, n-tile 1 = gates of the same 32 output columns");
     // row pitch, lanes per row, rows per wave-instruction (GLU: a row of the LDS tile is 32 values | 32 gates -> 32 output columns)
     constexpr int P = 32 * TN + 4, LPR = EPI == EPI_GLU ? 8 : 8 * TN, RPI = 64 / LPR;
     const int li = lane & 31, hf = lane >> 5;
-    if constexpr (WM == 2) {                                          // (8-wave tiles: the launcher guarantees vec_ok)
+    if constexpr (WM == 2 && WN == 2) {                               // (8-wave tiles: the launcher guarantees vec_ok)
         if (!gemm_epilogue_vec_ok(g, EPI)) {                          // (kernel-uniform)
             gemm_epilogue<BM, BN, EPI, TM, TN, F>(g, acc, m0, n0, wr, wc, li, hf);
             return;
@@ -443,7 +444,7 @@ __device__ __forceinline__ void gemm_epilogue_rows(const GemmArgs& g, const f32x
         if (wide) {                                                    // (kernel-uniform)
             constexpr int LPR8 = 4 * TN, RPI8 = 64 / LPR8, NIT8 = 32 / RPI8;
             const int rsub8 = lane / LPR8, c8 = (lane % LPR8) * 8;
-            const int col8 = n0 + wc * (BN / 2) + c8;
+            const int col8 = n0 + wc * (BN / WN) + c8;
             auto row8 = [&](int mt, int it) { return m0 + wr * (BM / WM) + mt * 32 + it * RPI8 + rsub8; };
             EpiOps b0, b1;
             gemm_epilogue_fetch_bias<EPI>(g, col8, b0);
@@ -492,7 +493,7 @@ __device__ __forceinline__ void gemm_epilogue_rows(const GemmArgs& g, const f32x
 
     // ---- 4 columns per lane
     const int rsub = lane / LPR, c4 = (lane % LPR) * 4;
-    const int col = n0 + (EPI == EPI_GLU ? wc * 32 : wc * (BN / 2)) + c4;
+    const int col = n0 + (EPI == EPI_GLU ? wc * 32 : wc * (BN / WN)) + c4;
     constexpr int NIT = 32 / RPI;
     auto row_of = [&](int mt, int it) { return m0 + wr * (BM / WM) + mt * 32 + it * RPI + rsub; };
     // Every load is issued ahead of the stores it would otherwise queue behind (see EpiOps): the bias once (a lane's columns

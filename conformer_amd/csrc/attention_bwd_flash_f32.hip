@@ -37,7 +37,7 @@ struct AttnBwdArgs {
     float* dq; float* dk; float* dv; int64_t ldg;
     float* dpos; int64_t lddp; float* du; float* dvb;
     int B, T, H, dh; float scale; float drop_p; unsigned long long drop_seed;
-    int prec;                             // CFM_PREC_*: under autocast the SCORE operands (q+u, q+v, K, table rows) and V are rounded to the
+    int prec;                             // CFM_PREC_*: under autocast the SCORE operands (q+u, q+v, K, table rows), V and dO are rounded to the
                                           // forward's 16-bit type, so the recomputed P matches the log-sum-exp the 16-bit forward kernel saved
     unsigned long long* trace;            // diagnostics: s_memrealtime stamps of wave 0 of workgroup (0,0), 16 per query tile
 };
@@ -550,8 +550,9 @@ static unsigned long long* g_atb_trace = nullptr;     // diagnostics only, set b
 // context `ctx` (B,T,H*dh; row stride ldo), its log-sum-exp `lse` (B,H,T) and the context gradient `dctx` (layout of ctx).
 // dq / dk / dv: row stride ldg (e.g. the three column slots of one (B*T, 3d) buffer).  dq, dpos (2T-1 rows, stride lddp),
 // du and dvbias (H*dh each) are ACCUMULATED INTO with fp32 atomics: the caller zero-fills them; dk / dv are written.
-// prec: CFM_PREC_F32, or the 16-bit type the forward ran in (cfm_relpos_attention_mfma16_f32): q+u, q+v, K, V and the table
-// rows are then rounded to it before the score / dW recompute (fp32 MFMAs throughout; everything else stays unrounded).
+// prec: CFM_PREC_F32, or the 16-bit type the forward ran in (cfm_relpos_attention_mfma16_f32): q+u, q+v, K, V, the table
+// rows and dO are then rounded to it where they are staged (score / dW recompute, D_i, dV, dK, d(Q+v), dpos); the K of
+// d(Q+u) = dS.K, P, W and dS stay unrounded (fp32 MFMAs throughout).
 extern "C" int cfm_relpos_attention_bwd_f32(const float* q, const float* k, const float* v, int64_t ld, const float* pos,
                                             int64_t ldp, const float* u, const float* vbias,
                                             const int64_t* lengths_or_null, const float* ctx, const float* dctx, int64_t ldo,

@@ -1101,6 +1101,13 @@ def relpos_attention_train(qkv, pos, u, v, lengths, n_heads, drop_p: float = 0.0
     B, T, d3 = qkv.shape
     d = d3 // 3
     dh = d // n_heads
+    if not (isinstance(pos, torch.Tensor) and pos.is_cuda and pos.dtype == torch.float32 and pos.dim() == 2
+            and pos.stride(1) == 1 and pos.shape == (2 * T - 1, d)):      # (any row stride: training passes a column slice)
+        raise _lib.ConformerHipError(f"pos: expected a ({2 * T - 1},{d}) fp32 HIP tensor with unit column stride")
+    if lengths is not None:
+        lengths = _req(lengths, "lengths", torch.int64)
+        if lengths.numel() != B:
+            raise _lib.ConformerHipError(f"lengths: expected {B} entries, got {lengths.numel()}")
     ctx = torch.empty(B, T, d, device=qkv.device, dtype=torch.float32)
     lse = torch.empty(B, n_heads, T, device=qkv.device, dtype=torch.float32)
     base = qkv.data_ptr()
@@ -1131,6 +1138,14 @@ def relpos_attention_bwd(qkv, pos, u, v, lengths, n_heads, ctx, lse, dctx, drop_
     B, T, d3 = qkv.shape
     d = d3 // 3
     dh = d // n_heads
+    if pos.shape != (2 * T - 1, d) or ctx.shape != (B, T, d) or dctx.shape != (B, T, d) or lse.shape != (B, n_heads, T):
+        raise _lib.ConformerHipError(f"relpos_attention_bwd: qkv{tuple(qkv.shape)} with {n_heads} heads needs pos ({2 * T - 1},{d}), "
+                                     f"ctx / dctx ({B},{T},{d}) and lse ({B},{n_heads},{T}); got pos{tuple(pos.shape)}, "
+                                     f"ctx{tuple(ctx.shape)}, dctx{tuple(dctx.shape)}, lse{tuple(lse.shape)}")
+    if lengths is not None:
+        lengths = _req(lengths, "lengths", torch.int64)
+        if lengths.numel() != B:
+            raise _lib.ConformerHipError(f"lengths: expected {B} entries, got {lengths.numel()}")
     ctx, dctx = ctx.contiguous(), dctx.contiguous()
     P = 2 * T - 1
     dqkv, dpos, du, dvb = _zeros_split(qkv.device, qkv.dtype, (B, T, d3), (P, d), (n_heads, dh), (n_heads, dh))

@@ -50,13 +50,16 @@ def rnd(*shape, seed=0):
 
 
 @pytest.mark.parametrize("amp", [None, torch.bfloat16])
-def test_attention_forward_backward_next_to_poison(dev, amp):
+@pytest.mark.parametrize("B,T,H,dh,lengths", [
+    (3, 49, 4, 36, [49, 33, 7]),                    # T not a multiple of 4 or 32; Conformer-S head size
+    (2, 257, 2, 64, [257, 100]),                    # a last key block and query tile of one row: clamped zero-valued atomics
+])
+def test_attention_forward_backward_next_to_poison(dev, amp, B, T, H, dh, lengths):
     from conformer_amd import ops
-    B, T, H, dh = 3, 49, 4, 36                      # T not a multiple of 4 or 32; Conformer-S head size
     d = H * dh
     qkv, pos = rnd(B, T, 3 * d, seed=1) * 0.5, rnd(2 * T - 1, d, seed=2) * 0.5
     u, v, dctx = rnd(H, dh, seed=3) * 0.3, rnd(H, dh, seed=4) * 0.3, rnd(B, T, d, seed=5)
-    L = torch.tensor([T, 33, 7])
+    L = torch.tensor(lengths)
     P = Poisoned(dev)
     G = lambda t: t.to(dev)
 

@@ -146,6 +146,9 @@ SIGNATURES = {
     "cfm_pack_conv2_weight_f32": (c_int, [_P, _P, _I, _P]),
     "cfm_subsample_conv2_relu_f32": (c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "cfm_pack_linear_weight_f32": (c_int, [_P, _P, _I, _I, _I, _P]),
+    "cfm_conv2_wino_plane_elems": (c_int64, [_I, _I, _I, _I]),
+    "cfm_pack_conv2_wino_weight_f32": (c_int, [_P, _P, _I, _P]),
+    "cfm_subsample_conv2_wino_relu_f32": (c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
 }
 
 

@@ -115,7 +115,10 @@ class ConvolutionSubsampling(nn.Module):
                                           "built (the reference never needs it: the input is data)")
             return ag.SubsampleStemFn.apply(x, self.conv_1.weight, self.conv_1.bias, self.conv_2.weight, self.conv_2.bias)
         w2p = self._packs.get("w2p", (self.conv_2.weight,), lambda: ops.pack_conv2_weight(self.conv_2.weight))
-        return ops.subsample_stem(x, self.conv_1.weight, self.conv_1.bias, w2p, self.conv_2.bias)
+        w2w = None
+        if ops.conv2_winograd_ok(self.conv_2.weight.shape[0]):
+            w2w = self._packs.get("w2w", (self.conv_2.weight,), lambda: ops.pack_conv2_wino_weight(self.conv_2.weight))
+        return ops.subsample_stem(x, self.conv_1.weight, self.conv_1.bias, w2p, self.conv_2.bias, w2w=w2w)
 
     def forward(self, x: torch.Tensor, lengths: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
         """Reference-compatible output layout (feature index c*F' + f); off the hot path (one permute copy)."""

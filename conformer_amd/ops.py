@@ -707,6 +707,34 @@ def pack_conv2_weight(w2: torch.Tensor) -> torch.Tensor:
     return out
 
 
+_CONV2_WINOGRAD = __import__("os").environ.get("CONFORMER_AMD_CONV2_WINOGRAD", "1") == "1"
+
+
+def set_conv2_winograd(on: bool) -> bool:
+    """Enable / disable the polyphase Winograd F(2x2,2x2) form of the stem's conv2 (fp32 inference, C % 256 == 0; csrc/
+    conv2_wino_f32.hip): 25 channel contractions per 2x2 output block instead of 36.  Default ON (CONFORMER_AMD_CONV2_WINOGRAD=0
+    disables); the direct implicit GEMM stays for training, autocast and the split-plane modes.  Returns the previous setting."""
+    global _CONV2_WINOGRAD
+    prev, _CONV2_WINOGRAD = _CONV2_WINOGRAD, bool(on)
+    return prev
+
+
+def conv2_winograd_ok(C: int) -> bool:
+    """Whether the inference stem takes the Winograd conv2.  Depends on the channel count and the precision mode only --
+    never on B, T or batch fill, so every utterance's h2 is computed the same way whatever batch it is in."""
+    return bool(_CONV2_WINOGRAD and C % 256 == 0 and not mfma16_prec() and not _fp32_planes)
+
+
+def pack_conv2_wino_weight(w2: torch.Tensor) -> torch.Tensor:
+    """w2 (C, C, 3, 3) -> the 25 transformed (C, C) matrices of the Winograd conv2, in the order its GEMMs walk them."""
+    w2 = _req(w2, "conv_2.weight")
+    C = w2.shape[0]
+    out = torch.empty(25 * C * C, device=w2.device, dtype=torch.float32)
+    _lib.check(_lib.load().cfm_pack_conv2_wino_weight_f32(w2.data_ptr(), out.data_ptr(), C, _stream()),
+               "cfm_pack_conv2_wino_weight_f32")
+    return out
+
+
 def pack_linear_weight(wl: torch.Tensor, C: int, F2: int) -> torch.Tensor:
     wl = _req(wl, "linear.weight")
     out = _f32_like(wl)
@@ -715,8 +743,9 @@ def pack_linear_weight(wl: torch.Tensor, C: int, F2: int) -> torch.Tensor:
     return out
 
 
-def subsample_stem(x: torch.Tensor, w1, b1, w2p, b2) -> torch.Tensor:
-    """x (B,F,T) -> h2 (B, T2, F2*C) channel-last flattening [f][c] (pair with pack_linear_weight)."""
+def subsample_stem(x: torch.Tensor, w1, b1, w2p, b2, w2w=None) -> torch.Tensor:
+    """x (B,F,T) -> h2 (B, T2, F2*C) channel-last flattening [f][c] (pair with pack_linear_weight).  w2w: the Winograd pack
+    (pack_conv2_wino_weight) when conv2_winograd_ok(C), which then computes conv2; w2p is used otherwise."""
     x = _req(x, "x"); w1 = _req(w1, "conv_1.weight"); b1 = _req(b1, "conv_1.bias")
     w2p = _req(w2p, "packed conv_2.weight"); b2 = _req(b2, "conv_2.bias")
     B, F, T = x.shape
@@ -735,6 +764,12 @@ def subsample_stem(x: torch.Tensor, w1, b1, w2p, b2) -> torch.Tensor:
         _lib.check(lib.cfm_subsample_conv1_relu_f32(x.data_ptr(), w1.data_ptr(), b1.data_ptr(), h1.data_ptr(), B, F, T, C,
                                                     _stream()), "cfm_subsample_conv1_relu_f32")
         h2 = torch.empty(B, T2, F2 * C, device=x.device, dtype=torch.float32)
+        if w2w is not None and conv2_winograd_ok(C):
+            planes = torch.empty(int(lib.cfm_conv2_wino_plane_elems(B, F1, T1, C)), device=x.device, dtype=torch.float32)
+            _lib.check(lib.cfm_subsample_conv2_wino_relu_f32(h1.data_ptr(), _req(w2w, "Winograd conv_2.weight").data_ptr(),
+                                                             b2.data_ptr(), planes.data_ptr(), h2.data_ptr(), B, F1, T1, C,
+                                                             _stream()), "cfm_subsample_conv2_wino_relu_f32")
+            return h2
     _conv2_relu(lib, h1, w2p, b2, h2, B, F1, T1, C)
     return h2
 

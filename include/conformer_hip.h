@@ -185,6 +185,14 @@ int cfm_pack_conv2_weight_f32(const float* w2, float* w2p, int C, cfm_stream_t s
 int cfm_subsample_conv2_relu_f32(const float* h1, const float* w2p, const float* b2, float* h2,
                                  int B, int F1, int T1, int C, cfm_stream_t stream);
 int cfm_pack_linear_weight_f32(const float* wl, float* wlp, int d_out, int C, int F2, cfm_stream_t stream);
+/* conv2 as polyphase Winograd F(2x2,2x2) (fp32 inference, C % 256 == 0): nine pattern GEMMs over 2x2 output blocks write
+ * planes (cfm_conv2_wino_plane_elems floats of scratch), a combine kernel writes h2 = relu(b2 + sum of four planes) at the
+ * valid (t2, f2) only.  wwp: cfm_pack_conv2_wino_weight_f32(w2 (C_out, C_in, 3, 3)), 25 C*C floats.  Same result as
+ * cfm_subsample_conv2_relu_f32 up to fp32 rounding (not bitwise). */
+int64_t cfm_conv2_wino_plane_elems(int B, int F1, int T1, int C);
+int cfm_pack_conv2_wino_weight_f32(const float* w2, float* wwp, int C, cfm_stream_t stream);
+int cfm_subsample_conv2_wino_relu_f32(const float* h1, const float* wwp, const float* b2, float* planes, float* h2,
+                                      int B, int F1, int T1, int C, cfm_stream_t stream);
 
 /* ---- 16-bit-MFMA GEMMs with fp32 storage: the arithmetic torch.autocast gives nn.Linear / Conv (train.py:6,232 runs the
  *      model under torch.cuda.amp.autocast = fp16; bf16 is the MI355X-preferred variant).  Operands

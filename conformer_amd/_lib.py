@@ -111,6 +111,13 @@ SIGNATURES = {
     "cfm_ctc_beam_lm_workspace_bytes": (ctypes.c_size_t, [_I, _I, _I, _I]),
     "cfm_ctc_beam_lm_decode_f32": (c_int, [_P, _P, _I, _I, _I, _I, _I, _I, _F, _F, _I, _P, ctypes.c_double, ctypes.c_double,
                                            ctypes.c_double, _I, _P, ctypes.c_size_t, _P, _P, _P, _P, _P, _P]),
+    "cfm_hotword_pack_bytes": (ctypes.c_size_t, [_I, _L, _I, _L, _I, _L]),
+    "cfm_hotword_pack": (c_int, [_I, _P, _P, _I, _P, _P, _I, _P, _P, _P, _P, ctypes.c_size_t]),
+    "cfm_hotword_count": (c_int, [_P, _P, _P, _I, ctypes.c_double, _P, _P, _P]),
+    "cfm_ctc_beam_hw_workspace_bytes": (ctypes.c_size_t, [_I, _I, _I, _I]),
+    "cfm_ctc_beam_hw_decode_f32": (c_int, [_P, _P, _I, _I, _I, _I, _I, _I, _F, _F, _I, _P, ctypes.c_double, ctypes.c_double,
+                                           ctypes.c_double, _I, _P, ctypes.c_double, _P, ctypes.c_size_t, _P, _P, _P, _P, _P,
+                                           _P]),
     "cfm_lstm_fwd_f32": (c_int, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "cfm_lstm_fwd_frag_f32": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "cfm_lstm_bwd_frag_f32": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),

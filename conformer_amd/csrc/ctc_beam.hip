@@ -28,8 +28,15 @@
 // trie node each extension reaches is kept in LDS (x_node) for the ranking passes and the next frame's state.  After the
 // last frame the hypotheses gain their end-of-utterance terms and are re-ranked by the final F.  beam_search_kernel<false>
 // is the LM-free search, unchanged.
+//
+// Hotword boosting (beam_search_kernel<LM, true>, INTEGRATION.md "Hotword boosting"), with or without the LM: F gains
+// weight * count(words) and the partial-word term R(p), the hotword bonus Q(p) where p is a prefix of a hotword unigram and
+// otherwise the LM penalty P(p) (0 without the LM).  Each hypothesis also carries the hotword-trie node of p, its decided
+// matches, its window of undecided words and its count (the window rule of hotword.h); the node each extension reaches is
+// kept in LDS (x_hn), and the window step a delimiter takes is done once per thread (x_hc, x_hd, x_hwl, x_hw).
 #include <float.h>
 #include "cfm_common.h"
+#include "hotword.h"
 #include "ngram_lm.h"
 
 namespace {
@@ -42,12 +49,20 @@ constexpr int LM_TOK_CP = 8;             // code points of a candidate token sta
 constexpr int LM_WALK = 8;               // trie walks a thread advances together
 constexpr double LN10 = 2.302585092994045684;
 
-template <bool LM> struct LmParams {};
-template <> struct LmParams<true> {
+template <bool LM, bool HW = false> struct LmParams {};
+template <> struct LmParams<true, false> {
     const void* tables;                  // cfm_ngram_lm_pack blob on the device
     double alpha, beta, unk_offset;
     int score_boundary;
     float* am_scores;
+};
+template <bool LM> struct LmParams<LM, true> {
+    const void* tables;                  // cfm_ngram_lm_pack blob on the device (LM only)
+    double alpha, beta, unk_offset;
+    int score_boundary;
+    float* am_scores;
+    const void* hw_tables;               // cfm_hotword_pack blob on the device
+    double hw_weight;
 };
 
 // P(p): 0 for an empty partial word or one that spells a prefix of some unigram (node >= 0)
@@ -169,11 +184,11 @@ __device__ bool same_sequence(const int2* nd, int a, int b, int len) {
 
 typedef unsigned __int128 u128;
 
-template <bool LM>
+template <bool LM, bool HW>
 __global__ __launch_bounds__(BEAM_MAX_W) void beam_search_kernel(
         const float* __restrict__ logits, const int64_t* __restrict__ lengths, BeamWs ws, int T, int V, int blank, int W,
         int K, double prune, int N, int64_t* __restrict__ tokens, int64_t* __restrict__ counts, float* __restrict__ scores,
-        int64_t* __restrict__ num_hyps, LmParams<LM> lp) {
+        int64_t* __restrict__ num_hyps, LmParams<LM, HW> lp) {
     // hypotheses in rank order, double-buffered across frames
     __shared__ double h_pb[2][BEAM_MAX_W], h_pnb[2][BEAM_MAX_W], h_s[2][BEAM_MAX_W];
     __shared__ unsigned long long h_hash[2][BEAM_MAX_W];
@@ -195,10 +210,15 @@ __global__ __launch_bounds__(BEAM_MAX_W) void beam_search_kernel(
     __shared__ double l_pb[BEAM_MAX_W], l_pnb[BEAM_MAX_W], l_s[BEAM_MAX_W];
     // language-model state of the hypotheses (double-buffered like the rest), this frame's candidate tokens, and per
     // thread: the word term its delimiters add, the word id they push, the trie node each candidate reaches
-    constexpr int LW = LM ? BEAM_MAX_W : 1, LK = LM ? BEAM_MAX_K : 1;
+    constexpr int LW = LM ? BEAM_MAX_W : 1, LK = LM ? BEAM_MAX_K : 1, TK = (LM || HW) ? BEAM_MAX_K : 1;
     __shared__ double h_lm[2][LW], x_term[LW];
     __shared__ int h_tn[2][LW], h_pl[2][LW], h_ctx[2][LM_CTX][LW], x_wid[LW], x_node[LK][LW];
-    __shared__ int c_kind[LK], c_len[LK], c_off[LK], c_cp[LK][LM_TOK_CP];
+    __shared__ int c_kind[TK], c_len[TK], c_off[TK], c_cp[TK][LM_TOK_CP];
+    // hotword state of the hypotheses (trie node of p, decided matches, window length, count, window), per thread the state
+    // after the word its delimiters complete, and the hotword-trie node each candidate reaches
+    constexpr int HWW = HW ? BEAM_MAX_W : 1, HK = HW ? BEAM_MAX_K : 1;
+    __shared__ int h_hn[2][HWW], h_hd[2][HWW], h_hwl[2][HWW], h_hc[2][HWW], x_hd[HWW], x_hwl[HWW], x_hc[HWW], x_hn[HK][HWW];
+    __shared__ short h_hw[2][HW_WIN][HWW], x_hw[HW_WIN][HWW];
 
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int n = beam_frames(lengths, b, T);
@@ -206,6 +226,13 @@ __global__ __launch_bounds__(BEAM_MAX_W) void beam_search_kernel(
     const unsigned V1 = (unsigned)V + 1u;
     [[maybe_unused]] LmView lmv;
     if constexpr (LM) lmv = lm_view(lp.tables);
+    [[maybe_unused]] HwView hwv;
+    [[maybe_unused]] const int32_t* tok_cp = nullptr;      // code points of the tokens (LM blob, else hotword blob)
+    if constexpr (HW) {
+        hwv = hw_view(lp.hw_tables);
+        if constexpr (LM) tok_cp = lmv.tok_cp;
+        else tok_cp = hwv.tok_cp;
+    }
 
     for (int i = tid; i < BEAM_TABLE; i += BEAM_MAX_W) table[i] = -1;
     if (tid == 0) {
@@ -216,6 +243,10 @@ __global__ __launch_bounds__(BEAM_MAX_W) void beam_search_kernel(
             h_lm[0][0] = 0.0; h_tn[0][0] = 0; h_pl[0][0] = 0;
             for (int i = 0; i < LM_CTX; ++i) h_ctx[0][i][0] = -1;
             if (lp.score_boundary) h_ctx[0][LM_CTX - 1][0] = lmv.bos;
+        }
+        if constexpr (HW) {
+            h_hn[0][0] = 0; h_hd[0][0] = 0; h_hwl[0][0] = 0; h_hc[0][0] = 0;
+            for (int u = 0; u < HW_WIN; ++u) h_hw[0][u][0] = -1;
         }
     }
     __syncthreads();
@@ -238,6 +269,15 @@ __global__ __launch_bounds__(BEAM_MAX_W) void beam_search_kernel(
                 c_kind[tid] = kind; c_off[tid] = o; c_len[tid] = l;
                 for (int q = 0; q < min(l, LM_TOK_CP); ++q) c_cp[tid][q] = lmv.tok_cp[o + q];
             }
+        } else if constexpr (HW) {
+            if (tid < nc) {
+                const int c = ws.ctok[row * K + tid];
+                int kind = LM_TOK_SKIP, o = 0, l = 0;
+                if (c < hwv.V) { kind = hwv.tok_kind[c]; o = hwv.tok_off[c]; l = hwv.tok_off[c + 1] - o; }
+                if (kind != LM_TOK_CHARS) l = 0;
+                c_kind[tid] = kind; c_off[tid] = o; c_len[tid] = l;
+                for (int q = 0; q < min(l, LM_TOK_CP); ++q) c_cp[tid][q] = hwv.tok_cp[o + q];
+            }
         }
         hist[0][tid] = 0u;
         if (tid == 0) n_kept = 0;
@@ -249,6 +289,9 @@ __global__ __launch_bounds__(BEAM_MAX_W) void beam_search_kernel(
         [[maybe_unused]] double lm = 0, lmp = 0, term = 0;
         [[maybe_unused]] int tn = 0, pl = 0;
         [[maybe_unused]] int ctx[LM_CTX];
+        // hotword state of the own hypothesis: trie node of p, count; weight * count, and after a delimiter's word
+        [[maybe_unused]] int hn = 0, hc = 0;
+        [[maybe_unused]] double hwc = 0, xhwc = 0;
         if (own) {
             pb = h_pb[cur][tid]; pnb = h_pnb[cur][tid]; s = h_s[cur][tid];
             last = h_last[cur][tid]; len = h_len[cur][tid]; node = h_node[cur][tid]; hash = h_hash[cur][tid];
@@ -256,6 +299,14 @@ __global__ __launch_bounds__(BEAM_MAX_W) void beam_search_kernel(
                 lm = h_lm[cur][tid]; tn = h_tn[cur][tid]; pl = h_pl[cur][tid];
                 for (int i = 0; i < LM_CTX; ++i) ctx[i] = h_ctx[cur][i][tid];
                 lmp = lm + lm_pen(tn, pl, lp.unk_offset);
+            }
+            if constexpr (HW) {
+                hn = h_hn[cur][tid]; hc = h_hc[cur][tid];
+                hwc = lp.hw_weight * (double)hc;
+                double r;
+                if constexpr (LM) r = hn >= 0 ? hw_bonus(hwv, hn, lp.hw_weight) : lm_pen(tn, pl, lp.unk_offset);
+                else r = hw_bonus(hwv, hn, lp.hw_weight);
+                lmp = (lm + hwc) + r;
             }
             st_pb = s + ((double)lrow[blank] - lse);
             st_pnb = last >= 0 ? pnb + ((double)lrow[last] - lse) : -INFINITY;
@@ -334,11 +385,79 @@ __global__ __launch_bounds__(BEAM_MAX_W) void beam_search_kernel(
                         if (k0 + u < nc) x_node[k0 + u][tid] = wn[u];
                 }
             }
+            if constexpr (HW) {
+                // the window step of the word a delimiter completes (the same for every delimiter candidate)
+                bool delim = false;
+                for (int k = 0; k < nc; ++k) delim |= !((mask >> k) & 1u) && c_kind[k] == LM_TOK_DELIM;
+                if (delim && hn != 0) {
+                    int ids[HW_WIN];
+#pragma unroll
+                    for (int u = 0; u < HW_WIN; ++u) ids[u] = h_hw[cur][u][tid];
+                    int wl = h_hwl[cur][tid], dec = h_hd[cur][tid];
+                    const int c = hw_push(hwv, ids, wl, dec, hn > 0 ? hwv.cnode[hn].x : -1);
+                    x_hc[tid] = c; x_hd[tid] = dec; x_hwl[tid] = wl;
+#pragma unroll
+                    for (int u = 0; u < HW_WIN; ++u) x_hw[u][tid] = (short)ids[u];
+                    xhwc = lp.hw_weight * (double)c;
+                }
+                // hotword-trie walks of the character candidates, LM_WALK at a time
+                auto cp_at = [&](int k, int q) { return q < LM_TOK_CP ? c_cp[k][q] : tok_cp[c_off[k] + q]; };
+                for (int k0 = 0; k0 < nc; k0 += LM_WALK) {
+                    int wn[LM_WALK], wq[LM_WALK];
+                    unsigned wsl[LM_WALK];
+                    bool wa[LM_WALK];
+#pragma unroll
+                    for (int u = 0; u < LM_WALK; ++u) {
+                        const int k = k0 + u;
+                        wn[u] = hn; wq[u] = 0; wsl[u] = 0u;
+                        wa[u] = k < nc && hn >= 0 && !((mask >> k) & 1u) && c_len[k] > 0;
+                        if (wa[u]) wsl[u] = (unsigned)trie_hash(hn, cp_at(k, 0)) & hwv.ctrie_mask;
+                    }
+                    for (;;) {
+                        bool any = false;
+#pragma unroll
+                        for (int u = 0; u < LM_WALK; ++u) any |= wa[u];
+                        if (!any) break;
+                        int4 e[LM_WALK];
+#pragma unroll
+                        for (int u = 0; u < LM_WALK; ++u)
+                            if (wa[u]) e[u] = hwv.ctrie[wsl[u]];
+#pragma unroll
+                        for (int u = 0; u < LM_WALK; ++u) {
+                            if (!wa[u]) continue;
+                            const int k = k0 + u, cp = cp_at(k, wq[u]);
+                            if (e[u].x == -1) {                                  // no such edge: no hotword unigram has this prefix
+                                wn[u] = -1; wa[u] = false;
+                            } else if (e[u].x == wn[u] && e[u].y == cp) {
+                                wn[u] = e[u].z;
+                                if (++wq[u] == c_len[k]) wa[u] = false;
+                                else wsl[u] = (unsigned)trie_hash(wn[u], cp_at(k, wq[u])) & hwv.ctrie_mask;
+                            } else {
+                                wsl[u] = (wsl[u] + 1u) & hwv.ctrie_mask;
+                            }
+                        }
+                    }
+#pragma unroll
+                    for (int u = 0; u < LM_WALK; ++u)
+                        if (k0 + u < nc) x_hn[k0 + u][tid] = wn[u];
+                }
+            }
         }
         __syncthreads();
         // lm + P after the own hypothesis is extended by candidate k (LM only)
         [[maybe_unused]] auto ext_lmp = [&](int k) -> double {
-            if constexpr (LM) {
+            if constexpr (HW) {
+                const int kind = c_kind[k];
+                if (kind == LM_TOK_CHARS) {
+                    const int xn = x_hn[k][tid];
+                    double r;
+                    if constexpr (LM) r = xn >= 0 ? hw_bonus(hwv, xn, lp.hw_weight) : lm_pen(x_node[k][tid], pl + c_len[k], lp.unk_offset);
+                    else r = hw_bonus(hwv, xn, lp.hw_weight);
+                    return (lm + hwc) + r;
+                }
+                if (kind == LM_TOK_DELIM && hn != 0) return ((lm + term) + xhwc) + 0.0;
+                return lmp;
+            } else if constexpr (LM) {
                 const int kind = c_kind[k];
                 if (kind == LM_TOK_CHARS) return lm + lm_pen(x_node[k][tid], pl + c_len[k], lp.unk_offset);
                 if (kind == LM_TOK_DELIM && pl > 0) return (lm + term) + 0.0;
@@ -355,13 +474,13 @@ __global__ __launch_bounds__(BEAM_MAX_W) void beam_search_kernel(
         if (own) {
             st_pnb = lae(st_pnb, m_val[tid]);
             st_score = lae(st_pb, st_pnb);
-            if constexpr (LM) { st_am = st_score; st_score = st_am + lmp; }         // stays rank by the fused score
+            if constexpr (LM || HW) { st_am = st_score; st_score = st_am + lmp; }         // stays rank by the fused score
             st_key = min((unsigned)tid * V1, m_key[tid]);
             best = st_score;
             for (int k = 0; k < nc; ++k) {
                 if ((mask >> k) & 1u) continue;
                 double e = (c_tok[k] == last ? pb : s) + c_lp[k];
-                if constexpr (LM) e = e + ext_lmp(k);
+                if constexpr (LM || HW) e = e + ext_lmp(k);
                 if (e > best) best = e;
             }
         }
@@ -379,7 +498,7 @@ __global__ __launch_bounds__(BEAM_MAX_W) void beam_search_kernel(
             for (int k = 0; k < nc; ++k) {
                 if ((mask >> k) & 1u) continue;
                 double e = (c_tok[k] == last ? pb : s) + c_lp[k];
-                if constexpr (LM) e = e + ext_lmp(k);
+                if constexpr (LM || HW) e = e + ext_lmp(k);
                 if (e >= thr) { ++cnt; omin = min(omin, ord64(e)); }
             }
         }
@@ -411,7 +530,7 @@ __global__ __launch_bounds__(BEAM_MAX_W) void beam_search_kernel(
                         else {
                             if ((mask >> k) & 1u) continue;
                             e = (c_tok[k] == last ? pb : s) + c_lp[k];
-                            if constexpr (LM) e = e + ext_lmp(k);
+                            if constexpr (LM || HW) e = e + ext_lmp(k);
                             key = (unsigned)tid * V1 + (unsigned)c_tok[k] + 1u;
                         }
                         if (!(e >= thr)) continue;
@@ -456,13 +575,13 @@ __global__ __launch_bounds__(BEAM_MAX_W) void beam_search_kernel(
                 unsigned key;
                 if (k < 0) {
                     e = st_score; key = st_key; ipb = st_pb; ipnb = st_pnb;
-                    if constexpr (LM) am = st_am;
+                    if constexpr (LM || HW) am = st_am;
                 } else {
                     if ((mask >> k) & 1u) continue;
                     e = (c_tok[k] == last ? pb : s) + c_lp[k];
                     key = (unsigned)tid * V1 + (unsigned)c_tok[k] + 1u;
                     ipb = -INFINITY; ipnb = e;
-                    if constexpr (LM) { am = e; e = e + ext_lmp(k); }
+                    if constexpr (LM || HW) { am = e; e = e + ext_lmp(k); }
                 }
                 if (!(e >= thr)) continue;
                 const u128 comp = ((u128)ord64(e) << 32) | (u128)(0xFFFFFFFFu - key);
@@ -471,7 +590,7 @@ __global__ __launch_bounds__(BEAM_MAX_W) void beam_search_kernel(
                 if (slot < W) {
                     l_ord[slot] = ord64(e); l_low[slot] = 0xFFFFFFFFu - key; l_item[slot] = tid * 64 + (k + 1);
                     l_pb[slot] = ipb; l_pnb[slot] = ipnb;
-                    if constexpr (LM) l_s[slot] = am;
+                    if constexpr (LM || HW) l_s[slot] = am;
                     else l_s[slot] = e;
                 }
             }
@@ -511,6 +630,17 @@ __global__ __launch_bounds__(BEAM_MAX_W) void beam_search_kernel(
                 for (int u = 0; u < LM_CTX; ++u)
                     h_ctx[nxt][u][q] = u + sh < LM_CTX ? h_ctx[cur][u + sh][i] : x_wid[i];
             }
+            if constexpr (HW) {
+                int nhn = h_hn[cur][i], nhd = h_hd[cur][i], nhl = h_hwl[cur][i], nhc = h_hc[cur][i];
+                bool word = false;
+                if (k >= 0) {
+                    const int kind = c_kind[k];
+                    if (kind == LM_TOK_CHARS) nhn = x_hn[k][i];
+                    else if (kind == LM_TOK_DELIM && nhn != 0) { nhn = 0; nhd = x_hd[i]; nhl = x_hwl[i]; nhc = x_hc[i]; word = true; }
+                }
+                h_hn[nxt][q] = nhn; h_hd[nxt][q] = nhd; h_hwl[nxt][q] = nhl; h_hc[nxt][q] = nhc;
+                for (int u = 0; u < HW_WIN; ++u) h_hw[nxt][u][q] = word ? x_hw[u][i] : h_hw[cur][u][i];
+            }
             int slot = (int)(qh & (BEAM_TABLE - 1));
             for (int p = 0; p < BEAM_TABLE && atomicCAS(&table[slot], -1, q) != -1; ++p) slot = (slot + 1) & (BEAM_TABLE - 1);
         }
@@ -519,20 +649,36 @@ __global__ __launch_bounds__(BEAM_MAX_W) void beam_search_kernel(
         nh = M;
     }
 
-    if constexpr (LM) {
-        // ---- end of utterance: drop P, score the partial word and </s>; re-rank by the final F (ties to the earlier rank)
+    if constexpr (LM || HW) {
+        // ---- end of utterance: drop P (and Q), score the partial word and </s>, count the matches with the partial word as
+        // the last word; re-rank by the final F (ties to the earlier rank)
         if (tid < nh) {
-            double lmf = h_lm[cur][tid];
-            const int tn = h_tn[cur][tid], pl = h_pl[cur][tid];
-            int ctx[LM_CTX];
-            for (int i = 0; i < LM_CTX; ++i) ctx[i] = h_ctx[cur][i][tid];
-            if (pl > 0) {
-                const int wd = tn >= 0 ? lmv.node_word[tn] : -1;
-                const int w = wd >= 0 ? wd : lmv.unk;
-                lmf = lmf + (lp.alpha * LN10 * (lm_cond_log10(lmv, ctx, w) + (wd >= 0 ? 0.0 : lp.unk_offset)) + lp.beta);
-                lm_ctx_push(ctx, w);
+            double lmf = 0.0;
+            if constexpr (LM) {
+                lmf = h_lm[cur][tid];
+                const int tn = h_tn[cur][tid], pl = h_pl[cur][tid];
+                int ctx[LM_CTX];
+                for (int i = 0; i < LM_CTX; ++i) ctx[i] = h_ctx[cur][i][tid];
+                if (pl > 0) {
+                    const int wd = tn >= 0 ? lmv.node_word[tn] : -1;
+                    const int w = wd >= 0 ? wd : lmv.unk;
+                    lmf = lmf + (lp.alpha * LN10 * (lm_cond_log10(lmv, ctx, w) + (wd >= 0 ? 0.0 : lp.unk_offset)) + lp.beta);
+                    lm_ctx_push(ctx, w);
+                }
+                if (lp.score_boundary) lmf = lmf + lp.alpha * LN10 * lm_cond_log10(lmv, ctx, lmv.eos);
             }
-            if (lp.score_boundary) lmf = lmf + lp.alpha * LN10 * lm_cond_log10(lmv, ctx, lmv.eos);
+            if constexpr (HW) {
+                const int fhn = h_hn[cur][tid];
+                int fc = h_hc[cur][tid];
+                if (fhn != 0) {
+                    int ids[HW_WIN];
+#pragma unroll
+                    for (int u = 0; u < HW_WIN; ++u) ids[u] = h_hw[cur][u][tid];
+                    int wl = h_hwl[cur][tid], dec = h_hd[cur][tid];
+                    fc = hw_push(hwv, ids, wl, dec, fhn > 0 ? hwv.cnode[fhn].x : -1);
+                }
+                lmf = lmf + lp.hw_weight * (double)fc;
+            }
             m_val[tid] = h_s[cur][tid] + lmf;
         }
         __syncthreads();
@@ -615,7 +761,7 @@ extern "C" int cfm_ctc_beam_decode_f32(const float* logits, const int64_t* lengt
     const int64_t rows = (int64_t)B * T;
     hipLaunchKernelGGL(beam_prep_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, logits, lengths_or_null, ws, B, T, V,
                        blank_id, max_candidates, (double)token_min_logp);
-    hipLaunchKernelGGL(beam_search_kernel<false>, dim3((unsigned)B), dim3(BEAM_MAX_W), 0, s, logits, lengths_or_null, ws, T, V,
+    hipLaunchKernelGGL((beam_search_kernel<false, false>), dim3((unsigned)B), dim3(BEAM_MAX_W), 0, s, logits, lengths_or_null, ws, T, V,
                        blank_id, beam_width, max_candidates, (double)beam_prune_logp, n_best, tokens, counts, scores, num_hyps,
                        LmParams<false>{});
     return cfm_launch_status();
@@ -649,8 +795,53 @@ extern "C" int cfm_ctc_beam_lm_decode_f32(const float* logits, const int64_t* le
     hipLaunchKernelGGL(beam_prep_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, logits, lengths_or_null, ws, B, T, V,
                        blank_id, max_candidates, (double)token_min_logp);
     const LmParams<true> lp{lm_tables, alpha, beta, unk_score_offset, score_boundary ? 1 : 0, am_scores};
-    hipLaunchKernelGGL(beam_search_kernel<true>, dim3((unsigned)B), dim3(BEAM_MAX_W), 0, s, logits, lengths_or_null, ws, T, V,
+    hipLaunchKernelGGL((beam_search_kernel<true, false>), dim3((unsigned)B), dim3(BEAM_MAX_W), 0, s, logits, lengths_or_null, ws, T, V,
                        blank_id, beam_width, max_candidates, (double)beam_prune_logp, n_best, tokens, counts, scores, num_hyps,
                        lp);
+    return cfm_launch_status();
+}
+
+extern "C" size_t cfm_ctc_beam_hw_workspace_bytes(int B, int T, int W, int K) {
+    if (B <= 0 || T <= 0 || W < 1 || W > BEAM_MAX_W || K < 1 || K > BEAM_MAX_K) return 0;
+    return beam_carve(B, T, W, K, nullptr, nullptr);
+}
+
+extern "C" int cfm_ctc_beam_hw_decode_f32(const float* logits, const int64_t* lengths_or_null, int B, int T, int V, int blank_id,
+                                          int beam_width, int max_candidates, float token_min_logp, float beam_prune_logp,
+                                          int n_best, const void* lm_tables_or_null, double alpha, double beta,
+                                          double unk_score_offset, int score_boundary, const void* hw_tables,
+                                          double hotword_weight, void* workspace, size_t workspace_bytes, int64_t* tokens,
+                                          int64_t* counts, float* scores, float* am_scores, int64_t* num_hyps,
+                                          cfm_stream_t stream) {
+    CFM_REQUIRE(logits && hw_tables && workspace && tokens && counts && scores && am_scores && num_hyps, CFM_ERR_NULL);
+    CFM_REQUIRE(B > 0 && T > 0 && V >= 2, CFM_ERR_BAD_SHAPE);
+    CFM_REQUIRE(beam_width >= 1 && beam_width <= BEAM_MAX_W, CFM_ERR_UNSUPPORTED);
+    CFM_REQUIRE(max_candidates >= 1 && max_candidates <= BEAM_MAX_K, CFM_ERR_UNSUPPORTED);
+    CFM_REQUIRE(n_best >= 1 && n_best <= beam_width, CFM_ERR_BAD_SHAPE);
+    CFM_REQUIRE(blank_id >= 0 && blank_id < V, CFM_ERR_BAD_SHAPE);
+    CFM_REQUIRE(V <= BEAM_MAX_V && (int64_t)T * beam_width < INT32_MAX, CFM_ERR_UNSUPPORTED);
+    CFM_REQUIRE(!(token_min_logp != token_min_logp) && !(beam_prune_logp != beam_prune_logp), CFM_ERR_BAD_SHAPE);   // NaN
+    CFM_REQUIRE(__builtin_isfinite(alpha) && __builtin_isfinite(beta) && __builtin_isfinite(unk_score_offset), CFM_ERR_BAD_SHAPE);
+    CFM_REQUIRE(__builtin_isfinite(hotword_weight), CFM_ERR_BAD_SHAPE);
+    CFM_REQUIRE(workspace_bytes >= beam_carve(B, T, beam_width, max_candidates, nullptr, nullptr), CFM_ERR_BAD_SHAPE);
+    BeamWs ws;
+    beam_carve(B, T, beam_width, max_candidates, static_cast<char*>(workspace), &ws);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int64_t rows = (int64_t)B * T;
+    hipLaunchKernelGGL(beam_prep_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, logits, lengths_or_null, ws, B, T, V,
+                       blank_id, max_candidates, (double)token_min_logp);
+    if (lm_tables_or_null) {
+        const LmParams<true, true> lp{lm_tables_or_null, alpha, beta, unk_score_offset, score_boundary ? 1 : 0, am_scores,
+                                      hw_tables, hotword_weight};
+        hipLaunchKernelGGL((beam_search_kernel<true, true>), dim3((unsigned)B), dim3(BEAM_MAX_W), 0, s, logits, lengths_or_null, ws,
+                           T, V, blank_id, beam_width, max_candidates, (double)beam_prune_logp, n_best, tokens, counts, scores,
+                           num_hyps, lp);
+    } else {
+        const LmParams<false, true> lp{nullptr, alpha, beta, unk_score_offset, score_boundary ? 1 : 0, am_scores, hw_tables,
+                                       hotword_weight};
+        hipLaunchKernelGGL((beam_search_kernel<false, true>), dim3((unsigned)B), dim3(BEAM_MAX_W), 0, s, logits, lengths_or_null,
+                           ws, T, V, blank_id, beam_width, max_candidates, (double)beam_prune_logp, n_best, tokens, counts,
+                           scores, num_hyps, lp);
+    }
     return cfm_launch_status();
 }

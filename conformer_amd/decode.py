@@ -9,14 +9,19 @@ Prefix beam search (reference: KenLanguageModel, processing/lm.py:6-75, without 
 standard CTC rule: a blank separates repeats.
 
 The same search fused with a word n-gram model (`conformer_amd.lm`, an ARPA file): `beam_ctc_lm_decode` and
-`BeamCTCDecoder(lm=...)`, semantics in INTEGRATION.md "Language-model fusion"."""
+`BeamCTCDecoder(lm=...)`, semantics in INTEGRATION.md "Language-model fusion".
+
+Hotword boosting, with or without the language model (`conformer_amd.hotwords`): `beam_ctc_hotword_decode` and
+`BeamCTCDecoder(hotwords=...)`, semantics in INTEGRATION.md "Hotword boosting"."""
 from __future__ import annotations
 
-from typing import Callable, List, Optional, Sequence, Tuple, Union
+import math
+from typing import Callable, Iterable, List, Optional, Sequence, Tuple, Union
 
 import torch
 
 from . import _lib, ops
+from .hotwords import Hotwords, as_hotwords
 from .lm import NgramLanguageModel, as_language_model
 
 
@@ -115,18 +120,72 @@ def beam_ctc_lm_decode(logits: torch.Tensor, blank_id: int, lm: Union[NgramLangu
     return tokens, counts, scores, am_scores, num_hyps
 
 
+def beam_ctc_hotword_decode(logits: torch.Tensor, blank_id: int, hotwords: Union[Hotwords, Iterable[str]],
+                            lengths: Optional[torch.Tensor] = None, *, vocab: Sequence[str], delim_token: str = "|",
+                            skip_ids: Sequence[int] = (), hotword_weight: float = 9.0,
+                            lm: Union[NgramLanguageModel, str, None] = None, alpha: float = 2.1, beta: float = 9.2,
+                            unk_score_offset: float = -10.0, score_boundary: bool = True, beam_width: int = 100,
+                            n_best: int = 1, token_min_logp: float = -5.0, beam_prune_logp: float = -10.0,
+                            max_candidates: int = 16
+                            ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """CTC prefix beam search with hotword boosting on the HIP device, fused with the word n-gram model `lm` when one is
+    given (an NgramLanguageModel or an ARPA path; alpha, beta, unk_score_offset, score_boundary as in beam_ctc_lm_decode).
+    `hotwords`: a Hotwords or a sequence of phrases (str); `hotword_weight` any finite float.  Words are formed from `vocab`
+    as in beam_ctc_lm_decode.  Hypotheses rank by the boosted score (INTEGRATION.md "Hotword boosting").  Returns (tokens
+    (B,N,T) int64 padded with -1, counts (B,N) int64, scores (B,N) fp32 final boosted score, am_scores (B,N) fp32 acoustic,
+    num_hyps (B) int64), best first by the final score; unused rows hold count 0, tokens -1 and scores -inf.  The device
+    tables are packed and copied once per (hotwords, vocab, delim_token, skip_ids); after that nothing synchronises with the
+    host."""
+    if not math.isfinite(float(hotword_weight)):
+        raise ValueError(f"hotword_weight must be finite, got {hotword_weight}")
+    if isinstance(logits, torch.Tensor) and logits.dtype in (torch.bfloat16, torch.float16):
+        logits = logits.float()
+    x = ops._req(logits, "logits")
+    if x.dim() != 3:
+        raise ValueError(f"logits: expected (B,T,V), got {tuple(x.shape)}")
+    B, T, V = x.shape
+    if len(vocab) != V:
+        raise ValueError(f"vocab has {len(vocab)} tokens, the logits {V}")
+    if lengths is not None:
+        lengths = ops._req(lengths, "lengths", torch.int64)
+    hw = hotwords if isinstance(hotwords, Hotwords) else Hotwords(hotwords)
+    hw_tables = hw.device_tables(vocab, delim_token, skip_ids, x.device)
+    lm_tables = None if lm is None else as_language_model(lm).device_tables(vocab, delim_token, skip_ids, x.device)
+    lib = _lib.load()
+    ws_bytes = lib.cfm_ctc_beam_hw_workspace_bytes(B, T, int(beam_width), int(max_candidates))
+    workspace = torch.empty(max(int(ws_bytes), 1), dtype=torch.uint8, device=x.device)
+    tokens = torch.empty(B, n_best, T, dtype=torch.int64, device=x.device)
+    counts = torch.empty(B, n_best, dtype=torch.int64, device=x.device)
+    scores = torch.empty(B, n_best, dtype=torch.float32, device=x.device)
+    am_scores = torch.empty(B, n_best, dtype=torch.float32, device=x.device)
+    num_hyps = torch.empty(B, dtype=torch.int64, device=x.device)
+    st = lib.cfm_ctc_beam_hw_decode_f32(x.data_ptr(), ops._p(lengths), B, T, V, int(blank_id), int(beam_width),
+                                        int(max_candidates), float(token_min_logp), float(beam_prune_logp), int(n_best),
+                                        None if lm_tables is None else lm_tables.data_ptr(), float(alpha), float(beta),
+                                        float(unk_score_offset), 1 if score_boundary else 0, hw_tables.data_ptr(),
+                                        float(hotword_weight), workspace.data_ptr(), int(ws_bytes), tokens.data_ptr(),
+                                        counts.data_ptr(), scores.data_ptr(), am_scores.data_ptr(), num_hyps.data_ptr(),
+                                        ops._stream())
+    _lib.check(st, "cfm_ctc_beam_hw_decode_f32")
+    return tokens, counts, scores, am_scores, num_hyps
+
+
 class BeamCTCDecoder:
     """Drop-in for the reference's KenLanguageModel (processing/lm.py:6-75) without the language model: the same
     `__call__(logits, lengths=None, decode_func=None)`, a str for (T,V) logits and a list of str for (B,T,V).
     The best hypothesis is joined as ''.join(vocab[id]) with `delim_token` read as a space (processor.py:319); ids in
     `skip_ids` (the unk id, for example) are dropped from the text, not from the search.
     With `lm` (an NgramLanguageModel or the path of an ARPA file) the search is fused with that word n-gram model, as
-    KenLanguageModel(lm_path, ..., alpha, beta) does: beam_ctc_lm_decode.  Without it the decoder is acoustic only."""
+    KenLanguageModel(lm_path, ..., alpha, beta) does: beam_ctc_lm_decode.  Without it the decoder is acoustic only.
+    With `hotwords` (phrases, or a Hotwords) the search boosts them by `hotword_weight`, with or without `lm`, as
+    KenLanguageModel(..., hotwords, hotword_weight) does: beam_ctc_hotword_decode.  None or an empty list leaves the
+    decoder as it is without them."""
 
     def __init__(self, vocab: Sequence[str], blank_id: int, skip_ids: Sequence[int] = (), delim_token: str = "|",
                  beam_width: int = 190, beam_prune_logp: float = -20.0, token_min_logp: float = -5.0,
                  max_candidates: int = 16, *, lm: Union[NgramLanguageModel, str, None] = None, alpha: float = 2.1,
-                 beta: float = 9.2, unk_score_offset: float = -10.0, score_boundary: bool = True) -> None:
+                 beta: float = 9.2, unk_score_offset: float = -10.0, score_boundary: bool = True,
+                 hotwords: Union[Hotwords, Iterable[str], None] = None, hotword_weight: float = 9.0) -> None:
         self.vocab = list(vocab)
         self.blank_id = int(blank_id)
         self.skip_ids = frozenset(int(i) for i in skip_ids)
@@ -140,6 +199,10 @@ class BeamCTCDecoder:
         self.beta = beta
         self.unk_score_offset = unk_score_offset
         self.score_boundary = score_boundary
+        self.hotwords = as_hotwords(hotwords)
+        if self.hotwords is not None and not math.isfinite(float(hotword_weight)):
+            raise ValueError(f"hotword_weight must be finite, got {hotword_weight}")
+        self.hotword_weight = hotword_weight
 
     def text(self, ids: Sequence[int]) -> str:
         joined = "".join(self.vocab[i] for i in ids if i not in self.skip_ids)
@@ -152,7 +215,14 @@ class BeamCTCDecoder:
             logits = logits.unsqueeze(0)
         if lengths is not None and not (isinstance(lengths, torch.Tensor) and lengths.is_cuda):
             lengths = torch.as_tensor(lengths, dtype=torch.int64).reshape(-1).to(logits.device)   # numpy lengths, as lm.py takes
-        if self.lm is None:
+        if self.hotwords is not None:
+            tokens, counts, _, _, _ = beam_ctc_hotword_decode(
+                logits, self.blank_id, self.hotwords, lengths, vocab=self.vocab, delim_token=self.delim_token,
+                skip_ids=tuple(sorted(self.skip_ids)), hotword_weight=self.hotword_weight, lm=self.lm, alpha=self.alpha,
+                beta=self.beta, unk_score_offset=self.unk_score_offset, score_boundary=self.score_boundary,
+                beam_width=self.beam_width, n_best=1, token_min_logp=self.token_min_logp,
+                beam_prune_logp=self.beam_prune_logp, max_candidates=self.max_candidates)
+        elif self.lm is None:
             tokens, counts, _, _ = beam_ctc_decode(logits, self.blank_id, lengths, beam_width=self.beam_width, n_best=1,
                                                    token_min_logp=self.token_min_logp, beam_prune_logp=self.beam_prune_logp,
                                                    max_candidates=self.max_candidates)

@@ -530,6 +530,36 @@ int cfm_ctc_beam_lm_decode_f32(const float* logits, const int64_t* lengths_or_nu
                                void* workspace, size_t workspace_bytes, int64_t* tokens, int64_t* counts, float* scores,
                                float* am_scores, int64_t* num_hyps, cfm_stream_t stream);
 
+/*      Hotword boosting for the CTC beam search (INTEGRATION.md "Hotword boosting"; conformer_amd/hotwords.py drives these).
+ *      HOST entries, no HIP call: cfm_hotword_pack writes one blob the caller copies to the device once.  uni_cp_offsets
+ *      (n_unigrams + 1) / uni_cp: CSR code points of each hotword unigram (non-empty, distinct spellings), n_unigrams in
+ *      [0,8192]; phrase_offsets (n_phrases + 1) / phrase_words: the unigram ids of each phrase (1 to 8 words), phrases in
+ *      priority order, n_phrases in [0,1024]; tok_cp_offsets / tok_cp / tok_kind as for cfm_ngram_lm_pack.
+ *      cfm_hotword_pack_bytes returns the blob size (0 for arguments out of range).
+ *      cfm_hotword_count runs the device's window step and partial-word bonus on the host over token sequences
+ *      tokens[offsets[s] .. offsets[s+1]) (ids in [0,V)) with the host copy of the blob: for every token i, counts[i] = the
+ *      matches among the completed words of the prefix ending at i and bonus[i] = Q of its partial word (fp64);
+ *      final_counts[s] = the matches with the last partial word taken as a word.  weight finite. */
+size_t cfm_hotword_pack_bytes(int n_unigrams, int64_t uni_cp_total, int n_phrases, int64_t phrase_word_total, int V,
+                              int64_t tok_cp_total);
+int cfm_hotword_pack(int n_unigrams, const int64_t* uni_cp_offsets, const int32_t* uni_cp, int n_phrases,
+                     const int64_t* phrase_offsets, const int32_t* phrase_words, int V, const int64_t* tok_cp_offsets,
+                     const int32_t* tok_cp, const int32_t* tok_kind, void* out, size_t out_bytes);
+int cfm_hotword_count(const void* hw_tables, const int32_t* tokens, const int64_t* offsets, int n_seqs, double weight,
+                      int32_t* counts, double* bonus, int32_t* final_counts);
+/*      CTC prefix beam search with hotword boosting, with the language model (lm_tables_or_null: its blob on the device, knobs
+ *      as cfm_ctc_beam_lm_decode_f32) or without it (NULL; alpha, beta, unk_score_offset, score_boundary unused but must be
+ *      finite).  hw_tables: the cfm_hotword_pack blob on the device, packed for this V; hotword_weight finite.  Arguments,
+ *      limits, workspace (cfm_ctc_beam_hw_workspace_bytes) and outputs as cfm_ctc_beam_lm_decode_f32: scores the final boosted
+ *      score, am_scores the acoustic score. */
+size_t cfm_ctc_beam_hw_workspace_bytes(int B, int T, int W, int K);
+int cfm_ctc_beam_hw_decode_f32(const float* logits, const int64_t* lengths_or_null, int B, int T, int V, int blank_id,
+                               int beam_width, int max_candidates, float token_min_logp, float beam_prune_logp, int n_best,
+                               const void* lm_tables_or_null, double alpha, double beta, double unk_score_offset,
+                               int score_boundary, const void* hw_tables, double hotword_weight, void* workspace,
+                               size_t workspace_bytes, int64_t* tokens, int64_t* counts, float* scores, float* am_scores,
+                               int64_t* num_hyps, cfm_stream_t stream);
+
 /* N1 decoder (decoder.py:10-27): LSTM recurrence over a packed batch.  gates_x (B,T,4H) = X.W_ih^T + b_ih + b_hh from
  *      one of the GEMM entries; w_hh (4H,H), gate order i|f|g|o; lengths_or_null: frames per utterance (outputs beyond are
  *      0, as pad_packed_sequence returns); y (B,T,H) <- h_t; c_state (B,H) scratch; save_* (B,T,4H)/(B,T,H) or NULL.

@@ -118,6 +118,16 @@ SIGNATURES = {
     "cfm_ctc_beam_hw_decode_f32": (c_int, [_P, _P, _I, _I, _I, _I, _I, _I, _F, _F, _I, _P, ctypes.c_double, ctypes.c_double,
                                            ctypes.c_double, _I, _P, ctypes.c_double, _P, ctypes.c_size_t, _P, _P, _P, _P, _P,
                                            _P]),
+    "cfm_ctc_beam_stream_state_bytes": (ctypes.c_size_t, [_I, _I, _I, _I, _I, _I]),
+    "cfm_ctc_beam_stream_init": (c_int, [_I, _I, _I, _I, _P, _I, _P, _P, ctypes.c_size_t, _P]),
+    "cfm_ctc_beam_stream_step_f32": (c_int, [_P, _P, _I, _I, _I, _I, _I, _I, _F, _F, _I, _P, ctypes.c_double, ctypes.c_double,
+                                             ctypes.c_double, _I, _P, ctypes.c_double, _P, ctypes.c_size_t, _I, _I, _P, _P, _P,
+                                             _P, _P, _P]),
+    "cfm_ctc_beam_stream_finish_f32": (c_int, [_I, _I, _I, _I, _P, ctypes.c_double, ctypes.c_double, ctypes.c_double, _I, _P,
+                                               ctypes.c_double, _P, ctypes.c_size_t, _I, _P, _P, _P, _P, _P, _P]),
+    "cfm_lstm_fwd_carry_f32": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
+    "cfm_lstm_fwd_frag_carry_f32": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
+    "cfm_lstm_fwd_mfma16_carry_f32": (c_int, [_I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "cfm_lstm_fwd_f32": (c_int, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "cfm_lstm_fwd_frag_f32": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "cfm_lstm_bwd_frag_f32": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),

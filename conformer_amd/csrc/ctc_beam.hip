@@ -65,6 +65,25 @@ template <bool LM> struct LmParams<LM, true> {
     double hw_weight;
 };
 
+// Resumable search (beam_search_kernel<LM, HW, true>, INTEGRATION.md "Streaming (resumable) search"): the state the one-shot
+// kernel keeps in LDS between frames, saved per utterance in the stream buffer of cfm_ctc_beam_stream_*.  Hypotheses are
+// stored in rank order; h_par and the hash table are rebuilt from the tree and the hashes when a step resumes.
+template <bool ST> struct StreamParams {};
+template <> struct StreamParams<true> {
+    int* frames;                         // (B) frames consumed so far (absolute frame index of the next frame)
+    int* nh;                             // (B) live hypotheses
+    double *pb, *pnb, *s;                // (B, W)
+    unsigned long long* hash;            // (B, W)
+    int *node, *last, *len;              // (B, W)
+    double* lm;                          // LM: (B, W) completed-word sum
+    int *tn, *pl, *ctx;                  // LM: (B, W) trie node, partial length; (B, LM_CTX, W) context
+    int *hn, *hd, *hwl, *hc;             // hotwords: (B, W)
+    short* hw;                           // hotwords: (B, HW_WIN, W) window
+    float* am_out;                       // interim acoustic scores (B, N) or null
+    int t_max;                           // frames the tree has room for
+    int finish;                          // 0: save the state and write the interim best; 1: end-of-utterance outputs
+};
+
 // P(p): 0 for an empty partial word or one that spells a prefix of some unigram (node >= 0)
 __device__ __forceinline__ double lm_pen(int node, int plen, double unk) {
     return (plen == 0 || node >= 0) ? 0.0 : unk * fmax(1.0, (double)plen / 6.0);
@@ -90,6 +109,40 @@ inline size_t beam_carve(int B, int T, int W, int K, char* base, BeamWs* ws) {
     char* clp = take(rows * K * sizeof(double));
     char* nodes = take((size_t)B * (1 + (size_t)T * W) * sizeof(int2));
     if (ws) *ws = BeamWs{(double*)lse, (int*)ncand, (int*)ctok, (double*)clp, (int2*)nodes};
+    return off;
+}
+
+// the stream buffer: the one-shot workspace for T_max frames (candidate rows of one chunk, the prefix tree of the whole
+// stream), then the saved search state
+inline size_t stream_carve(int B, int Tm, int W, int K, bool lm, bool hw, char* base, BeamWs* ws, StreamParams<true>* sp) {
+    size_t off = beam_carve(B, Tm, W, K, base, ws);
+    const size_t bw = (size_t)B * W;
+    auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += beam_align(bytes); return p; };
+    StreamParams<true> p{};
+    p.frames = (int*)take(B * sizeof(int));
+    p.nh = (int*)take(B * sizeof(int));
+    p.pb = (double*)take(bw * sizeof(double));
+    p.pnb = (double*)take(bw * sizeof(double));
+    p.s = (double*)take(bw * sizeof(double));
+    p.hash = (unsigned long long*)take(bw * sizeof(unsigned long long));
+    p.node = (int*)take(bw * sizeof(int));
+    p.last = (int*)take(bw * sizeof(int));
+    p.len = (int*)take(bw * sizeof(int));
+    if (lm) {
+        p.lm = (double*)take(bw * sizeof(double));
+        p.tn = (int*)take(bw * sizeof(int));
+        p.pl = (int*)take(bw * sizeof(int));
+        p.ctx = (int*)take(bw * LM_CTX * sizeof(int));
+    }
+    if (hw) {
+        p.hn = (int*)take(bw * sizeof(int));
+        p.hd = (int*)take(bw * sizeof(int));
+        p.hwl = (int*)take(bw * sizeof(int));
+        p.hc = (int*)take(bw * sizeof(int));
+        p.hw = (short*)take(bw * HW_WIN * sizeof(short));
+    }
+    p.t_max = Tm;
+    if (sp) *sp = p;
     return off;
 }
 
@@ -184,11 +237,11 @@ __device__ bool same_sequence(const int2* nd, int a, int b, int len) {
 
 typedef unsigned __int128 u128;
 
-template <bool LM, bool HW>
+template <bool LM, bool HW, bool ST = false>
 __global__ __launch_bounds__(BEAM_MAX_W) void beam_search_kernel(
         const float* __restrict__ logits, const int64_t* __restrict__ lengths, BeamWs ws, int T, int V, int blank, int W,
         int K, double prune, int N, int64_t* __restrict__ tokens, int64_t* __restrict__ counts, float* __restrict__ scores,
-        int64_t* __restrict__ num_hyps, LmParams<LM, HW> lp) {
+        int64_t* __restrict__ num_hyps, LmParams<LM, HW> lp, StreamParams<ST> sp = {}) {
     // hypotheses in rank order, double-buffered across frames
     __shared__ double h_pb[2][BEAM_MAX_W], h_pnb[2][BEAM_MAX_W], h_s[2][BEAM_MAX_W];
     __shared__ unsigned long long h_hash[2][BEAM_MAX_W];
@@ -221,8 +274,16 @@ __global__ __launch_bounds__(BEAM_MAX_W) void beam_search_kernel(
     __shared__ short h_hw[2][HW_WIN][HWW], x_hw[HW_WIN][HWW];
 
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int n = beam_frames(lengths, b, T);
-    int2* nd = ws.nodes + (int64_t)b * (1 + (int64_t)T * W);
+    // ST: T is the chunk's frame count; the tree and the outputs span the stream's TO = t_max frames, and frame t of the
+    // chunk is frame t0 + t of the utterance
+    int n = beam_frames(lengths, b, T), t0 = 0;
+    int TO = T;
+    if constexpr (ST) {
+        TO = sp.t_max;
+        t0 = sp.frames[b];
+        n = min(n, TO - t0);                                 // (the host refuses a chunk that could pass t_max)
+    }
+    int2* nd = ws.nodes + (int64_t)b * (1 + (int64_t)TO * W);
     const unsigned V1 = (unsigned)V + 1u;
     [[maybe_unused]] LmView lmv;
     if constexpr (LM) lmv = lm_view(lp.tables);
@@ -234,24 +295,51 @@ __global__ __launch_bounds__(BEAM_MAX_W) void beam_search_kernel(
         else tok_cp = hwv.tok_cp;
     }
 
-    for (int i = tid; i < BEAM_TABLE; i += BEAM_MAX_W) table[i] = -1;
-    if (tid == 0) {
-        h_pb[0][0] = 0.0; h_pnb[0][0] = -INFINITY; h_s[0][0] = 0.0;
-        h_hash[0][0] = ROOT_HASH; h_node[0][0] = 0; h_par[0][0] = -1; h_last[0][0] = -1; h_len[0][0] = 0;
-        nd[0] = make_int2(-1, -1);
-        if constexpr (LM) {
-            h_lm[0][0] = 0.0; h_tn[0][0] = 0; h_pl[0][0] = 0;
-            for (int i = 0; i < LM_CTX; ++i) h_ctx[0][i][0] = -1;
-            if (lp.score_boundary) h_ctx[0][LM_CTX - 1][0] = lmv.bos;
-        }
-        if constexpr (HW) {
-            h_hn[0][0] = 0; h_hd[0][0] = 0; h_hwl[0][0] = 0; h_hc[0][0] = 0;
-            for (int u = 0; u < HW_WIN; ++u) h_hw[0][u][0] = -1;
-        }
-    }
-    __syncthreads();
-    if (tid == 0) table[ROOT_HASH & (BEAM_TABLE - 1)] = 0;
     int cur = 0, nh = 1;
+    for (int i = tid; i < BEAM_TABLE; i += BEAM_MAX_W) table[i] = -1;
+    if constexpr (ST) {
+        // resume: the saved hypotheses in rank order, their parents from the tree, then the hash table (any insertion
+        // order gives the same merges: live hypotheses are distinct sequences and every hit is checked against the tree)
+        nh = sp.nh[b];
+        const int64_t o = (int64_t)b * W + tid;
+        if (tid < nh) {
+            h_pb[0][tid] = sp.pb[o]; h_pnb[0][tid] = sp.pnb[o]; h_s[0][tid] = sp.s[o]; h_hash[0][tid] = sp.hash[o];
+            const int node = sp.node[o];
+            h_node[0][tid] = node; h_par[0][tid] = node > 0 ? nd[node].x : -1;
+            h_last[0][tid] = sp.last[o]; h_len[0][tid] = sp.len[o];
+            if constexpr (LM) {
+                h_lm[0][tid] = sp.lm[o]; h_tn[0][tid] = sp.tn[o]; h_pl[0][tid] = sp.pl[o];
+                for (int i = 0; i < LM_CTX; ++i) h_ctx[0][i][tid] = sp.ctx[((int64_t)b * LM_CTX + i) * W + tid];
+            }
+            if constexpr (HW) {
+                h_hn[0][tid] = sp.hn[o]; h_hd[0][tid] = sp.hd[o]; h_hwl[0][tid] = sp.hwl[o]; h_hc[0][tid] = sp.hc[o];
+                for (int u = 0; u < HW_WIN; ++u) h_hw[0][u][tid] = sp.hw[((int64_t)b * HW_WIN + u) * W + tid];
+            }
+        }
+        __syncthreads();
+        if (tid < nh) {
+            int slot = (int)(h_hash[0][tid] & (BEAM_TABLE - 1));
+            for (int p = 0; p < BEAM_TABLE && atomicCAS(&table[slot], -1, tid) != -1; ++p) slot = (slot + 1) & (BEAM_TABLE - 1);
+        }
+        __syncthreads();
+    } else {
+        if (tid == 0) {
+            h_pb[0][0] = 0.0; h_pnb[0][0] = -INFINITY; h_s[0][0] = 0.0;
+            h_hash[0][0] = ROOT_HASH; h_node[0][0] = 0; h_par[0][0] = -1; h_last[0][0] = -1; h_len[0][0] = 0;
+            nd[0] = make_int2(-1, -1);
+            if constexpr (LM) {
+                h_lm[0][0] = 0.0; h_tn[0][0] = 0; h_pl[0][0] = 0;
+                for (int i = 0; i < LM_CTX; ++i) h_ctx[0][i][0] = -1;
+                if (lp.score_boundary) h_ctx[0][LM_CTX - 1][0] = lmv.bos;
+            }
+            if constexpr (HW) {
+                h_hn[0][0] = 0; h_hd[0][0] = 0; h_hwl[0][0] = 0; h_hc[0][0] = 0;
+                for (int u = 0; u < HW_WIN; ++u) h_hw[0][u][0] = -1;
+            }
+        }
+        __syncthreads();
+        if (tid == 0) table[ROOT_HASH & (BEAM_TABLE - 1)] = 0;
+    }
 
     for (int t = 0; t < n; ++t) {
         const int64_t row = (int64_t)b * T + t;
@@ -612,7 +700,7 @@ __global__ __launch_bounds__(BEAM_MAX_W) void beam_search_kernel(
                 h_node[nxt][q] = h_node[cur][i]; h_par[nxt][q] = h_par[cur][i]; h_last[nxt][q] = h_last[cur][i];
                 h_len[nxt][q] = h_len[cur][i];
             } else {
-                const int c = c_tok[k], id = 1 + t * W + q;
+                const int c = c_tok[k], id = 1 + (t0 + t) * W + q;
                 nd[id] = make_int2(h_node[cur][i], c);
                 qh = seq_hash(h_hash[cur][i], c);
                 h_node[nxt][q] = id; h_par[nxt][q] = h_node[cur][i]; h_last[nxt][q] = c; h_len[nxt][q] = h_len[cur][i] + 1;
@@ -649,6 +737,57 @@ __global__ __launch_bounds__(BEAM_MAX_W) void beam_search_kernel(
         nh = M;
     }
 
+    if constexpr (ST) {
+        if (!sp.finish) {
+            // ---- save the state in rank order; write the interim best: the hypotheses as they rank now, with F without the
+            // end-of-utterance terms (the fused score they were ranked by)
+            const int64_t o = (int64_t)b * W + tid;
+            double f = -INFINITY;
+            if (tid < nh) {
+                sp.pb[o] = h_pb[cur][tid]; sp.pnb[o] = h_pnb[cur][tid]; sp.s[o] = h_s[cur][tid]; sp.hash[o] = h_hash[cur][tid];
+                sp.node[o] = h_node[cur][tid]; sp.last[o] = h_last[cur][tid]; sp.len[o] = h_len[cur][tid];
+                [[maybe_unused]] double lm = 0.0, lmp = 0.0;
+                if constexpr (LM) {
+                    lm = h_lm[cur][tid];
+                    sp.lm[o] = lm; sp.tn[o] = h_tn[cur][tid]; sp.pl[o] = h_pl[cur][tid];
+                    for (int i = 0; i < LM_CTX; ++i) sp.ctx[((int64_t)b * LM_CTX + i) * W + tid] = h_ctx[cur][i][tid];
+                    lmp = lm + lm_pen(h_tn[cur][tid], h_pl[cur][tid], lp.unk_offset);
+                }
+                if constexpr (HW) {
+                    const int hn = h_hn[cur][tid], hc = h_hc[cur][tid];
+                    sp.hn[o] = hn; sp.hd[o] = h_hd[cur][tid]; sp.hwl[o] = h_hwl[cur][tid]; sp.hc[o] = hc;
+                    for (int u = 0; u < HW_WIN; ++u) sp.hw[((int64_t)b * HW_WIN + u) * W + tid] = h_hw[cur][u][tid];
+                    double r;
+                    if constexpr (LM) r = hn >= 0 ? hw_bonus(hwv, hn, lp.hw_weight) : lm_pen(h_tn[cur][tid], h_pl[cur][tid], lp.unk_offset);
+                    else r = hw_bonus(hwv, hn, lp.hw_weight);
+                    lmp = (lm + lp.hw_weight * (double)hc) + r;
+                }
+                f = h_s[cur][tid];
+                if constexpr (LM || HW) f = f + lmp;
+            }
+            if (tid == 0) { sp.frames[b] = t0 + n; sp.nh[b] = nh; }
+            if (tid < N) {
+                const int64_t r = (int64_t)b * N + tid;
+                int64_t* out = tokens + r * TO;
+                int len = 0;
+                if (tid < nh) {
+                    len = min(h_len[cur][tid], TO);
+                    int x = h_node[cur][tid];
+                    for (int p = len - 1; p >= 0 && x > 0; --p) {
+                        const int2 e = nd[x];
+                        out[p] = e.y;
+                        x = e.x;
+                    }
+                }
+                scores[r] = (float)f;
+                if (sp.am_out) sp.am_out[r] = tid < nh ? (float)h_s[cur][tid] : -INFINITY;
+                counts[r] = len;
+                for (int p = len; p < TO; ++p) out[p] = -1;
+            }
+            if (tid == 0) num_hyps[b] = min(nh, N);
+            return;
+        }
+    }
     if constexpr (LM || HW) {
         // ---- end of utterance: drop P (and Q), score the partial word and </s>, count the matches with the partial word as
         // the last word; re-rank by the final F (ties to the earlier rank)
@@ -690,10 +829,10 @@ __global__ __launch_bounds__(BEAM_MAX_W) void beam_search_kernel(
         }
         if (r < N) {
             const int64_t o = (int64_t)b * N + r;
-            int64_t* out = tokens + o * T;
+            int64_t* out = tokens + o * TO;
             int len = 0;
             if (tid < nh) {
-                len = min(h_len[cur][tid], T);
+                len = min(h_len[cur][tid], TO);
                 int x = h_node[cur][tid];
                 for (int p = len - 1; p >= 0 && x > 0; --p) {
                     const int2 e = nd[x];
@@ -707,7 +846,7 @@ __global__ __launch_bounds__(BEAM_MAX_W) void beam_search_kernel(
                 lp.am_scores[o] = -INFINITY;
             }
             counts[o] = len;
-            for (int p = len; p < T; ++p) out[p] = -1;
+            for (int p = len; p < TO; ++p) out[p] = -1;
         }
         if (tid == 0) num_hyps[b] = min(nh, N);
         return;
@@ -715,10 +854,10 @@ __global__ __launch_bounds__(BEAM_MAX_W) void beam_search_kernel(
     // ---- traceback: one thread per returned hypothesis
     if (tid < N) {
         const int64_t o = (int64_t)b * N + tid;
-        int64_t* out = tokens + o * T;
+        int64_t* out = tokens + o * TO;
         int len = 0;
         if (tid < nh) {
-            len = min(h_len[cur][tid], T);
+            len = min(h_len[cur][tid], TO);
             int x = h_node[cur][tid];
             for (int p = len - 1; p >= 0 && x > 0; --p) {
                 const int2 e = nd[x];
@@ -730,9 +869,30 @@ __global__ __launch_bounds__(BEAM_MAX_W) void beam_search_kernel(
             scores[o] = -INFINITY;
         }
         counts[o] = len;
-        for (int p = len; p < T; ++p) out[p] = -1;
+        for (int p = len; p < TO; ++p) out[p] = -1;
     }
     if (tid == 0) num_hyps[b] = min(nh, N);
+}
+
+// every utterance of a stream at the empty prefix, the state the one-shot kernel builds before its first frame
+template <bool LM, bool HW>
+__global__ void beam_stream_init_kernel(BeamWs ws, StreamParams<true> sp, int B, int W, const void* lm_tables, int score_boundary) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const int64_t o = (int64_t)b * W;
+    sp.frames[b] = 0; sp.nh[b] = 1;
+    sp.pb[o] = 0.0; sp.pnb[o] = -INFINITY; sp.s[o] = 0.0; sp.hash[o] = ROOT_HASH;
+    sp.node[o] = 0; sp.last[o] = -1; sp.len[o] = 0;
+    ws.nodes[(int64_t)b * (1 + (int64_t)sp.t_max * W)] = make_int2(-1, -1);
+    if constexpr (LM) {
+        sp.lm[o] = 0.0; sp.tn[o] = 0; sp.pl[o] = 0;
+        for (int i = 0; i < LM_CTX; ++i) sp.ctx[((int64_t)b * LM_CTX + i) * W] = -1;
+        if (score_boundary) sp.ctx[((int64_t)b * LM_CTX + LM_CTX - 1) * W] = lm_view(lm_tables).bos;
+    }
+    if constexpr (HW) {
+        sp.hn[o] = 0; sp.hd[o] = 0; sp.hwl[o] = 0; sp.hc[o] = 0;
+        for (int u = 0; u < HW_WIN; ++u) sp.hw[((int64_t)b * HW_WIN + u) * W] = -1;
+    }
 }
 
 }  // namespace
@@ -844,4 +1004,129 @@ extern "C" int cfm_ctc_beam_hw_decode_f32(const float* logits, const int64_t* le
                            scores, num_hyps, lp);
     }
     return cfm_launch_status();
+}
+
+// ---- streaming (resumable) search ----------------------------------------------------------------------------------------
+
+extern "C" size_t cfm_ctc_beam_stream_state_bytes(int B, int T_max, int W, int K, int lm, int hw) {
+    if (B <= 0 || T_max <= 0 || W < 1 || W > BEAM_MAX_W || K < 1 || K > BEAM_MAX_K || (int64_t)T_max * W >= INT32_MAX) return 0;
+    return stream_carve(B, T_max, W, K, lm != 0, hw != 0, nullptr, nullptr, nullptr);
+}
+
+extern "C" int cfm_ctc_beam_stream_init(int B, int T_max, int beam_width, int max_candidates, const void* lm_tables_or_null,
+                                        int score_boundary, const void* hw_tables_or_null, void* state, size_t state_bytes,
+                                        cfm_stream_t stream) {
+    CFM_REQUIRE(state, CFM_ERR_NULL);
+    CFM_REQUIRE(B > 0 && T_max > 0, CFM_ERR_BAD_SHAPE);
+    CFM_REQUIRE(beam_width >= 1 && beam_width <= BEAM_MAX_W, CFM_ERR_UNSUPPORTED);
+    CFM_REQUIRE(max_candidates >= 1 && max_candidates <= BEAM_MAX_K, CFM_ERR_UNSUPPORTED);
+    CFM_REQUIRE((int64_t)T_max * beam_width < INT32_MAX, CFM_ERR_UNSUPPORTED);
+    const bool lm = lm_tables_or_null != nullptr, hw = hw_tables_or_null != nullptr;
+    CFM_REQUIRE(state_bytes >= stream_carve(B, T_max, beam_width, max_candidates, lm, hw, nullptr, nullptr, nullptr),
+                CFM_ERR_BAD_SHAPE);
+    BeamWs ws;
+    StreamParams<true> sp;
+    stream_carve(B, T_max, beam_width, max_candidates, lm, hw, static_cast<char*>(state), &ws, &sp);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const dim3 grid((unsigned)((B + 255) / 256)), block(256);
+    const int sb = score_boundary ? 1 : 0;
+    if (lm && hw) hipLaunchKernelGGL((beam_stream_init_kernel<true, true>), grid, block, 0, s, ws, sp, B, beam_width, lm_tables_or_null, sb);
+    else if (lm) hipLaunchKernelGGL((beam_stream_init_kernel<true, false>), grid, block, 0, s, ws, sp, B, beam_width, lm_tables_or_null, sb);
+    else if (hw) hipLaunchKernelGGL((beam_stream_init_kernel<false, true>), grid, block, 0, s, ws, sp, B, beam_width, lm_tables_or_null, sb);
+    else hipLaunchKernelGGL((beam_stream_init_kernel<false, false>), grid, block, 0, s, ws, sp, B, beam_width, lm_tables_or_null, sb);
+    return cfm_launch_status();
+}
+
+namespace {
+
+// one launch of the resumable search in the mode the table pointers select (T = 0, logits unused: the finish)
+int beam_stream_launch(const float* logits, const int64_t* lengths, const BeamWs& ws, StreamParams<true> sp, int B, int T, int V,
+                       int blank, int W, int K, double prune, int N, const void* lm_tables, double alpha, double beta, double unk,
+                       int score_boundary, const void* hw_tables, double hw_weight, int64_t* tokens, int64_t* counts,
+                       float* scores, float* am_scores, int64_t* num_hyps, hipStream_t s) {
+    const dim3 grid((unsigned)B), block(BEAM_MAX_W);
+    const int sb = score_boundary ? 1 : 0;
+    if (lm_tables && hw_tables) {
+        const LmParams<true, true> lp{lm_tables, alpha, beta, unk, sb, am_scores, hw_tables, hw_weight};
+        hipLaunchKernelGGL((beam_search_kernel<true, true, true>), grid, block, 0, s, logits, lengths, ws, T, V, blank, W, K, prune,
+                           N, tokens, counts, scores, num_hyps, lp, sp);
+    } else if (lm_tables) {
+        const LmParams<true, false> lp{lm_tables, alpha, beta, unk, sb, am_scores};
+        hipLaunchKernelGGL((beam_search_kernel<true, false, true>), grid, block, 0, s, logits, lengths, ws, T, V, blank, W, K, prune,
+                           N, tokens, counts, scores, num_hyps, lp, sp);
+    } else if (hw_tables) {
+        const LmParams<false, true> lp{nullptr, alpha, beta, unk, sb, am_scores, hw_tables, hw_weight};
+        hipLaunchKernelGGL((beam_search_kernel<false, true, true>), grid, block, 0, s, logits, lengths, ws, T, V, blank, W, K, prune,
+                           N, tokens, counts, scores, num_hyps, lp, sp);
+    } else {
+        hipLaunchKernelGGL((beam_search_kernel<false, false, true>), grid, block, 0, s, logits, lengths, ws, T, V, blank, W, K, prune,
+                           N, tokens, counts, scores, num_hyps, LmParams<false>{}, sp);
+    }
+    return cfm_launch_status();
+}
+
+}  // namespace
+
+extern "C" int cfm_ctc_beam_stream_step_f32(const float* logits, const int64_t* lengths_or_null, int B, int Tc, int V,
+                                            int blank_id, int beam_width, int max_candidates, float token_min_logp,
+                                            float beam_prune_logp, int n_best, const void* lm_tables_or_null, double alpha,
+                                            double beta, double unk_score_offset, int score_boundary,
+                                            const void* hw_tables_or_null, double hotword_weight, void* state,
+                                            size_t state_bytes, int T_max, int t_used, int64_t* tokens, int64_t* counts,
+                                            float* scores, float* am_scores_or_null, int64_t* num_hyps, cfm_stream_t stream) {
+    CFM_REQUIRE(logits && state && tokens && counts && scores && num_hyps, CFM_ERR_NULL);
+    CFM_REQUIRE(B > 0 && Tc > 0 && T_max > 0 && V >= 2, CFM_ERR_BAD_SHAPE);
+    CFM_REQUIRE(beam_width >= 1 && beam_width <= BEAM_MAX_W, CFM_ERR_UNSUPPORTED);
+    CFM_REQUIRE(max_candidates >= 1 && max_candidates <= BEAM_MAX_K, CFM_ERR_UNSUPPORTED);
+    CFM_REQUIRE(n_best >= 1 && n_best <= beam_width, CFM_ERR_BAD_SHAPE);
+    CFM_REQUIRE(blank_id >= 0 && blank_id < V, CFM_ERR_BAD_SHAPE);
+    CFM_REQUIRE(V <= BEAM_MAX_V && (int64_t)T_max * beam_width < INT32_MAX, CFM_ERR_UNSUPPORTED);
+    // t_used: chunk frames passed to the earlier steps since the init, a bound on what any utterance consumed
+    CFM_REQUIRE(t_used >= 0 && t_used <= T_max && Tc <= T_max - t_used, CFM_ERR_BAD_SHAPE);
+    CFM_REQUIRE(!(token_min_logp != token_min_logp) && !(beam_prune_logp != beam_prune_logp), CFM_ERR_BAD_SHAPE);   // NaN
+    CFM_REQUIRE(__builtin_isfinite(alpha) && __builtin_isfinite(beta) && __builtin_isfinite(unk_score_offset), CFM_ERR_BAD_SHAPE);
+    CFM_REQUIRE(__builtin_isfinite(hotword_weight), CFM_ERR_BAD_SHAPE);
+    const bool lm = lm_tables_or_null != nullptr, hw = hw_tables_or_null != nullptr;
+    CFM_REQUIRE(state_bytes >= stream_carve(B, T_max, beam_width, max_candidates, lm, hw, nullptr, nullptr, nullptr),
+                CFM_ERR_BAD_SHAPE);
+    BeamWs ws;
+    StreamParams<true> sp;
+    stream_carve(B, T_max, beam_width, max_candidates, lm, hw, static_cast<char*>(state), &ws, &sp);
+    sp.am_out = am_scores_or_null;
+    sp.finish = 0;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int64_t rows = (int64_t)B * Tc;
+    hipLaunchKernelGGL(beam_prep_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, logits, lengths_or_null, ws, B, Tc, V,
+                       blank_id, max_candidates, (double)token_min_logp);
+    return beam_stream_launch(logits, lengths_or_null, ws, sp, B, Tc, V, blank_id, beam_width, max_candidates,
+                              (double)beam_prune_logp, n_best, lm_tables_or_null, alpha, beta, unk_score_offset, score_boundary,
+                              hw_tables_or_null, hotword_weight, tokens, counts, scores, am_scores_or_null, num_hyps, s);
+}
+
+extern "C" int cfm_ctc_beam_stream_finish_f32(int B, int beam_width, int max_candidates, int n_best, const void* lm_tables_or_null,
+                                              double alpha, double beta, double unk_score_offset, int score_boundary,
+                                              const void* hw_tables_or_null, double hotword_weight, void* state,
+                                              size_t state_bytes, int T_max, int64_t* tokens, int64_t* counts, float* scores,
+                                              float* am_scores_or_null, int64_t* num_hyps, cfm_stream_t stream) {
+    const bool lm = lm_tables_or_null != nullptr, hw = hw_tables_or_null != nullptr;
+    CFM_REQUIRE(state && tokens && counts && scores && num_hyps && (am_scores_or_null || !(lm || hw)), CFM_ERR_NULL);
+    CFM_REQUIRE(B > 0 && T_max > 0, CFM_ERR_BAD_SHAPE);
+    CFM_REQUIRE(beam_width >= 1 && beam_width <= BEAM_MAX_W, CFM_ERR_UNSUPPORTED);
+    CFM_REQUIRE(max_candidates >= 1 && max_candidates <= BEAM_MAX_K, CFM_ERR_UNSUPPORTED);
+    CFM_REQUIRE(n_best >= 1 && n_best <= beam_width, CFM_ERR_BAD_SHAPE);
+    CFM_REQUIRE((int64_t)T_max * beam_width < INT32_MAX, CFM_ERR_UNSUPPORTED);
+    CFM_REQUIRE(__builtin_isfinite(alpha) && __builtin_isfinite(beta) && __builtin_isfinite(unk_score_offset), CFM_ERR_BAD_SHAPE);
+    CFM_REQUIRE(__builtin_isfinite(hotword_weight), CFM_ERR_BAD_SHAPE);
+    CFM_REQUIRE(state_bytes >= stream_carve(B, T_max, beam_width, max_candidates, lm, hw, nullptr, nullptr, nullptr),
+                CFM_ERR_BAD_SHAPE);
+    BeamWs ws;
+    StreamParams<true> sp;
+    stream_carve(B, T_max, beam_width, max_candidates, lm, hw, static_cast<char*>(state), &ws, &sp);
+    sp.am_out = nullptr;
+    sp.finish = 1;
+    // no frames: the kernel resumes the saved state and goes straight to the end-of-utterance step (LM / hotwords) or the
+    // traceback (plain search)
+    return beam_stream_launch(nullptr, nullptr, ws, sp, B, 0, 2, 0, beam_width, max_candidates, 0.0, n_best, lm_tables_or_null,
+                              alpha, beta, unk_score_offset, score_boundary, hw_tables_or_null, hotword_weight, tokens, counts,
+                              scores, am_scores_or_null, num_hyps, static_cast<hipStream_t>(stream));
 }

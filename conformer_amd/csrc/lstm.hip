@@ -12,6 +12,7 @@
 // operands), partial tiles are summed through LDS, then one thread per (utterance, unit) applies the gate math.
 // h_{t-1} is read straight from the output tensor y[:, t-1, :].
 #include "cfm_common.h"
+#include "lstm_carry.h"
 
 namespace {
 
@@ -26,6 +27,7 @@ struct LstmArgs {
     int B, T, H;
     float* hfrag;                 // FRAG kernels: 2 x (16-utterance blocks) x H, h_t in operand-fragment order (double buffer)
     unsigned long long* trace;    // diagnostics: s_memrealtime stamps (8 per step) of thread 0 of workgroups (0,0) and (last,last)
+    const float* h0;              // CARRY kernels: (B, H) h_{-1}, row-major (the fragment-order kernel reads it from a.hfrag)
 };
 
 __device__ __forceinline__ float sigmoid_precise(float x) { return 1.0f / (1.0f + __expf(-x)); }
@@ -36,7 +38,9 @@ __device__ __forceinline__ float tanh_precise(float x) { return 1.0f - 2.0f / (_
 // of 16 rows x 64 B at a row stride (the step is bound by memory round trips, and a load that touches 16 lines completes
 // later than one that touches 8 consecutive ones).  W_hh is re-ordered by the caller once per call; h_t is written in
 // that order by the gate stage into a double buffer (a.hfrag) next to the row-major output y.  Needs H % 16 == 0.
-template <int RB, bool FRAG>      // 16-row blocks of utterances per workgroup
+// CARRY: step 0 starts from the carried state (h_{-1} = a.h0 or, FRAG, the fragment buffer of parity 1; c_{-1} = a.c) instead
+// of h = c = 0; every other step is the same code.
+template <int RB, bool FRAG, bool CARRY = false>      // 16-row blocks of utterances per workgroup
 __global__ __launch_bounds__(256) void lstm_step_kernel(const LstmArgs a, const int t) {
     __shared__ float part[4][RB * 16][17];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -59,13 +63,13 @@ __global__ __launch_bounds__(256) void lstm_step_kernel(const LstmArgs a, const 
     float gxv[4];
 #pragma unroll
     for (int q = 0; q < 4; ++q) gxv[q] = gxr[(int64_t)q * H];
-    const float cprev = t > 0 ? a.c[(int64_t)bc * H + uc] : 0.f;
+    const float cprev = (CARRY || t > 0) ? a.c[(int64_t)bc * H + uc] : 0.f;
     const bool live = !a.lengths || t < a.lengths[bc];
 
     f32x4 acc[RB];
 #pragma unroll
     for (int r = 0; r < RB; ++r) acc[r] = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (FRAG && t > 0) {
+    if (FRAG && (CARRY || t > 0)) {
         const int nchunk = H >> 4;
         const float* wf = a.whh + ((int64_t)blockIdx.x * nchunk) * 256 + lane * 4;
         const float* hf[RB];
@@ -92,13 +96,16 @@ __global__ __launch_bounds__(256) void lstm_step_kernel(const LstmArgs a, const 
             }
         }
     }
-    if (!FRAG && t > 0) {
+    if (!FRAG && (CARRY || t > 0)) {
         // B operand: column l16 = gate q (l16 >> 2), unit u0 + (l16 & 3)  ->  W_hh row q*H + unit
         // (columns of units >= H and rows of utterances >= B are computed on clamped addresses and never read back)
         const float* wrow = a.whh + ((int64_t)(l16 >> 2) * H + min(u0 + (l16 & 3), H - 1)) * H;
         const float* hrow[RB];
 #pragma unroll
-        for (int r = 0; r < RB; ++r) hrow[r] = a.y + ((int64_t)min(b0 + 16 * r + l16, a.B - 1) * a.T + (t - 1)) * H;
+        for (int r = 0; r < RB; ++r) {
+            const int64_t br = min(b0 + 16 * r + l16, a.B - 1);
+            hrow[r] = (CARRY && t == 0) ? a.h0 + br * H : a.y + (br * a.T + (t - 1)) * H;
+        }
         const int nchunk = (H + 15) / 16;
         constexpr int NBAT = 5;                               // chunks in flight per wave: ALL loads of a batch are issued first
         for (int c0 = wave; c0 < nchunk; c0 += 4 * NBAT) {
@@ -166,6 +173,16 @@ __global__ __launch_bounds__(256) void lstm_step_kernel(const LstmArgs a, const 
     LSTM_STAMP(4);
     if (tr) { __builtin_amdgcn_s_waitcnt(0); tr[5] = __builtin_amdgcn_s_memrealtime(); }
 #undef LSTM_STAMP
+}
+
+// h_state (B, H) -> the fragment-order h buffer of parity 1 (what step 0 reads), rows of utterances >= B zero
+__global__ __launch_bounds__(256) void lstm_h0_frag_kernel(const float* __restrict__ h_state, float* __restrict__ hfrag, int B,
+                                                           int Bp, int H) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)Bp * H) return;
+    const int b = (int)(i / H), unit = (int)(i % H);
+    float* dst = hfrag + (int64_t)Bp * H + ((int64_t)(b >> 4) * (H >> 4) + (unit >> 4)) * 256 + ((((unit >> 2) & 3) * 16 + (b & 15)) * 4 + (unit & 3));
+    *dst = b < B ? h_state[(int64_t)b * H + unit] : 0.f;
 }
 
 // ---- backward through time ---------------------------------------------------------------------------------------------
@@ -425,7 +442,7 @@ extern "C" int cfm_lstm_fwd_f32(const float* gates_x, const float* w_hh, const i
     CFM_REQUIRE(gates_x && w_hh && y && c_state, CFM_ERR_NULL);
     CFM_REQUIRE(B > 0 && T > 0 && H > 0 && (H & 3) == 0, CFM_ERR_BAD_SHAPE);
     CFM_REQUIRE(CFM_ALIGNED16(w_hh) && CFM_ALIGNED16(y), CFM_ERR_ALIGN);
-    const LstmArgs a{gates_x, w_hh, lengths_or_null, y, c_state, save_gates_or_null, save_c_or_null, B, T, H, nullptr, g_lstm_trace};
+    const LstmArgs a{gates_x, w_hh, lengths_or_null, y, c_state, save_gates_or_null, save_c_or_null, B, T, H, nullptr, g_lstm_trace, nullptr};
     hipStream_t s = static_cast<hipStream_t>(stream);
     const dim3 grid((unsigned)(H / 4), (unsigned)((B + 15) / 16));
     for (int t = 0; t < T; ++t) hipLaunchKernelGGL((lstm_step_kernel<1, false>), grid, dim3(256), 0, s, a, t);
@@ -443,10 +460,49 @@ extern "C" int cfm_lstm_fwd_frag_f32(const float* gates_x, const float* w_hh_fra
     CFM_REQUIRE(B > 0 && T > 0 && H > 0 && (H & 15) == 0, CFM_ERR_BAD_SHAPE);
     CFM_REQUIRE(CFM_ALIGNED16(w_hh_frag) && CFM_ALIGNED16(h_frag_scratch), CFM_ERR_ALIGN);
     const LstmArgs a{gates_x, w_hh_frag, lengths_or_null, y, c_state, save_gates_or_null, save_c_or_null, B, T, H, h_frag_scratch,
-                     g_lstm_trace};
+                     g_lstm_trace, nullptr};
     hipStream_t s = static_cast<hipStream_t>(stream);
     const dim3 grid((unsigned)(H / 4), (unsigned)((B + 15) / 16));
     for (int t = 0; t < T; ++t) hipLaunchKernelGGL((lstm_step_kernel<1, true>), grid, dim3(256), 0, s, a, t);
+    return cfm_launch_status();
+}
+
+// ---- carried state (streaming): the same recurrences started from (h_state, c_state) (B, H) fp32, which hold the state after
+// each utterance's last consumed frame on return (utterances with lengths[b] <= 0 keep theirs).  Running the frames in any
+// chunking with the state carried is bit-identical to one call over all of them: step 0 reads h_{-1} and c_{-1} from the
+// state instead of taking 0, and every product and sum is the one the uncarried step t > 0 computes.
+
+extern "C" int cfm_lstm_fwd_carry_f32(const float* gates_x, const float* w_hh, const int64_t* lengths_or_null, float* y,
+                                      float* h_state, float* c_state, float* save_gates_or_null, float* save_c_or_null, int B,
+                                      int T, int H, cfm_stream_t stream) {
+    CFM_REQUIRE(gates_x && w_hh && y && h_state && c_state, CFM_ERR_NULL);
+    CFM_REQUIRE(B > 0 && T > 0 && H > 0 && (H & 3) == 0, CFM_ERR_BAD_SHAPE);
+    CFM_REQUIRE(CFM_ALIGNED16(w_hh) && CFM_ALIGNED16(y) && CFM_ALIGNED16(h_state), CFM_ERR_ALIGN);
+    const LstmArgs a{gates_x, w_hh, lengths_or_null, y, c_state, save_gates_or_null, save_c_or_null, B, T, H, nullptr, g_lstm_trace,
+                     h_state};
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const dim3 grid((unsigned)(H / 4), (unsigned)((B + 15) / 16));
+    for (int t = 0; t < T; ++t) hipLaunchKernelGGL((lstm_step_kernel<1, false, true>), grid, dim3(256), 0, s, a, t);
+    const int64_t n = (int64_t)B * H;
+    hipLaunchKernelGGL(lstm_h_out_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, y, lengths_or_null, h_state, B, T, H);
+    return cfm_launch_status();
+}
+
+extern "C" int cfm_lstm_fwd_frag_carry_f32(const float* gates_x, const float* w_hh_frag, const int64_t* lengths_or_null, float* y,
+                                           float* h_state, float* c_state, float* h_frag_scratch, float* save_gates_or_null,
+                                           float* save_c_or_null, int B, int T, int H, cfm_stream_t stream) {
+    CFM_REQUIRE(gates_x && w_hh_frag && y && h_state && c_state && h_frag_scratch, CFM_ERR_NULL);
+    CFM_REQUIRE(B > 0 && T > 0 && H > 0 && (H & 15) == 0, CFM_ERR_BAD_SHAPE);
+    CFM_REQUIRE(CFM_ALIGNED16(w_hh_frag) && CFM_ALIGNED16(h_frag_scratch), CFM_ERR_ALIGN);
+    const LstmArgs a{gates_x, w_hh_frag, lengths_or_null, y, c_state, save_gates_or_null, save_c_or_null, B, T, H, h_frag_scratch,
+                     g_lstm_trace, nullptr};
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int Bp = (B + 15) / 16 * 16;
+    const int64_t np = (int64_t)Bp * H, n = (int64_t)B * H;
+    hipLaunchKernelGGL(lstm_h0_frag_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, s, h_state, h_frag_scratch, B, Bp, H);
+    const dim3 grid((unsigned)(H / 4), (unsigned)(Bp / 16));
+    for (int t = 0; t < T; ++t) hipLaunchKernelGGL((lstm_step_kernel<1, true, true>), grid, dim3(256), 0, s, a, t);
+    hipLaunchKernelGGL(lstm_h_out_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, y, lengths_or_null, h_state, B, T, H);
     return cfm_launch_status();
 }
 

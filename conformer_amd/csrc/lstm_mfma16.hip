@@ -28,6 +28,7 @@
 //     lane at a 5 KB row stride = 32 pieces per instruction), not by bytes
 //   * fragment order:                                          forward 4.4 us, backward 6.7 us.
 #include "cfm_common.h"
+#include "lstm_carry.h"
 
 namespace {
 
@@ -48,7 +49,8 @@ struct Lstm16Args {
 
 // Forward step.  grid = (H/8, ceil(B/32)), 256 threads.  Gate column c of the workgroup = 8*q + u  (gate q, unit u0 + u).
 // H % 32 == 0 (every wave contracts whole 16-element MFMA steps... H % 16 == 0 suffices; the launcher asks for % 32).
-template <typename T16>
+// CARRY: step 0 starts from the carried state (h_{-1}: the 16-bit buffer of parity 1, filled by lstm16_h0_kernel; c_{-1} = a.c).
+template <typename T16, bool CARRY = false>
 __global__ __launch_bounds__(256) void lstm_step16_kernel(const Lstm16Args a, const int t) {
     using x8 = typename Lowp<T16>::x8;
     __shared__ float part[4][32][33];
@@ -71,13 +73,13 @@ __global__ __launch_bounds__(256) void lstm_step16_kernel(const Lstm16Args a, co
     float gxv[4];
 #pragma unroll
     for (int q = 0; q < 4; ++q) gxv[q] = gxr[(int64_t)q * H];
-    const float cprev = t > 0 ? a.c[(int64_t)bc * H + uc] : 0.f;
+    const float cprev = (CARRY || t > 0) ? a.c[(int64_t)bc * H + uc] : 0.f;
     const bool live = !a.lengths || t < a.lengths[bc];
 
     f32x16 acc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-    if (t > 0) {
+    if (CARRY || t > 0) {
         // both operands are stored in MFMA FRAGMENT ORDER: the 64 lanes of a wave read one contiguous 1 KB block per operand and
         // step (lane (li, hf) -> element block (hf * 32 + li) * 8).  The row-major form (16 bytes per lane at a 1-5 KB row
         // stride: 32 cache-line pieces per instruction) was bound by the number of such pieces, not by bytes.
@@ -127,7 +129,11 @@ __global__ __launch_bounds__(256) void lstm_step16_kernel(const Lstm16Args a, co
     const float hn = og * tanh_p(cn);
     a.c[(int64_t)b * H + unit] = cn;
     *yo = hn;
-    h_next[hidx] = (T16)hn;
+    // the 16-bit copy is rounded from the fp32 h (kept opaque: fp16 would otherwise fold og * tanh(c) into one fma_mix, a
+    // single rounding that a carried fp32 state could not reproduce)
+    float hr = hn;
+    asm volatile("" : "+v"(hr));
+    h_next[hidx] = (T16)hr;
     if (a.save_c) a.save_c[((int64_t)b * a.T + t) * H + unit] = cn;
     if (a.save_gates) {
         float* sg = a.save_gates + ((int64_t)b * a.T + t) * 4 * H + unit;
@@ -249,6 +255,30 @@ int lstm_fwd16(const Lstm16Args& a, hipStream_t s) {
     return cfm_launch_status();
 }
 
+// h_state (B, H) fp32 -> the 16-bit h buffer of parity 1 in A-fragment order (what step 0 reads), rounded as the steps round
+// their own h; rows of utterances >= B zero
+template <typename T16>
+__global__ __launch_bounds__(256) void lstm16_h0_kernel(const float* __restrict__ h_state, void* h16, int B, int Bp, int H) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)Bp * H) return;
+    const int b = (int)(i / H), unit = (int)(i % H);
+    const int64_t nstep = H / 16;
+    T16* dst = static_cast<T16*>(h16) + (int64_t)Bp * H + (int64_t)(b >> 5) * nstep * 512 +
+               ((unit >> 4) * 2 + ((unit >> 3) & 1)) * 256 + (b & 31) * 8 + (unit & 7);
+    *dst = b < B ? (T16)h_state[(int64_t)b * H + unit] : (T16)0.f;
+}
+
+template <typename T16>
+int lstm_fwd16_carry(const Lstm16Args& a, float* h_state, hipStream_t s) {
+    const int Bp = (a.B + 31) / 32 * 32;
+    const int64_t np = (int64_t)Bp * a.H, n = (int64_t)a.B * a.H;
+    hipLaunchKernelGGL(lstm16_h0_kernel<T16>, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, s, h_state, a.h16, a.B, Bp, a.H);
+    const dim3 grid((unsigned)(a.H / 8), (unsigned)(Bp / 32));
+    for (int t = 0; t < a.T; ++t) hipLaunchKernelGGL((lstm_step16_kernel<T16, true>), grid, dim3(256), 0, s, a, t);
+    hipLaunchKernelGGL(lstm_h_out_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a.y, a.lengths, h_state, a.B, a.T, a.H);
+    return cfm_launch_status();
+}
+
 }  // namespace
 
 // cfm_lstm_fwd_f32 with the recurrent product on the 16-bit matrix pipe.  w_hh16: the 16-bit copy of W_hh (4H,H) re-ordered into
@@ -264,6 +294,22 @@ extern "C" int cfm_lstm_fwd_mfma16_f32(int prec, const float* gates_x, const voi
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (prec == CFM_PREC_BF16) return lstm_fwd16<__bf16>(a, s);
     if (prec == CFM_PREC_FP16) return lstm_fwd16<_Float16>(a, s);
+    return CFM_ERR_UNSUPPORTED;
+}
+
+// cfm_lstm_fwd_mfma16_f32 started from the carried state (h_state, c_state) (B, H) fp32, which hold the state after each
+// utterance's last consumed frame on return; any chunking with the state carried is bit-identical to one call (h_{-1} enters
+// the 16-bit buffer rounded as the steps round their own h).  See cfm_lstm_fwd_carry_f32.
+extern "C" int cfm_lstm_fwd_mfma16_carry_f32(int prec, const float* gates_x, const void* w_hh16, const int64_t* lengths_or_null,
+                                             float* y, float* h_state, float* c_state, void* h16_scratch, float* save_gates_or_null,
+                                             float* save_c_or_null, int B, int T, int H, cfm_stream_t stream) {
+    CFM_REQUIRE(gates_x && w_hh16 && y && h_state && c_state && h16_scratch, CFM_ERR_NULL);
+    CFM_REQUIRE(B > 0 && T > 0 && H > 0 && (H & 15) == 0, CFM_ERR_BAD_SHAPE);
+    CFM_REQUIRE(CFM_ALIGNED16(w_hh16) && CFM_ALIGNED16(h16_scratch), CFM_ERR_ALIGN);
+    const Lstm16Args a{gates_x, w_hh16, lengths_or_null, y, c_state, h16_scratch, save_gates_or_null, save_c_or_null, B, T, H};
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (prec == CFM_PREC_BF16) return lstm_fwd16_carry<__bf16>(a, h_state, s);
+    if (prec == CFM_PREC_FP16) return lstm_fwd16_carry<_Float16>(a, h_state, s);
     return CFM_ERR_UNSUPPORTED;
 }
 

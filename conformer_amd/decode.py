@@ -12,7 +12,10 @@ The same search fused with a word n-gram model (`conformer_amd.lm`, an ARPA file
 `BeamCTCDecoder(lm=...)`, semantics in INTEGRATION.md "Language-model fusion".
 
 Hotword boosting, with or without the language model (`conformer_amd.hotwords`): `beam_ctc_hotword_decode` and
-`BeamCTCDecoder(hotwords=...)`, semantics in INTEGRATION.md "Hotword boosting"."""
+`BeamCTCDecoder(hotwords=...)`, semantics in INTEGRATION.md "Hotword boosting".
+
+The same search resumed chunk by chunk over a stream, in every mode: `beam_ctc_stream_init/step/finish` and
+`BeamCTCDecoder.stream`, semantics in INTEGRATION.md "Streaming (resumable) search"."""
 from __future__ import annotations
 
 import math
@@ -204,6 +207,11 @@ class BeamCTCDecoder:
             raise ValueError(f"hotword_weight must be finite, got {hotword_weight}")
         self.hotword_weight = hotword_weight
 
+    def stream(self, batch: int, max_frames: int, device=None) -> "BeamCTCStream":
+        """A resumable search configured like this decoder (beam knobs, lm, hotwords) over `batch` utterances of at most
+        `max_frames` frames in all: BeamCTCStream."""
+        return BeamCTCStream(self, batch, max_frames, device)
+
     def text(self, ids: Sequence[int]) -> str:
         joined = "".join(self.vocab[i] for i in ids if i not in self.skip_ids)
         return " ".join(joined.replace(self.delim_token, " ").split())
@@ -238,3 +246,168 @@ class BeamCTCDecoder:
             text = self.text(row[:n])
             preds.append(decode_func(text) if decode_func is not None else text)
         return preds[0] if single else preds
+
+
+# ---- streaming (resumable) search: INTEGRATION.md "Streaming (resumable) search" ------------------------------------------
+
+class _StreamState:
+    """The device buffer of one resumable search and the mode it was initialised for (what beam_ctc_stream_* pass back)."""
+
+    def __init__(self, buf: torch.Tensor, B: int, t_max: int, beam_width: int, max_candidates: int, lm_tables, hw_tables,
+                 knobs: dict) -> None:
+        self.buf, self.B, self.t_max = buf, B, t_max
+        self.beam_width, self.max_candidates = beam_width, max_candidates
+        self.lm_tables, self.hw_tables = lm_tables, hw_tables
+        self.knobs = knobs
+        self.t_used = 0                    # chunk frames stepped since the init: a bound on what any utterance consumed
+
+
+def _stream_outputs(B: int, N: int, T: int, device, fused: bool):
+    tokens = torch.empty(B, N, T, dtype=torch.int64, device=device)
+    counts = torch.empty(B, N, dtype=torch.int64, device=device)
+    scores = torch.empty(B, N, dtype=torch.float32, device=device)
+    am_scores = torch.empty(B, N, dtype=torch.float32, device=device) if fused else None
+    num_hyps = torch.empty(B, dtype=torch.int64, device=device)
+    return tokens, counts, scores, am_scores, num_hyps
+
+
+def beam_ctc_stream_init(batch: int, max_frames: int, device, *, beam_width: int = 100, max_candidates: int = 16,
+                         lm_tables: Optional[torch.Tensor] = None, hw_tables: Optional[torch.Tensor] = None,
+                         alpha: float = 2.1, beta: float = 9.2, unk_score_offset: float = -10.0, score_boundary: bool = True,
+                         hotword_weight: float = 9.0) -> _StreamState:
+    """Allocate and initialise the state of a resumable CTC prefix beam search over `batch` utterances of at most
+    `max_frames` frames, every utterance at the empty prefix.  `lm_tables` / `hw_tables`: the device blobs of
+    NgramLanguageModel.device_tables / Hotwords.device_tables (None: not used).  Enqueues only."""
+    B, Tm = int(batch), int(max_frames)
+    W, K = int(beam_width), int(max_candidates)
+    lib = _lib.load()
+    nbytes = int(lib.cfm_ctc_beam_stream_state_bytes(B, Tm, W, K, int(lm_tables is not None), int(hw_tables is not None)))
+    if nbytes == 0:
+        raise ValueError(f"beam_ctc_stream_init: unsupported arguments (B={B}, max_frames={Tm}, beam_width={W}, "
+                         f"max_candidates={K})")
+    buf = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    st = _StreamState(buf, B, Tm, W, K, lm_tables, hw_tables,
+                      dict(alpha=float(alpha), beta=float(beta), unk_score_offset=float(unk_score_offset),
+                           score_boundary=1 if score_boundary else 0, hotword_weight=float(hotword_weight)))
+    beam_ctc_stream_reset(st)
+    return st
+
+
+def beam_ctc_stream_reset(st: _StreamState) -> None:
+    """Every utterance back at the empty prefix (enqueues only)."""
+    _lib.check(_lib.load().cfm_ctc_beam_stream_init(st.B, st.t_max, st.beam_width, st.max_candidates,
+                                                    ops._p(st.lm_tables), st.knobs["score_boundary"], ops._p(st.hw_tables),
+                                                    st.buf.data_ptr(), st.buf.numel(), ops._stream()),
+               "cfm_ctc_beam_stream_init")
+    st.t_used = 0
+
+
+def beam_ctc_stream_step(st: _StreamState, logits: torch.Tensor, blank_id: int, lengths: Optional[torch.Tensor] = None, *,
+                         n_best: int = 1, token_min_logp: float = -5.0, beam_prune_logp: float = -10.0):
+    """Consume the next chunk logits (B,Tc,V) (fp32, or bf16 / fp16 cast to fp32): per utterance its first lengths[b] frames
+    (None: all).  Returns the interim best (tokens (B,N,max_frames) int64 padded with -1, counts (B,N), scores (B,N) fp32
+    without end-of-utterance terms, am_scores (B,N) fp32 or None without LM and hotwords, num_hyps (B)), device tensors;
+    nothing synchronises with the host."""
+    if isinstance(logits, torch.Tensor) and logits.dtype in (torch.bfloat16, torch.float16):
+        logits = logits.float()
+    x = ops._req(logits, "logits")
+    if x.dim() != 3 or x.shape[0] != st.B:
+        raise ValueError(f"logits: expected ({st.B},Tc,V), got {tuple(x.shape)}")
+    _, Tc, V = x.shape
+    if Tc < 1:
+        raise ValueError("beam_ctc_stream_step: the chunk has no frames")
+    if Tc > st.t_max - st.t_used:
+        raise ValueError(f"beam_ctc_stream_step: {Tc} more frames would pass max_frames={st.t_max} "
+                         f"({st.t_used} stepped so far)")
+    if lengths is not None:
+        lengths = ops._req(lengths, "lengths", torch.int64)
+    fused = st.lm_tables is not None or st.hw_tables is not None
+    tokens, counts, scores, am_scores, num_hyps = _stream_outputs(st.B, int(n_best), st.t_max, x.device, fused)
+    k = st.knobs
+    status = _lib.load().cfm_ctc_beam_stream_step_f32(
+        x.data_ptr(), ops._p(lengths), st.B, Tc, V, int(blank_id), st.beam_width, st.max_candidates, float(token_min_logp),
+        float(beam_prune_logp), int(n_best), ops._p(st.lm_tables), k["alpha"], k["beta"], k["unk_score_offset"],
+        k["score_boundary"], ops._p(st.hw_tables), k["hotword_weight"], st.buf.data_ptr(), st.buf.numel(), st.t_max,
+        st.t_used, tokens.data_ptr(), counts.data_ptr(), scores.data_ptr(), ops._p(am_scores), num_hyps.data_ptr(),
+        ops._stream())
+    _lib.check(status, "cfm_ctc_beam_stream_step_f32")
+    st.t_used += Tc
+    return tokens, counts, scores, am_scores, num_hyps
+
+
+def beam_ctc_stream_finish(st: _StreamState, n_best: int = 1):
+    """The end-of-utterance step over the consumed frames: (tokens (B,N,max_frames), counts, scores, am_scores or None
+    without LM and hotwords, num_hyps), equal bit for bit to one-shot decoding of the consumed frames (with T = max_frames)."""
+    fused = st.lm_tables is not None or st.hw_tables is not None
+    tokens, counts, scores, am_scores, num_hyps = _stream_outputs(st.B, int(n_best), st.t_max, st.buf.device, fused)
+    k = st.knobs
+    status = _lib.load().cfm_ctc_beam_stream_finish_f32(
+        st.B, st.beam_width, st.max_candidates, int(n_best), ops._p(st.lm_tables), k["alpha"], k["beta"],
+        k["unk_score_offset"], k["score_boundary"], ops._p(st.hw_tables), k["hotword_weight"], st.buf.data_ptr(),
+        st.buf.numel(), st.t_max, tokens.data_ptr(), counts.data_ptr(), scores.data_ptr(), ops._p(am_scores),
+        num_hyps.data_ptr(), ops._stream())
+    _lib.check(status, "cfm_ctc_beam_stream_finish_f32")
+    return tokens, counts, scores, am_scores, num_hyps
+
+
+class BeamCTCStream:
+    """A BeamCTCDecoder's search over a stream of logits chunks (BeamCTCDecoder.stream).  `step` enqueues the chunk and returns
+    the interim best as device tensors; `partial_text` is the one call that synchronises; `finish` returns the strings
+    BeamCTCDecoder.__call__ returns on the concatenated logits; `reset` starts a new batch of utterances."""
+
+    def __init__(self, decoder: "BeamCTCDecoder", batch: int, max_frames: int, device=None) -> None:
+        self.decoder = decoder
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        d = decoder
+        lm_tables = hw_tables = None
+        if d.hotwords is not None or d.lm is not None:
+            skip = tuple(sorted(d.skip_ids))
+            if d.lm is not None:
+                lm_tables = d.lm.device_tables(d.vocab, d.delim_token, skip, self.device)
+            if d.hotwords is not None:
+                hw_tables = d.hotwords.device_tables(d.vocab, d.delim_token, skip, self.device)
+        self.state = beam_ctc_stream_init(batch, max_frames, self.device, beam_width=d.beam_width,
+                                          max_candidates=d.max_candidates, lm_tables=lm_tables, hw_tables=hw_tables,
+                                          alpha=d.alpha, beta=d.beta, unk_score_offset=d.unk_score_offset,
+                                          score_boundary=d.score_boundary, hotword_weight=d.hotword_weight)
+        self.finished = False
+        self.last = None                   # interim outputs of the latest step
+
+    def step(self, logits_chunk: torch.Tensor, lengths: Optional[torch.Tensor] = None):
+        """logits_chunk (B,Tc,V): the next frames of every utterance; `lengths` (B) int64: frames of the chunk to consume per
+        utterance (None: all).  Returns (tokens (B,1,max_frames), counts (B,1), scores (B,1)) of the interim best."""
+        if self.finished:
+            raise RuntimeError("BeamCTCStream.step after finish(): call reset() to start a new stream")
+        d = self.decoder
+        if lengths is not None and not (isinstance(lengths, torch.Tensor) and lengths.is_cuda):
+            lengths = torch.as_tensor(lengths, dtype=torch.int64).reshape(-1).to(self.device)
+        out = beam_ctc_stream_step(self.state, logits_chunk, d.blank_id, lengths, n_best=1, token_min_logp=d.token_min_logp,
+                                   beam_prune_logp=d.beam_prune_logp)
+        self.last = out
+        return out[0], out[1], out[2]
+
+    def _texts(self, tokens, counts, decode_func=None) -> List[str]:
+        preds = []
+        for row, n in zip(tokens[:, 0].cpu().tolist(), counts[:, 0].cpu().tolist()):
+            text = self.decoder.text(row[:n])
+            preds.append(decode_func(text) if decode_func is not None else text)
+        return preds
+
+    def partial_text(self) -> List[str]:
+        """The interim best transcript of every utterance after the latest step (empty strings before the first)."""
+        if self.last is None:
+            return [""] * self.state.B
+        return self._texts(self.last[0], self.last[1])
+
+    def finish(self, decode_func: Optional[Callable[[str], str]] = None) -> List[str]:
+        if self.finished:
+            raise RuntimeError("BeamCTCStream.finish() called twice: call reset() to start a new stream")
+        tokens, counts, _, _, _ = beam_ctc_stream_finish(self.state, n_best=1)
+        self.finished = True
+        return self._texts(tokens, counts, decode_func)
+
+    def reset(self) -> None:
+        beam_ctc_stream_reset(self.state)
+        self.finished = False
+        self.last = None
+

@@ -1285,18 +1285,33 @@ def subsample_stem_bwd(x, w1, b1, w2, h1, h2, dh2):
 
 
 # ---- N1 decoder: LSTM over a packed batch, Swish + BatchNorm(eval), vocabulary projection -------------------------------
-def lstm_forward(x, w_ih, w_hh, bias, lengths=None, save: bool = False):
+def lstm_forward(x, w_ih, w_hh, bias, lengths=None, save: bool = False, state=None):
     """nn.LSTM(batch_first) forward of one layer: x (B,T,D) -> y (B,T,H); bias = b_ih + b_hh (4H).  `lengths` (B) int64 on
     the device gives pack_padded_sequence semantics (outputs beyond an utterance's length are 0).  The input projection is
-    one GEMM; under autocast both it and the recurrent product run on the 16-bit matrix pipe.  save=True also returns (gates, cells)."""
-    x = _req(x, "x"); w_hh = _req(w_hh, "weight_hh")
-    B, T, _ = x.shape
+    one GEMM; under autocast both it and the recurrent product run on the 16-bit matrix pipe.  save=True also returns (gates, cells).
+    state=(h, c): (B,H) fp32 device tensors the recurrence starts from instead of zeros, updated in place to the state after
+    each utterance's last frame (streaming: any chunking with the state carried equals one call bit for bit)."""
+    x = _req(x, "x")
+    return lstm_recurrence(linear(x, w_ih, bias), w_hh, lengths, save, state)      # (B,T,4H) input projection, then the recurrence
+
+
+def lstm_recurrence(gx, w_hh, lengths=None, save: bool = False, state=None):
+    """The recurrence of lstm_forward over gx (B,T,4H) = x.W_ih^T + b_ih + b_hh (fp32); arguments and results as lstm_forward."""
+    gx = _req(gx, "gates_x"); w_hh = _req(w_hh, "weight_hh")
+    B, T, _ = gx.shape
     H = w_hh.shape[1]
-    gx = linear(x, w_ih, bias)                                        # (B,T,4H)
-    y = torch.empty(B, T, H, device=x.device, dtype=torch.float32)
-    c = torch.empty(B, H, device=x.device, dtype=torch.float32)
-    gates = torch.empty(B, T, 4 * H, device=x.device, dtype=torch.float32) if save else None
-    cells = torch.empty(B, T, H, device=x.device, dtype=torch.float32) if save else None
+    hs = None
+    if state is not None:
+        hs, c = state
+        for name, t in (("state h", hs), ("state c", c)):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+                    and tuple(t.shape) == (B, H)):
+                raise ValueError(f"lstm_forward: {name} must be a contiguous fp32 ({B}, {H}) tensor on the HIP device")
+    y = torch.empty(B, T, H, device=gx.device, dtype=torch.float32)
+    if hs is None:
+        c = torch.empty(B, H, device=gx.device, dtype=torch.float32)
+    gates = torch.empty(B, T, 4 * H, device=gx.device, dtype=torch.float32) if save else None
+    cells = torch.empty(B, T, H, device=gx.device, dtype=torch.float32) if save else None
     if lengths is not None:
         lengths = _req(lengths, "lengths", torch.int64)
     prec = mfma16_prec()
@@ -1304,9 +1319,14 @@ def lstm_forward(x, w_ih, w_hh, bias, lengths=None, save: bool = False):
     if w16 is not None:
         # under autocast the recurrent product runs on the 16-bit matrix pipe too (what autocast does to nn.LSTM on a GPU);
         # gate math, cell state and all stored tensors stay fp32
-        h16 = torch.empty(2 * ((B + 31) // 32) * 32 * H, device=x.device, dtype=_DT16[prec])
+        h16 = torch.empty(2 * ((B + 31) // 32) * 32 * H, device=gx.device, dtype=_DT16[prec])
         # W_hh in MFMA fragment order (H/8, H/16, 2, 32, 8): one contiguous 1 KB block per workgroup and contraction step
         w16 = w16.view(4, H // 8, 8, H // 16, 2, 8).permute(1, 3, 4, 0, 2, 5).contiguous()
+        if hs is not None:
+            _lib.check(_lib.load().cfm_lstm_fwd_mfma16_carry_f32(prec, gx.data_ptr(), w16.data_ptr(), _p(lengths), y.data_ptr(),
+                                                                 hs.data_ptr(), c.data_ptr(), h16.data_ptr(), _p(gates), _p(cells),
+                                                                 B, T, H, _stream()), "cfm_lstm_fwd_mfma16_carry_f32")
+            return (y, gates, cells) if save else y
         _lib.check(_lib.load().cfm_lstm_fwd_mfma16_f32(prec, gx.data_ptr(), w16.data_ptr(), _p(lengths), y.data_ptr(), c.data_ptr(),
                                                        h16.data_ptr(), _p(gates), _p(cells), B, T, H, _stream()),
                    "cfm_lstm_fwd_mfma16_f32")
@@ -1315,10 +1335,19 @@ def lstm_forward(x, w_ih, w_hh, bias, lengths=None, save: bool = False):
         # fp32 recurrence with both operands in MFMA fragment order (bit-identical to the row-major kernel, fewer cache
         # lines per load): W_hh -> (H/4, H/16, kq 4, gate 4, unit 4, 4)
         wf = w_hh.view(4, H // 4, 4, H // 16, 4, 4).permute(1, 3, 4, 0, 2, 5).contiguous()
-        hf = torch.empty(2 * ((B + 15) // 16) * 16 * H, device=x.device, dtype=torch.float32)
+        hf = torch.empty(2 * ((B + 15) // 16) * 16 * H, device=gx.device, dtype=torch.float32)
+        if hs is not None:
+            _lib.check(_lib.load().cfm_lstm_fwd_frag_carry_f32(gx.data_ptr(), wf.data_ptr(), _p(lengths), y.data_ptr(), hs.data_ptr(),
+                                                               c.data_ptr(), hf.data_ptr(), _p(gates), _p(cells), B, T, H, _stream()),
+                       "cfm_lstm_fwd_frag_carry_f32")
+            return (y, gates, cells) if save else y
         _lib.check(_lib.load().cfm_lstm_fwd_frag_f32(gx.data_ptr(), wf.data_ptr(), _p(lengths), y.data_ptr(), c.data_ptr(),
                                                      hf.data_ptr(), _p(gates), _p(cells), B, T, H, _stream()),
                    "cfm_lstm_fwd_frag_f32")
+        return (y, gates, cells) if save else y
+    if hs is not None:
+        _lib.check(_lib.load().cfm_lstm_fwd_carry_f32(gx.data_ptr(), w_hh.data_ptr(), _p(lengths), y.data_ptr(), hs.data_ptr(),
+                                                      c.data_ptr(), _p(gates), _p(cells), B, T, H, _stream()), "cfm_lstm_fwd_carry_f32")
         return (y, gates, cells) if save else y
     _lib.check(_lib.load().cfm_lstm_fwd_f32(gx.data_ptr(), w_hh.data_ptr(), _p(lengths), y.data_ptr(), c.data_ptr(), _p(gates),
                                             _p(cells), B, T, H, _stream()), "cfm_lstm_fwd_f32")

@@ -1,0 +1,80 @@
+"""Streaming transcription: mel chunks in, interim and final transcripts out (INTEGRATION.md "Streaming (resumable)
+search").
+
+StreamingTranscriber joins the chunked encoder (StreamingEncoder, cached K/V and depthwise state), the decoder with its LSTM
+state carried across chunks (ops.lstm_forward(state=...): any chunking equals one call bit for bit) and the resumable beam
+search of a BeamCTCDecoder (BeamCTCStream: any chunking equals one-shot decoding bit for bit).  Per chunk: encoder step ->
+LSTM layers -> Swish + BatchNorm (running statistics) -> vocabulary Linear on the new frames -> beam step.  All utterances of
+the batch advance in lockstep, as in StreamingEncoder; there are no ragged stream ends here.  Everything runs on the gfx950
+kernels; the model must be in eval mode on the HIP device.
+"""
+from __future__ import annotations
+
+from typing import Callable, List, Optional
+
+import torch
+
+from . import ops
+from .decode import BeamCTCDecoder, BeamCTCStream
+from .streaming import StreamingEncoder
+
+
+class StreamingTranscriber:
+    """model: a Conformer in eval() mode on the HIP device; decoder: the BeamCTCDecoder whose configuration (beam knobs, lm,
+    hotwords) the streamed search takes; batch utterances of at most max_mel_frames mel frames.  graphs: as StreamingEncoder."""
+
+    def __init__(self, model, decoder: BeamCTCDecoder, batch: int, max_mel_frames: int, graphs: bool = False) -> None:
+        if model.training:
+            raise RuntimeError("StreamingTranscriber: put the model in eval() mode (running BatchNorm statistics, no dropout)")
+        dec = model.decoder
+        p = next(dec.parameters())
+        if not p.is_cuda or p.dtype != torch.float32:
+            raise RuntimeError("StreamingTranscriber: the model must live on the HIP device in fp32 (no CPU fallback)")
+        if not dec._hip_eligible(p):
+            raise RuntimeError("StreamingTranscriber: the decoder LSTM has no HIP kernel (hidden size % 4 != 0, bidirectional, "
+                               "projected or with dropout)")
+        self.model = model
+        self.encoder = StreamingEncoder(model.encoder, batch, max_mel_frames, graphs=graphs)
+        self.B = int(batch)
+        H = dec.lstm.hidden_size
+        self.state = [(torch.zeros(self.B, H, device=p.device, dtype=torch.float32),
+                       torch.zeros(self.B, H, device=p.device, dtype=torch.float32)) for _ in range(dec.lstm.num_layers)]
+        self.beam: BeamCTCStream = decoder.stream(self.B, self.encoder.t_max, p.device)
+
+    def reset(self) -> None:
+        self.encoder.reset()
+        for h, c in self.state:
+            h.zero_()
+            c.zero_()
+        self.beam.reset()
+
+    @torch.no_grad()
+    def decode_frames(self, enc: torch.Tensor) -> torch.Tensor:
+        """The decoder (Decoder.fused in eval mode) on the chunk's new encoder frames (B, k, d), the LSTM state carried."""
+        dec = self.model.decoder
+        h = enc.float() if enc.dtype != torch.float32 else enc
+        for k, state in enumerate(self.state):
+            w_ih, w_hh = getattr(dec.lstm, f"weight_ih_l{k}"), getattr(dec.lstm, f"weight_hh_l{k}")
+            b_ih, b_hh = getattr(dec.lstm, f"bias_ih_l{k}"), getattr(dec.lstm, f"bias_hh_l{k}")
+            bias = dec._packs.get(f"bias{k}", (b_ih, b_hh), lambda: (b_ih + b_hh).detach().contiguous())
+            h = ops.lstm_forward(h, w_ih.detach(), w_hh.detach(), bias, None, state=state)
+        n = dec.norm
+        z = ops.swish_bn_eval(h, n.running_mean, n.running_var, n.weight.detach(), n.bias.detach(), n.eps)
+        return ops.linear(z, dec.linear.weight.detach(), dec.linear.bias.detach())
+
+    @torch.no_grad()
+    def step(self, mel_chunk: torch.Tensor) -> torch.Tensor:
+        """mel_chunk (B, n_mel, Tc): the next log-mel frames.  Returns the logits (B, k, V) of the encoder frames that became
+        computable (k may be 0) and advances the beam search over them; nothing synchronises with the host."""
+        enc = self.encoder.step(mel_chunk)
+        if enc.shape[1] == 0:
+            return enc.new_empty(self.B, 0, self.model.decoder.linear.out_features)
+        logits = self.decode_frames(enc)
+        self.beam.step(logits)
+        return logits
+
+    def partial_text(self) -> List[str]:
+        return self.beam.partial_text()
+
+    def finish(self, decode_func: Optional[Callable[[str], str]] = None) -> List[str]:
+        return self.beam.finish(decode_func)

@@ -560,6 +560,35 @@ int cfm_ctc_beam_hw_decode_f32(const float* logits, const int64_t* lengths_or_nu
                                size_t workspace_bytes, int64_t* tokens, int64_t* counts, float* scores, float* am_scores,
                                int64_t* num_hyps, cfm_stream_t stream);
 
+/*      Streaming (resumable) CTC prefix beam search, INTEGRATION.md "Streaming (resumable) search": one opaque device buffer
+ *      of cfm_ctc_beam_stream_state_bytes(B, T_max, W, K, lm, hw) bytes (0 for arguments out of range; lm / hw: whether the
+ *      stream fuses the language model / boosts hotwords) holds the prefix tree for T_max frames and the search state of B
+ *      utterances.  cfm_ctc_beam_stream_init puts every utterance at the empty prefix (lm_tables_or_null, score_boundary and
+ *      hw_tables_or_null select the mode and must be the ones the steps pass).  cfm_ctc_beam_stream_step_f32 consumes the
+ *      first lengths_or_null[b] (clamped to [0,Tc]; NULL = all) frames of the chunk logits (B,Tc,V) fp32, saves the state and
+ *      writes the interim N best in rank order: tokens (B,N,T_max) int64 padded with -1, counts (B,N), scores (B,N) fp32 (the
+ *      fused score without end-of-utterance terms), am_scores_or_null (B,N) fp32 acoustic, num_hyps (B).  t_used: chunk
+ *      frames passed to the earlier steps since the init; a step with Tc > T_max - t_used is refused.  Knobs and limits as
+ *      cfm_ctc_beam_hw_decode_f32 with both table pointers optional.  cfm_ctc_beam_stream_finish_f32 applies the
+ *      end-of-utterance step and writes the one-shot outputs with T = T_max (am_scores required with the LM or hotwords);
+ *      steps then finish over any chunking equal one-shot decoding of the consumed frames bit for bit.  Argument errors return
+ *      before any HIP call. */
+size_t cfm_ctc_beam_stream_state_bytes(int B, int T_max, int W, int K, int lm, int hw);
+int cfm_ctc_beam_stream_init(int B, int T_max, int beam_width, int max_candidates, const void* lm_tables_or_null,
+                             int score_boundary, const void* hw_tables_or_null, void* state, size_t state_bytes,
+                             cfm_stream_t stream);
+int cfm_ctc_beam_stream_step_f32(const float* logits, const int64_t* lengths_or_null, int B, int Tc, int V, int blank_id,
+                                 int beam_width, int max_candidates, float token_min_logp, float beam_prune_logp, int n_best,
+                                 const void* lm_tables_or_null, double alpha, double beta, double unk_score_offset,
+                                 int score_boundary, const void* hw_tables_or_null, double hotword_weight, void* state,
+                                 size_t state_bytes, int T_max, int t_used, int64_t* tokens, int64_t* counts, float* scores,
+                                 float* am_scores_or_null, int64_t* num_hyps, cfm_stream_t stream);
+int cfm_ctc_beam_stream_finish_f32(int B, int beam_width, int max_candidates, int n_best, const void* lm_tables_or_null,
+                                   double alpha, double beta, double unk_score_offset, int score_boundary,
+                                   const void* hw_tables_or_null, double hotword_weight, void* state, size_t state_bytes,
+                                   int T_max, int64_t* tokens, int64_t* counts, float* scores, float* am_scores_or_null,
+                                   int64_t* num_hyps, cfm_stream_t stream);
+
 /* N1 decoder (decoder.py:10-27): LSTM recurrence over a packed batch.  gates_x (B,T,4H) = X.W_ih^T + b_ih + b_hh from
  *      one of the GEMM entries; w_hh (4H,H), gate order i|f|g|o; lengths_or_null: frames per utterance (outputs beyond are
  *      0, as pad_packed_sequence returns); y (B,T,H) <- h_t; c_state (B,H) scratch; save_* (B,T,4H)/(B,T,H) or NULL.
@@ -590,6 +619,18 @@ int cfm_lstm_bwd_frag_f32(const float* dy, const float* gates, const float* cell
 int cfm_lstm_fwd_mfma16_f32(int prec, const float* gates_x, const void* w_hh16, const int64_t* lengths_or_null, float* y,
                             float* c_state, void* h16_scratch, float* save_gates_or_null, float* save_c_or_null, int B,
                             int T, int H, cfm_stream_t stream);
+/* Carried state (streaming): the three forward recurrences started from (h_state, c_state) (B,H) fp32 instead of h = c = 0;
+ * on return they hold the state after each utterance's last consumed frame (utterances with lengths[b] <= 0 keep theirs).
+ * Other arguments as the uncarried entries.  Any chunking with the state carried is bit-identical to one call. */
+int cfm_lstm_fwd_carry_f32(const float* gates_x, const float* w_hh, const int64_t* lengths_or_null, float* y, float* h_state,
+                           float* c_state, float* save_gates_or_null, float* save_c_or_null, int B, int T, int H,
+                           cfm_stream_t stream);
+int cfm_lstm_fwd_frag_carry_f32(const float* gates_x, const float* w_hh_frag, const int64_t* lengths_or_null, float* y,
+                                float* h_state, float* c_state, float* h_frag_scratch, float* save_gates_or_null,
+                                float* save_c_or_null, int B, int T, int H, cfm_stream_t stream);
+int cfm_lstm_fwd_mfma16_carry_f32(int prec, const float* gates_x, const void* w_hh16, const int64_t* lengths_or_null, float* y,
+                                  float* h_state, float* c_state, void* h16_scratch, float* save_gates_or_null,
+                                  float* save_c_or_null, int B, int T, int H, cfm_stream_t stream);
 int cfm_lstm_bwd_mfma16_f32(int prec, const float* dy, const float* gates, const float* cells, const void* whh_t16,
                             const int64_t* lengths_or_null, float* dgates, float* dc_state, void* dg16_scratch, int B,
                             int T, int H, cfm_stream_t stream);

@@ -5,6 +5,7 @@
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...
     python bench.py --train [--gpus N]                             # BASELINE cfg-3 / cfg-4: bf16 training step, B=64 per GPU, DDP
     python bench.py ... --dump-outputs DIR                         # also write rank 0's last timed step's outputs as DIR/*.npy
+    python bench.py --full [--no-roofline] [--no-secondary] [--no-cpu-baseline]   # also everything the headline does not need
 
 Without RANK/WORLD_SIZE in the environment and with --gpus N > 1 this process is only a PARENT: it parses the arguments,
 starts N child processes of this same file with RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR=127.0.0.1 / MASTER_PORT set
@@ -13,8 +14,11 @@ starts N child processes of this same file with RANK / LOCAL_RANK / WORLD_SIZE /
 A "step" = one pass of the hot path (Encoder.forward: conv-subsampling stem -> input Linear -> 16 Conformer
 blocks) over one synthetic batch that is already resident in HBM.  Utterances shard over the batch axis, so
 N GPUs run N independent replicas with their own B=32 (weak scaling, no data-path collective).
-Rank 0 prints ONE JSON line (see the driver contract in the task statement) carrying two extra objects:
+Rank 0 prints ONE JSON line.  A plain run does only what that line's headline needs: set up, warm up, time the steps,
+dump (--dump-outputs) and print.  --full adds the measurements that take runs of their own:
+  kernel_launches_per_forward -- C-ABI calls of one untimed eager forward (one call = one kernel launch)
   roofline      -- the dominant kernel (fp32 MFMA GEMM family) timed live with HIP events on the launch stream
+  secondary     -- the same forward in the opt-in precisions f32x6 / f32x3 / bf16 autocast (fp32, N=1 only)
   cpu_baseline  -- the CPU oracle (oracle/conformer_oracle.py, a restatement pinned against the reference)
                    timed on this host's cores on a bounded sample of the same workload (N=1 only).
 """
@@ -432,11 +436,14 @@ def main():
     ap.add_argument("--dump-outputs", metavar="DIR",
                     help="after the timed steps, write what the last one returned (rank 0) as DIR/<name>.npy, float32 / float64, "
                          "at most 64 MB; inputs and weights are seeded, so runs with the same arguments are comparable")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also count the kernel launches of one eager forward and add the \"roofline\" GEMM "
+                         "site table, the \"secondary\" opt-in precisions and the \"cpu_baseline\"; a plain run only times the steps")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip \"cpu_baseline\"")
+    ap.add_argument("--no-roofline", action="store_true", help="--full: skip \"roofline\"")
     ap.add_argument("--no-graph", action="store_true", help="launch the ~260 kernels eagerly instead of one hipGraph replay")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the extra (never headline) timings of the opt-in modes appended under \"secondary\"")
+                    help="--full: skip the extra (never headline) timings of the opt-in modes appended under \"secondary\"")
     ap.add_argument("--dtype", choices=["f32", "bf16", "f32x6", "f32x3"], default="f32",
                     help="f32 = the headline configuration (BASELINE cfg-2, native fp32 MFMA); bf16 = torch.autocast(bfloat16): "
                          "dense GEMMs on the bf16 matrix pipe with fp32 accumulate and fp32 tensors; f32x6 / f32x3 = fp32 GEMMs "
@@ -511,11 +518,13 @@ def main():
         dump_outputs(args.dump_outputs, {"encoder_out": y, "encoder_out_lengths": last["len"]})
     if not torch.isfinite(y).all():
         raise SystemExit("non-finite encoder output")
-    n0 = _lib.CALLS[0]
-    with torch.no_grad(), amp():
-        enc(x, lengths)                                        # one eager forward, untimed: how many kernels the path launches
-    torch.cuda.synchronize()
-    launches = _lib.CALLS[0] - n0
+    full = {}
+    if args.full:
+        n0 = _lib.CALLS[0]
+        with torch.no_grad(), amp():
+            enc(x, lengths)                                    # one eager forward, untimed: how many kernels the path launches
+        torch.cuda.synchronize()
+        full["kernel_launches_per_forward"] = _lib.CALLS[0] - n0
 
     frames = world * CFG["B"] * CFG["T"] * args.steps
     ms = dt / args.steps * 1e3
@@ -533,12 +542,12 @@ def main():
         "config": {"workload": "cfg2 Conformer-L Encoder.forward: B=32/GPU, T=1000 mel frames (T'=249), d=512, 16 blocks, "
                                "8 heads, k=31, fp32, eval, random-init weights, batch-sharded replicas",
                    "per_gpu_batch": CFG["B"], "mel_frames": CFG["T"]},
-        "kernel_launches_per_forward": launches, "layernorm_folded_into_gemms": bool(ops.ln_fold_ok(CFG["d"])) and args.dtype == "f32",
+        **full, "layernorm_folded_into_gemms": bool(ops.ln_fold_ok(CFG["d"])) and args.dtype == "f32",
         "path_tflops": flops / (ms * 1e-3) / 1e12,
         "path_frac_of_mfma_f32_peak": flops / (ms * 1e-3) / 1e12 / PEAK_MFMA_F32_TFLOPS,
     }
 
-    if rank == 0 and not args.no_roofline and args.dtype == "f32":
+    if args.full and rank == 0 and not args.no_roofline and args.dtype == "f32":
         rows = gemm_site_table(enc, x, iters=10)
         tot = sum(r["avg_ms"] * r["launches_per_step"] for r in rows)
         dom = max(rows, key=lambda r: r["avg_ms"] * r["launches_per_step"])
@@ -559,7 +568,7 @@ def main():
                                 if k not in ("flops", "pmc_name", "alg_bytes")}
                                for r in rows],
         }
-    if rank == 0 and world == 1 and args.dtype == "f32" and not args.no_secondary:
+    if args.full and rank == 0 and world == 1 and args.dtype == "f32" and not args.no_secondary:
         # The same forward in the opt-in modes, for the record only: `value` above is the native-fp32-MFMA path.
         sec = {}
         for name, mode, autocast in (("f32x6", "bf16x6", False), ("f32x3", "bf16x3", False), ("bf16_autocast", "native", True)):
@@ -584,7 +593,7 @@ def main():
         out["secondary"] = {"note": "opt-in modes, same workload, never the headline: f32x6 / f32x3 = fp32 GEMMs from exact "
                                     "bf16 operand expansions (6 / 3 bf16 MFMAs per K-step, fp32 accumulate, fp32 tensors); "
                                     "bf16_autocast = torch.autocast(bfloat16)", **sec}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(enc, sample_b=32)
     if rank == 0:
         print(json.dumps(out), flush=True)

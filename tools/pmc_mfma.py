@@ -3,7 +3,7 @@
 SQ_WAIT_ANY, SQ_WAIT_INST_ANY, SQ_ACTIVE_INST_ANY) + --kernel-trace of the same run.
 
     rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY \
-              --kernel-trace -d DIR -o p --output-format csv -- python3 bench.py --no-graph --no-cpu-baseline --no-secondary --steps 3
+              --kernel-trace -d DIR -o p --output-format csv -- python3 bench.py --full --no-graph --no-cpu-baseline --no-secondary --steps 3
     python tools/pmc_mfma.py DIR profiles/<out>.json
 
 mfma_util = MFMA busy cycles / (1024 SIMDs x shader cycles of the dispatch); shader cycles = GRBM_GUI_ACTIVE / 8 (rocprofv3

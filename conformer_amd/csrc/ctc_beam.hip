@@ -35,6 +35,7 @@
 // matches, its window of undecided words and its count (the window rule of hotword.h); the node each extension reaches is
 // kept in LDS (x_hn), and the window step a delimiter takes is done once per thread (x_hc, x_hd, x_hwl, x_hw).
 #include <float.h>
+#include <type_traits>
 #include "cfm_common.h"
 #include "hotword.h"
 #include "ngram_lm.h"
@@ -895,6 +896,101 @@ __global__ void beam_stream_init_kernel(BeamWs ws, StreamParams<true> sp, int B,
     }
 }
 
+// ---- host side ---------------------------------------------------------------------------------------------------------
+
+#define CFM_CHECK(call) do { const int st_ = (call); if (st_ != CFM_OK) return st_; } while (0)
+
+// The argument rules every search entry shares, in the order their statuses are reported.  T: the frames the tree has room
+// for (T_max for the stream entries).  The entries without logits pass V = 2, blank = 0 and zero knobs, which always pass;
+// the stream init (no outputs) also passes N = 1.
+int beam_check(int B, int T, int V, int W, int K, int N, int blank, float token_min_logp, float beam_prune_logp) {
+    CFM_REQUIRE(B > 0 && T > 0 && V >= 2, CFM_ERR_BAD_SHAPE);
+    CFM_REQUIRE(W >= 1 && W <= BEAM_MAX_W, CFM_ERR_UNSUPPORTED);
+    CFM_REQUIRE(K >= 1 && K <= BEAM_MAX_K, CFM_ERR_UNSUPPORTED);
+    CFM_REQUIRE(N >= 1 && N <= W, CFM_ERR_BAD_SHAPE);
+    CFM_REQUIRE(blank >= 0 && blank < V, CFM_ERR_BAD_SHAPE);
+    CFM_REQUIRE(V <= BEAM_MAX_V && (int64_t)T * W < INT32_MAX, CFM_ERR_UNSUPPORTED);
+    CFM_REQUIRE(!(token_min_logp != token_min_logp) && !(beam_prune_logp != beam_prune_logp), CFM_ERR_BAD_SHAPE);   // NaN
+    return CFM_OK;
+}
+
+// the fusion arguments of the C entries; a null table pointer leaves that term out (the LM-only entry passes weight 0)
+struct Fusion {
+    const void* lm_tables;
+    double alpha, beta, unk;
+    int score_boundary;
+    const void* hw_tables;
+    double hw_weight;
+    bool on() const { return lm_tables || hw_tables; }
+    bool finite() const {
+        return __builtin_isfinite(alpha) && __builtin_isfinite(beta) && __builtin_isfinite(unk) && __builtin_isfinite(hw_weight);
+    }
+};
+
+// f(std::bool_constant<LM>{}, std::bool_constant<HW>{}) in the mode the table pointers select
+template <class F> void beam_mode(const Fusion& fz, F&& f) {
+    if (fz.lm_tables && fz.hw_tables) f(std::true_type{}, std::true_type{});
+    else if (fz.lm_tables) f(std::true_type{}, std::false_type{});
+    else if (fz.hw_tables) f(std::false_type{}, std::true_type{});
+    else f(std::false_type{}, std::false_type{});
+}
+
+// the fusion group as the search of mode <LM, HW> takes it (tables is null in the hotword-only form)
+template <bool LM, bool HW> LmParams<LM, HW> lm_params(const Fusion& fz, float* am_scores) {
+    LmParams<LM, HW> lp{};
+    if constexpr (LM || HW) {
+        lp.tables = fz.lm_tables;
+        lp.alpha = fz.alpha; lp.beta = fz.beta; lp.unk_offset = fz.unk;
+        lp.score_boundary = fz.score_boundary ? 1 : 0;
+        lp.am_scores = am_scores;
+    }
+    if constexpr (HW) { lp.hw_tables = fz.hw_tables; lp.hw_weight = fz.hw_weight; }
+    return lp;
+}
+
+// The candidate rows of the T frames (none for T = 0: the finish), then the search in the mode fz selects; ST: the resumable
+// search on the stream state sp.
+template <bool ST>
+int beam_launch(const float* logits, const int64_t* lengths, const BeamWs& ws, StreamParams<ST> sp, int B, int T, int V,
+                int blank, int W, int K, float token_min_logp, float beam_prune_logp, int N, const Fusion& fz, int64_t* tokens,
+                int64_t* counts, float* scores, float* am_scores, int64_t* num_hyps, cfm_stream_t stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (T > 0) {
+        const int64_t rows = (int64_t)B * T;
+        hipLaunchKernelGGL(beam_prep_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, logits, lengths, ws, B, T, V,
+                           blank, K, (double)token_min_logp);
+    }
+    beam_mode(fz, [&](auto lm, auto hw) {
+        constexpr bool LM = decltype(lm)::value, HW = decltype(hw)::value;
+        hipLaunchKernelGGL((beam_search_kernel<LM, HW, ST>), dim3((unsigned)B), dim3(BEAM_MAX_W), 0, s, logits, lengths, ws, T,
+                           V, blank, W, K, (double)beam_prune_logp, N, tokens, counts, scores, num_hyps,
+                           lm_params<LM, HW>(fz, am_scores), sp);
+    });
+    return cfm_launch_status();
+}
+
+// the one-shot search of cfm_ctc_beam_{,lm_,hw_}decode_f32 after their pointer checks
+int beam_decode(const float* logits, const int64_t* lengths, int B, int T, int V, int blank, int W, int K, float token_min_logp,
+                float beam_prune_logp, int N, const Fusion& fz, void* workspace, size_t workspace_bytes, int64_t* tokens,
+                int64_t* counts, float* scores, float* am_scores, int64_t* num_hyps, cfm_stream_t stream) {
+    CFM_CHECK(beam_check(B, T, V, W, K, N, blank, token_min_logp, beam_prune_logp));
+    CFM_REQUIRE(!fz.on() || fz.finite(), CFM_ERR_BAD_SHAPE);
+    CFM_REQUIRE(workspace_bytes >= beam_carve(B, T, W, K, nullptr, nullptr), CFM_ERR_BAD_SHAPE);
+    BeamWs ws;
+    beam_carve(B, T, W, K, static_cast<char*>(workspace), &ws);
+    return beam_launch(logits, lengths, ws, StreamParams<false>{}, B, T, V, blank, W, K, token_min_logp, beam_prune_logp, N, fz,
+                       tokens, counts, scores, am_scores, num_hyps, stream);
+}
+
+// the stream buffer of the mode fz selects, carved (BAD_SHAPE when it is too small)
+int stream_state(int B, int T_max, int W, int K, const Fusion& fz, void* state, size_t state_bytes, BeamWs* ws,
+                 StreamParams<true>* sp) {
+    const bool lm = fz.lm_tables != nullptr, hw = fz.hw_tables != nullptr;
+    CFM_REQUIRE(state_bytes >= stream_carve(B, T_max, W, K, lm, hw, nullptr, nullptr, nullptr), CFM_ERR_BAD_SHAPE);
+    stream_carve(B, T_max, W, K, lm, hw, static_cast<char*>(state), ws, sp);
+    return CFM_OK;
+}
+
 }  // namespace
 
 extern "C" size_t cfm_ctc_beam_workspace_bytes(int B, int T, int W, int K) {
@@ -907,29 +1003,12 @@ extern "C" int cfm_ctc_beam_decode_f32(const float* logits, const int64_t* lengt
                                        int n_best, void* workspace, size_t workspace_bytes, int64_t* tokens, int64_t* counts,
                                        float* scores, int64_t* num_hyps, cfm_stream_t stream) {
     CFM_REQUIRE(logits && workspace && tokens && counts && scores && num_hyps, CFM_ERR_NULL);
-    CFM_REQUIRE(B > 0 && T > 0 && V >= 2, CFM_ERR_BAD_SHAPE);
-    CFM_REQUIRE(beam_width >= 1 && beam_width <= BEAM_MAX_W, CFM_ERR_UNSUPPORTED);
-    CFM_REQUIRE(max_candidates >= 1 && max_candidates <= BEAM_MAX_K, CFM_ERR_UNSUPPORTED);
-    CFM_REQUIRE(n_best >= 1 && n_best <= beam_width, CFM_ERR_BAD_SHAPE);
-    CFM_REQUIRE(blank_id >= 0 && blank_id < V, CFM_ERR_BAD_SHAPE);
-    CFM_REQUIRE(V <= BEAM_MAX_V && (int64_t)T * beam_width < INT32_MAX, CFM_ERR_UNSUPPORTED);
-    CFM_REQUIRE(!(token_min_logp != token_min_logp) && !(beam_prune_logp != beam_prune_logp), CFM_ERR_BAD_SHAPE);   // NaN
-    CFM_REQUIRE(workspace_bytes >= beam_carve(B, T, beam_width, max_candidates, nullptr, nullptr), CFM_ERR_BAD_SHAPE);
-    BeamWs ws;
-    beam_carve(B, T, beam_width, max_candidates, static_cast<char*>(workspace), &ws);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int64_t rows = (int64_t)B * T;
-    hipLaunchKernelGGL(beam_prep_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, logits, lengths_or_null, ws, B, T, V,
-                       blank_id, max_candidates, (double)token_min_logp);
-    hipLaunchKernelGGL((beam_search_kernel<false, false>), dim3((unsigned)B), dim3(BEAM_MAX_W), 0, s, logits, lengths_or_null, ws, T, V,
-                       blank_id, beam_width, max_candidates, (double)beam_prune_logp, n_best, tokens, counts, scores, num_hyps,
-                       LmParams<false>{});
-    return cfm_launch_status();
+    return beam_decode(logits, lengths_or_null, B, T, V, blank_id, beam_width, max_candidates, token_min_logp, beam_prune_logp,
+                       n_best, Fusion{}, workspace, workspace_bytes, tokens, counts, scores, nullptr, num_hyps, stream);
 }
 
 extern "C" size_t cfm_ctc_beam_lm_workspace_bytes(int B, int T, int W, int K) {
-    if (B <= 0 || T <= 0 || W < 1 || W > BEAM_MAX_W || K < 1 || K > BEAM_MAX_K) return 0;
-    return beam_carve(B, T, W, K, nullptr, nullptr);
+    return cfm_ctc_beam_workspace_bytes(B, T, W, K);
 }
 
 extern "C" int cfm_ctc_beam_lm_decode_f32(const float* logits, const int64_t* lengths_or_null, int B, int T, int V, int blank_id,
@@ -939,31 +1018,13 @@ extern "C" int cfm_ctc_beam_lm_decode_f32(const float* logits, const int64_t* le
                                           int64_t* counts, float* scores, float* am_scores, int64_t* num_hyps,
                                           cfm_stream_t stream) {
     CFM_REQUIRE(logits && lm_tables && workspace && tokens && counts && scores && am_scores && num_hyps, CFM_ERR_NULL);
-    CFM_REQUIRE(B > 0 && T > 0 && V >= 2, CFM_ERR_BAD_SHAPE);
-    CFM_REQUIRE(beam_width >= 1 && beam_width <= BEAM_MAX_W, CFM_ERR_UNSUPPORTED);
-    CFM_REQUIRE(max_candidates >= 1 && max_candidates <= BEAM_MAX_K, CFM_ERR_UNSUPPORTED);
-    CFM_REQUIRE(n_best >= 1 && n_best <= beam_width, CFM_ERR_BAD_SHAPE);
-    CFM_REQUIRE(blank_id >= 0 && blank_id < V, CFM_ERR_BAD_SHAPE);
-    CFM_REQUIRE(V <= BEAM_MAX_V && (int64_t)T * beam_width < INT32_MAX, CFM_ERR_UNSUPPORTED);
-    CFM_REQUIRE(!(token_min_logp != token_min_logp) && !(beam_prune_logp != beam_prune_logp), CFM_ERR_BAD_SHAPE);   // NaN
-    CFM_REQUIRE(__builtin_isfinite(alpha) && __builtin_isfinite(beta) && __builtin_isfinite(unk_score_offset), CFM_ERR_BAD_SHAPE);
-    CFM_REQUIRE(workspace_bytes >= beam_carve(B, T, beam_width, max_candidates, nullptr, nullptr), CFM_ERR_BAD_SHAPE);
-    BeamWs ws;
-    beam_carve(B, T, beam_width, max_candidates, static_cast<char*>(workspace), &ws);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int64_t rows = (int64_t)B * T;
-    hipLaunchKernelGGL(beam_prep_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, logits, lengths_or_null, ws, B, T, V,
-                       blank_id, max_candidates, (double)token_min_logp);
-    const LmParams<true> lp{lm_tables, alpha, beta, unk_score_offset, score_boundary ? 1 : 0, am_scores};
-    hipLaunchKernelGGL((beam_search_kernel<true, false>), dim3((unsigned)B), dim3(BEAM_MAX_W), 0, s, logits, lengths_or_null, ws, T, V,
-                       blank_id, beam_width, max_candidates, (double)beam_prune_logp, n_best, tokens, counts, scores, num_hyps,
-                       lp);
-    return cfm_launch_status();
+    return beam_decode(logits, lengths_or_null, B, T, V, blank_id, beam_width, max_candidates, token_min_logp, beam_prune_logp,
+                       n_best, Fusion{lm_tables, alpha, beta, unk_score_offset, score_boundary, nullptr, 0.0}, workspace,
+                       workspace_bytes, tokens, counts, scores, am_scores, num_hyps, stream);
 }
 
 extern "C" size_t cfm_ctc_beam_hw_workspace_bytes(int B, int T, int W, int K) {
-    if (B <= 0 || T <= 0 || W < 1 || W > BEAM_MAX_W || K < 1 || K > BEAM_MAX_K) return 0;
-    return beam_carve(B, T, W, K, nullptr, nullptr);
+    return cfm_ctc_beam_workspace_bytes(B, T, W, K);
 }
 
 extern "C" int cfm_ctc_beam_hw_decode_f32(const float* logits, const int64_t* lengths_or_null, int B, int T, int V, int blank_id,
@@ -974,36 +1035,9 @@ extern "C" int cfm_ctc_beam_hw_decode_f32(const float* logits, const int64_t* le
                                           int64_t* counts, float* scores, float* am_scores, int64_t* num_hyps,
                                           cfm_stream_t stream) {
     CFM_REQUIRE(logits && hw_tables && workspace && tokens && counts && scores && am_scores && num_hyps, CFM_ERR_NULL);
-    CFM_REQUIRE(B > 0 && T > 0 && V >= 2, CFM_ERR_BAD_SHAPE);
-    CFM_REQUIRE(beam_width >= 1 && beam_width <= BEAM_MAX_W, CFM_ERR_UNSUPPORTED);
-    CFM_REQUIRE(max_candidates >= 1 && max_candidates <= BEAM_MAX_K, CFM_ERR_UNSUPPORTED);
-    CFM_REQUIRE(n_best >= 1 && n_best <= beam_width, CFM_ERR_BAD_SHAPE);
-    CFM_REQUIRE(blank_id >= 0 && blank_id < V, CFM_ERR_BAD_SHAPE);
-    CFM_REQUIRE(V <= BEAM_MAX_V && (int64_t)T * beam_width < INT32_MAX, CFM_ERR_UNSUPPORTED);
-    CFM_REQUIRE(!(token_min_logp != token_min_logp) && !(beam_prune_logp != beam_prune_logp), CFM_ERR_BAD_SHAPE);   // NaN
-    CFM_REQUIRE(__builtin_isfinite(alpha) && __builtin_isfinite(beta) && __builtin_isfinite(unk_score_offset), CFM_ERR_BAD_SHAPE);
-    CFM_REQUIRE(__builtin_isfinite(hotword_weight), CFM_ERR_BAD_SHAPE);
-    CFM_REQUIRE(workspace_bytes >= beam_carve(B, T, beam_width, max_candidates, nullptr, nullptr), CFM_ERR_BAD_SHAPE);
-    BeamWs ws;
-    beam_carve(B, T, beam_width, max_candidates, static_cast<char*>(workspace), &ws);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int64_t rows = (int64_t)B * T;
-    hipLaunchKernelGGL(beam_prep_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, logits, lengths_or_null, ws, B, T, V,
-                       blank_id, max_candidates, (double)token_min_logp);
-    if (lm_tables_or_null) {
-        const LmParams<true, true> lp{lm_tables_or_null, alpha, beta, unk_score_offset, score_boundary ? 1 : 0, am_scores,
-                                      hw_tables, hotword_weight};
-        hipLaunchKernelGGL((beam_search_kernel<true, true>), dim3((unsigned)B), dim3(BEAM_MAX_W), 0, s, logits, lengths_or_null, ws,
-                           T, V, blank_id, beam_width, max_candidates, (double)beam_prune_logp, n_best, tokens, counts, scores,
-                           num_hyps, lp);
-    } else {
-        const LmParams<false, true> lp{nullptr, alpha, beta, unk_score_offset, score_boundary ? 1 : 0, am_scores, hw_tables,
-                                       hotword_weight};
-        hipLaunchKernelGGL((beam_search_kernel<false, true>), dim3((unsigned)B), dim3(BEAM_MAX_W), 0, s, logits, lengths_or_null,
-                           ws, T, V, blank_id, beam_width, max_candidates, (double)beam_prune_logp, n_best, tokens, counts,
-                           scores, num_hyps, lp);
-    }
-    return cfm_launch_status();
+    const Fusion fz{lm_tables_or_null, alpha, beta, unk_score_offset, score_boundary, hw_tables, hotword_weight};
+    return beam_decode(logits, lengths_or_null, B, T, V, blank_id, beam_width, max_candidates, token_min_logp, beam_prune_logp,
+                       n_best, fz, workspace, workspace_bytes, tokens, counts, scores, am_scores, num_hyps, stream);
 }
 
 // ---- streaming (resumable) search ----------------------------------------------------------------------------------------
@@ -1017,55 +1051,18 @@ extern "C" int cfm_ctc_beam_stream_init(int B, int T_max, int beam_width, int ma
                                         int score_boundary, const void* hw_tables_or_null, void* state, size_t state_bytes,
                                         cfm_stream_t stream) {
     CFM_REQUIRE(state, CFM_ERR_NULL);
-    CFM_REQUIRE(B > 0 && T_max > 0, CFM_ERR_BAD_SHAPE);
-    CFM_REQUIRE(beam_width >= 1 && beam_width <= BEAM_MAX_W, CFM_ERR_UNSUPPORTED);
-    CFM_REQUIRE(max_candidates >= 1 && max_candidates <= BEAM_MAX_K, CFM_ERR_UNSUPPORTED);
-    CFM_REQUIRE((int64_t)T_max * beam_width < INT32_MAX, CFM_ERR_UNSUPPORTED);
-    const bool lm = lm_tables_or_null != nullptr, hw = hw_tables_or_null != nullptr;
-    CFM_REQUIRE(state_bytes >= stream_carve(B, T_max, beam_width, max_candidates, lm, hw, nullptr, nullptr, nullptr),
-                CFM_ERR_BAD_SHAPE);
+    CFM_CHECK(beam_check(B, T_max, 2, beam_width, max_candidates, 1, 0, 0.f, 0.f));
+    const Fusion fz{lm_tables_or_null, 0.0, 0.0, 0.0, score_boundary, hw_tables_or_null, 0.0};
     BeamWs ws;
     StreamParams<true> sp;
-    stream_carve(B, T_max, beam_width, max_candidates, lm, hw, static_cast<char*>(state), &ws, &sp);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const dim3 grid((unsigned)((B + 255) / 256)), block(256);
+    CFM_CHECK(stream_state(B, T_max, beam_width, max_candidates, fz, state, state_bytes, &ws, &sp));
     const int sb = score_boundary ? 1 : 0;
-    if (lm && hw) hipLaunchKernelGGL((beam_stream_init_kernel<true, true>), grid, block, 0, s, ws, sp, B, beam_width, lm_tables_or_null, sb);
-    else if (lm) hipLaunchKernelGGL((beam_stream_init_kernel<true, false>), grid, block, 0, s, ws, sp, B, beam_width, lm_tables_or_null, sb);
-    else if (hw) hipLaunchKernelGGL((beam_stream_init_kernel<false, true>), grid, block, 0, s, ws, sp, B, beam_width, lm_tables_or_null, sb);
-    else hipLaunchKernelGGL((beam_stream_init_kernel<false, false>), grid, block, 0, s, ws, sp, B, beam_width, lm_tables_or_null, sb);
+    beam_mode(fz, [&](auto lm, auto hw) {
+        hipLaunchKernelGGL((beam_stream_init_kernel<decltype(lm)::value, decltype(hw)::value>), dim3((unsigned)((B + 255) / 256)),
+                           dim3(256), 0, static_cast<hipStream_t>(stream), ws, sp, B, beam_width, lm_tables_or_null, sb);
+    });
     return cfm_launch_status();
 }
-
-namespace {
-
-// one launch of the resumable search in the mode the table pointers select (T = 0, logits unused: the finish)
-int beam_stream_launch(const float* logits, const int64_t* lengths, const BeamWs& ws, StreamParams<true> sp, int B, int T, int V,
-                       int blank, int W, int K, double prune, int N, const void* lm_tables, double alpha, double beta, double unk,
-                       int score_boundary, const void* hw_tables, double hw_weight, int64_t* tokens, int64_t* counts,
-                       float* scores, float* am_scores, int64_t* num_hyps, hipStream_t s) {
-    const dim3 grid((unsigned)B), block(BEAM_MAX_W);
-    const int sb = score_boundary ? 1 : 0;
-    if (lm_tables && hw_tables) {
-        const LmParams<true, true> lp{lm_tables, alpha, beta, unk, sb, am_scores, hw_tables, hw_weight};
-        hipLaunchKernelGGL((beam_search_kernel<true, true, true>), grid, block, 0, s, logits, lengths, ws, T, V, blank, W, K, prune,
-                           N, tokens, counts, scores, num_hyps, lp, sp);
-    } else if (lm_tables) {
-        const LmParams<true, false> lp{lm_tables, alpha, beta, unk, sb, am_scores};
-        hipLaunchKernelGGL((beam_search_kernel<true, false, true>), grid, block, 0, s, logits, lengths, ws, T, V, blank, W, K, prune,
-                           N, tokens, counts, scores, num_hyps, lp, sp);
-    } else if (hw_tables) {
-        const LmParams<false, true> lp{nullptr, alpha, beta, unk, sb, am_scores, hw_tables, hw_weight};
-        hipLaunchKernelGGL((beam_search_kernel<false, true, true>), grid, block, 0, s, logits, lengths, ws, T, V, blank, W, K, prune,
-                           N, tokens, counts, scores, num_hyps, lp, sp);
-    } else {
-        hipLaunchKernelGGL((beam_search_kernel<false, false, true>), grid, block, 0, s, logits, lengths, ws, T, V, blank, W, K, prune,
-                           N, tokens, counts, scores, num_hyps, LmParams<false>{}, sp);
-    }
-    return cfm_launch_status();
-}
-
-}  // namespace
 
 extern "C" int cfm_ctc_beam_stream_step_f32(const float* logits, const int64_t* lengths_or_null, int B, int Tc, int V,
                                             int blank_id, int beam_width, int max_candidates, float token_min_logp,
@@ -1075,32 +1072,19 @@ extern "C" int cfm_ctc_beam_stream_step_f32(const float* logits, const int64_t* 
                                             size_t state_bytes, int T_max, int t_used, int64_t* tokens, int64_t* counts,
                                             float* scores, float* am_scores_or_null, int64_t* num_hyps, cfm_stream_t stream) {
     CFM_REQUIRE(logits && state && tokens && counts && scores && num_hyps, CFM_ERR_NULL);
-    CFM_REQUIRE(B > 0 && Tc > 0 && T_max > 0 && V >= 2, CFM_ERR_BAD_SHAPE);
-    CFM_REQUIRE(beam_width >= 1 && beam_width <= BEAM_MAX_W, CFM_ERR_UNSUPPORTED);
-    CFM_REQUIRE(max_candidates >= 1 && max_candidates <= BEAM_MAX_K, CFM_ERR_UNSUPPORTED);
-    CFM_REQUIRE(n_best >= 1 && n_best <= beam_width, CFM_ERR_BAD_SHAPE);
-    CFM_REQUIRE(blank_id >= 0 && blank_id < V, CFM_ERR_BAD_SHAPE);
-    CFM_REQUIRE(V <= BEAM_MAX_V && (int64_t)T_max * beam_width < INT32_MAX, CFM_ERR_UNSUPPORTED);
+    CFM_REQUIRE(Tc > 0, CFM_ERR_BAD_SHAPE);
+    CFM_CHECK(beam_check(B, T_max, V, beam_width, max_candidates, n_best, blank_id, token_min_logp, beam_prune_logp));
     // t_used: chunk frames passed to the earlier steps since the init, a bound on what any utterance consumed
     CFM_REQUIRE(t_used >= 0 && t_used <= T_max && Tc <= T_max - t_used, CFM_ERR_BAD_SHAPE);
-    CFM_REQUIRE(!(token_min_logp != token_min_logp) && !(beam_prune_logp != beam_prune_logp), CFM_ERR_BAD_SHAPE);   // NaN
-    CFM_REQUIRE(__builtin_isfinite(alpha) && __builtin_isfinite(beta) && __builtin_isfinite(unk_score_offset), CFM_ERR_BAD_SHAPE);
-    CFM_REQUIRE(__builtin_isfinite(hotword_weight), CFM_ERR_BAD_SHAPE);
-    const bool lm = lm_tables_or_null != nullptr, hw = hw_tables_or_null != nullptr;
-    CFM_REQUIRE(state_bytes >= stream_carve(B, T_max, beam_width, max_candidates, lm, hw, nullptr, nullptr, nullptr),
-                CFM_ERR_BAD_SHAPE);
+    const Fusion fz{lm_tables_or_null, alpha, beta, unk_score_offset, score_boundary, hw_tables_or_null, hotword_weight};
+    CFM_REQUIRE(fz.finite(), CFM_ERR_BAD_SHAPE);
     BeamWs ws;
     StreamParams<true> sp;
-    stream_carve(B, T_max, beam_width, max_candidates, lm, hw, static_cast<char*>(state), &ws, &sp);
+    CFM_CHECK(stream_state(B, T_max, beam_width, max_candidates, fz, state, state_bytes, &ws, &sp));
     sp.am_out = am_scores_or_null;
     sp.finish = 0;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int64_t rows = (int64_t)B * Tc;
-    hipLaunchKernelGGL(beam_prep_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, logits, lengths_or_null, ws, B, Tc, V,
-                       blank_id, max_candidates, (double)token_min_logp);
-    return beam_stream_launch(logits, lengths_or_null, ws, sp, B, Tc, V, blank_id, beam_width, max_candidates,
-                              (double)beam_prune_logp, n_best, lm_tables_or_null, alpha, beta, unk_score_offset, score_boundary,
-                              hw_tables_or_null, hotword_weight, tokens, counts, scores, am_scores_or_null, num_hyps, s);
+    return beam_launch(logits, lengths_or_null, ws, sp, B, Tc, V, blank_id, beam_width, max_candidates, token_min_logp,
+                       beam_prune_logp, n_best, fz, tokens, counts, scores, am_scores_or_null, num_hyps, stream);
 }
 
 extern "C" int cfm_ctc_beam_stream_finish_f32(int B, int beam_width, int max_candidates, int n_best, const void* lm_tables_or_null,
@@ -1108,25 +1092,17 @@ extern "C" int cfm_ctc_beam_stream_finish_f32(int B, int beam_width, int max_can
                                               const void* hw_tables_or_null, double hotword_weight, void* state,
                                               size_t state_bytes, int T_max, int64_t* tokens, int64_t* counts, float* scores,
                                               float* am_scores_or_null, int64_t* num_hyps, cfm_stream_t stream) {
-    const bool lm = lm_tables_or_null != nullptr, hw = hw_tables_or_null != nullptr;
-    CFM_REQUIRE(state && tokens && counts && scores && num_hyps && (am_scores_or_null || !(lm || hw)), CFM_ERR_NULL);
-    CFM_REQUIRE(B > 0 && T_max > 0, CFM_ERR_BAD_SHAPE);
-    CFM_REQUIRE(beam_width >= 1 && beam_width <= BEAM_MAX_W, CFM_ERR_UNSUPPORTED);
-    CFM_REQUIRE(max_candidates >= 1 && max_candidates <= BEAM_MAX_K, CFM_ERR_UNSUPPORTED);
-    CFM_REQUIRE(n_best >= 1 && n_best <= beam_width, CFM_ERR_BAD_SHAPE);
-    CFM_REQUIRE((int64_t)T_max * beam_width < INT32_MAX, CFM_ERR_UNSUPPORTED);
-    CFM_REQUIRE(__builtin_isfinite(alpha) && __builtin_isfinite(beta) && __builtin_isfinite(unk_score_offset), CFM_ERR_BAD_SHAPE);
-    CFM_REQUIRE(__builtin_isfinite(hotword_weight), CFM_ERR_BAD_SHAPE);
-    CFM_REQUIRE(state_bytes >= stream_carve(B, T_max, beam_width, max_candidates, lm, hw, nullptr, nullptr, nullptr),
-                CFM_ERR_BAD_SHAPE);
+    const Fusion fz{lm_tables_or_null, alpha, beta, unk_score_offset, score_boundary, hw_tables_or_null, hotword_weight};
+    CFM_REQUIRE(state && tokens && counts && scores && num_hyps && (am_scores_or_null || !fz.on()), CFM_ERR_NULL);
+    CFM_CHECK(beam_check(B, T_max, 2, beam_width, max_candidates, n_best, 0, 0.f, 0.f));
+    CFM_REQUIRE(fz.finite(), CFM_ERR_BAD_SHAPE);
     BeamWs ws;
     StreamParams<true> sp;
-    stream_carve(B, T_max, beam_width, max_candidates, lm, hw, static_cast<char*>(state), &ws, &sp);
+    CFM_CHECK(stream_state(B, T_max, beam_width, max_candidates, fz, state, state_bytes, &ws, &sp));
     sp.am_out = nullptr;
     sp.finish = 1;
     // no frames: the kernel resumes the saved state and goes straight to the end-of-utterance step (LM / hotwords) or the
     // traceback (plain search)
-    return beam_stream_launch(nullptr, nullptr, ws, sp, B, 0, 2, 0, beam_width, max_candidates, 0.0, n_best, lm_tables_or_null,
-                              alpha, beta, unk_score_offset, score_boundary, hw_tables_or_null, hotword_weight, tokens, counts,
-                              scores, am_scores_or_null, num_hyps, static_cast<hipStream_t>(stream));
+    return beam_launch(nullptr, nullptr, ws, sp, B, 0, 2, 0, beam_width, max_candidates, 0.f, 0.f, n_best, fz, tokens, counts,
+                       scores, am_scores_or_null, num_hyps, stream);
 }

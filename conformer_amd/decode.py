@@ -51,6 +51,73 @@ def tokens_to_text(tokens: torch.Tensor, counts: torch.Tensor, vocab: Sequence[s
     return ["".join(vocab[i] for i in row[:n]).replace(delim_token, " ") for row, n in zip(tk, ct)]
 
 
+class _Fusion:
+    """The fusion group of a search: the device tables of the language model and of the hotwords (None: not used) and the
+    knobs.  `args` is the group as the C entries take it (lm_tables, alpha, beta, unk_score_offset, score_boundary, hw_tables,
+    hotword_weight); `fused`: the search has LM or hotword terms (and returns am_scores)."""
+
+    def __init__(self, lm_tables: Optional[torch.Tensor], hw_tables: Optional[torch.Tensor], alpha: float, beta: float,
+                 unk_score_offset: float, score_boundary: bool, hotword_weight: float = 0.0) -> None:
+        self.lm_tables, self.hw_tables = lm_tables, hw_tables
+        self.score_boundary = 1 if score_boundary else 0
+        self.fused = lm_tables is not None or hw_tables is not None
+        self.args = (ops._p(lm_tables), float(alpha), float(beta), float(unk_score_offset), self.score_boundary,
+                     ops._p(hw_tables), float(hotword_weight))
+
+
+_PLAIN = _Fusion(None, None, 0.0, 0.0, 0.0, False)
+
+
+def _logits(logits: torch.Tensor) -> torch.Tensor:
+    """fp32 logits on the device (bf16 / fp16 cast to fp32)"""
+    if isinstance(logits, torch.Tensor) and logits.dtype in (torch.bfloat16, torch.float16):
+        logits = logits.float()
+    return ops._req(logits, "logits")
+
+
+def _beam_outputs(B: int, N: int, T: int, device, fused: bool):
+    tokens = torch.empty(B, N, T, dtype=torch.int64, device=device)
+    counts = torch.empty(B, N, dtype=torch.int64, device=device)
+    scores = torch.empty(B, N, dtype=torch.float32, device=device)
+    am_scores = torch.empty(B, N, dtype=torch.float32, device=device) if fused else None
+    num_hyps = torch.empty(B, dtype=torch.int64, device=device)
+    return tokens, counts, scores, am_scores, num_hyps
+
+
+def _beam_search(logits: torch.Tensor, blank_id: int, lengths: Optional[torch.Tensor], n_best: int, beam_width: int,
+                 token_min_logp: float, beam_prune_logp: float, max_candidates: int, vocab: Optional[Sequence[str]] = None,
+                 fusion: Optional[Callable[[torch.device], _Fusion]] = None):
+    """The one-shot search behind beam_ctc_decode / beam_ctc_lm_decode / beam_ctc_hotword_decode and BeamCTCDecoder.
+    `fusion(device)` builds the fusion group on the logits' device (None: the plain search); `vocab` must then have V tokens.
+    Returns (tokens, counts, scores, num_hyps), with am_scores before num_hyps when fused."""
+    x = _logits(logits)
+    if x.dim() != 3:
+        raise ValueError(f"logits: expected (B,T,V), got {tuple(x.shape)}")
+    B, T, V = x.shape
+    if fusion is not None and len(vocab) != V:
+        raise ValueError(f"vocab has {len(vocab)} tokens, the logits {V}")
+    if lengths is not None:
+        lengths = ops._req(lengths, "lengths", torch.int64)
+    f = _PLAIN if fusion is None else fusion(x.device)
+    lib = _lib.load()
+    ws_bytes = lib.cfm_ctc_beam_workspace_bytes(B, T, int(beam_width), int(max_candidates))
+    workspace = torch.empty(max(int(ws_bytes), 1), dtype=torch.uint8, device=x.device)
+    tokens, counts, scores, am_scores, num_hyps = _beam_outputs(B, int(n_best), T, x.device, f.fused)
+    search = (x.data_ptr(), ops._p(lengths), B, T, V, int(blank_id), int(beam_width), int(max_candidates),
+              float(token_min_logp), float(beam_prune_logp), int(n_best))
+    out = (workspace.data_ptr(), int(ws_bytes), tokens.data_ptr(), counts.data_ptr(), scores.data_ptr())
+    if f.hw_tables is not None:
+        name, args = "cfm_ctc_beam_hw_decode_f32", search + f.args + out + (am_scores.data_ptr(),)
+    elif f.lm_tables is not None:      # the LM entry takes the group without the hotword pair
+        name, args = "cfm_ctc_beam_lm_decode_f32", search + f.args[:5] + out + (am_scores.data_ptr(),)
+    else:
+        name, args = "cfm_ctc_beam_decode_f32", search + out
+    _lib.check(getattr(lib, name)(*args, num_hyps.data_ptr(), ops._stream()), name)
+    if f.fused:
+        return tokens, counts, scores, am_scores, num_hyps
+    return tokens, counts, scores, num_hyps
+
+
 def beam_ctc_decode(logits: torch.Tensor, blank_id: int, lengths: Optional[torch.Tensor] = None, beam_width: int = 100,
                     n_best: int = 1, token_min_logp: float = -5.0, beam_prune_logp: float = -10.0, max_candidates: int = 16
                     ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
@@ -58,27 +125,7 @@ def beam_ctc_decode(logits: torch.Tensor, blank_id: int, lengths: Optional[torch
     Returns (tokens (B,N,T) int64 padded with -1, counts (B,N) int64, scores (B,N) fp32, num_hyps (B) int64), N = n_best,
     hypotheses best first; unused rows hold count 0, tokens -1 and score -inf.  `lengths` (B) int64 on the device: frames
     to consume per utterance (clamped to [0,T]; None = all).  Nothing synchronises with the host."""
-    if isinstance(logits, torch.Tensor) and logits.dtype in (torch.bfloat16, torch.float16):
-        logits = logits.float()
-    x = ops._req(logits, "logits")
-    if x.dim() != 3:
-        raise ValueError(f"logits: expected (B,T,V), got {tuple(x.shape)}")
-    B, T, V = x.shape
-    if lengths is not None:
-        lengths = ops._req(lengths, "lengths", torch.int64)
-    lib = _lib.load()
-    ws_bytes = lib.cfm_ctc_beam_workspace_bytes(B, T, int(beam_width), int(max_candidates))
-    workspace = torch.empty(max(int(ws_bytes), 1), dtype=torch.uint8, device=x.device)
-    tokens = torch.empty(B, n_best, T, dtype=torch.int64, device=x.device)
-    counts = torch.empty(B, n_best, dtype=torch.int64, device=x.device)
-    scores = torch.empty(B, n_best, dtype=torch.float32, device=x.device)
-    num_hyps = torch.empty(B, dtype=torch.int64, device=x.device)
-    st = lib.cfm_ctc_beam_decode_f32(x.data_ptr(), ops._p(lengths), B, T, V, int(blank_id), int(beam_width),
-                                     int(max_candidates), float(token_min_logp), float(beam_prune_logp), int(n_best),
-                                     workspace.data_ptr(), int(ws_bytes), tokens.data_ptr(), counts.data_ptr(),
-                                     scores.data_ptr(), num_hyps.data_ptr(), ops._stream())
-    _lib.check(st, "cfm_ctc_beam_decode_f32")
-    return tokens, counts, scores, num_hyps
+    return _beam_search(logits, blank_id, lengths, n_best, beam_width, token_min_logp, beam_prune_logp, max_candidates)
 
 
 def beam_ctc_lm_decode(logits: torch.Tensor, blank_id: int, lm: Union[NgramLanguageModel, str],
@@ -94,33 +141,11 @@ def beam_ctc_lm_decode(logits: torch.Tensor, blank_id: int, lm: Union[NgramLangu
     acoustic, num_hyps (B) int64), best first by the final fused score; unused rows hold count 0, tokens -1 and scores
     -inf.  The device tables are packed and copied once per (lm, vocab, delim_token, skip_ids); after that nothing
     synchronises with the host."""
-    if isinstance(logits, torch.Tensor) and logits.dtype in (torch.bfloat16, torch.float16):
-        logits = logits.float()
-    x = ops._req(logits, "logits")
-    if x.dim() != 3:
-        raise ValueError(f"logits: expected (B,T,V), got {tuple(x.shape)}")
-    B, T, V = x.shape
-    if len(vocab) != V:
-        raise ValueError(f"vocab has {len(vocab)} tokens, the logits {V}")
-    if lengths is not None:
-        lengths = ops._req(lengths, "lengths", torch.int64)
-    tables = as_language_model(lm).device_tables(vocab, delim_token, skip_ids, x.device)
-    lib = _lib.load()
-    ws_bytes = lib.cfm_ctc_beam_lm_workspace_bytes(B, T, int(beam_width), int(max_candidates))
-    workspace = torch.empty(max(int(ws_bytes), 1), dtype=torch.uint8, device=x.device)
-    tokens = torch.empty(B, n_best, T, dtype=torch.int64, device=x.device)
-    counts = torch.empty(B, n_best, dtype=torch.int64, device=x.device)
-    scores = torch.empty(B, n_best, dtype=torch.float32, device=x.device)
-    am_scores = torch.empty(B, n_best, dtype=torch.float32, device=x.device)
-    num_hyps = torch.empty(B, dtype=torch.int64, device=x.device)
-    st = lib.cfm_ctc_beam_lm_decode_f32(x.data_ptr(), ops._p(lengths), B, T, V, int(blank_id), int(beam_width),
-                                        int(max_candidates), float(token_min_logp), float(beam_prune_logp), int(n_best),
-                                        tables.data_ptr(), float(alpha), float(beta), float(unk_score_offset),
-                                        1 if score_boundary else 0, workspace.data_ptr(), int(ws_bytes), tokens.data_ptr(),
-                                        counts.data_ptr(), scores.data_ptr(), am_scores.data_ptr(), num_hyps.data_ptr(),
-                                        ops._stream())
-    _lib.check(st, "cfm_ctc_beam_lm_decode_f32")
-    return tokens, counts, scores, am_scores, num_hyps
+    def fusion(device):
+        return _Fusion(as_language_model(lm).device_tables(vocab, delim_token, skip_ids, device), None, alpha, beta,
+                       unk_score_offset, score_boundary)
+    return _beam_search(logits, blank_id, lengths, n_best, beam_width, token_min_logp, beam_prune_logp, max_candidates,
+                        vocab, fusion)
 
 
 def beam_ctc_hotword_decode(logits: torch.Tensor, blank_id: int, hotwords: Union[Hotwords, Iterable[str]],
@@ -141,36 +166,14 @@ def beam_ctc_hotword_decode(logits: torch.Tensor, blank_id: int, hotwords: Union
     host."""
     if not math.isfinite(float(hotword_weight)):
         raise ValueError(f"hotword_weight must be finite, got {hotword_weight}")
-    if isinstance(logits, torch.Tensor) and logits.dtype in (torch.bfloat16, torch.float16):
-        logits = logits.float()
-    x = ops._req(logits, "logits")
-    if x.dim() != 3:
-        raise ValueError(f"logits: expected (B,T,V), got {tuple(x.shape)}")
-    B, T, V = x.shape
-    if len(vocab) != V:
-        raise ValueError(f"vocab has {len(vocab)} tokens, the logits {V}")
-    if lengths is not None:
-        lengths = ops._req(lengths, "lengths", torch.int64)
-    hw = hotwords if isinstance(hotwords, Hotwords) else Hotwords(hotwords)
-    hw_tables = hw.device_tables(vocab, delim_token, skip_ids, x.device)
-    lm_tables = None if lm is None else as_language_model(lm).device_tables(vocab, delim_token, skip_ids, x.device)
-    lib = _lib.load()
-    ws_bytes = lib.cfm_ctc_beam_hw_workspace_bytes(B, T, int(beam_width), int(max_candidates))
-    workspace = torch.empty(max(int(ws_bytes), 1), dtype=torch.uint8, device=x.device)
-    tokens = torch.empty(B, n_best, T, dtype=torch.int64, device=x.device)
-    counts = torch.empty(B, n_best, dtype=torch.int64, device=x.device)
-    scores = torch.empty(B, n_best, dtype=torch.float32, device=x.device)
-    am_scores = torch.empty(B, n_best, dtype=torch.float32, device=x.device)
-    num_hyps = torch.empty(B, dtype=torch.int64, device=x.device)
-    st = lib.cfm_ctc_beam_hw_decode_f32(x.data_ptr(), ops._p(lengths), B, T, V, int(blank_id), int(beam_width),
-                                        int(max_candidates), float(token_min_logp), float(beam_prune_logp), int(n_best),
-                                        None if lm_tables is None else lm_tables.data_ptr(), float(alpha), float(beta),
-                                        float(unk_score_offset), 1 if score_boundary else 0, hw_tables.data_ptr(),
-                                        float(hotword_weight), workspace.data_ptr(), int(ws_bytes), tokens.data_ptr(),
-                                        counts.data_ptr(), scores.data_ptr(), am_scores.data_ptr(), num_hyps.data_ptr(),
-                                        ops._stream())
-    _lib.check(st, "cfm_ctc_beam_hw_decode_f32")
-    return tokens, counts, scores, am_scores, num_hyps
+
+    def fusion(device):
+        hw = hotwords if isinstance(hotwords, Hotwords) else Hotwords(hotwords)
+        hw_tables = hw.device_tables(vocab, delim_token, skip_ids, device)
+        lm_tables = None if lm is None else as_language_model(lm).device_tables(vocab, delim_token, skip_ids, device)
+        return _Fusion(lm_tables, hw_tables, alpha, beta, unk_score_offset, score_boundary, hotword_weight)
+    return _beam_search(logits, blank_id, lengths, n_best, beam_width, token_min_logp, beam_prune_logp, max_candidates,
+                        vocab, fusion)
 
 
 class BeamCTCDecoder:
@@ -216,6 +219,24 @@ class BeamCTCDecoder:
         joined = "".join(self.vocab[i] for i in ids if i not in self.skip_ids)
         return " ".join(joined.replace(self.delim_token, " ").split())
 
+    def _fusion(self, device) -> _Fusion:
+        """The decoder's fusion group on `device`: its LM and hotword tables (packed and copied once per device) and knobs."""
+        if self.lm is None and self.hotwords is None:
+            return _PLAIN
+        skip = tuple(sorted(self.skip_ids))
+        lm_tables = None if self.lm is None else self.lm.device_tables(self.vocab, self.delim_token, skip, device)
+        hw_tables = None if self.hotwords is None else self.hotwords.device_tables(self.vocab, self.delim_token, skip, device)
+        return _Fusion(lm_tables, hw_tables, self.alpha, self.beta, self.unk_score_offset, self.score_boundary,
+                       self.hotword_weight)
+
+    def _texts(self, tokens: torch.Tensor, counts: torch.Tensor, decode_func: Optional[Callable[[str], str]] = None
+               ) -> List[str]:
+        preds = []
+        for row, n in zip(tokens[:, 0].cpu().tolist(), counts[:, 0].cpu().tolist()):
+            text = self.text(row[:n])
+            preds.append(decode_func(text) if decode_func is not None else text)
+        return preds
+
     def __call__(self, logits: torch.Tensor, lengths: Optional[torch.Tensor] = None,
                  decode_func: Optional[Callable[[str], str]] = None) -> Union[str, List[str]]:
         single = logits.dim() == 2
@@ -223,28 +244,10 @@ class BeamCTCDecoder:
             logits = logits.unsqueeze(0)
         if lengths is not None and not (isinstance(lengths, torch.Tensor) and lengths.is_cuda):
             lengths = torch.as_tensor(lengths, dtype=torch.int64).reshape(-1).to(logits.device)   # numpy lengths, as lm.py takes
-        if self.hotwords is not None:
-            tokens, counts, _, _, _ = beam_ctc_hotword_decode(
-                logits, self.blank_id, self.hotwords, lengths, vocab=self.vocab, delim_token=self.delim_token,
-                skip_ids=tuple(sorted(self.skip_ids)), hotword_weight=self.hotword_weight, lm=self.lm, alpha=self.alpha,
-                beta=self.beta, unk_score_offset=self.unk_score_offset, score_boundary=self.score_boundary,
-                beam_width=self.beam_width, n_best=1, token_min_logp=self.token_min_logp,
-                beam_prune_logp=self.beam_prune_logp, max_candidates=self.max_candidates)
-        elif self.lm is None:
-            tokens, counts, _, _ = beam_ctc_decode(logits, self.blank_id, lengths, beam_width=self.beam_width, n_best=1,
-                                                   token_min_logp=self.token_min_logp, beam_prune_logp=self.beam_prune_logp,
-                                                   max_candidates=self.max_candidates)
-        else:
-            tokens, counts, _, _, _ = beam_ctc_lm_decode(
-                logits, self.blank_id, self.lm, lengths, vocab=self.vocab, delim_token=self.delim_token,
-                skip_ids=tuple(sorted(self.skip_ids)), alpha=self.alpha, beta=self.beta,
-                unk_score_offset=self.unk_score_offset, score_boundary=self.score_boundary, beam_width=self.beam_width,
-                n_best=1, token_min_logp=self.token_min_logp, beam_prune_logp=self.beam_prune_logp,
-                max_candidates=self.max_candidates)
-        preds = []
-        for row, n in zip(tokens[:, 0].cpu().tolist(), counts[:, 0].cpu().tolist()):
-            text = self.text(row[:n])
-            preds.append(decode_func(text) if decode_func is not None else text)
+        fusion = None if self.lm is None and self.hotwords is None else self._fusion
+        out = _beam_search(logits, self.blank_id, lengths, 1, self.beam_width, self.token_min_logp, self.beam_prune_logp,
+                           self.max_candidates, self.vocab, fusion)
+        preds = self._texts(out[0], out[1], decode_func)
         return preds[0] if single else preds
 
 
@@ -253,22 +256,11 @@ class BeamCTCDecoder:
 class _StreamState:
     """The device buffer of one resumable search and the mode it was initialised for (what beam_ctc_stream_* pass back)."""
 
-    def __init__(self, buf: torch.Tensor, B: int, t_max: int, beam_width: int, max_candidates: int, lm_tables, hw_tables,
-                 knobs: dict) -> None:
+    def __init__(self, buf: torch.Tensor, B: int, t_max: int, beam_width: int, max_candidates: int, fusion: _Fusion) -> None:
         self.buf, self.B, self.t_max = buf, B, t_max
         self.beam_width, self.max_candidates = beam_width, max_candidates
-        self.lm_tables, self.hw_tables = lm_tables, hw_tables
-        self.knobs = knobs
+        self.fusion = fusion
         self.t_used = 0                    # chunk frames stepped since the init: a bound on what any utterance consumed
-
-
-def _stream_outputs(B: int, N: int, T: int, device, fused: bool):
-    tokens = torch.empty(B, N, T, dtype=torch.int64, device=device)
-    counts = torch.empty(B, N, dtype=torch.int64, device=device)
-    scores = torch.empty(B, N, dtype=torch.float32, device=device)
-    am_scores = torch.empty(B, N, dtype=torch.float32, device=device) if fused else None
-    num_hyps = torch.empty(B, dtype=torch.int64, device=device)
-    return tokens, counts, scores, am_scores, num_hyps
 
 
 def beam_ctc_stream_init(batch: int, max_frames: int, device, *, beam_width: int = 100, max_candidates: int = 16,
@@ -286,18 +278,18 @@ def beam_ctc_stream_init(batch: int, max_frames: int, device, *, beam_width: int
         raise ValueError(f"beam_ctc_stream_init: unsupported arguments (B={B}, max_frames={Tm}, beam_width={W}, "
                          f"max_candidates={K})")
     buf = torch.empty(nbytes, dtype=torch.uint8, device=device)
-    st = _StreamState(buf, B, Tm, W, K, lm_tables, hw_tables,
-                      dict(alpha=float(alpha), beta=float(beta), unk_score_offset=float(unk_score_offset),
-                           score_boundary=1 if score_boundary else 0, hotword_weight=float(hotword_weight)))
+    st = _StreamState(buf, B, Tm, W, K,
+                      _Fusion(lm_tables, hw_tables, alpha, beta, unk_score_offset, score_boundary, hotword_weight))
     beam_ctc_stream_reset(st)
     return st
 
 
 def beam_ctc_stream_reset(st: _StreamState) -> None:
     """Every utterance back at the empty prefix (enqueues only)."""
-    _lib.check(_lib.load().cfm_ctc_beam_stream_init(st.B, st.t_max, st.beam_width, st.max_candidates,
-                                                    ops._p(st.lm_tables), st.knobs["score_boundary"], ops._p(st.hw_tables),
-                                                    st.buf.data_ptr(), st.buf.numel(), ops._stream()),
+    f = st.fusion
+    _lib.check(_lib.load().cfm_ctc_beam_stream_init(st.B, st.t_max, st.beam_width, st.max_candidates, ops._p(f.lm_tables),
+                                                    f.score_boundary, ops._p(f.hw_tables), st.buf.data_ptr(),
+                                                    st.buf.numel(), ops._stream()),
                "cfm_ctc_beam_stream_init")
     st.t_used = 0
 
@@ -308,9 +300,7 @@ def beam_ctc_stream_step(st: _StreamState, logits: torch.Tensor, blank_id: int, 
     (None: all).  Returns the interim best (tokens (B,N,max_frames) int64 padded with -1, counts (B,N), scores (B,N) fp32
     without end-of-utterance terms, am_scores (B,N) fp32 or None without LM and hotwords, num_hyps (B)), device tensors;
     nothing synchronises with the host."""
-    if isinstance(logits, torch.Tensor) and logits.dtype in (torch.bfloat16, torch.float16):
-        logits = logits.float()
-    x = ops._req(logits, "logits")
+    x = _logits(logits)
     if x.dim() != 3 or x.shape[0] != st.B:
         raise ValueError(f"logits: expected ({st.B},Tc,V), got {tuple(x.shape)}")
     _, Tc, V = x.shape
@@ -321,15 +311,11 @@ def beam_ctc_stream_step(st: _StreamState, logits: torch.Tensor, blank_id: int, 
                          f"({st.t_used} stepped so far)")
     if lengths is not None:
         lengths = ops._req(lengths, "lengths", torch.int64)
-    fused = st.lm_tables is not None or st.hw_tables is not None
-    tokens, counts, scores, am_scores, num_hyps = _stream_outputs(st.B, int(n_best), st.t_max, x.device, fused)
-    k = st.knobs
+    tokens, counts, scores, am_scores, num_hyps = _beam_outputs(st.B, int(n_best), st.t_max, x.device, st.fusion.fused)
     status = _lib.load().cfm_ctc_beam_stream_step_f32(
         x.data_ptr(), ops._p(lengths), st.B, Tc, V, int(blank_id), st.beam_width, st.max_candidates, float(token_min_logp),
-        float(beam_prune_logp), int(n_best), ops._p(st.lm_tables), k["alpha"], k["beta"], k["unk_score_offset"],
-        k["score_boundary"], ops._p(st.hw_tables), k["hotword_weight"], st.buf.data_ptr(), st.buf.numel(), st.t_max,
-        st.t_used, tokens.data_ptr(), counts.data_ptr(), scores.data_ptr(), ops._p(am_scores), num_hyps.data_ptr(),
-        ops._stream())
+        float(beam_prune_logp), int(n_best), *st.fusion.args, st.buf.data_ptr(), st.buf.numel(), st.t_max, st.t_used,
+        tokens.data_ptr(), counts.data_ptr(), scores.data_ptr(), ops._p(am_scores), num_hyps.data_ptr(), ops._stream())
     _lib.check(status, "cfm_ctc_beam_stream_step_f32")
     st.t_used += Tc
     return tokens, counts, scores, am_scores, num_hyps
@@ -338,14 +324,11 @@ def beam_ctc_stream_step(st: _StreamState, logits: torch.Tensor, blank_id: int, 
 def beam_ctc_stream_finish(st: _StreamState, n_best: int = 1):
     """The end-of-utterance step over the consumed frames: (tokens (B,N,max_frames), counts, scores, am_scores or None
     without LM and hotwords, num_hyps), equal bit for bit to one-shot decoding of the consumed frames (with T = max_frames)."""
-    fused = st.lm_tables is not None or st.hw_tables is not None
-    tokens, counts, scores, am_scores, num_hyps = _stream_outputs(st.B, int(n_best), st.t_max, st.buf.device, fused)
-    k = st.knobs
+    tokens, counts, scores, am_scores, num_hyps = _beam_outputs(st.B, int(n_best), st.t_max, st.buf.device,
+                                                                st.fusion.fused)
     status = _lib.load().cfm_ctc_beam_stream_finish_f32(
-        st.B, st.beam_width, st.max_candidates, int(n_best), ops._p(st.lm_tables), k["alpha"], k["beta"],
-        k["unk_score_offset"], k["score_boundary"], ops._p(st.hw_tables), k["hotword_weight"], st.buf.data_ptr(),
-        st.buf.numel(), st.t_max, tokens.data_ptr(), counts.data_ptr(), scores.data_ptr(), ops._p(am_scores),
-        num_hyps.data_ptr(), ops._stream())
+        st.B, st.beam_width, st.max_candidates, int(n_best), *st.fusion.args, st.buf.data_ptr(), st.buf.numel(), st.t_max,
+        tokens.data_ptr(), counts.data_ptr(), scores.data_ptr(), ops._p(am_scores), num_hyps.data_ptr(), ops._stream())
     _lib.check(status, "cfm_ctc_beam_stream_finish_f32")
     return tokens, counts, scores, am_scores, num_hyps
 
@@ -358,16 +341,9 @@ class BeamCTCStream:
     def __init__(self, decoder: "BeamCTCDecoder", batch: int, max_frames: int, device=None) -> None:
         self.decoder = decoder
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        d = decoder
-        lm_tables = hw_tables = None
-        if d.hotwords is not None or d.lm is not None:
-            skip = tuple(sorted(d.skip_ids))
-            if d.lm is not None:
-                lm_tables = d.lm.device_tables(d.vocab, d.delim_token, skip, self.device)
-            if d.hotwords is not None:
-                hw_tables = d.hotwords.device_tables(d.vocab, d.delim_token, skip, self.device)
+        d, f = decoder, decoder._fusion(self.device)
         self.state = beam_ctc_stream_init(batch, max_frames, self.device, beam_width=d.beam_width,
-                                          max_candidates=d.max_candidates, lm_tables=lm_tables, hw_tables=hw_tables,
+                                          max_candidates=d.max_candidates, lm_tables=f.lm_tables, hw_tables=f.hw_tables,
                                           alpha=d.alpha, beta=d.beta, unk_score_offset=d.unk_score_offset,
                                           score_boundary=d.score_boundary, hotword_weight=d.hotword_weight)
         self.finished = False
@@ -386,25 +362,18 @@ class BeamCTCStream:
         self.last = out
         return out[0], out[1], out[2]
 
-    def _texts(self, tokens, counts, decode_func=None) -> List[str]:
-        preds = []
-        for row, n in zip(tokens[:, 0].cpu().tolist(), counts[:, 0].cpu().tolist()):
-            text = self.decoder.text(row[:n])
-            preds.append(decode_func(text) if decode_func is not None else text)
-        return preds
-
     def partial_text(self) -> List[str]:
         """The interim best transcript of every utterance after the latest step (empty strings before the first)."""
         if self.last is None:
             return [""] * self.state.B
-        return self._texts(self.last[0], self.last[1])
+        return self.decoder._texts(self.last[0], self.last[1])
 
     def finish(self, decode_func: Optional[Callable[[str], str]] = None) -> List[str]:
         if self.finished:
             raise RuntimeError("BeamCTCStream.finish() called twice: call reset() to start a new stream")
         tokens, counts, _, _, _ = beam_ctc_stream_finish(self.state, n_best=1)
         self.finished = True
-        return self._texts(tokens, counts, decode_func)
+        return self.decoder._texts(tokens, counts, decode_func)
 
     def reset(self) -> None:
         beam_ctc_stream_reset(self.state)

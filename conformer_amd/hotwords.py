@@ -15,18 +15,19 @@ from typing import Dict, Iterable, List, Optional, Sequence, Tuple, Union
 import numpy as np
 
 from . import _lib
-from .lm import TOK_CHARS, TOK_DELIM, TOK_SKIP
+from .lm import TOK_CHARS, TOK_DELIM, TOK_SKIP, PackedTables, token_code_points
 
 MAX_WORDS = 8            # words per phrase
 MAX_PHRASES = 1024
 
 
-class Hotwords:
+class Hotwords(PackedTables):
     """A hotword list: `phrases` normalised in the given order (split on whitespace and re-joined with single spaces, empty
     entries and duplicates dropped, the first kept), `priority` the same phrases by code-point length descending (stable),
     `unigrams` every word of every phrase (first seen in priority order).  Matching is by exact code points."""
 
     def __init__(self, phrases: Iterable[str]) -> None:
+        super().__init__()
         if isinstance(phrases, (str, bytes)):
             raise ValueError("hotwords: expected a sequence of str, got a single string")
         out: List[str] = []
@@ -56,8 +57,6 @@ class Hotwords:
                     self.unigrams.append(w)
                 ids.append(uid[w])
             self.phrase_ids.append(ids)
-        self._packed: Dict[tuple, np.ndarray] = {}
-        self._device: Dict[tuple, object] = {}
 
     def __len__(self) -> int:
         return len(self.phrases)
@@ -77,18 +76,9 @@ class Hotwords:
         return kinds
 
     # ---- device tables
-    def pack(self, vocab: Sequence[str], delim_token: str = "|", skip_ids: Iterable[int] = ()) -> np.ndarray:
-        """The hotword tables (uint8) for this vocabulary: a token equal to `delim_token` or " " is a word delimiter, tokens
-        in `skip_ids` have no characters, every other token spells its code points."""
-        skip = frozenset(int(i) for i in skip_ids)
-        key = (tuple(vocab), delim_token, skip)
-        if key in self._packed:
-            return self._packed[key]
+    def _pack(self, vocab: Sequence[str], delim_token: str, skip: frozenset) -> np.ndarray:
         kinds = self.token_kinds(vocab, delim_token, skip)
-        tok_cps = [[ord(ch) for ch in t] if k == TOK_CHARS else [] for t, k in zip(vocab, kinds)]
-        tok_off = np.zeros(len(vocab) + 1, dtype=np.int64)
-        tok_off[1:] = np.cumsum([len(c) for c in tok_cps])
-        tok_cp = np.array([c for cs in tok_cps for c in cs], dtype=np.int32)
+        tok_off, tok_cp = token_code_points(vocab, kinds)
         uni_off = np.zeros(len(self.unigrams) + 1, dtype=np.int64)
         uni_off[1:] = np.cumsum([len(w) for w in self.unigrams])
         uni_cp = np.array([ord(ch) for w in self.unigrams for ch in w], dtype=np.int32)
@@ -107,20 +97,7 @@ class Hotwords:
                                   tok_off.ctypes.data_as(ctypes.c_void_p), p(tok_cp), kinds.ctypes.data_as(ctypes.c_void_p),
                                   blob.ctypes.data_as(ctypes.c_void_p), blob.nbytes)
         _lib.check(st, "cfm_hotword_pack")
-        self._packed[key] = blob
         return blob
-
-    def device_tables(self, vocab: Sequence[str], delim_token: str = "|", skip_ids: Iterable[int] = (), device=None):
-        """The packed tables as a uint8 tensor on `device`, packed and copied once per (vocab, delimiter, skip ids, device)."""
-        import torch
-        device = torch.device(device if device is not None else "cuda")
-        skip = frozenset(int(i) for i in skip_ids)
-        key = (tuple(vocab), delim_token, skip, str(device))
-        t = self._device.get(key)
-        if t is None:
-            t = torch.from_numpy(self.pack(vocab, delim_token, skip)).to(device)
-            self._device[key] = t
-        return t
 
     def count(self, sequences: Sequence[Sequence[int]], vocab: Sequence[str], delim_token: str = "|",
               skip_ids: Iterable[int] = (), weight: float = 9.0) -> List[Tuple[List[int], List[float], int]]:

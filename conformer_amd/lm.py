@@ -33,12 +33,55 @@ def _open_arpa(path: str):
     return open(path, "r", encoding="utf-8")
 
 
-class NgramLanguageModel:
+class PackedTables:
+    """What NgramLanguageModel and Hotwords share: the tables `_pack` writes for a vocabulary, cached per (vocab, delimiter,
+    skip ids) on the host and per device."""
+
+    def __init__(self) -> None:
+        self._packed: Dict[tuple, np.ndarray] = {}
+        self._device: Dict[tuple, object] = {}
+
+    def _pack(self, vocab: Sequence[str], delim_token: str, skip: frozenset) -> np.ndarray:
+        raise NotImplementedError
+
+    def pack(self, vocab: Sequence[str], delim_token: str = "|", skip_ids: Iterable[int] = ()) -> np.ndarray:
+        """The device tables (uint8) for this vocabulary: a token equal to `delim_token` or " " is a word delimiter, tokens in
+        `skip_ids` have no characters, every other token spells its code points."""
+        skip = frozenset(int(i) for i in skip_ids)
+        key = (tuple(vocab), delim_token, skip)
+        blob = self._packed.get(key)
+        if blob is None:
+            blob = self._packed[key] = self._pack(vocab, delim_token, skip)
+        return blob
+
+    def device_tables(self, vocab: Sequence[str], delim_token: str = "|", skip_ids: Iterable[int] = (), device=None):
+        """The packed tables as a uint8 tensor on `device`, packed and copied once per (vocab, delimiter, skip ids, device)."""
+        import torch
+        device = torch.device(device if device is not None else "cuda")
+        skip = frozenset(int(i) for i in skip_ids)
+        key = (tuple(vocab), delim_token, skip, str(device))
+        t = self._device.get(key)
+        if t is None:
+            t = torch.from_numpy(self.pack(vocab, delim_token, skip)).to(device)
+            self._device[key] = t
+        return t
+
+
+def token_code_points(vocab: Sequence[str], kinds: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+    """CSR code points of the vocabulary tokens of kind TOK_CHARS (the others spell nothing): (offsets (V+1), code points)."""
+    tok_cps = [[ord(ch) for ch in t] if k == TOK_CHARS else [] for t, k in zip(vocab, kinds)]
+    tok_off = np.zeros(len(vocab) + 1, dtype=np.int64)
+    tok_off[1:] = np.cumsum([len(c) for c in tok_cps])
+    return tok_off, np.array([c for cs in tok_cps for c in cs], dtype=np.int32)
+
+
+class NgramLanguageModel(PackedTables):
     """An ARPA word n-gram model: `words[i]` is the word with id i (the order of the 1-gram section; `<unk>` appended with
     log10 p = -100 when the file has none); `ngrams[n-1] = (ids (count, n) int32, logp (count,) float32, backoff (count,)
     float32)` for n = 1..order, backoff 0 where the file gives none."""
 
     def __init__(self, words: List[str], ngrams: List[Tuple[np.ndarray, np.ndarray, np.ndarray]]) -> None:
+        super().__init__()
         self.words = list(words)
         self.word_id: Dict[str, int] = {w: i for i, w in enumerate(self.words)}
         if len(self.word_id) != len(self.words):
@@ -51,8 +94,6 @@ class NgramLanguageModel:
             if name not in self.word_id:
                 raise ValueError(f"the model has no {name}")
         self.bos, self.eos, self.unk = self.word_id["<s>"], self.word_id["</s>"], self.word_id["<unk>"]
-        self._packed: Dict[tuple, np.ndarray] = {}
-        self._device: Dict[tuple, object] = {}
 
     @property
     def counts(self) -> List[int]:
@@ -170,19 +211,10 @@ class NgramLanguageModel:
         return cls(words, ngrams)
 
     # ---- device tables
-    def pack(self, vocab: Sequence[str], delim_token: str = "|", skip_ids: Iterable[int] = ()) -> np.ndarray:
-        """The device tables (uint8) for this vocabulary: a token equal to `delim_token` or " " is a word delimiter, tokens in
-        `skip_ids` have no characters, every other token spells its code points."""
-        skip = frozenset(int(i) for i in skip_ids)
-        key = (tuple(vocab), delim_token, skip)
-        if key in self._packed:
-            return self._packed[key]
+    def _pack(self, vocab: Sequence[str], delim_token: str, skip: frozenset) -> np.ndarray:
         kinds = np.array([TOK_SKIP if i in skip else TOK_DELIM if t in (delim_token, " ") else TOK_CHARS
                           for i, t in enumerate(vocab)], dtype=np.int32)
-        tok_cps = [[ord(ch) for ch in t] if k == TOK_CHARS else [] for t, k in zip(vocab, kinds)]
-        tok_off = np.zeros(len(vocab) + 1, dtype=np.int64)
-        tok_off[1:] = np.cumsum([len(c) for c in tok_cps])
-        tok_cp = np.array([c for cs in tok_cps for c in cs], dtype=np.int32)
+        tok_off, tok_cp = token_code_points(vocab, kinds)
         word_off = np.zeros(len(self.words) + 1, dtype=np.int64)
         word_off[1:] = np.cumsum([len(w) for w in self.words])
         word_cp = np.array([ord(ch) for w in self.words for ch in w], dtype=np.int32)
@@ -202,20 +234,7 @@ class NgramLanguageModel:
                                    self.unk, len(vocab), tok_off.ctypes.data_as(ctypes.c_void_p), p(tok_cp),
                                    kinds.ctypes.data_as(ctypes.c_void_p), blob.ctypes.data_as(ctypes.c_void_p), blob.nbytes)
         _lib.check(st, "cfm_ngram_lm_pack")
-        self._packed[key] = blob
         return blob
-
-    def device_tables(self, vocab: Sequence[str], delim_token: str = "|", skip_ids: Iterable[int] = (), device=None):
-        """The packed tables as a uint8 tensor on `device`, packed and copied once per (vocab, delimiter, skip ids, device)."""
-        import torch
-        device = torch.device(device if device is not None else "cuda")
-        skip = frozenset(int(i) for i in skip_ids)
-        key = (tuple(vocab), delim_token, skip, str(device))
-        t = self._device.get(key)
-        if t is None:
-            t = torch.from_numpy(self.pack(vocab, delim_token, skip)).to(device)
-            self._device[key] = t
-        return t
 
     def score_sentences(self, sentences: Sequence[Sequence[Union[str, int]]], boundary: bool = True, device=None):
         """log10 probability of each sentence (a list of words or word ids; unknown words score as <unk>) on the device,

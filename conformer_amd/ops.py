@@ -1054,6 +1054,13 @@ def linear_bwd(x2d, w, dy2d, *, alpha: float = 1.0, Z=None, need_dx: bool = True
         # a producer wrote its gradient in the 16-bit type for a consumer whose shape the aligned 16-bit kernels do not cover
         # (d % 8 == 4): widen it and take the general kernels rather than refuse (off the tuned shapes; one stock cast)
         dy2d, dy16 = dy2d.float(), False
+    if x2d.dtype != torch.float32:
+        if not (prec and x2d.dtype == _DT16[prec]):
+            raise _lib.ConformerHipError("a 16-bit x needs the matching 16-bit precision mode")
+        if k % 8 or x2d.stride(0) % 8 or x2d.stride(1) != 1:
+            # the 16-bit B operand of the weight-gradient kernels needs 8-element rows: widen (the kernels round it back to
+            # the same 16-bit values while staging)
+            x2d = x2d.float()
     if dy2d.stride(0) & 3:                        # e.g. the vocabulary projection (N = 370): rows must start 16-byte aligned
         padded = torch.zeros(m, (n + 3) // 4 * 4, device=dy2d.device, dtype=dy2d.dtype)
         padded[:, :n] = dy2d

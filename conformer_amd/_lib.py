@@ -125,6 +125,7 @@ SIGNATURES = {
                                              _P, _P, _P]),
     "cfm_ctc_beam_stream_finish_f32": (c_int, [_I, _I, _I, _I, _P, ctypes.c_double, ctypes.c_double, ctypes.c_double, _I, _P,
                                                ctypes.c_double, _P, ctypes.c_size_t, _I, _P, _P, _P, _P, _P, _P]),
+    "cfm_ctc_beam_stream_reset_slots": (c_int, [_I, _I, _I, _I, _P, _I, _P, _P, _I, _P, ctypes.c_size_t, _P]),
     "cfm_lstm_fwd_carry_f32": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "cfm_lstm_fwd_frag_carry_f32": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "cfm_lstm_fwd_mfma16_carry_f32": (c_int, [_I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
@@ -148,6 +149,7 @@ SIGNATURES = {
     "cfm_ctc_loss_fwd_f32": (c_int, [_P, _P, _P, _L, _L, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "cfm_ctc_loss_bwd_f32": (c_int, [_P, _P, _P, _L, _L, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "cfm_relpos_attention_rows_f32": (c_int, [_P, _P, _P, _L, _P, _L, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "cfm_relpos_attention_slots_f32": (c_int, [_P, _P, _P, _L, _P, _L, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _P, _P]),
     "cfm_debug_attention_trace_f32": (c_int, [_P, _P, _P, _L, _P, _L, _P, _P, _P, _P, _L, _I, _I, _I, _I, _P, _P]),
     "cfm_debug_set_bwd_tile": (c_int, [_I]),
     "cfm_debug_set_attention_waves": (c_int, [_I]),

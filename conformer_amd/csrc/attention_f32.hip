@@ -23,6 +23,7 @@
 // underflows to exactly 0; lengths[b] <= 0 reproduces its uniform-softmax degenerate case).
 #include "cfm_common.h"
 #include <math.h>
+#include <type_traits>
 
 namespace {
 
@@ -40,6 +41,27 @@ struct AttnArgs {
     unsigned long long* trace;                      // diagnostics (cfm_debug_attention_trace_f32): phase stamps of one wave
 };
 
+// Independent streams (cfm_relpos_attention_slots_f32): slot b computes cache rows [slot_begin[b], slot_begin[b] + slot_count[b])
+// into the COMPACT rows ctx[b, 0 .. q_max) (rows >= its count written as zeros).  The device values are clamped here, never
+// trusted: a slot's rows stay inside [0, T) and [0, q_max) whatever the arrays hold.
+struct SlotAttnArgs : AttnArgs {
+    const int64_t* slot_begin; const int64_t* slot_count; int q_max;
+};
+template <bool SLOTS> using AttnArgsT = std::conditional_t<SLOTS, SlotAttnArgs, AttnArgs>;
+
+// rows of one (b, h) the partial results / compact output hold: the launch's rows, or q_max per slot
+template <bool SLOTS> __device__ __forceinline__ int launch_rows(const AttnArgsT<SLOTS>& a) {
+    if constexpr (SLOTS) return a.q_max;
+    else return a.q_end - a.q_begin;
+}
+
+__device__ __forceinline__ void slot_rows(const SlotAttnArgs& a, int b, int& q_begin, int& q_end) {
+    const int64_t qb = min(max(a.slot_begin[b], (int64_t)0), (int64_t)a.T);
+    const int64_t qn = min(max(a.slot_count[b], (int64_t)0), min((int64_t)a.q_max, (int64_t)a.T - qb));
+    q_begin = (int)qb;
+    q_end = (int)(qb + qn);
+}
+
 // NW = 4: a workgroup is 4 waves = 128 query rows; a key tile is staged, then every wave runs phase 1 (content + band products)
 //         and phase 2 (skew, softmax, P.V), one barrier per key tile (rounds 1-2).
 // NW = 8 (round 3): 8 waves = 256 query rows = a whole (batch, head) of the T' = 249 workload, so K / V are staged ONCE per
@@ -48,8 +70,10 @@ struct AttnArgs {
 //         LDS section + 32 MFMAs), and vice versa in the next interval; one barrier per interval.  The round-2 kernel put two
 //         independent 4-wave workgroups on a CU: both ran the same program in the same phase (MFMA pipe contended, then idle
 //         under the softmax): matrix pipe 0.53 busy (profiles/r03_pmc_mfma.json).
-template <int NC, int ND, int NW>
-__global__ __launch_bounds__(64 * NW, 2) void relpos_attn_fwd_kernel(const AttnArgs a) {
+// SLOTS (cfm_relpos_attention_slots_f32): the query rows, the output rows and the key split are per slot (SlotAttnArgs); a
+// workgroup past its slot's rows only zero-fills (key split: the merge does), before reading anything.
+template <int NC, int ND, int NW, bool SLOTS = false>
+__global__ __launch_bounds__(64 * NW, 2) void relpos_attn_fwd_kernel(const AttnArgsT<SLOTS> a) {
     constexpr int RING = NW == 8 ? 9 : 0;        // NW = 8: 32-row blocks of the positional table kept in LDS (see below)
     __shared__ __attribute__((aligned(16))) float smem[2 * 32 * KROW + 2 * 32 * 64 + NW * 32 * 32 + RING * 32 * KROW];
     float* Ksb = smem;                           // [2][32][KROW]
@@ -63,9 +87,32 @@ __global__ __launch_bounds__(64 * NW, 2) void relpos_attn_fwd_kernel(const AttnA
     const int T = a.T, dh = a.dh;
     constexpr int QB = 32 * NW;                                          // query rows per workgroup
     const int split = a.nsplit > 1 ? (int)(blockIdx.x % (unsigned)a.nsplit) : 0;
-    const int q0 = a.q_begin + (int)(a.nsplit > 1 ? blockIdx.x / (unsigned)a.nsplit : blockIdx.x) * QB;
+    int q_begin = a.q_begin, q_end = a.q_end;
+    if constexpr (SLOTS) slot_rows(a, b, q_begin, q_end);
+    const int q0 = q_begin + (int)(a.nsplit > 1 ? blockIdx.x / (unsigned)a.nsplit : blockIdx.x) * QB;
     const int i0 = q0 + wave * 32;
-    const bool active = i0 < a.q_end;                                    // wave-uniform; idle waves still stage + barrier
+    const bool active = i0 < q_end;                                      // wave-uniform; idle waves still stage + barrier
+    // SLOTS: compact row il = i (query) - q_begin of slot b; rows [q_end - q_begin, q_max) are zeros
+    [[maybe_unused]] auto zero_row = [&]() {
+        if constexpr (SLOTS) {
+            const int il = i0 + li - q_begin;
+            if (il >= a.q_max) return;
+            float* orow = a.ctx + ((int64_t)b * a.q_max + il) * a.ldo + h * dh;
+#pragma unroll
+            for (int n = 0; n < ND; ++n)
+#pragma unroll
+                for (int gq = 0; gq < 4; ++gq) {
+                    const int dd = 32 * n + 8 * gq + 4 * hf;
+                    if (dd < dh) *reinterpret_cast<f32x4*>(orow + dd) = f32x4{0.f, 0.f, 0.f, 0.f};
+                }
+        }
+    };
+    if constexpr (SLOTS) {
+        if (q0 >= q_end) {                                               // no query row of this slot here: Q / K / V unread
+            if (a.nsplit == 1) zero_row();
+            return;
+        }
+    }
     const bool tracer = NW == 4 && a.trace && blockIdx.x == 0 && blockIdx.y == 0 && tid == 0;
     if (tracer) a.trace[9] = __builtin_amdgcn_s_memrealtime();           // kernel entry
 
@@ -119,7 +166,9 @@ __global__ __launch_bounds__(64 * NW, 2) void relpos_attn_fwd_kernel(const AttnA
     // (profiles/r03_attn_fwd_trace.txt).  Block b lives in slot b mod 9 from the interval it is committed in until wave 7 of
     // the lagging half has read it (tile b + 7): blocks -8 .. 0 are loaded in the prologue (block -w - 1 = wave w's band tile 1 of
     // the first key tile).
-    const int R0 = T - 1 - q0;
+    // (the ring's block index counts key tiles from kt_begin: with a key split the slots form shifts the table rows by the
+    //  split's first tile; the rows entry never pairs the 8-wave form with a key split, its instantiations keep the plain base)
+    const int R0 = T - 1 - q0 + (SLOTS ? 32 * kt_begin : 0);
     [[maybe_unused]] f32x4 pr;
     [[maybe_unused]] auto ring_slot = [](int blk) { return ((blk % 9) + 9) % 9; };
     [[maybe_unused]] auto ring_load = [&](int blk) {              // thread (row srow, chunk sch) of block blk -> register
@@ -416,10 +465,11 @@ __global__ __launch_bounds__(64 * NW, 2) void relpos_attn_fwd_kernel(const AttnA
     if (tracer) a.trace[11] = __builtin_amdgcn_s_memrealtime();          // key loop done
 
     // ---- normalise and store: lane = query row, registers = head dims (4 consecutive dims per r>>2 group)
-    if (active && i0 + li < a.q_end) {
+    if (active && i0 + li < q_end) {
         const float inv = 1.0f / lrow;
-        const int qc = a.q_end - a.q_begin, il = i0 + li - a.q_begin;
+        const int qc = launch_rows<SLOTS>(a), il = i0 + li - q_begin;
         float* orow = a.nsplit > 1 ? a.part_ctx + (((int64_t)split * a.B + b) * qc + il) * a.ldo + h * dh
+                    : SLOTS        ? a.ctx + ((int64_t)b * qc + il) * a.ldo + h * dh
                                    : a.ctx + ((int64_t)b * T + i0 + li) * a.ldo + h * dh;
 #pragma unroll
         for (int n = 0; n < ND; ++n)
@@ -436,6 +486,8 @@ __global__ __launch_bounds__(64 * NW, 2) void relpos_attn_fwd_kernel(const AttnA
         } else if (a.lse && hf == 0) {
             a.lse[((int64_t)b * a.H + h) * T + i0 + li] = mrow * 0.69314718055994530942f + logf(lrow);
         }
+    } else if constexpr (SLOTS) {
+        if (a.nsplit == 1) zero_row();
     }
     if (tracer) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -686,8 +738,10 @@ __global__ __launch_bounds__(512, 2) void relpos_attn_fwd8p_kernel(const AttnArg
 }
 
 // ctx[b, q_begin+il, h*dh + :] = sum_s exp(lse_s - lse) * part_s, lse = logsumexp over the splits that own keys of utterance b
-__global__ __launch_bounds__(256) void attn_merge_splits_kernel(const AttnArgs a) {
-    const int qc = a.q_end - a.q_begin, d4 = a.dh / 4;
+// SLOTS: ctx[b, il, h*dh + :] (compact rows), zeros for il >= the slot's row count
+template <bool SLOTS = false>
+__global__ __launch_bounds__(256) void attn_merge_splits_kernel(const AttnArgsT<SLOTS> a) {
+    const int qc = launch_rows<SLOTS>(a), d4 = a.dh / 4;
     const int64_t total = (int64_t)a.B * qc * a.H * d4;
     const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= total) return;
@@ -695,6 +749,14 @@ __global__ __launch_bounds__(256) void attn_merge_splits_kernel(const AttnArgs a
     const int h = (int)((idx / d4) % a.H);
     const int il = (int)((idx / ((int64_t)d4 * a.H)) % qc);
     const int b = (int)(idx / ((int64_t)d4 * a.H * qc));
+    if constexpr (SLOTS) {
+        int qb, qe;
+        slot_rows(a, b, qb, qe);
+        if (il >= qe - qb) {
+            *reinterpret_cast<f32x4*>(a.ctx + ((int64_t)b * qc + il) * a.ldo + h * a.dh + 4 * c4) = f32x4{0.f, 0.f, 0.f, 0.f};
+            return;
+        }
+    }
     int klen = a.T;
     if (a.lengths) { const int64_t L = a.lengths[b]; if (L > 0 && L < a.T) klen = (int)L; }
     const int ntiles_all = (klen + 31) / 32, tps = (ntiles_all + a.nsplit - 1) / a.nsplit;
@@ -710,7 +772,8 @@ __global__ __launch_bounds__(256) void attn_merge_splits_kernel(const AttnArgs a
         wsum += w;
     }
     const float inv = 1.0f / wsum;
-    *reinterpret_cast<f32x4*>(a.ctx + ((int64_t)b * a.T + a.q_begin + il) * a.ldo + h * a.dh + 4 * c4) = acc * inv;
+    if constexpr (SLOTS) *reinterpret_cast<f32x4*>(a.ctx + ((int64_t)b * qc + il) * a.ldo + h * a.dh + 4 * c4) = acc * inv;
+    else *reinterpret_cast<f32x4*>(a.ctx + ((int64_t)b * a.T + a.q_begin + il) * a.ldo + h * a.dh + 4 * c4) = acc * inv;
 }
 
 }  // namespace
@@ -829,7 +892,54 @@ static int attention_launch(const float* q, const float* k, const float* v, int6
 #undef ATT_LAUNCH
     if (nsplit > 1) {
         const int64_t total = (int64_t)B * q_count * H * (dh / 4);
-        hipLaunchKernelGGL(attn_merge_splits_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, a);
+        hipLaunchKernelGGL(attn_merge_splits_kernel<false>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, a);
+    }
+    return cfm_launch_status();
+}
+
+// Independent streams (conformer_amd/slots.py): slot b's query rows are cache rows [q_begin[b], q_begin[b] + q_count[b]) of its
+// own K/V cache, keys < lengths[b]; the results go to the COMPACT ctx (B, q_max, ldo), rows >= q_count[b] zero-filled.  The three
+// device arrays are clamped in the kernels (a slot never reads or writes outside the cache, the table or ctx); a slot with
+// q_count[b] == 0 reads nothing.  nsplit > 1: the key split of cfm_relpos_attention_rows_f32 per slot (workspace:
+// nsplit*B*q_max*(H*dh + H) floats, ldo == H*dh).
+extern "C" int cfm_relpos_attention_slots_f32(const float* q, const float* k, const float* v, int64_t ld, const float* pos,
+                                              int64_t ldp, const float* u, const float* vbias, const int64_t* q_begin,
+                                              const int64_t* q_count, const int64_t* lengths, float* ctx, int64_t ldo, int B, int T,
+                                              int H, int dh, int q_max, int nsplit, float* workspace_or_null,
+                                              cfm_stream_t stream) {
+    CFM_REQUIRE(q && k && v && pos && u && vbias && q_begin && q_count && lengths && ctx, CFM_ERR_NULL);
+    CFM_REQUIRE(B > 0 && T > 0 && H > 0 && dh > 0 && (dh & 3) == 0, CFM_ERR_BAD_SHAPE);
+    CFM_REQUIRE((ld & 3) == 0 && (ldp & 3) == 0 && (ldo & 3) == 0 && ldo >= (int64_t)H * dh, CFM_ERR_BAD_SHAPE);
+    CFM_REQUIRE(dh <= 64, CFM_ERR_UNSUPPORTED);
+    CFM_REQUIRE(CFM_ALIGNED16(q) && CFM_ALIGNED16(k) && CFM_ALIGNED16(v) && CFM_ALIGNED16(pos) && CFM_ALIGNED16(u) &&
+                CFM_ALIGNED16(vbias) && CFM_ALIGNED16(ctx), CFM_ERR_ALIGN);
+    CFM_REQUIRE((int64_t)B * H <= 65535 && T < (1 << 28), CFM_ERR_UNSUPPORTED);
+    CFM_REQUIRE(q_max >= 1 && q_max <= T, CFM_ERR_BAD_SHAPE);
+    CFM_REQUIRE(nsplit >= 1 && nsplit <= 16 && (nsplit == 1 || (workspace_or_null && ldo == (int64_t)H * dh)), CFM_ERR_BAD_SHAPE);
+    SlotAttnArgs a{};
+    static_cast<AttnArgs&>(a) = AttnArgs{q, k, v, ld, pos, ldp, u, vbias, lengths, ctx, ldo, nullptr, B, T, H, dh,
+                                         1.0f / sqrtf((float)dh), 0, q_max, nsplit, workspace_or_null,
+                                         workspace_or_null ? workspace_or_null + (int64_t)nsplit * B * q_max * ldo : nullptr,
+                                         0.f, 0, nullptr};
+    a.slot_begin = q_begin;
+    a.slot_count = q_count;
+    a.q_max = q_max;
+    // the workgroup shape of the rows entry (no pipelined form here); cfm_debug_set_attention_waves(4 | 8) overrides
+    int nw = (g_attn_force_nw == 4 || g_attn_force_nw == 8) ? g_attn_force_nw : g_attn_force_nw == 9 ? 8
+             : ((q_max > 128 && nsplit == 1) ? 8 : 4);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const dim3 grid((unsigned)((q_max + 32 * nw - 1) / (32 * nw)) * nsplit, (unsigned)(B * H)), block(64 * nw);
+#define ATT_LAUNCH(NC, ND) do { if (nw == 8) hipLaunchKernelGGL((relpos_attn_fwd_kernel<NC, ND, 8, true>), grid, block, 0, s, a); \
+                                else hipLaunchKernelGGL((relpos_attn_fwd_kernel<NC, ND, 4, true>), grid, block, 0, s, a); } while (0)
+    if (dh <= 8) ATT_LAUNCH(1, 1);
+    else if (dh <= 16) ATT_LAUNCH(2, 1);
+    else if (dh <= 32) ATT_LAUNCH(4, 1);
+    else if (dh <= 40) ATT_LAUNCH(5, 2);
+    else ATT_LAUNCH(8, 2);
+#undef ATT_LAUNCH
+    if (nsplit > 1) {
+        const int64_t total = (int64_t)B * q_max * H * (dh / 4);
+        hipLaunchKernelGGL(attn_merge_splits_kernel<true>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, a);
     }
     return cfm_launch_status();
 }

@@ -875,11 +875,10 @@ __global__ __launch_bounds__(BEAM_MAX_W) void beam_search_kernel(
     if (tid == 0) num_hyps[b] = min(nh, N);
 }
 
-// every utterance of a stream at the empty prefix, the state the one-shot kernel builds before its first frame
+// utterance b of a stream at the empty prefix, the state the one-shot kernel builds before its first frame
 template <bool LM, bool HW>
-__global__ void beam_stream_init_kernel(BeamWs ws, StreamParams<true> sp, int B, int W, const void* lm_tables, int score_boundary) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= B) return;
+__device__ __forceinline__ void beam_stream_init_one(const BeamWs& ws, const StreamParams<true>& sp, int b, int W,
+                                                     const void* lm_tables, int score_boundary) {
     const int64_t o = (int64_t)b * W;
     sp.frames[b] = 0; sp.nh[b] = 1;
     sp.pb[o] = 0.0; sp.pnb[o] = -INFINITY; sp.s[o] = 0.0; sp.hash[o] = ROOT_HASH;
@@ -894,6 +893,25 @@ __global__ void beam_stream_init_kernel(BeamWs ws, StreamParams<true> sp, int B,
         sp.hn[o] = 0; sp.hd[o] = 0; sp.hwl[o] = 0; sp.hc[o] = 0;
         for (int u = 0; u < HW_WIN; ++u) sp.hw[((int64_t)b * HW_WIN + u) * W] = -1;
     }
+}
+
+// every utterance of a stream at the empty prefix
+template <bool LM, bool HW>
+__global__ void beam_stream_init_kernel(BeamWs ws, StreamParams<true> sp, int B, int W, const void* lm_tables, int score_boundary) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    beam_stream_init_one<LM, HW>(ws, sp, b, W, lm_tables, score_boundary);
+}
+
+// the utterances slots[0 .. n) at the empty prefix (independent streams: a slot reopened); entries outside [0, B) are skipped
+template <bool LM, bool HW>
+__global__ void beam_stream_reset_slots_kernel(BeamWs ws, StreamParams<true> sp, int B, int W, const void* lm_tables,
+                                               int score_boundary, const int64_t* slots, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int64_t b = slots[i];
+    if (b < 0 || b >= B) return;
+    beam_stream_init_one<LM, HW>(ws, sp, (int)b, W, lm_tables, score_boundary);
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------
@@ -1060,6 +1078,27 @@ extern "C" int cfm_ctc_beam_stream_init(int B, int T_max, int beam_width, int ma
     beam_mode(fz, [&](auto lm, auto hw) {
         hipLaunchKernelGGL((beam_stream_init_kernel<decltype(lm)::value, decltype(hw)::value>), dim3((unsigned)((B + 255) / 256)),
                            dim3(256), 0, static_cast<hipStream_t>(stream), ws, sp, B, beam_width, lm_tables_or_null, sb);
+    });
+    return cfm_launch_status();
+}
+
+// independent streams (conformer_amd/slots.py): the utterances slots[0 .. n_slots) back at the empty prefix, the others untouched.
+// The step's `t_used` is a bound only; with slots at different positions the caller passes max_b(frames_b + lengths_b) - Tc.
+extern "C" int cfm_ctc_beam_stream_reset_slots(int B, int T_max, int beam_width, int max_candidates, const void* lm_tables_or_null,
+                                               int score_boundary, const void* hw_tables_or_null, const int64_t* slots,
+                                               int n_slots, void* state, size_t state_bytes, cfm_stream_t stream) {
+    CFM_REQUIRE(state && slots, CFM_ERR_NULL);
+    CFM_CHECK(beam_check(B, T_max, 2, beam_width, max_candidates, 1, 0, 0.f, 0.f));
+    CFM_REQUIRE(n_slots >= 1 && n_slots <= B, CFM_ERR_BAD_SHAPE);
+    const Fusion fz{lm_tables_or_null, 0.0, 0.0, 0.0, score_boundary, hw_tables_or_null, 0.0};
+    BeamWs ws;
+    StreamParams<true> sp;
+    CFM_CHECK(stream_state(B, T_max, beam_width, max_candidates, fz, state, state_bytes, &ws, &sp));
+    const int sb = score_boundary ? 1 : 0;
+    beam_mode(fz, [&](auto lm, auto hw) {
+        hipLaunchKernelGGL((beam_stream_reset_slots_kernel<decltype(lm)::value, decltype(hw)::value>),
+                           dim3((unsigned)((n_slots + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), ws, sp, B,
+                           beam_width, lm_tables_or_null, sb, slots, n_slots);
     });
     return cfm_launch_status();
 }

@@ -294,30 +294,49 @@ def beam_ctc_stream_reset(st: _StreamState) -> None:
     st.t_used = 0
 
 
+def beam_ctc_stream_reset_slots(st: _StreamState, slots: torch.Tensor) -> None:
+    """The utterances `slots` ((n) int64 device tensor of batch rows) back at the empty prefix, the others untouched
+    (independent streams, conformer_amd/slots.py; enqueues only)."""
+    slots = ops._req(slots, "slots", torch.int64)
+    if slots.dim() != 1 or not 1 <= slots.numel() <= st.B or not slots.is_contiguous():
+        raise ValueError(f"beam_ctc_stream_reset_slots: expected 1..{st.B} slot indices, got shape {tuple(slots.shape)}")
+    f = st.fusion
+    _lib.check(_lib.load().cfm_ctc_beam_stream_reset_slots(st.B, st.t_max, st.beam_width, st.max_candidates,
+                                                           ops._p(f.lm_tables), f.score_boundary, ops._p(f.hw_tables),
+                                                           slots.data_ptr(), slots.numel(), st.buf.data_ptr(), st.buf.numel(),
+                                                           ops._stream()),
+               "cfm_ctc_beam_stream_reset_slots")
+
+
 def beam_ctc_stream_step(st: _StreamState, logits: torch.Tensor, blank_id: int, lengths: Optional[torch.Tensor] = None, *,
-                         n_best: int = 1, token_min_logp: float = -5.0, beam_prune_logp: float = -10.0):
+                         n_best: int = 1, token_min_logp: float = -5.0, beam_prune_logp: float = -10.0,
+                         t_used: Optional[int] = None):
     """Consume the next chunk logits (B,Tc,V) (fp32, or bf16 / fp16 cast to fp32): per utterance its first lengths[b] frames
     (None: all).  Returns the interim best (tokens (B,N,max_frames) int64 padded with -1, counts (B,N), scores (B,N) fp32
     without end-of-utterance terms, am_scores (B,N) fp32 or None without LM and hotwords, num_hyps (B)), device tensors;
-    nothing synchronises with the host."""
+    nothing synchronises with the host.  t_used: the caller's own bound on the frames any utterance consumed before this
+    step (independent streams pass max_b(frames_b + lengths_b) - Tc, having checked frames_b + lengths_b <= max_frames);
+    None: the chunk frames stepped since the init, which this call then advances."""
     x = _logits(logits)
     if x.dim() != 3 or x.shape[0] != st.B:
         raise ValueError(f"logits: expected ({st.B},Tc,V), got {tuple(x.shape)}")
     _, Tc, V = x.shape
     if Tc < 1:
         raise ValueError("beam_ctc_stream_step: the chunk has no frames")
-    if Tc > st.t_max - st.t_used:
+    used = st.t_used if t_used is None else int(t_used)
+    if used < 0 or Tc > st.t_max - used:
         raise ValueError(f"beam_ctc_stream_step: {Tc} more frames would pass max_frames={st.t_max} "
-                         f"({st.t_used} stepped so far)")
+                         f"({used} stepped so far)")
     if lengths is not None:
         lengths = ops._req(lengths, "lengths", torch.int64)
     tokens, counts, scores, am_scores, num_hyps = _beam_outputs(st.B, int(n_best), st.t_max, x.device, st.fusion.fused)
     status = _lib.load().cfm_ctc_beam_stream_step_f32(
         x.data_ptr(), ops._p(lengths), st.B, Tc, V, int(blank_id), st.beam_width, st.max_candidates, float(token_min_logp),
-        float(beam_prune_logp), int(n_best), *st.fusion.args, st.buf.data_ptr(), st.buf.numel(), st.t_max, st.t_used,
+        float(beam_prune_logp), int(n_best), *st.fusion.args, st.buf.data_ptr(), st.buf.numel(), st.t_max, used,
         tokens.data_ptr(), counts.data_ptr(), scores.data_ptr(), ops._p(am_scores), num_hyps.data_ptr(), ops._stream())
     _lib.check(status, "cfm_ctc_beam_stream_step_f32")
-    st.t_used += Tc
+    if t_used is None:
+        st.t_used += Tc
     return tokens, counts, scores, am_scores, num_hyps
 
 

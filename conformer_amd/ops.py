@@ -676,6 +676,49 @@ def relpos_attention_rows(qkv: torch.Tensor, pos: torch.Tensor, u: torch.Tensor,
     return ctx
 
 
+def relpos_attention_slots(qkv: torch.Tensor, pos: torch.Tensor, u: torch.Tensor, v: torch.Tensor, lengths: torch.Tensor,
+                           n_heads: int, q_begin: torch.Tensor, q_count: torch.Tensor, q_max: int,
+                           ctx: Optional[torch.Tensor] = None, keys_hint: Optional[int] = None) -> torch.Tensor:
+    """Incremental attention of independent streams (slots) over their K/V caches: qkv (S,Tmax,3d) and pos as in
+    relpos_attention_rows; slot b computes the query rows [q_begin[b], q_begin[b]+q_count[b]) of its own cache against its
+    keys < lengths[b] into the COMPACT rows ctx[b, :q_count[b]] of ctx (S,q_max,d); rows q_count[b]..q_max-1 are zeros.
+    q_begin, q_count, lengths: (S) int64 device tensors (nothing synchronises; the kernel clamps them, so no value makes an
+    out-of-bounds access).  keys_hint: host-side upper bound of `lengths` (default Tmax) choosing the key split as
+    relpos_attention_rows does.  fp32 only (the 16-bit form is not implemented: refused under autocast)."""
+    qkv = _req(qkv, "qkv"); u = _req(u, "content_bias"); v = _req(v, "position_bias")
+    B, T, d3 = qkv.shape
+    d = d3 // 3
+    q_max = int(q_max)
+    if not (pos.is_cuda and pos.dtype == torch.float32 and pos.dim() == 2 and pos.stride(1) == 1 and pos.shape == (2 * T - 1, d)):
+        raise _lib.ConformerHipError(f"pos: expected a ({2 * T - 1},{d}) fp32 HIP tensor with unit column stride")
+    if not qkv.is_contiguous():
+        raise _lib.ConformerHipError("relpos_attention_slots: qkv (S,T,3d) must be a contiguous cache buffer")
+    if mfma16_prec() != PREC_F32:
+        raise _lib.ConformerHipError("relpos_attention_slots: fp32 only (no 16-bit form under autocast)")
+    if ctx is None:
+        ctx = torch.empty(B, q_max, d, device=qkv.device, dtype=torch.float32)
+    ctx = _req(ctx, "ctx")
+    if ctx.shape != (B, q_max, d) or not ctx.is_contiguous():
+        raise _lib.ConformerHipError(f"relpos_attention_slots: ctx must be a contiguous ({B},{q_max},{d}) tensor")
+    lengths = _req(lengths, "lengths", torch.int64)
+    q_begin = _req(q_begin, "q_begin", torch.int64)
+    q_count = _req(q_count, "q_count", torch.int64)
+    for name, t in (("lengths", lengths), ("q_begin", q_begin), ("q_count", q_count)):
+        if t.shape != (B,) or not t.is_contiguous():
+            raise _lib.ConformerHipError(f"relpos_attention_slots: {name} must be a contiguous ({B},) int64 tensor")
+    tiles = ((T if keys_hint is None else min(int(keys_hint), T)) + 31) // 32
+    blocks = B * n_heads * ((q_max + 127) // 128)
+    nsplit = max(1, min(16, tiles // 8, -(-1024 // blocks)))          # the heuristic of relpos_attention_rows
+    ws = torch.empty(nsplit * B * q_max * (d + n_heads), device=qkv.device, dtype=torch.float32) if nsplit > 1 else None
+    base = qkv.data_ptr()
+    st = _lib.load().cfm_relpos_attention_slots_f32(base, base + 4 * d, base + 8 * d, d3, pos.data_ptr(), pos.stride(0),
+                                                    u.data_ptr(), v.data_ptr(), q_begin.data_ptr(), q_count.data_ptr(),
+                                                    lengths.data_ptr(), ctx.data_ptr(), d, B, T, n_heads, d // n_heads, q_max,
+                                                    nsplit, _p(ws), _stream())
+    _lib.check(st, "cfm_relpos_attention_slots_f32")
+    return ctx
+
+
 def dwconv_bn_swish(g, w, b, bn_w, bn_b, bn_mean, bn_var, eps: float = 1e-5, for_gemm: bool = False) -> torch.Tensor:
     """for_gemm: see layernorm (the result feeds the pointwise_conv_2 GEMM of contraction length C)."""
     g = _req(g, "g"); w = _req(w, "dw weight"); b = _req(b, "dw bias")

@@ -1,0 +1,314 @@
+"""Independent streams in one batch (INTEGRATION.md "Independent streams (slots)").
+
+A streaming service holds a fixed set of batch SLOTS, each carrying one utterance of its own: a slot is opened when a call
+starts, fed whatever mel frames have arrived (any count per step, 0 included), and closed when the call ends; then another
+call reuses it.  Every slot keeps its own position -- K/V cache length, depthwise-convolution state, buffered mel tail, LSTM
+(h, c) and beam-search state -- where StreamingEncoder / StreamingTranscriber move the whole batch in lockstep.
+
+Per step the slots' new rows are COMPACT: slot b contributes k_b new encoder frames as rows 0 .. k_b-1 of (S, k_max, .)
+tensors, so the stem, the GEMMs, LayerNorm, the feed-forward modules and the GLU run once for all slots.  Only these parts are
+per slot: the cache append at row frames_b, the attention of the new rows (ops.relpos_attention_slots), the depthwise window
+(GLU rows >= k_b are the zero padding of frames not received yet) with its carried state, and the mel tail.  The per-slot
+counts come from the caller, so the host knows every offset; they reach the device as one small non-blocking copy per step and
+nothing synchronises except partial_text() and close().
+
+Semantics: for each slot, the sequence of frame counts it received from open to close is that utterance's own chunking, and
+its results are those of a one-utterance StreamingEncoder / StreamingTranscriber fed the same chunks (to GEMM rounding: the
+compact rows may tile differently).  fp32 inference only.
+"""
+from __future__ import annotations
+
+from typing import Callable, Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import ops
+from .decode import BeamCTCDecoder, beam_ctc_stream_finish, beam_ctc_stream_init, beam_ctc_stream_reset_slots, \
+    beam_ctc_stream_step
+from .model.modules.encoder import Encoder
+from .streaming import StreamingEncoder
+from .transcribe import decode_frames
+
+_TAIL = 8                  # mel-tail buffer width: a slot carries 0..6 un-consumed frames
+
+
+def slot_plan(tails: Sequence[int], frames: Sequence[int]) -> Tuple[List[int], List[int]]:
+    """The host bookkeeping of one step: per slot, with tails[b] buffered mel frames and frames[b] new ones, the encoder frames
+    k_b that become computable and the new tail.  Encoder frame t covers mel frames 4t .. 4t+6 of the slot's stream."""
+    ks, new_tails = [], []
+    for t, f in zip(tails, frames):
+        total = int(t) + int(f)
+        k = max(0, ((total - 1) // 2 - 1) // 2)
+        ks.append(k)
+        new_tails.append(total - 4 * k)
+    return ks, new_tails
+
+
+def _refuse_autocast(who: str) -> None:
+    if torch.is_autocast_enabled("cuda"):
+        raise RuntimeError(f"{who}: fp32 only; leave torch.autocast before stepping (the 16-bit slot path does not exist)")
+
+
+class _Step:
+    """Device views of one step's per-slot offsets (one pinned host buffer, one non-blocking copy)."""
+
+    def __init__(self, dev: torch.device, tails, totals, n0, ks, k_max: int, t_max: int) -> None:
+        S = len(ks)
+        src = [b * k_max + r for b in range(S) for r in range(ks[b])]          # compact row -> cache row of the append
+        dst = [b * t_max + n0[b] + r for b in range(S) for r in range(ks[b])]
+        nk = len(src)
+        host = torch.empty(5 * S + 2 * nk, dtype=torch.int64, pin_memory=True)
+        h = host.numpy()
+        h[0:S], h[S:2 * S], h[2 * S:3 * S], h[3 * S:4 * S] = tails, totals, n0, ks
+        h[4 * S:5 * S] = np.asarray(n0) + np.asarray(ks)
+        h[5 * S:5 * S + nk], h[5 * S + nk:] = src, dst
+        d = host.to(dev, non_blocking=True)
+        self.tail, self.total, self.q_begin, self.k, self.lengths = (d[j * S:(j + 1) * S] for j in range(5))
+        self.src, self.dst = d[5 * S:5 * S + nk], d[5 * S + nk:]
+        self.nk, self.k_max = nk, k_max
+        self.keys_hint = max(a + b for a, b in zip(n0, ks))
+        self._keep: Dict[int, torch.Tensor] = {}
+        self._mask: Optional[torch.Tensor] = None
+
+    def mel_index(self, pos: torch.Tensor, tc: int) -> torch.Tensor:
+        """Column of [tail (8) | chunk (tc) | zero] that holds position `pos` (S, P) of each slot's buffered stream."""
+        tail, total = self.tail[:, None], self.total[:, None]
+        zero = torch.full_like(pos, _TAIL + tc)
+        return torch.where(pos < tail, pos, torch.where(pos < total, pos + (_TAIL - tail), zero))
+
+    def glu_mask(self) -> torch.Tensor:
+        """(S, k_max, 1) bool: the rows of each slot that are frames it received."""
+        if self._mask is None:
+            self._mask = (torch.arange(self.k_max, device=self.k.device)[None, :] < self.k[:, None])[:, :, None]
+        return self._mask
+
+    def keep_index(self, half: int) -> torch.Tensor:
+        """(S, half, 1): rows k_b .. k_b+half-1 of [state ; g], the depthwise state after the step."""
+        if half not in self._keep:
+            self._keep[half] = (self.k[:, None] + torch.arange(half, device=self.k.device)[None, :])[:, :, None]
+        return self._keep[half]
+
+
+class SlotStreamingEncoder(StreamingEncoder):
+    """The chunked encoder of StreamingEncoder over `slots` independent streams of at most max_mel_frames mel frames each.
+    open(s) starts a stream in a free slot, step(mel, frames) feeds every slot its own number of new frames, close(s) frees the
+    slot.  Returns compact rows: step -> ((S, k_max, d), k) with slot b's new encoder frames in rows 0 .. k[b]-1."""
+
+    def __init__(self, encoder: Encoder, slots: int, max_mel_frames: int) -> None:
+        super().__init__(encoder, slots, max_mel_frames, graphs=False)
+        self.ctx = None                                                    # the compact context is allocated per step
+        self.S = self.B
+        self.max_mel = int(max_mel_frames)
+        self.is_open = [False] * self.S
+        self.n0 = [0] * self.S                                             # encoder frames per slot so far
+        self.tails = [0] * self.S                                          # buffered mel frames per slot (0..6)
+        self.mel_seen = [0] * self.S                                       # mel frames received per slot
+        self._cur: Optional[_Step] = None                                 # the step being enqueued
+        self.last_step: Optional[_Step] = None                            # the latest step's device offsets (k: SlotTranscriber)
+
+    def _check_slot(self, s: int, want_open: bool) -> int:
+        s = int(s)
+        if not 0 <= s < self.S:
+            raise ValueError(f"slot {s} out of range [0, {self.S})")
+        if self.is_open[s] != want_open:
+            raise RuntimeError(f"slot {s} is {'free' if want_open else 'already open'}")
+        return s
+
+    def open(self, s: int) -> None:
+        """Start a new stream in free slot s: K/V length, depthwise state and mel tail back to empty (enqueues only)."""
+        s = self._check_slot(s, want_open=False)
+        self.lengths[s:s + 1].zero_()
+        for t in self.conv_state:
+            t[s].zero_()
+        self.n0[s] = self.tails[s] = self.mel_seen[s] = 0
+        self.is_open[s] = True
+
+    def close(self, s: int) -> None:
+        s = self._check_slot(s, want_open=True)
+        self.is_open[s] = False
+
+    def reset(self) -> None:
+        """Every slot free."""
+        self.is_open = [False] * self.S
+
+    def plan(self, mel_chunk: torch.Tensor, frames: Sequence[int]) -> Tuple[torch.Tensor, List[int], List[int]]:
+        """Check a step's arguments against the slots (raises before anything is enqueued): (mel, k, new tails)."""
+        if self.enc.training:
+            raise RuntimeError("SlotStreamingEncoder: put the encoder in eval() mode (running BatchNorm statistics, no dropout)")
+        _refuse_autocast("SlotStreamingEncoder")
+        x = ops._req(mel_chunk, "mel_chunk")
+        if x.dim() != 3 or x.shape[0] != self.S:
+            raise ValueError(f"mel_chunk: expected ({self.S}, n_mel, Tc), got {tuple(x.shape)}")
+        frames = [int(f) for f in frames]
+        if len(frames) != self.S:
+            raise ValueError(f"frames: expected {self.S} counts, got {len(frames)}")
+        Tc = x.shape[2]
+        for b, f in enumerate(frames):
+            if not 0 <= f <= Tc:
+                raise ValueError(f"frames[{b}] = {f} outside [0, {Tc}]")
+            if f and not self.is_open[b]:
+                raise RuntimeError(f"frames given for free slot {b}: open() it first")
+            if self.mel_seen[b] + f > self.max_mel:
+                raise RuntimeError(f"slot {b}: {self.mel_seen[b] + f} mel frames would pass max_mel_frames={self.max_mel}")
+        ks, new_tails = slot_plan(self.tails, frames)
+        return x, ks, new_tails
+
+    @torch.no_grad()
+    def step(self, mel_chunk: torch.Tensor, frames: Sequence[int]) -> Tuple[torch.Tensor, List[int]]:
+        """mel_chunk (S, n_mel, Tc): slot b's next frames[b] mel frames are mel_chunk[b, :, :frames[b]] (the rest is ignored).
+        Returns the compact new encoder frames (S, k_max, d) and k (host list): rows >= k[b] of slot b are padding."""
+        x, ks, new_tails = self.plan(mel_chunk, frames)
+        frames = [int(f) for f in frames]
+        S, Tc, dev = self.S, x.shape[2], x.device
+        k_max = max(ks)
+        if self.mel_tail_buf is None:
+            self.mel_tail_buf = torch.zeros(S, x.shape[1], _TAIL, device=dev, dtype=torch.float32)
+        totals = [t + f for t, f in zip(self.tails, frames)]
+        cur = _Step(dev, self.tails, totals, self.n0, ks, k_max, self.t_max)
+        src = torch.cat([self.mel_tail_buf, x, x.new_zeros(S, x.shape[1], 1)], dim=2)   # [tail | chunk | zero column]
+        n_mel = x.shape[1]
+        keep = cur.k[:, None] * 4 + torch.arange(_TAIL, device=dev)[None, :]
+        new_tail = torch.gather(src, 2, cur.mel_index(keep, Tc)[:, None, :].expand(S, n_mel, _TAIL))
+        out = x.new_empty(S, 0, self.d)
+        if k_max > 0:
+            W = 4 * k_max + 3                                              # the mel frames of k_max encoder frames
+            pos = torch.arange(W, device=dev)[None, :].expand(S, W)
+            mel = torch.gather(src, 2, cur.mel_index(pos, Tc)[:, None, :].expand(S, n_mel, W))
+            self._cur = cur
+            out = self._step_rows(mel)
+            self._cur = None
+        self.mel_tail_buf.copy_(new_tail)
+        for b in range(S):
+            self.n0[b] += ks[b]
+            self.mel_seen[b] += frames[b]
+        self.tails = new_tails
+        self.last_step = cur
+        return out, ks
+
+    def _step_rows(self, mel: torch.Tensor) -> torch.Tensor:
+        enc, d, cur = self.enc, self.d, self._cur
+        h = enc.downsampling_conv.channel_last(mel.contiguous())          # (S, k_max, F'*C): the stem is local in time
+        wlp = enc._packs.get("wlp", (enc.linear.weight,), lambda: ops.pack_linear_weight(enc.linear.weight, d, enc.n_freq_out))
+        h = ops.linear(h, wlp, enc.linear.bias)
+        self.lengths.copy_(cur.lengths)
+        st = None
+        for i, blk in enumerate(enc.layers):
+            h, st = self._block(i, blk, h, 0, cur.k_max, st, want_stats=i + 1 < len(enc.layers))
+        return h
+
+    # ---- the per-slot parts of StreamingEncoder._block
+    def _attend(self, i: int, a, qkv_new: torch.Tensor, n0: int, k: int) -> torch.Tensor:
+        d, cur = self.d, self._cur
+        if cur.nk:
+            self.qkv[i].view(-1, 3 * d).index_copy_(0, cur.dst, qkv_new.reshape(-1, 3 * d).index_select(0, cur.src))
+        return ops.relpos_attention_slots(self.qkv[i], self.pos_all[:, i * d:(i + 1) * d], a.content_bias, a.position_bias,
+                                          self.lengths, a.n_heads, cur.q_begin, cur.k, cur.k_max, keys_hint=cur.keys_hint)
+
+    def _conv_window(self, i: int, g: torch.Tensor) -> torch.Tensor:
+        return torch.cat([self.conv_state[i], g.masked_fill(~self._cur.glu_mask(), 0.0)], dim=1)
+
+    def _conv_keep(self, i: int, buf: torch.Tensor) -> None:
+        half = self.half[i]
+        idx = self._cur.keep_index(half).expand(self.S, half, buf.shape[2])
+        self.conv_state[i].copy_(torch.gather(buf, 1, idx))
+
+
+class SlotTranscriber:
+    """Independent streaming transcription in `slots` batch slots: SlotStreamingEncoder -> the decoder with per-slot LSTM state
+    -> the resumable beam search of `decoder` (a BeamCTCDecoder: beam knobs, lm, hotwords) with per-slot progress.
+
+        tr.open(s); logits, k = tr.step(mel, frames); tr.partial_text(); text = tr.close(s)
+
+    close(s) returns what decoder(...) returns on that slot's concatenated logits.  fp32 eval mode only."""
+
+    def __init__(self, model, decoder: BeamCTCDecoder, slots: int, max_mel_frames: int) -> None:
+        if model.training:
+            raise RuntimeError("SlotTranscriber: put the model in eval() mode (running BatchNorm statistics, no dropout)")
+        dec = model.decoder
+        p = next(dec.parameters())
+        if not p.is_cuda or p.dtype != torch.float32:
+            raise RuntimeError("SlotTranscriber: the model must live on the HIP device in fp32 (no CPU fallback)")
+        if not dec._hip_eligible(p):
+            raise RuntimeError("SlotTranscriber: the decoder LSTM has no HIP kernel (hidden size % 4 != 0, bidirectional, "
+                               "projected or with dropout)")
+        self.model = model
+        self.decoder = decoder
+        self.encoder = SlotStreamingEncoder(model.encoder, slots, max_mel_frames)
+        self.S = self.encoder.S
+        self.device = p.device
+        H = dec.lstm.hidden_size
+        self.state = [(torch.zeros(self.S, H, device=p.device, dtype=torch.float32),
+                       torch.zeros(self.S, H, device=p.device, dtype=torch.float32)) for _ in range(dec.lstm.num_layers)]
+        f = decoder._fusion(p.device)
+        self.beam = beam_ctc_stream_init(self.S, self.encoder.t_max, p.device, beam_width=decoder.beam_width,
+                                         max_candidates=decoder.max_candidates, lm_tables=f.lm_tables, hw_tables=f.hw_tables,
+                                         alpha=decoder.alpha, beta=decoder.beta, unk_score_offset=decoder.unk_score_offset,
+                                         score_boundary=decoder.score_boundary, hotword_weight=decoder.hotword_weight)
+        self._last = None                  # interim outputs of the latest beam step
+        self._fresh = set()                # slots opened since it
+
+    @property
+    def is_open(self) -> List[bool]:
+        return list(self.encoder.is_open)
+
+    def _reset_beam(self, s: int) -> None:
+        idx = torch.tensor([s], dtype=torch.int64).pin_memory().to(self.device, non_blocking=True)
+        beam_ctc_stream_reset_slots(self.beam, idx)
+
+    def open(self, s: int) -> None:
+        """Start an utterance in free slot s (enqueues only)."""
+        self.encoder.open(s)
+        for h, c in self.state:
+            h[s].zero_()
+            c[s].zero_()
+        self._reset_beam(s)
+        self._fresh.add(int(s))
+
+    @torch.no_grad()
+    def step(self, mel_chunk: torch.Tensor, frames: Sequence[int]) -> Tuple[torch.Tensor, List[int]]:
+        """mel_chunk (S, n_mel, Tc), frames: S host counts <= Tc (0 = nothing for that slot; free slots take 0).  Returns the
+        logits (S, k_max, V) of the new encoder frames (slot b's in rows 0 .. k[b]-1) and k; advances each slot's search over
+        its own rows.  Nothing synchronises with the host."""
+        if self.model.training:
+            raise RuntimeError("SlotTranscriber: the model is in training mode; put it back in eval()")
+        _refuse_autocast("SlotTranscriber")
+        n0 = list(self.encoder.n0)
+        enc, ks = self.encoder.step(mel_chunk, frames)
+        k_max = max(ks)
+        if k_max == 0:
+            return enc.new_empty(self.S, 0, self.model.decoder.linear.out_features), ks
+        k_dev = self.encoder.last_step.k
+        logits = decode_frames(self.model, self.state, enc, k_dev)
+        d = self.decoder
+        # the search's bound: the furthest slot after this step, less the chunk (each slot's own frames_b + k_b <= T_max
+        # holds: the encoder refused more than max_mel_frames)
+        t_used = max(a + b for a, b in zip(n0, ks)) - k_max
+        self._last = beam_ctc_stream_step(self.beam, logits, d.blank_id, k_dev, n_best=1, token_min_logp=d.token_min_logp,
+                                          beam_prune_logp=d.beam_prune_logp, t_used=t_used)
+        self._fresh.clear()
+        return logits, ks
+
+    def partial_text(self) -> Dict[int, str]:
+        """The interim best transcript of every open slot (the one step-side call that synchronises)."""
+        open_slots = [s for s in range(self.S) if self.encoder.is_open[s]]
+        if self._last is None:
+            return {s: "" for s in open_slots}
+        texts = self.decoder._texts(self._last[0], self._last[1])
+        return {s: "" if s in self._fresh else texts[s] for s in open_slots}
+
+    def close(self, s: int, decode_func: Optional[Callable[[str], str]] = None) -> str:
+        """End slot s's utterance: its final transcript (BeamCTCDecoder on its logits); the slot becomes free.  The finish
+        saves no search state, so the other slots go on untouched."""
+        s = self.encoder._check_slot(s, want_open=True)
+        tokens, counts, _, _, _ = beam_ctc_stream_finish(self.beam, n_best=1)
+        text = self.decoder._texts(tokens[s:s + 1], counts[s:s + 1], decode_func)[0]
+        self._reset_beam(s)
+        self.encoder.close(s)
+        return text
+
+    def reset(self) -> None:
+        """Every slot free (their states are reset when they are opened again)."""
+        self.encoder.reset()
+        self._last = None
+        self._fresh.clear()

@@ -145,7 +145,6 @@ class StreamingEncoder:
         path (ops.ln_fold_ok) the residual GEMMs emit the statistics the next sub-layer's LayerNorm needs, as in
         ConformerBlock.fused_chain; a sub-layer whose producer took the split-K form instead (FFN out at chunk sizes) runs its
         LayerNorm kernel."""
-        d = self.d
         fold = blk._ln_fold(x)
         y, st = blk.ffn_1.fused(x, residual=x, alpha=0.5, stats=x_stats, emit_stats=True) if fold else \
             (blk.ffn_1.fused(x, residual=x, alpha=0.5), None)
@@ -158,10 +157,7 @@ class StreamingEncoder:
             qkv_new = ops.linear_lnfold(y, st, wf, bf, cs, ln.eps)
         else:
             qkv_new = ops.linear(ops.layernorm(y, att.layer_norm.weight, att.layer_norm.bias, att.layer_norm.eps), w, b)
-        self.qkv[i][:, n0:n0 + k].copy_(qkv_new)
-        ops.relpos_attention_rows(self.qkv[i], self.pos_all[:, i * d:(i + 1) * d], a.content_bias, a.position_bias,
-                                  self.lengths, a.n_heads, n0, k, self.ctx, keys_hint=n0 + k)
-        rows = self.ctx[:, n0:n0 + k].contiguous()
+        rows = self._attend(i, a, qkv_new, n0, k)
         y, st = ops.linear_residual(rows, a.out_proj.weight, a.out_proj.bias, y, 1.0, emit_stats=True) if fold else \
             (ops.linear_residual(rows, a.out_proj.weight, a.out_proj.bias, y, 1.0), None)
         # ---- convolution module: the depthwise window reaches (K-1)/2 frames back into the cached GLU outputs
@@ -175,10 +171,10 @@ class StreamingEncoder:
         else:
             hn = ops.layernorm(y, cv.layer_norm.weight, cv.layer_norm.bias, cv.layer_norm.eps)
             g = ops.linear_glu(hn, cv.pointwise_conv_1.weight, cv.pointwise_conv_1.bias)
-        buf = torch.cat([self.conv_state[i], g], dim=1)                    # (B, half + k, C)
+        buf = self._conv_window(i, g)                                      # (B, half + k, C)
         s = ops.dwconv_bn_swish(buf, cv.deepwise_conv.weight, cv.deepwise_conv.bias, bn.weight, bn.bias, bn.running_mean,
                                 bn.running_var, bn.eps)
-        self.conv_state[i].copy_(buf[:, buf.shape[1] - half:])            # fixed buffer (the graph replays write the same address)
+        self._conv_keep(i, buf)
         rows = s[:, half:].contiguous()
         y, st = ops.linear_residual(rows, cv.pointwise_conv_2.weight, cv.pointwise_conv_2.bias, y, 1.0, emit_stats=True) if fold else \
             (ops.linear_residual(rows, cv.pointwise_conv_2.weight, cv.pointwise_conv_2.bias, y, 1.0), None)
@@ -187,6 +183,24 @@ class StreamingEncoder:
         if fold and want_stats:
             return ops.layernorm(y, ln.weight, ln.bias, ln.eps, emit_stats=True)
         return ops.layernorm(y, ln.weight, ln.bias, ln.eps), None
+
+    # ---- the per-stream parts of _block (conformer_amd/slots.py overrides them for independent streams)
+    def _attend(self, i: int, a, qkv_new: torch.Tensor, n0: int, k: int) -> torch.Tensor:
+        """Append the chunk's Q|K|V rows to layer i's cache and return the attention context of the new rows (B, k, d)."""
+        d = self.d
+        self.qkv[i][:, n0:n0 + k].copy_(qkv_new)
+        ops.relpos_attention_rows(self.qkv[i], self.pos_all[:, i * d:(i + 1) * d], a.content_bias, a.position_bias,
+                                  self.lengths, a.n_heads, n0, k, self.ctx, keys_hint=n0 + k)
+        return self.ctx[:, n0:n0 + k].contiguous()
+
+    def _conv_window(self, i: int, g: torch.Tensor) -> torch.Tensor:
+        """The depthwise convolution's input: layer i's carried GLU rows, then the chunk's."""
+        return torch.cat([self.conv_state[i], g], dim=1)
+
+    def _conv_keep(self, i: int, buf: torch.Tensor) -> None:
+        """Carry the last (K-1)/2 GLU rows into the next chunk."""
+        half = self.half[i]
+        self.conv_state[i].copy_(buf[:, buf.shape[1] - half:])            # fixed buffer (the graph replays write the same address)
 
     def run(self, mel: torch.Tensor, chunk_frames: int = 640) -> torch.Tensor:
         """Feeds mel (B, n_mel, T) in chunks of `chunk_frames` and returns the concatenated (B, T', d) output."""

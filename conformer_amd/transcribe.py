@@ -19,6 +19,22 @@ from .decode import BeamCTCDecoder, BeamCTCStream
 from .streaming import StreamingEncoder
 
 
+@torch.no_grad()
+def decode_frames(model, state, enc: torch.Tensor, lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The decoder (Decoder.fused in eval mode) on new encoder frames (B, k, d) with the LSTM state `state` ([(h, c)] per
+    layer, (B, H) each) carried; `lengths` (B) int64 on the device: frames per utterance (None: all k)."""
+    dec = model.decoder
+    h = enc.float() if enc.dtype != torch.float32 else enc
+    for k, st in enumerate(state):
+        w_ih, w_hh = getattr(dec.lstm, f"weight_ih_l{k}"), getattr(dec.lstm, f"weight_hh_l{k}")
+        b_ih, b_hh = getattr(dec.lstm, f"bias_ih_l{k}"), getattr(dec.lstm, f"bias_hh_l{k}")
+        bias = dec._packs.get(f"bias{k}", (b_ih, b_hh), lambda: (b_ih + b_hh).detach().contiguous())
+        h = ops.lstm_forward(h, w_ih.detach(), w_hh.detach(), bias, lengths, state=st)
+    n = dec.norm
+    z = ops.swish_bn_eval(h, n.running_mean, n.running_var, n.weight.detach(), n.bias.detach(), n.eps)
+    return ops.linear(z, dec.linear.weight.detach(), dec.linear.bias.detach())
+
+
 class StreamingTranscriber:
     """model: a Conformer in eval() mode on the HIP device; decoder: the BeamCTCDecoder whose configuration (beam knobs, lm,
     hotwords) the streamed search takes; batch utterances of at most max_mel_frames mel frames.  graphs: as StreamingEncoder."""
@@ -51,16 +67,7 @@ class StreamingTranscriber:
     @torch.no_grad()
     def decode_frames(self, enc: torch.Tensor) -> torch.Tensor:
         """The decoder (Decoder.fused in eval mode) on the chunk's new encoder frames (B, k, d), the LSTM state carried."""
-        dec = self.model.decoder
-        h = enc.float() if enc.dtype != torch.float32 else enc
-        for k, state in enumerate(self.state):
-            w_ih, w_hh = getattr(dec.lstm, f"weight_ih_l{k}"), getattr(dec.lstm, f"weight_hh_l{k}")
-            b_ih, b_hh = getattr(dec.lstm, f"bias_ih_l{k}"), getattr(dec.lstm, f"bias_hh_l{k}")
-            bias = dec._packs.get(f"bias{k}", (b_ih, b_hh), lambda: (b_ih + b_hh).detach().contiguous())
-            h = ops.lstm_forward(h, w_ih.detach(), w_hh.detach(), bias, None, state=state)
-        n = dec.norm
-        z = ops.swish_bn_eval(h, n.running_mean, n.running_var, n.weight.detach(), n.bias.detach(), n.eps)
-        return ops.linear(z, dec.linear.weight.detach(), dec.linear.bias.detach())
+        return decode_frames(self.model, self.state, enc)
 
     @torch.no_grad()
     def step(self, mel_chunk: torch.Tensor) -> torch.Tensor:

@@ -588,6 +588,14 @@ int cfm_ctc_beam_stream_finish_f32(int B, int beam_width, int max_candidates, in
                                    const void* hw_tables_or_null, double hotword_weight, void* state, size_t state_bytes,
                                    int T_max, int64_t* tokens, int64_t* counts, float* scores, float* am_scores_or_null,
                                    int64_t* num_hyps, cfm_stream_t stream);
+/*      Independent streams (INTEGRATION.md "Independent streams (slots)"): cfm_ctc_beam_stream_reset_slots puts the utterances
+ *      slots[0 .. n_slots) (a device int64 array; entries outside [0,B) are skipped) back at the empty prefix and leaves the
+ *      others as they are; mode arguments as cfm_ctc_beam_stream_init.  The finish saves no state, so closing one slot is
+ *      finish -> take that slot's row -> reset that slot.  With slots at different positions a step's t_used is passed as
+ *      max_b(frames_b + lengths_b) - Tc (the caller checks frames_b + lengths_b <= T_max per slot). */
+int cfm_ctc_beam_stream_reset_slots(int B, int T_max, int beam_width, int max_candidates, const void* lm_tables_or_null,
+                                    int score_boundary, const void* hw_tables_or_null, const int64_t* slots, int n_slots,
+                                    void* state, size_t state_bytes, cfm_stream_t stream);
 
 /* N1 decoder (decoder.py:10-27): LSTM recurrence over a packed batch.  gates_x (B,T,4H) = X.W_ih^T + b_ih + b_hh from
  *      one of the GEMM entries; w_hh (4H,H), gate order i|f|g|o; lengths_or_null: frames per utterance (outputs beyond are
@@ -686,6 +694,16 @@ int cfm_relpos_attention_rows_f32(const float* q, const float* k, const float* v
                                   int64_t ldp, const float* u, const float* vbias, const int64_t* lengths_or_null,
                                   float* ctx, int64_t ldo, int B, int T, int H, int dh, int q_begin, int q_count,
                                   int nsplit, float* workspace_or_null, cfm_stream_t stream);
+/*      independent streams (INTEGRATION.md "Independent streams (slots)"): slot b computes the query rows
+ *      [q_begin[b], q_begin[b] + q_count[b]) of its own cache (keys < lengths[b]) into the COMPACT ctx (B, q_max, ldo) rows
+ *      0 .. q_count[b)-1; rows q_count[b] .. q_max-1 are written as zeros and a slot with q_count[b] == 0 reads nothing.  q_begin,
+ *      q_count, lengths: device int64 (B), clamped on the device (q_begin to [0,T], q_count to [0, min(q_max, T - q_begin)]): no
+ *      value makes an access outside the cache, the (2T-1, .) table or ctx.  q_max in [1,T]; nsplit as the rows entry
+ *      (workspace: nsplit*B*q_max*(H*dh + H) floats, ldo == H*dh). */
+int cfm_relpos_attention_slots_f32(const float* q, const float* k, const float* v, int64_t ld, const float* pos, int64_t ldp,
+                                   const float* u, const float* vbias, const int64_t* q_begin, const int64_t* q_count,
+                                   const int64_t* lengths, float* ctx, int64_t ldo, int B, int T, int H, int dh, int q_max,
+                                   int nsplit, float* workspace_or_null, cfm_stream_t stream);
 
 /* diagnostics only: cfm_relpos_attention_fwd_f32 + s_memrealtime stamps of one wave (trace: 16*ceil(T/32) uint64) */
 int cfm_debug_attention_trace_f32(const float* q, const float* k, const float* v, int64_t ld, const float* pos,

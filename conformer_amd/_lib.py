@@ -92,6 +92,7 @@ SIGNATURES = {
     "cfm_debug_attention_bwd_trace_mfma16": (c_int, [_P]),
     "cfm_debug_gemm_mfma16_trace": (c_int, [_P]),
     "cfm_debug_gemm_mfma16_force_tile": (c_int, [_I]),
+    "cfm_debug_gemm_last_tile": (c_int, [_I, _P]),
     "cfm_relpos_attention_bwd_mfma16_f32": (c_int, [_I, _P, _P, _P, _L, _P, _L, _P, _P, _P, _P, _P, _L, _P, _P, _P, _P, _L, _P, _L,
                                                     _P, _P, _I, _I, _I, _I, _F, _U, _P]),
     "cfm_relpos_attention_bwd_f32": (c_int, [_P, _P, _P, _L, _P, _L, _P, _P, _P, _P, _P, _L, _P, _P, _P, _P, _L, _P, _L, _P, _P,

@@ -303,6 +303,7 @@ int launch_cfg(GemmArgs g, hipStream_t s) {
         pad = per > kStatic ? (size_t)((per - kStatic) & ~255) : 0;
     }
     const unsigned gy = g.ksplit_len > 0 ? (unsigned)((g.K + g.ksplit_len - 1) / g.ksplit_len) : 1u;
+    gemm_last_tile(0) = {BM, BN, 4, (int)gy, 0, 0};
     hipLaunchKernelGGL((gemm_f32_kernel<BM, BN, EPI, CONV, LN, BK>), dim3(g.tiles_m * g.tiles_n, gy), dim3(256), pad, s, g);
     return cfm_launch_status();
 }
@@ -736,6 +737,22 @@ extern "C" int cfm_debug_set_conv2_bk(int bk) {
     if (bk == 0 || bk == 1) g_conv2_kperm = bk;
     if (bk >= 100 && bk <= 102) g_conv2_tile = bk - 100;
     return prev;
+}
+
+GemmTileRecord& gemm_last_tile(int family) {
+    static thread_local GemmTileRecord rec[3];              // per host thread: launches on other threads neither race nor show
+    return rec[family];
+}
+
+// diagnostics (tests): out[0..5] = {BM, BN, waves, K slices, operand form, 16-bit C} of the last launch of GEMM family 0 (fp32),
+// 1 (16-bit) or 2 (split-plane) made by the calling thread since the previous call (all zero if none); the record is cleared.
+extern "C" int cfm_debug_gemm_last_tile(int family, int* out) {
+    CFM_REQUIRE(out != nullptr, CFM_ERR_NULL);
+    CFM_REQUIRE(family >= 0 && family <= 2, CFM_ERR_BAD_SHAPE);
+    GemmTileRecord& r = gemm_last_tile(family);
+    out[0] = r.bm; out[1] = r.bn; out[2] = r.waves; out[3] = r.ksplits; out[4] = r.form; out[5] = r.c16;
+    r = GemmTileRecord{};
+    return CFM_OK;
 }
 
 // Tuning / diagnostics: the residual-epilogue GEMM with a forced block-tile shape

@@ -275,6 +275,7 @@ int launch_cfg(GemmArgs g, int src16, hipStream_t s) {          // src16: 0 = fp
     g.tiles_m = (unsigned)((g.M + BM - 1) / BM);
     g.tiles_n = (unsigned)((ncols + bn - 1) / bn);
     const dim3 grid(g.tiles_m * g.tiles_n);
+    gemm_last_tile(1) = {BM, BN, 4, 1, src16, g.c_prec != 0};
     // dropout only exists for the bias / Swish / residual epilogues of the training forward (and, as a mask replay, in EPI_DSWISH)
     constexpr bool CAN_DROP = EPI == EPI_BIAS || EPI == EPI_SWISH || EPI == EPI_RESID;
     constexpr int FN = EPI == EPI_DSWISH ? 0 : EPF_NO_DROPOUT;
@@ -305,6 +306,7 @@ int launch_big(GemmArgs g, int src16, hipStream_t s) {          // 512-thread wo
     g.tiles_m = (unsigned)((g.M + BM - 1) / BM);
     g.tiles_n = (unsigned)((g.N + BN - 1) / BN);
     const dim3 grid(g.tiles_m * g.tiles_n);
+    gemm_last_tile(1) = {BM, BN, 8, 1, src16, g.c_prec != 0};
     constexpr bool CAN_DROP = EPI == EPI_BIAS || EPI == EPI_SWISH || EPI == EPI_RESID;
     constexpr int FN = EPI == EPI_DSWISH ? 0 : EPF_NO_DROPOUT;
     if constexpr (CONV != 0) {
@@ -422,7 +424,9 @@ extern "C" int cfm_debug_gemm_mfma16_trace(void* trace_or_null) {
     return CFM_OK;
 }
 
-// tuning only (tools/gemm16_sites.py sweep): 0 = built-in choice, 1 = 128x128 / 64x64 family, 2 = 256x128, 3 = 256x256
+// tuning only (tools/gemm16_sites.py sweep): 0 = built-in choice, 1 = the 4-wave tiles by shape (128x128 / 128x64 / 64x64),
+// 2 = 256x128, 3 = 256x256 (both: 16-bit W and the vectorised epilogue, else the 4-wave choice), 4 = 128x64 (bias / residual
+// epilogues; the others 64x64), 5 = 64x64
 extern "C" int cfm_debug_gemm_mfma16_force_tile(int tile) {
     g_gemm16_force_tile = tile;
     return CFM_OK;

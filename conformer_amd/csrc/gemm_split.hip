@@ -181,6 +181,7 @@ int launch_cfg(GemmArgs g, int planes, hipStream_t s) {
     g.tiles_m = (unsigned)((g.M + BM - 1) / BM);
     g.tiles_n = (unsigned)((ncols + bn - 1) / bn);
     const dim3 grid(g.tiles_m * g.tiles_n);
+    gemm_last_tile(2) = {BM, BN, 4, 1, planes, 0};
     if (planes == 3) hipLaunchKernelGGL((gemm_split_kernel<BM, BN, EPI, CONV, 3>), grid, dim3(256), 0, s, g);
     else hipLaunchKernelGGL((gemm_split_kernel<BM, BN, EPI, CONV, 2>), grid, dim3(256), 0, s, g);
     return cfm_launch_status();

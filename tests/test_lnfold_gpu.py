@@ -11,7 +11,7 @@ import pytest
 import torch
 
 from oracle import conformer_oracle as O
-from tests.util import rel_l2
+from tests.util import merged, ref_partials, rel_l2
 
 pytestmark = pytest.mark.gpu
 TOL = 2e-5
@@ -33,23 +33,6 @@ def G(t):
 def rnd(*shape, seed=0, scale=1.0):
     g = torch.Generator().manual_seed(seed)
     return torch.randn(*shape, generator=g) * scale
-
-
-def ref_partials(y, width):
-    """(sum, M2 about the group's own mean) of every `width` consecutive values of each row, float64."""
-    g = y.double().reshape(y.shape[0], -1, width)
-    s = g.sum(-1)
-    m2 = ((g - g.mean(-1, keepdim=True)) ** 2).sum(-1)
-    return torch.stack([s, m2], dim=-1)
-
-
-def merged(stats, d):
-    """(mean, var) of each row from its partials (the merge the consumer kernel performs), float64."""
-    st = stats.double().cpu()
-    n = d // st.shape[1]
-    mean = st[..., 0].sum(-1) / d
-    m2 = st[..., 1].sum(-1) + (n * (st[..., 0] / n - mean[:, None]) ** 2).sum(-1)
-    return mean, m2 / d
 
 
 @pytest.mark.parametrize("M,N,K", [(1, 32, 16), (100, 64, 144), (257, 512, 512), (7968, 512, 2048), (130, 256, 20), (333, 128, 64)])

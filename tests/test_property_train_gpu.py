@@ -19,7 +19,7 @@ hypothesis = pytest.importorskip("hypothesis")
 from hypothesis import example, given, settings, strategies as st, HealthCheck  # noqa: E402
 
 from oracle import conformer_oracle as O  # noqa: E402
-from tests.util import rel_l2  # noqa: E402
+from tests.util import Calls as _Calls, rel_l2  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 TOL = 2e-5                   # fp32 kernels
@@ -53,32 +53,6 @@ def leaf(t):
 def dswish(z):
     s = torch.sigmoid(z)
     return s * (1 + z * (1 - s))
-
-
-class _Calls:
-    """Records which of the named library entry points run inside the block: the route a wrapper took."""
-
-    def __init__(self, *names):
-        self.names, self.seen, self.saved = names, set(), {}
-
-    def _spy(self, name, fn):
-        def call(*args):
-            self.seen.add(name)
-            return fn(*args)
-        return call
-
-    def __enter__(self):
-        from conformer_amd import _lib
-        self.lib = _lib.load()
-        for n in self.names:
-            self.saved[n] = getattr(self.lib, n)
-            setattr(self.lib, n, self._spy(n, self.saved[n]))
-        return self.seen
-
-    def __exit__(self, *exc):
-        for n, fn in self.saved.items():
-            setattr(self.lib, n, fn)
-        return False
 
 
 # ---- 1. LayerNorm: forward statistics + backward (one pass for d <= 2048, dx kernel + parameter kernel above) --------------

@@ -45,3 +45,46 @@ def golden_find(g: dict, stem: str):
         if k.startswith(stem + "@s"):
             return k
     return None
+
+
+def ref_partials(y, width):
+    """(sum, M2 about the group's own mean) of every `width` consecutive values of each row, float64."""
+    g = y.double().reshape(y.shape[0], -1, width)
+    s = g.sum(-1)
+    m2 = ((g - g.mean(-1, keepdim=True)) ** 2).sum(-1)
+    return torch.stack([s, m2], dim=-1)
+
+
+def merged(stats, d):
+    """(mean, var) of each row from its partials (the merge the consumer kernel performs), float64."""
+    st = stats.double().cpu()
+    n = d // st.shape[1]
+    mean = st[..., 0].sum(-1) / d
+    m2 = st[..., 1].sum(-1) + (n * (st[..., 0] / n - mean[:, None]) ** 2).sum(-1)
+    return mean, m2 / d
+
+
+class Calls:
+    """Records which of the named library entry points run inside the block: the route a wrapper took."""
+
+    def __init__(self, *names):
+        self.names, self.seen, self.saved = names, set(), {}
+
+    def _spy(self, name, fn):
+        def call(*args):
+            self.seen.add(name)
+            return fn(*args)
+        return call
+
+    def __enter__(self):
+        from conformer_amd import _lib
+        self.lib = _lib.load()
+        for n in self.names:
+            self.saved[n] = getattr(self.lib, n)
+            setattr(self.lib, n, self._spy(n, self.saved[n]))
+        return self.seen
+
+    def __exit__(self, *exc):
+        for n, fn in self.saved.items():
+            setattr(self.lib, n, fn)
+        return False

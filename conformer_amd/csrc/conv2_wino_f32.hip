@@ -16,9 +16,12 @@
 // channel-chunk-major K walk (the terms of a 32-channel chunk reuse the same h1 lines) and row-major epilogue.  The staging
 // differs: an A element is a +-1 combination of 1, 2 or 4 h1 pixels, so the raw pixels of a K-tile take up to 4x the staging
 // registers; the tile is staged ONE K-tile ahead in one register set (the direct kernel: two ahead in two sets).  A K-tile
-// of 64 MFMAs per wave at two waves per SIMD covers about 8000 cycles of load latency.  Pixels outside T1 / F1 (the ragged
-// last blocks) are loaded from clamped addresses and zeroed by a select.  The whole 32-channel chunk is unrolled, so every
-// K-tile's term -- its pixel count and signs -- is a compile-time constant and no load sits behind a branch.
+// of 64 MFMAs per wave at two waves per SIMD covers about 8000 cycles of load latency (two ahead for the centre and edge
+// problems, which have the registers for it, measured no faster).  The whole 32-channel chunk is unrolled, so every K-tile's
+// term -- its pixel count and signs -- is a compile-time constant and no load sits behind a branch.  A load's offset is one
+// per-row register plus a wave-uniform part (pixel, channel chunk, K position) that rides in the instruction's scalar offset:
+// added per lane instead, the sums took address registers that pushed the corner loop to 256 VGPRs and into spills, whose
+// reloads queue behind the K-tile's loads (4.27 -> 3.94 ms at B = 32; DESIGN.md section 5, "Tuning pass").
 #include <algorithm>
 #include <utility>
 
@@ -45,18 +48,26 @@ __device__ __forceinline__ void static_for(Fn&& f) {   // f(integral_constant<in
 __host__ __device__ constexpr int wino_nt(int a) { return a == 1 ? 1 : 2; }
 __host__ __device__ constexpr int wino_terms(int p) { return wino_nt(p / 3) * wino_nt(p % 3); }
 
+// Dead rows.  With F2 odd the s = 1 output of the last frequency block (jb = TJ - 1) does not exist, and the b = 2 patterns
+// feed nothing else; likewise a = 2 at ib = TI - 1 with T2 odd.  Those patterns run over TJ - 1 (TI - 1) blocks: pattern p's
+// rows are the blocks (bb, ib, jb) of its own TI_p x TJ_p grid, stored densely at the head of its plane (the plane stride
+// stays M), and the combine kernel reads a short plane only at the blocks it holds.
 struct WinoArgs {
     const float* h1; const float* w; float* planes;
-    int64_t M;                      // output blocks B * TI * TJ
+    int64_t M;                      // output blocks nb * TI * TJ (plane stride in rows)
     unsigned h1_bytes;
-    int T1, F1, C, TI, TJ;
-    unsigned tiles_m, tiles_n;
+    int T1, F1, C, TI, TJ, nb;
+    int odd_t, odd_f;               // T2 / F2 odd: the a = 2 / b = 2 patterns have one block less in that dimension
+    unsigned tiles_n;
     unsigned grp_blk[4];            // workgroup ranges of the corner / edge / centre groups (starts are multiples of 8)
+    unsigned grp_tm[3][4];          // per group: row tiles of its patterns, ascending (the centre: 0, 0, 0, tiles)
+    unsigned grp_pat[3];            // per group: the patterns in that order, one nibble each
 };
 
 // Launch order: the four corner patterns (K = 4C), then the four edges (2C), then the centre (C) -- the long problems first so
 // the last round holds short tiles.  Within a group, the tile list (tm, pattern, tn) is cut into 8 contiguous ranges, one per
-// XCD (workgroup w runs on XCD w % 8), so the 2 x 4 tiles of one row block (they read the same h1 lines) share an L2.
+// XCD (workgroup w runs on XCD w % 8), so the 2 x 4 tiles of one row block (they read the same h1 lines) share an L2.  A
+// pattern with fewer row tiles than the others of its group simply drops out of the list from its last tile on.
 
 template <int ST, int SF>
 __device__ __forceinline__ void wino_tile(const WinoArgs& g, int p, int64_t m0, int n0, float* lds) {
@@ -76,18 +87,19 @@ __device__ __forceinline__ void wino_tile(const WinoArgs& g, int p, int64_t m0, 
     const int chunk = tid & (CPR - 1), srow = tid / CPR;
     // per staged row: byte offset of its 5x5 patch in h1 (h1 < 4 GiB: the entry point splits the batch).  The pixels of a term
     // are the uniform offsets of the distinct d used per dimension (index 0: d[4 sg], or d[2] in a one-term dimension; 1: d[2];
-    // 2: d[1 + 2 sg]).  No pixel of a VALID output lies outside T1 x F1 (t2 < T2 gives 4 i + 4 <= T1 - 1); the ones beyond
-    // the edge feed only pattern-2 terms of outputs that are never written, so they are read as they fall -- the next frame or
-    // utterance, or zero past the end of h1 (the buffer's range check) -- and need no select.
+    // 2: d[1 + 2 sg]).  No pixel of a VALID output lies outside T1 x F1 (t2 < T2 gives 4 i + 4 <= T1 - 1), and the blocks
+    // whose pattern-2 terms would reach beyond the edge are not among a pattern-2 problem's rows: every load is inside h1 and
+    // needs no select.  (It has to be: the scalar offset is not part of the buffer's range check.)
     unsigned row_off[PA];
-    const int64_t pos_per_b = (int64_t)g.TI * g.TJ;
+    const int TJp = g.TJ - (b == 2 ? g.odd_f : 0);                  // this pattern's block grid (see WinoArgs)
+    const int64_t pos_per_b = (int64_t)(g.TI - (a == 2 ? g.odd_t : 0)) * TJp, Mp = g.nb * pos_per_b;
 #pragma unroll
     for (int i = 0; i < PA; ++i) {
         int64_t m = m0 + srow + RPP * i;
-        if (m >= g.M) m = g.M - 1;                                  // loaded, never stored
+        if (m >= Mp) m = Mp - 1;                                    // loaded, never stored
         const int64_t bb = m / pos_per_b;
         const int r = (int)(m - bb * pos_per_b);
-        const int ib = r / g.TJ, jb = r - ib * g.TJ;
+        const int ib = r / TJp, jb = r - ib * TJp;
         row_off[i] = (unsigned)((((bb * g.T1 + 4 * ib) * g.F1 + 4 * jb) * (int64_t)g.C + chunk * 4) * 4);
     }
     const __amdgpu_buffer_rsrc_t h1_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(g.h1), (short)0, (int)g.h1_bytes, 0x00020000);
@@ -99,9 +111,7 @@ __device__ __forceinline__ void wino_tile(const WinoArgs& g, int p, int64_t m0, 
     const int K = NT * g.C;
     const __amdgpu_buffer_rsrc_t w_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(g.w + woff * g.C * g.C), (short)0,
                                                                             K * g.C * 4, 0x00020000);
-    unsigned w_off[PB];
-#pragma unroll
-    for (int i = 0; i < PB; ++i) w_off[i] = (unsigned)(((n0 + srow + RPP * i) * K + chunk * 4) * 4);
+    const unsigned w_off = (unsigned)(((n0 + srow) * K + chunk * 4) * 4), w_step = (unsigned)(RPP * K * 4);
 
     // term u = ut * SF + uf is the product of a time and a frequency term: a two-pixel dimension term is d-index 0 minus
     // d-index 1, a one-pixel term d-index 2 (two-term dimension) or 0 (one-term dimension); raw[i][x * NYF + y]
@@ -118,11 +128,11 @@ __device__ __forceinline__ void wino_tile(const WinoArgs& g, int p, int64_t m0, 
                 const unsigned po = pix_t[X1 + x] + pix_f[Y1 + y] + ci4;
 #pragma unroll
                 for (int i = 0; i < PA; ++i)
-                    raw[i][x * NYF + y] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(h1_rsrc, row_off[i] + po, 0, 0));
+                    raw[i][x * NYF + y] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(h1_rsrc, row_off[i], po, 0));
             }
         const unsigned k4 = (unsigned)(NT * 32 * c32 + 32 * U + 16 * half) * 4;
 #pragma unroll
-        for (int i = 0; i < PB; ++i) rb[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(w_rsrc, w_off[i] + k4, 0, 0));
+        for (int i = 0; i < PB; ++i) rb[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(w_rsrc, w_off, k4 + w_step * i, 0));
     };
     auto store_tile = [&](auto U_, int buf) __attribute__((always_inline)) {
         constexpr int U = decltype(U_)::value, UT = U / SF, UF = U % SF;
@@ -190,7 +200,7 @@ __device__ __forceinline__ void wino_tile(const WinoArgs& g, int p, int64_t m0, 
     __syncthreads();
     GemmArgs ge{};
     ge.C = g.planes + (int64_t)p * g.M * g.C;
-    ge.M = g.M; ge.N = g.C; ge.K = K; ge.ldc = g.C; ge.alpha = 1.f;
+    ge.M = Mp; ge.N = g.C; ge.K = K; ge.ldc = g.C; ge.alpha = 1.f;
     gemm_epilogue_rows<BM, BN, EPI_BIAS, TM, TN, 2, false, EPF_INFER | EPF_NO_BIAS, WN>(ge, acc, m0, n0, wr, wc, lane,
                                                                                         lds + wave * 32 * (32 * TN + 4));
 }
@@ -201,14 +211,20 @@ __global__ __launch_bounds__(512, 2) void conv2_wino_gemm_kernel(const WinoArgs 
     __shared__ __attribute__((aligned(16))) float lds[LDS_STAGE];
     const unsigned bid = blockIdx.x;
     const int grp = bid < g.grp_blk[1] ? 0 : (bid < g.grp_blk[2] ? 1 : 2);
-    const unsigned npat = grp == 2 ? 1u : 4u;
-    const unsigned ntile = npat * g.tiles_m * g.tiles_n;
     const unsigned local = bid - g.grp_blk[grp], per_xcd = (g.grp_blk[grp + 1] - g.grp_blk[grp]) / 8;
-    const unsigned tile = (local & 7u) * per_xcd + (local >> 3);
-    if (tile >= ntile) return;                                       // (padding of the group to a multiple of 8)
+    unsigned tile = (local & 7u) * per_xcd + (local >> 3);
+    // row tiles [grp_tm[k - 1], grp_tm[k]) are run by the patterns k .. 3 of the sorted list
+    unsigned k = 0, lo = 0;
+    for (; k < 4; ++k) {
+        const unsigned seg = (g.grp_tm[grp][k] - lo) * (4 - k) * g.tiles_n;
+        if (tile < seg) break;
+        tile -= seg;
+        lo = g.grp_tm[grp][k];
+    }
+    if (k == 4) return;                                              // (padding of the group to a multiple of 8)
     const unsigned tn = tile % g.tiles_n, rest = tile / g.tiles_n;
-    const unsigned pi = rest % npat, tm = rest / npat;
-    const int p = (int)(((grp == 0 ? 0x8620u : grp == 1 ? 0x5371u : 0x4u) >> (4 * pi)) & 15u);
+    const unsigned pi = k + rest % (4 - k), tm = lo + rest / (4 - k);
+    const int p = (int)((g.grp_pat[grp] >> (4 * pi)) & 15u);
     const int64_t m0 = (int64_t)tm * 256;
     const int n0 = (int)tn * 256;
     const int nta = wino_nt(p / 3), ntb = wino_nt(p % 3);
@@ -220,7 +236,8 @@ __global__ __launch_bounds__(512, 2) void conv2_wino_gemm_kernel(const WinoArgs 
 
 // h2[b][t2][f2][c] = relu(b2[c] + sum of the four planes of (t2 & 1, f2 & 1)), one thread per (block, 4 channels): the nine
 // plane values are read once and the block's (up to) four valid outputs written.  Fixed summation order:
-// ((P_a0 + P_a1) for a = r, then r + 1 ...) -- see the body.
+// ((P_a0 + P_a1) for a = r, then r + 1 ...) -- see the body.  A short plane (a = 2 with T2 odd, b = 2 with F2 odd) has no row
+// for a block of the last time / frequency column; it is not read there, and feeds no output that exists.
 __global__ __launch_bounds__(256) void conv2_wino_combine_kernel(const float* __restrict__ planes, const float* __restrict__ b2,
                                                                  float* __restrict__ h2, int64_t M, int T2, int F2, int TI,
                                                                  int TJ, int C) {
@@ -234,9 +251,16 @@ __global__ __launch_bounds__(256) void conv2_wino_combine_kernel(const float* __
     const int r = (int)(m - bb * per_b);
     const int ib = r / TJ, jb = r - ib * TJ;
     const int64_t plane = M * (int64_t)C;
+    const int TIs = TI - (T2 & 1), TJs = TJ - (F2 & 1);
     f32x4 P[9];
 #pragma unroll
-    for (int q = 0; q < 9; ++q) P[q] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(planes + q * plane + m * C + c));
+    for (int q = 0; q < 9; ++q) {
+        const bool st = q / 3 == 2, sf = q % 3 == 2;                  // pattern q's rows: its own (TI or TIs) x (TJ or TJs) grid
+        const int64_t mq = (bb * (st ? TIs : TI) + ib) * (sf ? TJs : TJ) + jb;
+        P[q] = f32x4{0.f, 0.f, 0.f, 0.f};
+        if ((!st || ib < TIs) && (!sf || jb < TJs))
+            P[q] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(planes + q * plane + mq * C + c));
+    }
     const f32x4 bias = *reinterpret_cast<const f32x4*>(b2 + c);
 #pragma unroll
     for (int rt = 0; rt < 2; ++rt) {
@@ -320,6 +344,7 @@ extern "C" int cfm_subsample_conv2_wino_relu_f32(const float* h1, const float* w
     WinoArgs g{};
     g.w = wp;
     g.T1 = T1; g.F1 = F1; g.C = C; g.TI = (T2 + 1) / 2; g.TJ = (F2 + 1) / 2;
+    g.odd_t = T2 & 1; g.odd_f = F2 & 1;
     g.tiles_n = (unsigned)(C / 256);
     const int64_t per_b = (int64_t)g.TI * g.TJ;
     const int group = (int)std::min<int64_t>(B, limit / utt_bytes);
@@ -329,11 +354,27 @@ extern "C" int cfm_subsample_conv2_wino_relu_f32(const float* h1, const float* w
         g.h1 = h1 + b0 * (utt_bytes / 4);
         g.h1_bytes = (unsigned)(nb * utt_bytes);
         g.M = nb * per_b;
+        g.nb = nb;
         g.planes = planes + 9 * (b0 * per_b) * C;
-        g.tiles_m = (unsigned)((g.M + 255) / 256);
-        const unsigned group_n[3] = {4, 4, 1};                         // patterns per group (conv2_wino_gemm_kernel)
+        // per group: its patterns sorted by row tiles, ascending and stable (conv2_wino_gemm_kernel walks them from the back)
+        static const int group_pat[3][4] = {{0, 2, 6, 8}, {1, 7, 3, 5}, {-1, -1, -1, 4}};
         g.grp_blk[0] = 0;
-        for (int q = 0; q < 3; ++q) g.grp_blk[q + 1] = g.grp_blk[q] + (group_n[q] * g.tiles_m * g.tiles_n + 7) / 8 * 8;
+        for (int q = 0; q < 3; ++q) {
+            int pat[4];
+            unsigned tm[4], total = 0;
+            for (int i = 0; i < 4; ++i) {
+                const int p = group_pat[q][i];
+                const int64_t Mp = p < 0 ? 0 : (int64_t)nb * (g.TI - (p / 3 == 2 ? g.odd_t : 0)) * (g.TJ - (p % 3 == 2 ? g.odd_f : 0));
+                const unsigned t = (unsigned)((Mp + 255) / 256);
+                int j = i;
+                for (; j > 0 && tm[j - 1] > t; --j) { tm[j] = tm[j - 1]; pat[j] = pat[j - 1]; }
+                tm[j] = t; pat[j] = p < 0 ? 0 : p;
+                total += t;
+            }
+            g.grp_pat[q] = 0;
+            for (int i = 0; i < 4; ++i) { g.grp_tm[q][i] = tm[i]; g.grp_pat[q] |= (unsigned)pat[i] << (4 * i); }
+            g.grp_blk[q + 1] = g.grp_blk[q] + (total * g.tiles_n + 7) / 8 * 8;
+        }
         hipLaunchKernelGGL(conv2_wino_gemm_kernel, dim3(g.grp_blk[3]), dim3(512), 0, s, g);
         int st = cfm_launch_status();
         if (st) return st;

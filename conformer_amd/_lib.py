@@ -149,6 +149,8 @@ SIGNATURES = {
     "cfm_ctc_workspace_floats": (ctypes.c_int64, [_I, _I, _I]),
     "cfm_ctc_loss_fwd_f32": (c_int, [_P, _P, _P, _L, _L, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "cfm_ctc_loss_bwd_f32": (c_int, [_P, _P, _P, _L, _L, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "cfm_ctc_align_workspace_bytes": (ctypes.c_size_t, [_I, _I, _I]),
+    "cfm_ctc_align_f32": (c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, ctypes.c_size_t, _P, _P, _P, _P, _P, _P, _P, _P]),
     "cfm_relpos_attention_rows_f32": (c_int, [_P, _P, _P, _L, _P, _L, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     "cfm_relpos_attention_slots_f32": (c_int, [_P, _P, _P, _L, _P, _L, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _P, _P]),
     "cfm_debug_attention_trace_f32": (c_int, [_P, _P, _P, _L, _P, _L, _P, _P, _P, _P, _L, _I, _I, _I, _I, _P, _P]),

@@ -1,0 +1,237 @@
+"""CTC forced alignment on the device: token and word timestamps (INTEGRATION.md "Forced alignment").
+
+`ctc_forced_align` aligns known targets to logits: the best path of the CTC lattice (the one the loss sums over), its
+frames, the span and mean log-probability of every target token and the path's log-probability.  `CTCAligner` puts words
+on top: texts or token ids in, `Word(text, start_frame, end_frame, start, end, score)` out; `CTCAligner.hypotheses` does
+the same for what a `BeamCTCDecoder` search returned.  Timestamps of a finished stream (`StreamingTranscriber`,
+`SlotTranscriber`) come from aligning the final text against the collected logits.
+
+There is no CPU path: the alignment runs as gfx950 kernels (conformer_amd/csrc/ctc_align.hip)."""
+from __future__ import annotations
+
+from typing import List, NamedTuple, Optional, Sequence, Union
+
+import torch
+
+from . import _lib, ops
+
+MAX_FRAMES = 16384          # CFM_CTC_ALIGN_MAX_FRAMES of include/conformer_hip.h
+MAX_TARGET = 4096           # CFM_CTC_ALIGN_MAX_TARGET
+
+
+class Alignment(NamedTuple):
+    """Device tensors; B utterances, T frames, Lmax target slots.  Padding: -1 (int64), -inf (scores), False (ok)."""
+    frame_tokens: torch.Tensor     # (B,T) int64: symbol emitted at each frame (blank id or a label)
+    frame_index: torch.Tensor      # (B,T) int64: index into the target for label frames, -1 for blank frames
+    token_start: torch.Tensor      # (B,Lmax) int64: first frame of target token i
+    token_end: torch.Tensor        # (B,Lmax) int64: one past its last frame
+    token_score: torch.Tensor      # (B,Lmax) fp32: mean over the run of log_softmax(x[t])[y_i]
+    score: torch.Tensor            # (B,) float64: sum over the frames of the log-probability of the emitted symbol
+    ok: torch.Tensor               # (B,) bool: the target fits the frames
+
+
+class Word(NamedTuple):
+    text: str
+    start_frame: int
+    end_frame: int                 # exclusive
+    start: float                   # seconds
+    end: float
+    score: float                   # frame-weighted mean of the tokens' scores
+
+
+def ctc_forced_align(logits: torch.Tensor, targets: torch.Tensor, blank_id: int, lengths: Optional[torch.Tensor] = None,
+                     target_lengths: Optional[torch.Tensor] = None) -> Alignment:
+    """Align targets (B,Lmax) int64 (padded, as the CTC loss takes them) to logits (B,T,V) on the HIP device (fp32, or
+    bf16 / fp16 cast to fp32).  `lengths` / `target_lengths` (B) int64 on the device: frames / labels per utterance
+    (clamped to [0,T] / [0,Lmax]; None = all).  The path is the maximum of the sum of raw logits over the lattice's paths,
+    ties resolved to the latest alignment.  An utterance with no frames, or fewer frames than labels plus adjacent
+    repeats, is not an error: ok False, score -inf, padding elsewhere.
+
+    Target ids are clamped to [0,V) on the device, as the loss does (checking them would synchronise with the host); a
+    target equal to `blank_id` is not detected here and is aligned as a label that emits the blank symbol.  CTCAligner,
+    which builds the targets on the host, refuses both.  Logits are expected to be finite.  Nothing synchronises with
+    the host."""
+    if isinstance(logits, torch.Tensor) and logits.dtype in (torch.bfloat16, torch.float16):
+        logits = logits.float()
+    x = ops._req(logits, "logits")
+    if x.dim() != 3:
+        raise ValueError(f"logits: expected (B,T,V), got {tuple(x.shape)}")
+    B, T, V = x.shape
+    y = ops._req(targets, "targets", torch.int64)
+    if y.dim() != 2 or y.shape[0] != B:
+        raise ValueError(f"targets: expected ({B},Lmax), got {tuple(y.shape)}")
+    L = int(y.shape[1])
+    if not 0 <= int(blank_id) < V:
+        raise ValueError(f"blank_id {blank_id} outside [0,{V})")
+    if B < 1 or T < 1 or V < 2:
+        raise ValueError(f"logits: empty or degenerate shape {tuple(x.shape)}")
+    if T > MAX_FRAMES or L > MAX_TARGET:
+        raise ValueError(f"ctc_forced_align supports T <= {MAX_FRAMES} and Lmax <= {MAX_TARGET}, got T={T}, Lmax={L}")
+    for name, t in (("lengths", lengths), ("target_lengths", target_lengths)):
+        if t is not None and tuple(ops._req(t, name, torch.int64).shape) != (B,):
+            raise ValueError(f"{name}: expected ({B},), got {tuple(t.shape)}")
+    lengths = None if lengths is None else ops._req(lengths, "lengths", torch.int64)
+    target_lengths = None if target_lengths is None else ops._req(target_lengths, "target_lengths", torch.int64)
+    dev = x.device
+    if L == 0:                                    # no target slot at all: one unused slot, every target length 0
+        y = torch.zeros(B, 1, dtype=torch.int64, device=dev)
+        target_lengths = torch.zeros(B, dtype=torch.int64, device=dev)
+    lmax = max(L, 1)
+    lib = _lib.load()
+    ws_bytes = int(lib.cfm_ctc_align_workspace_bytes(B, T, lmax))
+    if ws_bytes == 0:
+        raise ValueError(f"ctc_forced_align: unsupported shape (B={B}, T={T}, Lmax={L})")
+    workspace = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    frame_tokens = torch.empty(B, T, dtype=torch.int64, device=dev)
+    frame_index = torch.empty(B, T, dtype=torch.int64, device=dev)
+    token_start = torch.empty(B, lmax, dtype=torch.int64, device=dev)
+    token_end = torch.empty(B, lmax, dtype=torch.int64, device=dev)
+    token_score = torch.empty(B, lmax, dtype=torch.float32, device=dev)
+    score = torch.empty(B, dtype=torch.float64, device=dev)
+    ok = torch.empty(B, dtype=torch.bool, device=dev)
+    status = lib.cfm_ctc_align_f32(x.data_ptr(), y.data_ptr(), ops._p(lengths), ops._p(target_lengths), B, T, V, lmax,
+                                   int(blank_id), workspace.data_ptr(), ws_bytes, frame_tokens.data_ptr(),
+                                   frame_index.data_ptr(), token_start.data_ptr(), token_end.data_ptr(),
+                                   token_score.data_ptr(), score.data_ptr(), ok.data_ptr(), ops._stream())
+    _lib.check(status, "cfm_ctc_align_f32")
+    return Alignment(frame_tokens, frame_index, token_start[:, :L], token_end[:, :L], token_score[:, :L], score, ok)
+
+
+def group_words(ids: Sequence[int], starts: Sequence[int], ends: Sequence[int], scores: Sequence[float],
+                vocab: Sequence[str], delim_id: Optional[int], frame_seconds: float, skip_ids=frozenset()) -> List[Word]:
+    """Words are the runs of tokens between delimiter tokens (delimiters at the ends and doubled delimiters make no empty
+    word).  A word spans the first start to the last end of its tokens; its score is the mean of its tokens' scores
+    weighted by their frames.  Tokens in `skip_ids` take part in the span and the score but add no characters."""
+    words: List[Word] = []
+    text, first, last, acc, frames = [], -1, -1, 0.0, 0
+
+    def close():
+        nonlocal text, first, last, acc, frames
+        if frames > 0 and text:
+            words.append(Word("".join(text), first, last, first * frame_seconds, last * frame_seconds, acc / frames))
+        text, first, last, acc, frames = [], -1, -1, 0.0, 0
+
+    for tok, s, e, sc in zip(ids, starts, ends, scores):
+        if delim_id is not None and tok == delim_id:
+            close()
+            continue
+        if tok not in skip_ids:
+            text.append(vocab[tok])
+        first = s if frames == 0 else first
+        last = e
+        acc += sc * (e - s)
+        frames += e - s
+    close()
+    return words
+
+
+class CTCAligner:
+    """Word timestamps from a known transcript: `aligner(logits, texts_or_token_ids, lengths=None)` returns per utterance
+    a list of Word.  `vocab` (V strings) spells the tokens, `delim_token` separates words, `blank_id` is the CTC blank.
+
+    `frame_seconds` converts frames to seconds.  The default 0.04 is the encoder's subsampling of 4 times the front end's
+    hop of 160 samples at 16 kHz.  Encoder frame t' is computed from the mel frames 4t' .. 4t'+6 (two 3-tap stride-2
+    convolutions), so a word's `start` is the time of the first mel frame its first encoder frame sees.
+
+    A text is tokenised greedily, longest vocabulary token first, with a space read as `delim_token`; token-id sequences
+    are taken as they are.  An id outside [0,V), the blank id, or a character no token spells raises ValueError."""
+
+    def __init__(self, vocab: Sequence[str], blank_id: int, delim_token: str = "|", frame_seconds: float = 0.04,
+                 skip_ids: Sequence[int] = ()) -> None:
+        self.vocab = list(vocab)
+        self.blank_id = int(blank_id)
+        if not 0 <= self.blank_id < len(self.vocab):
+            raise ValueError(f"blank_id {blank_id} outside the vocabulary of {len(self.vocab)} tokens")
+        self.delim_token = delim_token
+        self.delim_id = self.vocab.index(delim_token) if delim_token in self.vocab else None
+        self.frame_seconds = float(frame_seconds)
+        self.skip_ids = frozenset(int(i) for i in skip_ids)
+        spell = {}
+        for i, tok in enumerate(self.vocab):
+            if tok and i != self.blank_id and i not in self.skip_ids:
+                spell.setdefault(tok, i)
+        self._spell = spell
+        self._longest = max((len(t) for t in spell), default=1)
+
+    @classmethod
+    def from_decoder(cls, decoder, frame_seconds: float = 0.04) -> "CTCAligner":
+        """Vocabulary, blank, delimiter and skipped ids of a BeamCTCDecoder."""
+        return cls(decoder.vocab, decoder.blank_id, decoder.delim_token, frame_seconds, tuple(sorted(decoder.skip_ids)))
+
+    def tokenize(self, text: str) -> List[int]:
+        s = text.replace(" ", self.delim_token) if self.delim_id is not None else text
+        ids, i = [], 0
+        while i < len(s):
+            for n in range(min(self._longest, len(s) - i), 0, -1):
+                tok = self._spell.get(s[i:i + n])
+                if tok is not None:
+                    ids.append(tok)
+                    i += n
+                    break
+            else:
+                raise ValueError(f"no vocabulary token spells {s[i]!r} (position {i} of {text!r})")
+        return ids
+
+    def _ids(self, item) -> List[int]:
+        if isinstance(item, str):
+            return self.tokenize(item)
+        if isinstance(item, torch.Tensor):
+            item = item.tolist()
+        ids = [int(i) for i in item]
+        for i in ids:
+            if not 0 <= i < len(self.vocab) or i == self.blank_id:
+                raise ValueError(f"target id {i} is outside [0,{len(self.vocab)}) or is the blank id {self.blank_id}")
+        return ids
+
+    def align(self, logits: torch.Tensor, targets: Sequence, lengths: Optional[torch.Tensor] = None):
+        """The targets as id lists and the Alignment of ctc_forced_align for them."""
+        ids = [self._ids(t) for t in targets]
+        if logits.dim() != 3 or logits.shape[0] != len(ids):
+            raise ValueError(f"logits: expected ({len(ids)},T,V), got {tuple(logits.shape)}")
+        if logits.shape[2] != len(self.vocab):
+            raise ValueError(f"vocab has {len(self.vocab)} tokens, the logits {logits.shape[2]}")
+        lmax = max((len(i) for i in ids), default=0)
+        padded = torch.tensor([i + [0] * (lmax - len(i)) for i in ids], dtype=torch.int64).reshape(len(ids), lmax)
+        tlen = torch.tensor([len(i) for i in ids], dtype=torch.int64)
+        if lengths is not None and not (isinstance(lengths, torch.Tensor) and lengths.is_cuda):
+            lengths = torch.as_tensor(lengths, dtype=torch.int64).reshape(-1).to(logits.device)
+        return ids, ctc_forced_align(logits, padded.to(logits.device), self.blank_id, lengths, tlen.to(logits.device))
+
+    def words(self, ids: Sequence[Sequence[int]], al: Alignment) -> List[List[Word]]:
+        """Words of every utterance from its Alignment (one device-to-host copy; an infeasible utterance gives [])."""
+        ok = al.ok.cpu().tolist()
+        starts, ends, scores = al.token_start.cpu().tolist(), al.token_end.cpu().tolist(), al.token_score.cpu().tolist()
+        out = []
+        for b, row in enumerate(ids):
+            n = len(row)
+            out.append(group_words(row, starts[b][:n], ends[b][:n], scores[b][:n], self.vocab, self.delim_id,
+                                   self.frame_seconds, self.skip_ids) if ok[b] else [])
+        return out
+
+    def __call__(self, logits: torch.Tensor, targets: Union[Sequence[str], Sequence[Sequence[int]]],
+                 lengths: Optional[torch.Tensor] = None) -> List[List[Word]]:
+        single = logits.dim() == 2
+        if single:
+            logits, targets = logits.unsqueeze(0), [targets]
+        ids, al = self.align(logits, targets, lengths)
+        out = self.words(ids, al)
+        return out[0] if single else out
+
+    def hypotheses(self, logits: torch.Tensor, tokens: torch.Tensor, counts: torch.Tensor,
+                   lengths: Optional[torch.Tensor] = None, n_best: int = 1) -> Union[List[List[Word]], List[List[List[Word]]]]:
+        """Words of what a beam search returned: tokens (B,N,T) int64 padded with -1 and counts (B,N), as
+        beam_ctc_decode / BeamCTCDecoder's searches give them.  The best row only by default (a list of Word per
+        utterance); with n_best > 1 a list of up to n_best word lists per utterance.  The scores are acoustic: the mean
+        log-probability of the words' frames, without the language-model or hotword terms of the search."""
+        if tokens.dim() != 3 or counts.dim() != 2 or tokens.shape[:2] != counts.shape:
+            raise ValueError(f"tokens / counts: expected (B,N,T) and (B,N), got {tuple(tokens.shape)}, {tuple(counts.shape)}")
+        tk, ct = tokens.cpu().tolist(), counts.cpu().tolist()
+        rows = min(int(n_best), tokens.shape[1])
+        per_rank = []
+        for r in range(rows):
+            targets = [tk[b][r][:max(ct[b][r], 0)] for b in range(len(tk))]
+            ids, al = self.align(logits, targets, lengths)
+            per_rank.append(self.words(ids, al))
+        if int(n_best) == 1:
+            return per_rank[0]
+        return [[per_rank[r][b] for r in range(rows)] for b in range(len(tk))]

@@ -1,0 +1,421 @@
+// CTC forced alignment (INTEGRATION.md "Forced alignment"): the max-product (Viterbi) recursion over the 2L+1 state
+// lattice the loss walks (ctc.hip), with back-pointers, the back-trace and per-token / per-utterance scores.
+//
+//   chain  : a thread owns P consecutive (blank, label) state pairs in registers, as ctc_chain_kernel does, so a time step
+//            needs ONE cross-lane value (the label state left of the thread's first pair).  One wave per utterance up to
+//            L = 1023 (P = 1..16); beyond that one WORKGROUP per utterance with P = 8: the value crosses a wave boundary
+//            through a double-buffered LDS word, one barrier per frame.  The recursion runs on the RAW logits (the
+//            per-frame normaliser shifts all paths alike), gathered straight from the logits row a block of steps ahead:
+//            no emission matrix is written.  The lattice is re-centred on its own maximum (exact on grid inputs; the
+//            offset is never needed again: scores are recomputed from the path).  Each step stores the moves (0 stay,
+//            1 advance, 2 skip) of the thread's 2P states, 2 bits each: state s at bits 2*(s%4) of byte s/4 of the row.
+//   trace  : one wave per utterance walks the moves backwards in windows of 64 frames: a window can lower the state by at
+//            most 126, so its moves are a 64 x (<= 9 dword) patch, loaded one row per lane into LDS and walked there
+//            (a chain of T dependent global loads otherwise).  Writes frame_tokens / frame_index and their padding.
+//   frames : one wave per frame: float64 log-sum-exp of the row (as beam_prep_kernel) -> log-probability of the emitted symbol.
+//   spans  : one workgroup per utterance: run boundaries of frame_index -> token_start / token_end (each token has one
+//            run, so every element has one writer: no atomics), a wave per token for the mean, a fixed-order float64
+//            reduction for the utterance score.
+// Latency-bound on the T sequential steps, like the loss; nothing synchronises with the host and nothing is allocated.
+#include "cfm_common.h"
+
+namespace {
+
+struct AlignArgs {
+    const float* logits; const int64_t* targets; const int64_t* in_len; const int64_t* tgt_len;
+    unsigned char* moves;            // (B, T, row_bytes)
+    double* frame_lp;                // (B, T) log-probability of the emitted symbol
+    int* end_state;                  // (B) last state of the path, -1: infeasible
+    int64_t* frame_tokens; int64_t* frame_index; int64_t* token_start; int64_t* token_end;
+    float* token_score; double* score; unsigned char* ok;
+    int64_t tgt_numel;
+    int B, T, V, Lmax, blank, P, threads, row_bytes;
+};
+
+constexpr float NEG_INF = -__builtin_inff();
+
+// utterance geometry, clamped so that no index derived from it can leave a buffer (ctc_geometry of ctc.hip, padded targets)
+__device__ __forceinline__ void align_geometry(const AlignArgs& a, int b, int& Tb, int& Lb, int64_t& off) {
+    off = (int64_t)b * a.Lmax;
+    off = off > a.tgt_numel ? a.tgt_numel : off;
+    int64_t L = a.tgt_len ? a.tgt_len[b] : a.Lmax;
+    L = L < 0 ? 0 : L;
+    L = L > a.Lmax ? a.Lmax : L;
+    L = L > a.tgt_numel - off ? a.tgt_numel - off : L;
+    Lb = (int)L;
+    const int64_t t = a.in_len ? a.in_len[b] : a.T;
+    Tb = (int)(t < 0 ? 0 : (t > a.T ? a.T : t));
+}
+__device__ __forceinline__ int align_label(const AlignArgs& a, int64_t off, int i) {
+    const int64_t v = a.targets[off + i];
+    return (int)(v < 0 ? 0 : (v >= a.V ? a.V - 1 : v));
+}
+
+template <int P> struct MoveStore;       // the 4P move bits of a thread -> its P/2 bytes of the row
+template <> struct MoveStore<1> {
+    static __device__ __forceinline__ void put(unsigned char* row, int tid, unsigned long long bits) {
+        const unsigned other = __shfl_down((unsigned)bits, 1, 64);       // two lanes share a byte
+        if ((tid & 1) == 0) row[tid >> 1] = (unsigned char)((unsigned)bits | (other << 4));
+    }
+};
+template <> struct MoveStore<2> {
+    static __device__ __forceinline__ void put(unsigned char* row, int tid, unsigned long long bits) { row[tid] = (unsigned char)bits; }
+};
+template <> struct MoveStore<4> {
+    static __device__ __forceinline__ void put(unsigned char* row, int tid, unsigned long long bits) {
+        reinterpret_cast<unsigned short*>(row)[tid] = (unsigned short)bits;
+    }
+};
+template <> struct MoveStore<8> {
+    static __device__ __forceinline__ void put(unsigned char* row, int tid, unsigned long long bits) {
+        reinterpret_cast<unsigned*>(row)[tid] = (unsigned)bits;
+    }
+};
+template <> struct MoveStore<16> {
+    static __device__ __forceinline__ void put(unsigned char* row, int tid, unsigned long long bits) {
+        reinterpret_cast<uint2*>(row)[tid] = make_uint2((unsigned)bits, (unsigned)(bits >> 32));
+    }
+};
+
+constexpr int ALIGN_MAX_WAVES = 10;      // workgroup form: 8 * 64 * 10 pairs >= CFM_CTC_ALIGN_MAX_TARGET + 1
+constexpr int RECENTRE_EVERY = 64;       // workgroup form: steps between two re-centrings (two barriers each)
+
+// Thread tid owns the pairs i = tid*P .. tid*P+P-1: blank state 2i (exists for i <= L) and label state 2i+1 (i < L).
+// WG: several waves per utterance (blockDim.x = a.threads), else one.
+template <int P, bool WG>
+__global__ __launch_bounds__(WG ? 64 * ALIGN_MAX_WAVES : 64) void align_chain_kernel(const AlignArgs a) {
+    constexpr int U = 32 / P > 16 ? 16 : 32 / P;                          // time steps per prefetch block
+    __shared__ float edge[2][ALIGN_MAX_WAVES];                            // last label state of each wave, double-buffered
+    __shared__ float red[ALIGN_MAX_WAVES];
+    __shared__ int red_i[ALIGN_MAX_WAVES];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int nwaves = WG ? (int)(blockDim.x >> 6) : 1;
+    int Tb, Lb; int64_t off;
+    align_geometry(a, b, Tb, Lb, off);
+
+    int lab[P];
+    bool hop[P];                  // state 2i+1 may be entered from 2i-1
+#pragma unroll
+    for (int p = 0; p < P; ++p) {
+        const int i = tid * P + p;
+        lab[p] = i < Lb ? align_label(a, off, i) : -1 - i;               // distinct negatives: never equal to a neighbour
+    }
+    int prev_lab = __shfl_up(lab[P - 1], 1, 64);
+    if (WG) {
+        if (lane == 63) red_i[wave] = lab[P - 1];
+        __syncthreads();
+        if (lane == 0 && wave > 0) prev_lab = red_i[wave - 1];
+        __syncthreads();
+    }
+    int repeats = 0;
+#pragma unroll
+    for (int p = 0; p < P; ++p) {
+        const int i = tid * P + p;
+        const int prv = p == 0 ? prev_lab : lab[p - 1];
+        hop[p] = (i >= 1) && (i < Lb) && lab[p] != prv;
+        repeats += (i >= 1 && i < Lb && lab[p] == prv) ? 1 : 0;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) repeats += __shfl_xor(repeats, o, 64);
+    if (WG) {
+        if (lane == 0) red_i[wave] = repeats;
+        __syncthreads();
+        repeats = 0;
+        for (int w = 0; w < nwaves; ++w) repeats += red_i[w];
+    }
+    if (Tb == 0 || Tb < Lb + repeats) {                                   // infeasible (uniform over the workgroup)
+        if (tid == 0) a.end_state[b] = -1;
+        return;
+    }
+    int col[P];                   // column of the label's logit, in range for threads past the target too
+#pragma unroll
+    for (int p = 0; p < P; ++p) col[p] = lab[p] >= 0 ? lab[p] : a.blank;
+
+    const float* x = a.logits + (int64_t)b * a.T * a.V;
+    unsigned char* moves = a.moves + (int64_t)b * a.T * a.row_bytes;
+    float sb[P], sl[P];           // current value of the thread's blank / label states
+    float cb[U], cl[U][P], nb[U], nl[U][P];
+    auto load_block = [&](int t_first, float (&vb)[U], float (&vl)[U][P]) {      // clamped: always in range
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const float* row = x + (int64_t)min(t_first + u, Tb - 1) * a.V;
+            vb[u] = row[a.blank];
+#pragma unroll
+            for (int p = 0; p < P; ++p) vl[u][p] = row[col[p]];
+        }
+    };
+    load_block(0, cb, cl);
+    int par = 0;
+    for (int t0 = 0; t0 < Tb; t0 += U) {
+        load_block(t0 + U, nb, nl);
+        __builtin_amdgcn_sched_barrier(0);
+        if (t0 > 0 && (!WG || t0 % RECENTRE_EVERY == 0)) {                       // re-centre the lattice on its maximum
+            float m = NEG_INF;
+#pragma unroll
+            for (int p = 0; p < P; ++p) m = fmaxf(m, fmaxf(sb[p], sl[p]));
+            m = wave_max(m);
+            if (WG) {
+                if (lane == 0) red[wave] = m;
+                __syncthreads();
+                for (int w = 0; w < nwaves; ++w) m = fmaxf(m, red[w]);
+            }
+            if (m > NEG_INF && m < -NEG_INF) {
+#pragma unroll
+                for (int p = 0; p < P; ++p) { sb[p] -= m; sl[p] -= m; }
+            }
+            if (WG) {                                                            // the published edge values move with it
+                if (lane == 63) edge[par][wave] = sl[P - 1];
+                __syncthreads();
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            if (t0 + u >= Tb) break;                                             // uniform
+            const int t = t0 + u;
+            unsigned long long bits = 0;
+            if (t == 0) {
+#pragma unroll
+                for (int p = 0; p < P; ++p) {
+                    const int i = tid * P + p;
+                    sb[p] = i == 0 ? cb[u] : NEG_INF;                            // state 0
+                    sl[p] = (i == 0 && Lb > 0) ? cl[u][p] : NEG_INF;             // state 1
+                }
+            } else {
+                float left = __shfl_up(sl[P - 1], 1, 64);
+                if (lane == 0) left = (WG && wave > 0) ? edge[par][wave - 1] : NEG_INF;
+#pragma unroll
+                for (int p = 0; p < P; ++p) {
+                    const int i = tid * P + p;
+                    const float ob = sb[p], ol = sl[p];
+                    // ties take the smaller move: a larger move wins only when strictly greater
+                    const unsigned mb = left > ob ? 1u : 0u;
+                    const float vb = (mb ? left : ob) + cb[u];
+                    unsigned ml = ob > ol ? 1u : 0u;
+                    float best = ml ? ob : ol;
+                    if (hop[p] && left > best) { ml = 2u; best = left; }
+                    const float vl = best + cl[u][p];
+                    sb[p] = i <= Lb ? vb : NEG_INF;
+                    sl[p] = i < Lb ? vl : NEG_INF;
+                    bits |= (unsigned long long)(mb | (ml << 2)) << (4 * p);
+                    left = ol;
+                }
+            }
+            if (WG) {
+                par ^= 1;
+                if (lane == 63) edge[par][wave] = sl[P - 1];
+                __syncthreads();
+            }
+            MoveStore<P>::put(moves + (int64_t)t * a.row_bytes, tid, bits);
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            cb[u] = nb[u];
+#pragma unroll
+            for (int p = 0; p < P; ++p) cl[u][p] = nl[u][p];
+        }
+    }
+    // the path ends in state 2L or 2L-1, a tie in 2L
+    float fb = NEG_INF, fl = NEG_INF;
+#pragma unroll
+    for (int p = 0; p < P; ++p) {
+        const int i = tid * P + p;
+        if (i == Lb) fb = sb[p];
+        if (i == Lb - 1) fl = sl[p];
+    }
+    fb = wave_max(fb); fl = wave_max(fl);
+    if (WG) {
+        __syncthreads();
+        if (lane == 0) { red[wave] = fb; edge[0][wave] = fl; }
+        __syncthreads();
+        for (int w = 0; w < nwaves; ++w) { fb = fmaxf(fb, red[w]); fl = fmaxf(fl, edge[0][w]); }
+    }
+    if (tid == 0) a.end_state[b] = (Lb > 0 && fl > fb) ? 2 * Lb - 1 : 2 * Lb;
+}
+
+constexpr int TRACE_WIN = 64;            // frames per window = lanes
+constexpr int TRACE_DW = 10;             // dwords of a row a window can touch: 127 states at any alignment span <= 9
+
+__global__ __launch_bounds__(64) void align_trace_kernel(const AlignArgs a) {
+    __shared__ unsigned patch[TRACE_WIN][TRACE_DW + 1];
+    const int b = blockIdx.x, lane = threadIdx.x;
+    int Tb, Lb; int64_t off;
+    align_geometry(a, b, Tb, Lb, off);
+    int s = a.end_state[b];
+    const bool ok = s >= 0 && s <= 2 * Lb && Tb > 0;
+    int64_t* ftok = a.frame_tokens + (int64_t)b * a.T;
+    int64_t* fidx = a.frame_index + (int64_t)b * a.T;
+    for (int t = (ok ? Tb : 0) + lane; t < a.T; t += 64) { ftok[t] = -1; fidx[t] = -1; }
+    if (!ok) return;
+    const unsigned* moves = reinterpret_cast<const unsigned*>(a.moves + (int64_t)b * a.T * a.row_bytes);
+    const int row_dw = a.row_bytes >> 2;
+    for (int t_hi = Tb - 1; t_hi >= 0; t_hi -= TRACE_WIN) {
+        const int d_lo = max(s - 2 * (TRACE_WIN - 1), 0) >> 4;
+        const int t_mine = max(t_hi - lane, 0);
+#pragma unroll
+        for (int k = 0; k < TRACE_DW; ++k)
+            patch[lane][k] = moves[(int64_t)t_mine * row_dw + min(d_lo + k, row_dw - 1)];
+        __syncthreads();
+        int mine = 0;
+        const int n = min(TRACE_WIN, t_hi + 1);
+        for (int c = 0; c < n; ++c) {                                    // every lane walks the same states
+            if (c == lane) mine = s;
+            const int d = min(max((s >> 4) - d_lo, 0), TRACE_DW - 1);
+            const unsigned mv = (patch[c][d] >> (2 * (s & 15))) & 3u;
+            if (t_hi - c > 0) s = max(s - (int)min(mv, 2u), 0);
+        }
+        __syncthreads();
+        if (lane < n) {
+            const int t = t_hi - lane;
+            const bool is_label = (mine & 1) != 0;
+            const int i = min(mine >> 1, max(Lb - 1, 0));
+            ftok[t] = is_label ? align_label(a, off, i) : a.blank;
+            fidx[t] = is_label ? i : -1;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void align_frame_kernel(const AlignArgs a) {
+    const int lane = threadIdx.x & 63;
+    const int64_t frame = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (frame >= (int64_t)a.B * a.T) return;
+    const int b = (int)(frame / a.T), t = (int)(frame - (int64_t)b * a.T);
+    int Tb, Lb; int64_t off;
+    align_geometry(a, b, Tb, Lb, off);
+    if (t >= Tb || a.end_state[b] < 0) return;
+    const float* r = a.logits + frame * a.V;
+    float m = NEG_INF;
+    for (int c = lane; c < a.V; c += 64) m = fmaxf(m, r[c]);
+    m = wave_max(m);
+    double sum = 0.0;
+    for (int c = lane; c < a.V; c += 64) sum += exp((double)r[c] - (double)m);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+    const double lse = (double)m + log(sum);
+    if (lane == 0) {
+        const int64_t tok = a.frame_tokens[frame];
+        const int c = (int)(tok < 0 ? 0 : (tok >= a.V ? a.V - 1 : tok));
+        a.frame_lp[frame] = (double)r[c] - lse;
+    }
+}
+
+__global__ __launch_bounds__(256) void align_span_kernel(const AlignArgs a) {
+    __shared__ double part[256];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int Tb, Lb; int64_t off;
+    align_geometry(a, b, Tb, Lb, off);
+    const bool ok = a.end_state[b] >= 0;
+    int64_t* ts = a.token_start + (int64_t)b * a.Lmax;
+    int64_t* te = a.token_end + (int64_t)b * a.Lmax;
+    float* tsc = a.token_score + (int64_t)b * a.Lmax;
+    for (int i = (ok ? Lb : 0) + tid; i < a.Lmax; i += 256) { ts[i] = -1; te[i] = -1; tsc[i] = NEG_INF; }
+    if (!ok) {
+        if (tid == 0) { a.score[b] = (double)NEG_INF; a.ok[b] = 0; }
+        return;
+    }
+    const int64_t* fidx = a.frame_index + (int64_t)b * a.T;
+    const double* flp = a.frame_lp + (int64_t)b * a.T;
+    // each thread sums a contiguous slice of the frames, the slices are then added in order: one fixed summation order
+    const int per = (Tb + 255) / 256;
+    double acc = 0.0;
+    for (int t = tid * per; t < min(tid * per + per, Tb); ++t) {
+        acc += flp[t];
+        const int64_t i = fidx[t];
+        if (i < 0 || i >= Lb) continue;
+        if (t == 0 || fidx[t - 1] != i) ts[i] = t;
+        if (t == Tb - 1 || fidx[t + 1] != i) te[i] = t + 1;
+    }
+    part[tid] = acc;
+    __threadfence();
+    __syncthreads();
+    if (tid == 0) {
+        double s = 0.0;
+        for (int k = 0; k < 256; ++k) s += part[k];
+        a.score[b] = s;
+        a.ok[b] = 1;
+    }
+    for (int i = wave; i < Lb; i += 4) {                                 // a wave per token
+        const int64_t t0 = ts[i], t1 = te[i];
+        const bool run = t0 >= 0 && t1 > t0 && t1 <= Tb;
+        double sum = 0.0;
+        if (run)
+            for (int t = (int)t0 + lane; t < (int)t1; t += 64) sum += flp[t];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+        if (lane == 0) tsc[i] = run ? (float)(sum / (double)(t1 - t0)) : NEG_INF;
+    }
+}
+
+// wave form: 64*P >= Lmax + 1, P a power of two <= 16; workgroup form: P = 8, threads a multiple of 64
+void align_shape(int Lmax, int& P, int& threads) {
+    if (Lmax <= CFM_CTC_ALIGN_WAVE_MAX_TARGET) {
+        P = 1;
+        while (64 * P < Lmax + 1) P *= 2;
+        threads = 64;
+    } else {
+        P = 8;
+        threads = ((Lmax + 1 + 7) / 8 + 63) / 64 * 64;
+    }
+}
+
+bool align_in_range(int B, int T, int Lmax) {
+    return B > 0 && T > 0 && T <= CFM_CTC_ALIGN_MAX_FRAMES && Lmax >= 1 && Lmax <= CFM_CTC_ALIGN_MAX_TARGET;
+}
+
+// workspace: frame_lp (B*T doubles) | end_state (B ints, padded to 16 bytes) | moves (B*T rows)
+size_t align_layout(int B, int T, int Lmax, AlignArgs* a) {
+    int P, threads;
+    align_shape(Lmax, P, threads);
+    const size_t frames = (size_t)B * T, row_bytes = (size_t)threads * P / 2;
+    const size_t lp_bytes = frames * sizeof(double), end_bytes = ((size_t)B * sizeof(int) + 15) / 16 * 16;
+    if (a) {
+        a->P = P; a->threads = threads; a->row_bytes = (int)row_bytes;
+        char* base = reinterpret_cast<char*>(a->frame_lp);
+        a->end_state = reinterpret_cast<int*>(base + lp_bytes);
+        a->moves = reinterpret_cast<unsigned char*>(base + lp_bytes + end_bytes);
+    }
+    return lp_bytes + end_bytes + frames * row_bytes;
+}
+
+}  // namespace
+
+extern "C" size_t cfm_ctc_align_workspace_bytes(int B, int T, int Lmax) {
+    return align_in_range(B, T, Lmax) ? align_layout(B, T, Lmax, nullptr) : 0;
+}
+
+extern "C" int cfm_ctc_align_f32(const float* logits, const int64_t* targets, const int64_t* lengths_or_null,
+                                 const int64_t* target_lengths_or_null, int B, int T, int V, int Lmax, int blank_id,
+                                 void* workspace, size_t workspace_bytes, int64_t* frame_tokens, int64_t* frame_index,
+                                 int64_t* token_start, int64_t* token_end, float* token_score, double* score,
+                                 unsigned char* ok, cfm_stream_t stream) {
+    CFM_REQUIRE(logits && targets && workspace && frame_tokens && frame_index && token_start && token_end && token_score &&
+                score && ok, CFM_ERR_NULL);
+    CFM_REQUIRE(B > 0 && T > 0 && V >= 2 && Lmax >= 1 && blank_id >= 0 && blank_id < V, CFM_ERR_BAD_SHAPE);
+    CFM_REQUIRE(align_in_range(B, T, Lmax), CFM_ERR_UNSUPPORTED);
+    CFM_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, CFM_ERR_ALIGN);
+    AlignArgs a{};
+    a.logits = logits; a.targets = targets; a.in_len = lengths_or_null; a.tgt_len = target_lengths_or_null;
+    a.frame_lp = reinterpret_cast<double*>(workspace);
+    CFM_REQUIRE(workspace_bytes >= align_layout(B, T, Lmax, &a), CFM_ERR_BAD_SHAPE);
+    a.frame_tokens = frame_tokens; a.frame_index = frame_index; a.token_start = token_start; a.token_end = token_end;
+    a.token_score = token_score; a.score = score; a.ok = ok;
+    a.tgt_numel = (int64_t)B * Lmax;
+    a.B = B; a.T = T; a.V = V; a.Lmax = Lmax; a.blank = blank_id;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const dim3 grid((unsigned)B);
+    if (a.threads > 64) {
+        hipLaunchKernelGGL((align_chain_kernel<8, true>), grid, dim3((unsigned)a.threads), 0, s, a);
+    } else {
+        switch (a.P) {
+            case 1: hipLaunchKernelGGL((align_chain_kernel<1, false>), grid, dim3(64), 0, s, a); break;
+            case 2: hipLaunchKernelGGL((align_chain_kernel<2, false>), grid, dim3(64), 0, s, a); break;
+            case 4: hipLaunchKernelGGL((align_chain_kernel<4, false>), grid, dim3(64), 0, s, a); break;
+            case 8: hipLaunchKernelGGL((align_chain_kernel<8, false>), grid, dim3(64), 0, s, a); break;
+            default: hipLaunchKernelGGL((align_chain_kernel<16, false>), grid, dim3(64), 0, s, a); break;
+        }
+    }
+    hipLaunchKernelGGL(align_trace_kernel, grid, dim3(64), 0, s, a);
+    const int64_t frames = (int64_t)B * T;
+    hipLaunchKernelGGL(align_frame_kernel, dim3((unsigned)((frames + 3) / 4)), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(align_span_kernel, grid, dim3(256), 0, s, a);
+    return cfm_launch_status();
+}

@@ -689,6 +689,25 @@ int cfm_ctc_loss_bwd_f32(const float* logits, const int64_t* targets, const int6
                          int B, int T, int V, int Lmax, int blank, float* workspace, const float* grad_out,
                          float* dlogits, cfm_stream_t stream);
 
+/*      CTC forced alignment (INTEGRATION.md "Forced alignment"): the best path of the loss's lattice (max-product recursion
+ *      on the raw logits, ties to the smaller move, a tie at the end to the last blank) for targets (B,Lmax) int64 padded,
+ *      ids clamped to [0,V) on the device.  lengths_or_null / target_lengths_or_null: int64 (B) on the device, clamped to
+ *      [0,T] / [0,Lmax] (NULL: T / Lmax).  T <= CFM_CTC_ALIGN_MAX_FRAMES, 1 <= Lmax <= CFM_CTC_ALIGN_MAX_TARGET (one wave
+ *      per utterance up to CFM_CTC_ALIGN_WAVE_MAX_TARGET, one workgroup beyond), blank_id in [0,V), V >= 2.
+ *      workspace: cfm_ctc_align_workspace_bytes(B,T,Lmax) bytes (0 for arguments out of range), 16-byte aligned, no
+ *      initialisation needed.  Outputs: frame_tokens, frame_index (B,T) int64; token_start, token_end (B,Lmax) int64;
+ *      token_score (B,Lmax) fp32; score (B) float64; ok (B) bytes 0 / 1.  An utterance with T_b = 0 or T_b < L_b + adjacent
+ *      repeats is infeasible: ok 0, score -inf, padding elsewhere (-1, -inf).  Enqueues only: no host synchronisation, no
+ *      allocation.  Argument errors return before any HIP call. */
+#define CFM_CTC_ALIGN_MAX_FRAMES 16384
+#define CFM_CTC_ALIGN_MAX_TARGET 4096
+#define CFM_CTC_ALIGN_WAVE_MAX_TARGET 1023
+size_t cfm_ctc_align_workspace_bytes(int B, int T, int Lmax);
+int cfm_ctc_align_f32(const float* logits, const int64_t* targets, const int64_t* lengths_or_null,
+                      const int64_t* target_lengths_or_null, int B, int T, int V, int Lmax, int blank_id, void* workspace,
+                      size_t workspace_bytes, int64_t* frame_tokens, int64_t* frame_index, int64_t* token_start,
+                      int64_t* token_end, float* token_score, double* score, unsigned char* ok, cfm_stream_t stream);
+
 /* incremental / streaming attention (no reference counterpart: the reference has no streaming code; BASELINE cfg-5): as
  *      cfm_relpos_attention_fwd_f32 but only the query rows [q_begin, q_begin+q_count) are computed; q/k/v/ctx are the
  *      whole (B,T,.) buffers (a K/V cache that grows in place), lengths = keys visible so far.  nsplit in [1,16]: > 1

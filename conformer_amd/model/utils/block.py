@@ -41,28 +41,44 @@ class ConformerBlock(nn.Module):
 
     def fused_chain(self, x: torch.Tensor, pos_table: torch.Tensor, lengths: Optional[torch.Tensor],
                     pos_projected: Optional[torch.Tensor] = None, x_stats: Optional[torch.Tensor] = None,
-                    want_stats: bool = False):
+                    want_stats: bool = False, stream=None):
         """Returns (block output, LayerNorm statistics partials of its rows or None).  On the folded path (fp32 inference) every
         residual GEMM's epilogue emits the statistics of the rows it stores and the next sub-layer's first GEMM applies the
         LayerNorm from them (ops.linear_lnfold): the LayerNorms of ffn.py:16, attention.py:15 and convolution.py:22 are not
         launched; the closing LayerNorm (block.py:27) runs and hands the statistics of ITS output to the next block
-        (x_stats / want_stats).  12 launches per block instead of 16."""
+        (x_stats / want_stats).  12 launches per block instead of 16.
+
+        stream (inference only; conformer_amd/streaming.py, slots.py): x holds only the NEW rows of a chunked evaluation and two
+        steps are the stream's: stream.attend(attention, qkv) appends the projected rows to its K/V cache and returns their
+        context (instead of pos_proj + ops.relpos_attention: pos_table, lengths and pos_projected are unused), and
+        stream.depthwise(conv, g) runs the depthwise kernel over a window that reaches back into its carried GLU rows.
+        Deliberately, a stream launches what streaming launched when it had a chain of its own: (1) the LayerNorms in front of
+        the q|k|v projection and of pointwise_conv_1, and that projection, are not `for_gemm` (the K/V caches are fp32); (2) the
+        depthwise kernel is not `for_gemm`; (3) FFN2 does not absorb the closing LayerNorm, and the row chains, which have no
+        seam, are not taken.  Whether a stream should adopt the one-kernel FFN2 + closing LayerNorm at large row counts is an
+        open question that needs a measurement."""
+        if stream is not None:
+            bn = self.conv.batch_norm
+            if bn.training or bn.running_mean is None or ag.needs_grad(self, x):
+                raise RuntimeError("ConformerBlock.fused_chain: a stream context is for inference only (eval-mode BatchNorm "
+                                   "under torch.no_grad())")
         if not self._ln_fold(x):
             y = self.ffn_1.fused(x, residual=x, alpha=0.5)
-            y = self.attention.fused(y, pos_table, lengths, residual=y, pos_projected=pos_projected)
-            y = self.conv.fused(y, residual=y)
+            y = self.attention.fused(y, pos_table, lengths, residual=y, pos_projected=pos_projected, stream=stream)
+            y = self.conv.fused(y, residual=y, stream=stream)
             y = self.ffn_2.fused(y, residual=y, alpha=0.5)
             if ag.needs_grad(self.layer_norm, y):
                 return ag.LayerNormFn.apply(y, self.layer_norm.weight, self.layer_norm.bias, self.layer_norm.eps), None
             return ops.layernorm(y, self.layer_norm.weight, self.layer_norm.bias, self.layer_norm.eps), None
-        if x_stats is not None and x.is_contiguous() and ops.rowchain_ok(x.shape[-1], self.ffn_1.hidden_linear.out_features,
-                                                                          x.numel() // x.shape[-1]):
+        if stream is None and x_stats is not None and x.is_contiguous() and ops.rowchain_ok(
+                x.shape[-1], self.ffn_1.hidden_linear.out_features, x.numel() // x.shape[-1]):
             return self._row_chains(x, pos_table, lengths, pos_projected, x_stats, want_stats)
         y, st = self.ffn_1.fused(x, residual=x, alpha=0.5, stats=x_stats, emit_stats=True)
-        y, st = self.attention.fused(y, pos_table, lengths, residual=y, pos_projected=pos_projected, stats=st, emit_stats=True)
-        y, st = self.conv.fused(y, residual=y, stats=st, emit_stats=True)
+        y, st = self.attention.fused(y, pos_table, lengths, residual=y, pos_projected=pos_projected, stats=st, emit_stats=True,
+                                      stream=stream)
+        y, st = self.conv.fused(y, residual=y, stats=st, emit_stats=True, stream=stream)
         ln = self.layer_norm
-        if self.ffn_2.fuses(y, y, st):                  # FFN2 + the closing LayerNorm in the one-kernel feed-forward
+        if stream is None and self.ffn_2.fuses(y, y, st):   # FFN2 + the closing LayerNorm in one kernel; never for a stream: (3)
             if want_stats:
                 return self.ffn_2.fused(y, residual=y, alpha=0.5, stats=st, emit_stats=True, closing_ln=ln)
             return self.ffn_2.fused(y, residual=y, alpha=0.5, stats=st, closing_ln=ln), None
@@ -76,7 +92,7 @@ class ConformerBlock(nn.Module):
         depthwise conv + BatchNorm + Swish, K3 = pointwise_conv_2 + FFN2 + closing LayerNorm -- every row-local stretch of
         block.py:17-29 in one kernel per 32 rows (csrc/rowchain_f32.hip)."""
         f1, f2, att, cv = self.ffn_1, self.ffn_2, self.attention, self.conv
-        a, ln_a, ln_c, bn = att.attention, att.layer_norm, cv.layer_norm, cv.batch_norm
+        a, ln_a, ln_c = att.attention, att.layer_norm, cv.layer_norm
         for m, name in ((f1, "FeedForwardModule"), (att, "MultiHeadSelfAttentionModule"), (a, "RelativeMultiHeadAttention"),
                         (cv, "ConvolutionModule"), (f2, "FeedForwardModule")):
             refuse_dropout(m, name)
@@ -100,8 +116,7 @@ class ConformerBlock(nn.Module):
         pos = pos_projected if pos_projected is not None else ops.linear(pos_table, a.pos_proj.weight, a.pos_proj.bias)
         ctx = ops.relpos_attention(qkv, pos, a.content_bias, a.position_bias, lengths, a.n_heads)
         y2, g = ops.rowchain_out_glu(ctx, wo_p, a.out_proj.bias, y, wg_p, bg_f, csg, ln_c.eps)
-        c = ops.dwconv_bn_swish(g, cv.deepwise_conv.weight, cv.deepwise_conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var,
-                                bn.eps)
+        c = cv.depthwise_eval(g)
         ln = self.layer_norm
         return ops.rowchain_pw2_ffn_ln(c, w2_p, pw2.bias, y2, ffn2, f2.out_linear.bias, 0.5, f2.layer_norm.eps,
                                        (ln.weight, ln.bias, ln.eps), want_stats)

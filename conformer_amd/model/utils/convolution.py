@@ -36,10 +36,17 @@ class ConvolutionModule(nn.Module):
         self.dropout = nn.Dropout(p=dropout_rate)
         self._packs = PackCache()
 
+    def depthwise_eval(self, g: torch.Tensor, for_gemm: bool = False) -> torch.Tensor:
+        """Depthwise Conv1d + BatchNorm1d (running statistics) + Swish of the GLU rows g (B,T,C), zero padding either side."""
+        bn = self.batch_norm
+        return ops.dwconv_bn_swish(g, self.deepwise_conv.weight, self.deepwise_conv.bias, bn.weight, bn.bias,
+                                   bn.running_mean, bn.running_var, bn.eps, for_gemm=for_gemm)
+
     def fused(self, x: torch.Tensor, residual: Optional[torch.Tensor] = None, stats: Optional[torch.Tensor] = None,
-              emit_stats: bool = False):
+              emit_stats: bool = False, stream=None):
         """stats / emit_stats: see FeedForwardModule.fused (the LayerNorm of convolution.py:22 folds into the pointwise_conv_1 +
-        GLU GEMM; eval-mode BatchNorm only)."""
+        GLU GEMM; eval-mode BatchNorm only).  stream: from ConformerBlock.fused_chain, which has refused gradients and
+        training-mode BatchNorm: stream.depthwise(self, g) stands in for depthwise_eval(g)."""
         refuse_dropout(self, "ConvolutionModule")
         bn = self.batch_norm
         train_bn = bn.training or bn.running_mean is None      # nn.BatchNorm1d semantics: the BN sub-module's own flag
@@ -76,10 +83,10 @@ class ConvolutionModule(nn.Module):
                                          lambda: ops.fold_layernorm(pw1.weight, pw1.bias, ln.weight, ln.bias))
             g = ops.linear_lnfold(x, stats, wf, bf, cs, ln.eps, glu=True)
         else:
-            h = ops.layernorm(x, self.layer_norm.weight, self.layer_norm.bias, self.layer_norm.eps, for_gemm=True)
+            h = ops.layernorm(x, self.layer_norm.weight, self.layer_norm.bias, self.layer_norm.eps, for_gemm=stream is None)
             g = ops.linear_glu(h, self.pointwise_conv_1.weight, self.pointwise_conv_1.bias)
-        s = ops.dwconv_bn_swish(g, self.deepwise_conv.weight, self.deepwise_conv.bias, bn.weight, bn.bias,
-                                bn.running_mean, bn.running_var, bn.eps, for_gemm=True)
+        # a stream's window reaches back into its carried rows; neither its LayerNorm nor its depthwise kernel is for_gemm
+        s = self.depthwise_eval(g, for_gemm=True) if stream is None else stream.depthwise(self, g)
         if residual is None:
             if emit_stats:
                 return ops.linear(s, self.pointwise_conv_2.weight, self.pointwise_conv_2.bias, emit_stats=True)

@@ -593,6 +593,19 @@ def relpos_table(div_term: torch.Tensor, t: int) -> torch.Tensor:
     return pe
 
 
+def _req_pos(pos: torch.Tensor, T: int, d: int) -> None:
+    if not (isinstance(pos, torch.Tensor) and pos.is_cuda and pos.dtype == torch.float32 and pos.dim() == 2
+            and pos.stride(1) == 1 and pos.shape == (2 * T - 1, d)):
+        raise _lib.ConformerHipError(f"pos: expected a ({2 * T - 1},{d}) fp32 HIP tensor with unit column stride")
+
+
+def _key_split(B: int, n_heads: int, q_rows: int, T: int, keys_hint: Optional[int]) -> int:
+    """Key slices of the incremental attention kernels: >= 8 key tiles of 32 per slice, aiming at ~1024 workgroups."""
+    tiles = ((T if keys_hint is None else min(int(keys_hint), T)) + 31) // 32
+    blocks = B * n_heads * ((q_rows + 127) // 128)
+    return max(1, min(16, tiles // 8, -(-1024 // blocks)))
+
+
 def relpos_attention(qkv: torch.Tensor, pos: torch.Tensor, u: torch.Tensor, v: torch.Tensor,
                      lengths: Optional[torch.Tensor], n_heads: int, for_gemm: bool = False) -> torch.Tensor:
     """qkv: (B,T,3d) fused projections [q|k|v]; pos: (2T-1,d) projected table; returns ctx (B,T,d).
@@ -609,9 +622,7 @@ def relpos_attention(qkv: torch.Tensor, pos: torch.Tensor, u: torch.Tensor, v: t
     B, T, d3 = qkv.shape
     d = d3 // 3
     dh = d // n_heads
-    if not (isinstance(pos, torch.Tensor) and pos.is_cuda and pos.dtype == torch.float32 and pos.dim() == 2
-            and pos.stride(1) == 1 and pos.shape == (2 * T - 1, d)):
-        raise _lib.ConformerHipError(f"pos: expected a ({2 * T - 1},{d}) fp32 HIP tensor with unit column stride")
+    _req_pos(pos, T, d)
     ldp = pos.stride(0)
     if lengths is not None:
         lengths = _req(lengths, "lengths", torch.int64)
@@ -650,8 +661,7 @@ def relpos_attention_rows(qkv: torch.Tensor, pos: torch.Tensor, u: torch.Tensor,
     qkv = _req(qkv, "qkv"); u = _req(u, "content_bias"); v = _req(v, "position_bias"); ctx = _req(ctx, "ctx")
     B, T, d3 = qkv.shape
     d = d3 // 3
-    if not (pos.is_cuda and pos.dtype == torch.float32 and pos.dim() == 2 and pos.stride(1) == 1 and pos.shape == (2 * T - 1, d)):
-        raise _lib.ConformerHipError(f"pos: expected a ({2 * T - 1},{d}) fp32 HIP tensor with unit column stride")
+    _req_pos(pos, T, d)
     if ctx.shape != (B, T, d) or not qkv.is_contiguous() or not ctx.is_contiguous():
         raise _lib.ConformerHipError("relpos_attention_rows: qkv (B,T,3d) and ctx (B,T,d) must be contiguous cache buffers")
     lengths = _req(lengths, "lengths", torch.int64)
@@ -664,9 +674,7 @@ def relpos_attention_rows(qkv: torch.Tensor, pos: torch.Tensor, u: torch.Tensor,
                                                               n_heads, d // n_heads, int(q_begin), int(q_count), _stream())
         _lib.check(st, "cfm_relpos_attention_rows_mfma16_f32")
         return ctx
-    tiles = ((T if keys_hint is None else min(int(keys_hint), T)) + 31) // 32
-    blocks = B * n_heads * ((q_count + 127) // 128)
-    nsplit = max(1, min(16, tiles // 8, -(-1024 // blocks)))          # >= 8 key tiles per split, aim at ~1024 workgroups
+    nsplit = _key_split(B, n_heads, q_count, T, keys_hint)
     ws = torch.empty(nsplit * B * q_count * (d + n_heads), device=qkv.device, dtype=torch.float32) if nsplit > 1 else None
     base = qkv.data_ptr()
     st = _lib.load().cfm_relpos_attention_rows_f32(base, base + 4 * d, base + 8 * d, d3, pos.data_ptr(), pos.stride(0),
@@ -689,8 +697,7 @@ def relpos_attention_slots(qkv: torch.Tensor, pos: torch.Tensor, u: torch.Tensor
     B, T, d3 = qkv.shape
     d = d3 // 3
     q_max = int(q_max)
-    if not (pos.is_cuda and pos.dtype == torch.float32 and pos.dim() == 2 and pos.stride(1) == 1 and pos.shape == (2 * T - 1, d)):
-        raise _lib.ConformerHipError(f"pos: expected a ({2 * T - 1},{d}) fp32 HIP tensor with unit column stride")
+    _req_pos(pos, T, d)
     if not qkv.is_contiguous():
         raise _lib.ConformerHipError("relpos_attention_slots: qkv (S,T,3d) must be a contiguous cache buffer")
     if mfma16_prec() != PREC_F32:
@@ -706,9 +713,7 @@ def relpos_attention_slots(qkv: torch.Tensor, pos: torch.Tensor, u: torch.Tensor
     for name, t in (("lengths", lengths), ("q_begin", q_begin), ("q_count", q_count)):
         if t.shape != (B,) or not t.is_contiguous():
             raise _lib.ConformerHipError(f"relpos_attention_slots: {name} must be a contiguous ({B},) int64 tensor")
-    tiles = ((T if keys_hint is None else min(int(keys_hint), T)) + 31) // 32
-    blocks = B * n_heads * ((q_max + 127) // 128)
-    nsplit = max(1, min(16, tiles // 8, -(-1024 // blocks)))          # the heuristic of relpos_attention_rows
+    nsplit = _key_split(B, n_heads, q_max, T, keys_hint)
     ws = torch.empty(nsplit * B * q_max * (d + n_heads), device=qkv.device, dtype=torch.float32) if nsplit > 1 else None
     base = qkv.data_ptr()
     st = _lib.load().cfm_relpos_attention_slots_f32(base, base + 4 * d, base + 8 * d, d3, pos.data_ptr(), pos.stride(0),

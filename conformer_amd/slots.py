@@ -27,8 +27,8 @@ from . import ops
 from .decode import BeamCTCDecoder, beam_ctc_stream_finish, beam_ctc_stream_init, beam_ctc_stream_reset_slots, \
     beam_ctc_stream_step
 from .model.modules.encoder import Encoder
-from .streaming import StreamingEncoder
-from .transcribe import decode_frames
+from .streaming import StreamingEncoder, encoder_frames
+from .transcribe import decode_frames, lstm_state
 
 _TAIL = 8                  # mel-tail buffer width: a slot carries 0..6 un-consumed frames
 
@@ -39,7 +39,7 @@ def slot_plan(tails: Sequence[int], frames: Sequence[int]) -> Tuple[List[int], L
     ks, new_tails = [], []
     for t, f in zip(tails, frames):
         total = int(t) + int(f)
-        k = max(0, ((total - 1) // 2 - 1) // 2)
+        k = max(0, encoder_frames(total))
         ks.append(k)
         new_tails.append(total - 4 * k)
     return ks, new_tails
@@ -90,6 +90,31 @@ class _Step:
         return self._keep[half]
 
 
+class _SlotStream:
+    """The stream context of ConformerBlock.fused_chain for one slot step: slot b's new rows are the compact rows 0 .. k_b-1,
+    `cur` holds the step's device offsets; `i` is the layer the chain is in (StreamingEncoder._encode sets it)."""
+
+    def __init__(self, st: "SlotStreamingEncoder", cur: _Step) -> None:
+        self.st, self.cur, self.i = st, cur, 0
+
+    def attend(self, a, qkv_new: torch.Tensor) -> torch.Tensor:
+        """Append every slot's new Q|K|V rows at its own cache row and return the compact context (S, k_max, d)."""
+        st, cur, i, d = self.st, self.cur, self.i, self.st.d
+        if cur.nk:
+            st.qkv[i].view(-1, 3 * d).index_copy_(0, cur.dst, qkv_new.reshape(-1, 3 * d).index_select(0, cur.src))
+        return ops.relpos_attention_slots(st.qkv[i], st.pos_all[:, i * d:(i + 1) * d], a.content_bias, a.position_bias,
+                                          st.lengths, a.n_heads, cur.q_begin, cur.k, cur.k_max, keys_hint=cur.keys_hint)
+
+    def depthwise(self, cv, g: torch.Tensor) -> torch.Tensor:
+        """Window: the slot's carried GLU rows, then its new ones (rows >= k_b: zero padding); rows k_b .. k_b+half-1 carry on."""
+        state, cur = self.st.conv_state[self.i], self.cur
+        half = state.shape[1]
+        buf = torch.cat([state, g.masked_fill(~cur.glu_mask(), 0.0)], dim=1)
+        s = cv.depthwise_eval(buf)
+        state.copy_(torch.gather(buf, 1, cur.keep_index(half).expand(buf.shape[0], half, buf.shape[2])))
+        return s[:, half:].contiguous()
+
+
 class SlotStreamingEncoder(StreamingEncoder):
     """The chunked encoder of StreamingEncoder over `slots` independent streams of at most max_mel_frames mel frames each.
     open(s) starts a stream in a free slot, step(mel, frames) feeds every slot its own number of new frames, close(s) frees the
@@ -104,7 +129,6 @@ class SlotStreamingEncoder(StreamingEncoder):
         self.n0 = [0] * self.S                                             # encoder frames per slot so far
         self.tails = [0] * self.S                                          # buffered mel frames per slot (0..6)
         self.mel_seen = [0] * self.S                                       # mel frames received per slot
-        self._cur: Optional[_Step] = None                                 # the step being enqueued
         self.last_step: Optional[_Step] = None                            # the latest step's device offsets (k: SlotTranscriber)
 
     def _check_slot(self, s: int, want_open: bool) -> int:
@@ -175,9 +199,7 @@ class SlotStreamingEncoder(StreamingEncoder):
             W = 4 * k_max + 3                                              # the mel frames of k_max encoder frames
             pos = torch.arange(W, device=dev)[None, :].expand(S, W)
             mel = torch.gather(src, 2, cur.mel_index(pos, Tc)[:, None, :].expand(S, n_mel, W))
-            self._cur = cur
-            out = self._step_rows(mel)
-            self._cur = None
+            out = self._encode(mel, _SlotStream(self, cur), lambda: self.lengths.copy_(cur.lengths))
         self.mel_tail_buf.copy_(new_tail)
         for b in range(S):
             self.n0[b] += ks[b]
@@ -185,33 +207,6 @@ class SlotStreamingEncoder(StreamingEncoder):
         self.tails = new_tails
         self.last_step = cur
         return out, ks
-
-    def _step_rows(self, mel: torch.Tensor) -> torch.Tensor:
-        enc, d, cur = self.enc, self.d, self._cur
-        h = enc.downsampling_conv.channel_last(mel.contiguous())          # (S, k_max, F'*C): the stem is local in time
-        wlp = enc._packs.get("wlp", (enc.linear.weight,), lambda: ops.pack_linear_weight(enc.linear.weight, d, enc.n_freq_out))
-        h = ops.linear(h, wlp, enc.linear.bias)
-        self.lengths.copy_(cur.lengths)
-        st = None
-        for i, blk in enumerate(enc.layers):
-            h, st = self._block(i, blk, h, 0, cur.k_max, st, want_stats=i + 1 < len(enc.layers))
-        return h
-
-    # ---- the per-slot parts of StreamingEncoder._block
-    def _attend(self, i: int, a, qkv_new: torch.Tensor, n0: int, k: int) -> torch.Tensor:
-        d, cur = self.d, self._cur
-        if cur.nk:
-            self.qkv[i].view(-1, 3 * d).index_copy_(0, cur.dst, qkv_new.reshape(-1, 3 * d).index_select(0, cur.src))
-        return ops.relpos_attention_slots(self.qkv[i], self.pos_all[:, i * d:(i + 1) * d], a.content_bias, a.position_bias,
-                                          self.lengths, a.n_heads, cur.q_begin, cur.k, cur.k_max, keys_hint=cur.keys_hint)
-
-    def _conv_window(self, i: int, g: torch.Tensor) -> torch.Tensor:
-        return torch.cat([self.conv_state[i], g.masked_fill(~self._cur.glu_mask(), 0.0)], dim=1)
-
-    def _conv_keep(self, i: int, buf: torch.Tensor) -> None:
-        half = self.half[i]
-        idx = self._cur.keep_index(half).expand(self.S, half, buf.shape[2])
-        self.conv_state[i].copy_(torch.gather(buf, 1, idx))
 
 
 class SlotTranscriber:
@@ -223,25 +218,13 @@ class SlotTranscriber:
     close(s) returns what decoder(...) returns on that slot's concatenated logits.  fp32 eval mode only."""
 
     def __init__(self, model, decoder: BeamCTCDecoder, slots: int, max_mel_frames: int) -> None:
-        if model.training:
-            raise RuntimeError("SlotTranscriber: put the model in eval() mode (running BatchNorm statistics, no dropout)")
-        dec = model.decoder
-        p = next(dec.parameters())
-        if not p.is_cuda or p.dtype != torch.float32:
-            raise RuntimeError("SlotTranscriber: the model must live on the HIP device in fp32 (no CPU fallback)")
-        if not dec._hip_eligible(p):
-            raise RuntimeError("SlotTranscriber: the decoder LSTM has no HIP kernel (hidden size % 4 != 0, bidirectional, "
-                               "projected or with dropout)")
+        self.device, self.state = lstm_state(model, "SlotTranscriber", int(slots))
         self.model = model
         self.decoder = decoder
         self.encoder = SlotStreamingEncoder(model.encoder, slots, max_mel_frames)
         self.S = self.encoder.S
-        self.device = p.device
-        H = dec.lstm.hidden_size
-        self.state = [(torch.zeros(self.S, H, device=p.device, dtype=torch.float32),
-                       torch.zeros(self.S, H, device=p.device, dtype=torch.float32)) for _ in range(dec.lstm.num_layers)]
-        f = decoder._fusion(p.device)
-        self.beam = beam_ctc_stream_init(self.S, self.encoder.t_max, p.device, beam_width=decoder.beam_width,
+        f = decoder._fusion(self.device)
+        self.beam = beam_ctc_stream_init(self.S, self.encoder.t_max, self.device, beam_width=decoder.beam_width,
                                          max_candidates=decoder.max_candidates, lm_tables=f.lm_tables, hw_tables=f.hw_tables,
                                          alpha=decoder.alpha, beta=decoder.beta, unk_score_offset=decoder.unk_score_offset,
                                          score_boundary=decoder.score_boundary, hotword_weight=decoder.hotword_weight)

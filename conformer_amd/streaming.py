@@ -28,6 +28,37 @@ from . import ops
 from .model.modules.encoder import Encoder
 
 
+def encoder_frames(mel_frames: int) -> int:
+    """Encoder frames the stem makes of `mel_frames` mel frames (convolution.py:55; <= 0: none yet).  Host arithmetic, per step."""
+    return ((mel_frames - 1) // 2 - 1) // 2
+
+
+class _Stream:
+    """The stream context of ConformerBlock.fused_chain for one lockstep chunk step: the chunk is rows n0 .. n0+k-1 of every
+    utterance; `i` is the layer the chain is in (StreamingEncoder._encode sets it)."""
+
+    def __init__(self, st: "StreamingEncoder", n0: int, k: int) -> None:
+        self.st, self.n0, self.k, self.i = st, n0, k, 0
+
+    def attend(self, a, qkv_new: torch.Tensor) -> torch.Tensor:
+        """Append the chunk's Q|K|V rows to the layer's cache and return the attention context of the new rows (B, k, d)."""
+        st, i, n0, k = self.st, self.i, self.n0, self.k
+        st.qkv[i][:, n0:n0 + k].copy_(qkv_new)
+        ops.relpos_attention_rows(st.qkv[i], st.pos_all[:, i * st.d:(i + 1) * st.d], a.content_bias, a.position_bias,
+                                  st.lengths, a.n_heads, n0, k, st.ctx, keys_hint=n0 + k)
+        return st.ctx[:, n0:n0 + k].contiguous()
+
+    def depthwise(self, cv, g: torch.Tensor) -> torch.Tensor:
+        """The depthwise window reaches (K-1)/2 frames back into the layer's carried GLU rows; the last (K-1)/2 rows are
+        carried into the next chunk (a fixed buffer: the graph replays write the same address)."""
+        state = self.st.conv_state[self.i]
+        half = state.shape[1]
+        buf = torch.cat([state, g], dim=1)                                 # (B, half + k, C)
+        s = cv.depthwise_eval(buf)
+        state.copy_(buf[:, buf.shape[1] - half:])
+        return s[:, half:].contiguous()
+
+
 class StreamingEncoder:
     """graphs=True: every distinct chunk step -- keyed on (frames so far, chunk length, buffered tail) -- is captured ONCE as a
     hipGraph and replayed from then on (the next utterance batch of a streaming service walks through the same keys): one host
@@ -44,18 +75,18 @@ class StreamingEncoder:
         self.enc = encoder
         self.B = int(batch)
         self.d = encoder.linear.out_features
-        self.t_max = ((int(max_mel_frames) - 1) // 2 - 1) // 2
+        self.t_max = encoder_frames(int(max_mel_frames))
         if self.t_max < 1:
             raise ValueError("max_mel_frames must give at least one encoder frame (>= 7)")
         dev = p.device
         layers = list(encoder.layers)
-        self.half = [(l.conv.deepwise_conv.kernel_size[0] - 1) // 2 for l in layers]
         with torch.no_grad():
             self.table = encoder.rel_pe.table(self.t_max)
             self.pos_all = encoder._projected_positions(self.table)       # (2T'max-1, L*d): every layer's pos_proj, once
         self.qkv = [torch.zeros(self.B, self.t_max, 3 * self.d, device=dev, dtype=torch.float32) for _ in layers]
         self.ctx = torch.zeros(self.B, self.t_max, self.d, device=dev, dtype=torch.float32)     # scratch shared by the layers
-        self.conv_state = [torch.zeros(self.B, h, self.d, device=dev, dtype=torch.float32) for h in self.half]
+        halves = [(l.conv.deepwise_conv.kernel_size[0] - 1) // 2 for l in layers]     # the carried GLU rows: (K-1)/2 per layer
+        self.conv_state = [torch.zeros(self.B, h, self.d, device=dev, dtype=torch.float32) for h in halves]
         self.lengths = torch.zeros(self.B, dtype=torch.int64, device=dev)
         self.mel_tail_buf: Optional[torch.Tensor] = None                   # (B, n_mel, 6): the un-consumed 0..6 mel frames
         self.tail_len = 0
@@ -83,7 +114,7 @@ class StreamingEncoder:
             self.mel_tail_buf = torch.zeros(self.B, x_in.shape[1], 8, device=x_in.device, dtype=torch.float32)
         n0, tail = self.frames, self.tail_len
         total = tail + x_in.shape[2]
-        k = max(0, ((total - 1) // 2 - 1) // 2)
+        k = max(0, encoder_frames(total))
         if k <= 0:
             # not enough frames for one encoder frame yet: just buffer (<= 6 frames; tiny copy, never graphed)
             self.mel_tail_buf[:, :, tail:total].copy_(x_in)
@@ -126,81 +157,26 @@ class StreamingEncoder:
 
     def _step_core(self, x_in: torch.Tensor, n0: int, tail: int, k: int) -> torch.Tensor:
         """The device work of one chunk: capture-safe (fixed state buffers, no host synchronisation, no data-dependent shapes)."""
-        enc, d = self.enc, self.d
         x = x_in if tail == 0 else torch.cat([self.mel_tail_buf[:, :, :tail], x_in], dim=2)
         # encoder frame t covers mel frames 4t .. 4t+6: the buffer starts at mel frame 4*n0, keep what frame n0+k needs
         rest = x.shape[2] - 4 * k
         self.mel_tail_buf[:, :, :rest].copy_(x[:, :, 4 * k:])
-        h = enc.downsampling_conv.channel_last(x.contiguous())             # (B, k, F'*C): the stem is local in time
-        wlp = enc._packs.get("wlp", (enc.linear.weight,), lambda: ops.pack_linear_weight(enc.linear.weight, d, enc.n_freq_out))
+        return self._encode(x, _Stream(self, n0, k), lambda: self.lengths.fill_(n0 + k))
+
+    def _encode(self, mel: torch.Tensor, stream, set_lengths) -> torch.Tensor:
+        """Stem, input Linear and the blocks on the mel frames of a step's new encoder frames (the stem is local in time);
+        `stream` takes the new rows through the two seams of every block (ConformerBlock.fused_chain); set_lengths() enqueues
+        the step's key limits (self.lengths) in front of the blocks."""
+        enc = self.enc
+        h = enc.downsampling_conv.channel_last(mel.contiguous())           # (B, k, F'*C)
+        wlp = enc._packs.get("wlp", (enc.linear.weight,), lambda: ops.pack_linear_weight(enc.linear.weight, self.d, enc.n_freq_out))
         h = ops.linear(h, wlp, enc.linear.bias)
-        self.lengths.fill_(n0 + k)
-        st = None
+        set_lengths()
+        stats = None
         for i, blk in enumerate(enc.layers):
-            h, st = self._block(i, blk, h, n0, k, st, want_stats=i + 1 < len(enc.layers))
+            stream.i = i
+            h, stats = blk.fused_chain(h, None, None, x_stats=stats, want_stats=i + 1 < len(enc.layers), stream=stream)
         return h
-
-    def _block(self, i: int, blk, x: torch.Tensor, n0: int, k: int, x_stats=None, want_stats: bool = False):
-        """One Conformer block on the chunk's rows.  Returns (y, LayerNorm statistics of y's rows or None).  On the folded-LayerNorm
-        path (ops.ln_fold_ok) the residual GEMMs emit the statistics the next sub-layer's LayerNorm needs, as in
-        ConformerBlock.fused_chain; a sub-layer whose producer took the split-K form instead (FFN out at chunk sizes) runs its
-        LayerNorm kernel."""
-        fold = blk._ln_fold(x)
-        y, st = blk.ffn_1.fused(x, residual=x, alpha=0.5, stats=x_stats, emit_stats=True) if fold else \
-            (blk.ffn_1.fused(x, residual=x, alpha=0.5), None)
-        # ---- self-attention of the new rows against the whole cache
-        att, a = blk.attention, blk.attention.attention
-        w, b = a._qkv_params()
-        if st is not None:
-            ln = att.layer_norm
-            wf, bf, cs = a._packs.get("qkv_ln_fold", (w, b, ln.weight, ln.bias), lambda: ops.fold_layernorm(w, b, ln.weight, ln.bias))
-            qkv_new = ops.linear_lnfold(y, st, wf, bf, cs, ln.eps)
-        else:
-            qkv_new = ops.linear(ops.layernorm(y, att.layer_norm.weight, att.layer_norm.bias, att.layer_norm.eps), w, b)
-        rows = self._attend(i, a, qkv_new, n0, k)
-        y, st = ops.linear_residual(rows, a.out_proj.weight, a.out_proj.bias, y, 1.0, emit_stats=True) if fold else \
-            (ops.linear_residual(rows, a.out_proj.weight, a.out_proj.bias, y, 1.0), None)
-        # ---- convolution module: the depthwise window reaches (K-1)/2 frames back into the cached GLU outputs
-        cv, half = blk.conv, self.half[i]
-        bn = cv.batch_norm
-        if st is not None:
-            ln, pw1 = cv.layer_norm, cv.pointwise_conv_1
-            wf, bf, cs = cv._packs.get("ln_fold", (pw1.weight, pw1.bias, ln.weight, ln.bias),
-                                       lambda: ops.fold_layernorm(pw1.weight, pw1.bias, ln.weight, ln.bias))
-            g = ops.linear_lnfold(y, st, wf, bf, cs, ln.eps, glu=True)
-        else:
-            hn = ops.layernorm(y, cv.layer_norm.weight, cv.layer_norm.bias, cv.layer_norm.eps)
-            g = ops.linear_glu(hn, cv.pointwise_conv_1.weight, cv.pointwise_conv_1.bias)
-        buf = self._conv_window(i, g)                                      # (B, half + k, C)
-        s = ops.dwconv_bn_swish(buf, cv.deepwise_conv.weight, cv.deepwise_conv.bias, bn.weight, bn.bias, bn.running_mean,
-                                bn.running_var, bn.eps)
-        self._conv_keep(i, buf)
-        rows = s[:, half:].contiguous()
-        y, st = ops.linear_residual(rows, cv.pointwise_conv_2.weight, cv.pointwise_conv_2.bias, y, 1.0, emit_stats=True) if fold else \
-            (ops.linear_residual(rows, cv.pointwise_conv_2.weight, cv.pointwise_conv_2.bias, y, 1.0), None)
-        y = blk.ffn_2.fused(y, residual=y, alpha=0.5, stats=st)
-        ln = blk.layer_norm
-        if fold and want_stats:
-            return ops.layernorm(y, ln.weight, ln.bias, ln.eps, emit_stats=True)
-        return ops.layernorm(y, ln.weight, ln.bias, ln.eps), None
-
-    # ---- the per-stream parts of _block (conformer_amd/slots.py overrides them for independent streams)
-    def _attend(self, i: int, a, qkv_new: torch.Tensor, n0: int, k: int) -> torch.Tensor:
-        """Append the chunk's Q|K|V rows to layer i's cache and return the attention context of the new rows (B, k, d)."""
-        d = self.d
-        self.qkv[i][:, n0:n0 + k].copy_(qkv_new)
-        ops.relpos_attention_rows(self.qkv[i], self.pos_all[:, i * d:(i + 1) * d], a.content_bias, a.position_bias,
-                                  self.lengths, a.n_heads, n0, k, self.ctx, keys_hint=n0 + k)
-        return self.ctx[:, n0:n0 + k].contiguous()
-
-    def _conv_window(self, i: int, g: torch.Tensor) -> torch.Tensor:
-        """The depthwise convolution's input: layer i's carried GLU rows, then the chunk's."""
-        return torch.cat([self.conv_state[i], g], dim=1)
-
-    def _conv_keep(self, i: int, buf: torch.Tensor) -> None:
-        """Carry the last (K-1)/2 GLU rows into the next chunk."""
-        half = self.half[i]
-        self.conv_state[i].copy_(buf[:, buf.shape[1] - half:])            # fixed buffer (the graph replays write the same address)
 
     def run(self, mel: torch.Tensor, chunk_frames: int = 640) -> torch.Tensor:
         """Feeds mel (B, n_mel, T) in chunks of `chunk_frames` and returns the concatenated (B, T', d) output."""
@@ -213,7 +189,7 @@ def chunk_ends(total_mel_frames: int, chunk_frames: Iterable[int]) -> List[int]:
     ends, got = [], 0
     for c in chunk_frames:
         got += c
-        n = ((got - 1) // 2 - 1) // 2
+        n = encoder_frames(got)
         if n > 0 and (not ends or n > ends[-1]):
             ends.append(n)
     return ends

@@ -35,27 +35,33 @@ def decode_frames(model, state, enc: torch.Tensor, lengths: Optional[torch.Tenso
     return ops.linear(z, dec.linear.weight.detach(), dec.linear.bias.detach())
 
 
+def lstm_state(model, who: str, batch: int):
+    """Refuses what the streaming transcribers (`who`: the class the message names) cannot run; returns the model's device and
+    the zero LSTM state, [(h, c)] per layer, (batch, H) each."""
+    if model.training:
+        raise RuntimeError(f"{who}: put the model in eval() mode (running BatchNorm statistics, no dropout)")
+    dec = model.decoder
+    p = next(dec.parameters())
+    if not p.is_cuda or p.dtype != torch.float32:
+        raise RuntimeError(f"{who}: the model must live on the HIP device in fp32 (no CPU fallback)")
+    if not dec._hip_eligible(p):
+        raise RuntimeError(f"{who}: the decoder LSTM has no HIP kernel (hidden size % 4 != 0, bidirectional, projected or "
+                           "with dropout)")
+    H = dec.lstm.hidden_size
+    return p.device, [(torch.zeros(batch, H, device=p.device, dtype=torch.float32),
+                       torch.zeros(batch, H, device=p.device, dtype=torch.float32)) for _ in range(dec.lstm.num_layers)]
+
+
 class StreamingTranscriber:
     """model: a Conformer in eval() mode on the HIP device; decoder: the BeamCTCDecoder whose configuration (beam knobs, lm,
     hotwords) the streamed search takes; batch utterances of at most max_mel_frames mel frames.  graphs: as StreamingEncoder."""
 
     def __init__(self, model, decoder: BeamCTCDecoder, batch: int, max_mel_frames: int, graphs: bool = False) -> None:
-        if model.training:
-            raise RuntimeError("StreamingTranscriber: put the model in eval() mode (running BatchNorm statistics, no dropout)")
-        dec = model.decoder
-        p = next(dec.parameters())
-        if not p.is_cuda or p.dtype != torch.float32:
-            raise RuntimeError("StreamingTranscriber: the model must live on the HIP device in fp32 (no CPU fallback)")
-        if not dec._hip_eligible(p):
-            raise RuntimeError("StreamingTranscriber: the decoder LSTM has no HIP kernel (hidden size % 4 != 0, bidirectional, "
-                               "projected or with dropout)")
+        self.B = int(batch)
+        device, self.state = lstm_state(model, "StreamingTranscriber", self.B)
         self.model = model
         self.encoder = StreamingEncoder(model.encoder, batch, max_mel_frames, graphs=graphs)
-        self.B = int(batch)
-        H = dec.lstm.hidden_size
-        self.state = [(torch.zeros(self.B, H, device=p.device, dtype=torch.float32),
-                       torch.zeros(self.B, H, device=p.device, dtype=torch.float32)) for _ in range(dec.lstm.num_layers)]
-        self.beam: BeamCTCStream = decoder.stream(self.B, self.encoder.t_max, p.device)
+        self.beam: BeamCTCStream = decoder.stream(self.B, self.encoder.t_max, device)
 
     def reset(self) -> None:
         self.encoder.reset()

@@ -212,7 +212,7 @@ def _single_stream_encoder(enc, x, chunks, dev):
     return torch.cat(outs, dim=1)[0]
 
 
-@pytest.mark.parametrize("d,heads", [(32, 4), (512, 8)], ids=["small", "cfg5_width"])
+@pytest.mark.parametrize("d,heads", [(32, 4), (48, 4), (512, 8)], ids=["small", "unfolded", "cfg5_width"])  # 48: not ln_fold_ok
 def test_slot_encoder_matches_chunked_oracle(dev, d, heads):
     from conformer_amd.slots import SlotStreamingEncoder
     from conformer_amd.streaming import chunk_ends

@@ -26,10 +26,17 @@ def _encoder(P, n_mel, n_blocks, d, H, K, dev):
     return enc.to(dev).eval()
 
 
-@pytest.mark.parametrize("chunks", [[64] * 7, [200, 7, 1, 130, 3, 62], [403], [9, 394]])
-def test_streaming_matches_masked_restatement(dev, chunks):
+CHUNK_LISTS = [[64] * 7, [200, 7, 1, 130, 3, 62], [403], [9, 394]]
+
+
+# d = 32 takes the folded-LayerNorm branch of ConformerBlock.fused_chain, d = 48 (not ops.ln_fold_ok) the other one
+@pytest.mark.parametrize("chunks,d", [(c, d) for d in (32, 48) for c in CHUNK_LISTS],
+                         ids=[f"chunks{i}" + ("" if d == 32 else f"-d{d}") for d in (32, 48) for i in range(len(CHUNK_LISTS))])
+def test_streaming_matches_masked_restatement(dev, chunks, d):
+    from conformer_amd import ops
     from conformer_amd.streaming import StreamingEncoder, chunk_ends
-    d, H, L, K = 32, 4, 2, 31
+    H, L, K = 4, 2, 31
+    assert ops.ln_fold_ok(d) == (d == 32)
     P = O.make_params(vocab=8, n_mel=80, n_blocks=L, d=d, n_heads=H, ksize=K, lstm_hidden=8, seed=11, dtype=torch.float64,
                       with_decoder=False)
     T = sum(chunks)
@@ -179,6 +186,35 @@ def test_attention_rows_kernel_vs_reference_block_triangular_mask(dev, case):
         start = e
     y = ops.linear(ctx, P[a + "attention.out_proj.weight"], P[a + "attention.out_proj.bias"])
     assert rel_l2(y, g["mhsa_y"]) < 2e-5
+
+
+@pytest.mark.parametrize("case", ["training_mode", "input_requires_grad"])
+def test_block_chain_refuses_a_stream_outside_inference(dev, case):
+    """ConformerBlock.fused_chain takes a stream context for inference only: with BatchNorm in training mode, or with gradients
+    wanted, it raises before anything runs, so the stream's caches stay as they were."""
+    from conformer_amd.streaming import StreamingEncoder, _Stream
+    P = O.make_params(vocab=8, n_mel=80, n_blocks=1, d=32, n_heads=4, ksize=31, lstm_hidden=8, seed=14, with_decoder=False)
+    enc = _encoder(P, 80, 1, 32, 4, 31, dev)
+    st = StreamingEncoder(enc, batch=2, max_mel_frames=67)               # T' = 16
+    assert st.t_max == 16
+    st.step(torch.randn(2, 80, 35, device=dev))                          # 8 frames: the caches hold something
+    before = [t.clone() for t in st.qkv + st.conv_state + [st.ctx, st.lengths]]
+    x = torch.randn(2, 8, 32, device=dev)
+    blk = enc.layers[0]
+    if case == "training_mode":
+        blk.train()
+        with torch.no_grad(), pytest.raises(RuntimeError, match="inference only"):
+            blk.fused_chain(x, None, None, stream=_Stream(st, 8, 8))
+        blk.eval()
+    else:
+        blk.requires_grad_(False)                                        # nothing but the input asks for a gradient
+        with pytest.raises(RuntimeError, match="inference only"):
+            blk.fused_chain(x.requires_grad_(), None, None, stream=_Stream(st, 8, 8))
+    for t, b in zip(st.qkv + st.conv_state + [st.ctx, st.lengths], before):
+        assert torch.equal(t, b)
+    with torch.no_grad():                                                # and the same call is fine in inference
+        y, _ = blk.fused_chain(x.detach(), None, None, stream=_Stream(st, 8, 8))
+    assert y.shape == x.shape and torch.isfinite(y).all()
 
 
 @pytest.mark.parametrize("dt", [torch.bfloat16, torch.float16])

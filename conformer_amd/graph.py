@@ -10,12 +10,7 @@ from typing import Optional, Tuple
 
 import torch
 
-
-def _weights_fingerprint(module: torch.nn.Module, tensors=None):
-    from conformer_amd.model.utils._guard import _EPOCH, _ver
-    if tensors is None:
-        tensors = list(module.parameters()) + list(module.buffers())
-    return (_EPOCH[0],) + tuple((t.data_ptr(), _ver(t)) for t in tensors)
+from ._derived import fingerprint
 
 
 class GraphedEncoder:
@@ -61,7 +56,7 @@ class GraphedEncoder:
         with torch.no_grad(), torch.cuda.graph(self.graph), amp():
             self.static_y, self.static_out_len = encoder(self.static_x, self.static_len)
         self._tensors = list(encoder.parameters()) + list(encoder.buffers())     # (walked once per capture, not per replay)
-        self._fingerprint = _weights_fingerprint(encoder, self._tensors)
+        self._fingerprint = fingerprint(self._tensors)
         self.captures += 1
 
     def __call__(self, x: torch.Tensor, lengths: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
@@ -69,7 +64,7 @@ class GraphedEncoder:
             raise ValueError(f"graph captured for input {tuple(self.static_x.shape)}, got {tuple(x.shape)}")
         if self.encoder.training:
             raise ValueError("GraphedEncoder replays the inference path: the wrapped encoder was switched to .train()")
-        if self.check_weights and _weights_fingerprint(self.encoder, self._tensors) != self._fingerprint:
+        if self.check_weights and fingerprint(self._tensors) != self._fingerprint:
             self._capture()                              # weights changed since the capture: never replay stale packs
         if x.data_ptr() != self.static_x.data_ptr():
             self.static_x.copy_(x)

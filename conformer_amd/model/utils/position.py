@@ -11,6 +11,7 @@ import torch
 import torch.nn as nn
 
 from ... import ops
+from ..._derived import DerivedCache
 
 
 class RelativePositionalEncoding(nn.Module):
@@ -19,15 +20,10 @@ class RelativePositionalEncoding(nn.Module):
         self.d_model = d_model
         freq = torch.exp(torch.arange(0, d_model, 2) * -(math.log(10000.0) / d_model))
         self.div_term = nn.Parameter(freq.unsqueeze(0), requires_grad=False)
-        self._cache = {}
+        self._cache = DerivedCache()
 
     def table(self, n_frames: int) -> torch.Tensor:
-        key = (n_frames, self.div_term.data_ptr(), self.div_term._version)
-        hit = self._cache.get("t")
-        if hit is None or hit[0] != key:
-            hit = (key, ops.relpos_table(self.div_term, n_frames))
-            self._cache["t"] = hit
-        return hit[1]
+        return self._cache.get("t", (self.div_term,), lambda: ops.relpos_table(self.div_term, n_frames), extra=n_frames)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         return self.table(x.size(1)).unsqueeze(0).expand(x.size(0), -1, -1).contiguous()

@@ -7,12 +7,12 @@ from __future__ import annotations
 
 import threading
 import ctypes
-import weakref
 from typing import Optional, Tuple
 
 import torch
 
 from . import _lib
+from ._derived import DerivedCache
 
 
 def _stream() -> int:
@@ -84,39 +84,25 @@ def bf16_mfma_active() -> bool:
     return mfma16_prec() == PREC_BF16
 
 
-def _ver(t: torch.Tensor) -> int:
-    """`_version` of a weight, 0 for inference tensors (packs built under torch.inference_mode() carry no version counter;
-    they are never modified in place -- PackCache rebuilds them as new tensors when a source parameter changes)."""
-    return 0 if t.is_inference() else t._version
-
-
-_W16_CACHE = {}        # data_ptr -> (weakref(base tensor), version, prec, shape, 16-bit tensor): per-optimizer-step weight casts
+_WEIGHT_COPIES = DerivedCache()      # (address, transposed | "split") -> 16-bit / split-plane copy of a weight, for every module
 def weight16(w: torch.Tensor, prec: int, transposed: bool = False) -> Optional[torch.Tensor]:
     """The weight matrix rounded to the 16-bit matrix-pipe type, cached until the parameter changes in place (optimizer
     step / load_state_dict bump `_version`).  None when the 16-bit operand path does not apply (K % 8 != 0).
     transposed: the (K, N) transpose of the (N, K) weight (the backward's dX = dY.W as a row-major-A forward GEMM)."""
     if w.shape[-1] % 8 or w.numel() % 4 or (transposed and w.shape[0] % 8):
         return None
-    key = (w.data_ptr(), transposed)
-    base = w._base if w._base is not None else w     # views are re-created per call; the owning tensor identifies the weight
-    hit = _W16_CACHE.get(key)
-    # (a freed temporary -- e.g. last step's fused QKV matrix -- can hand its address to a new tensor: the weak reference
-    # to the owner tells the two apart; `_version` catches in-place updates of a live parameter)
-    if hit is not None and hit[0]() is base and hit[1] == _ver(w) and hit[2] == prec and hit[3] == w.shape:
-        return hit[4]
-    if transposed:
-        out = torch.empty(w.shape[1], w.shape[0], device=w.device, dtype=_DT16[prec])
-        item = (_lib.CastItem * 1)()
-        item[0].src, item[0].dst, item[0].rows, item[0].cols, item[0].transpose = w.data_ptr(), out.data_ptr(), w.shape[0], w.shape[1], 1
-        _lib.check(_lib.load().cfm_cast16_multi_f32(prec, ctypes.addressof(item), 1, _stream()), "cfm_cast16_multi_f32")
-    else:
-        out = torch.empty(w.shape, device=w.device, dtype=_DT16[prec])
-        _lib.check(_lib.load().cfm_cast16_f32(prec, w.data_ptr(), out.data_ptr(), w.numel(), _stream()), "cfm_cast16_f32")
-    if len(_W16_CACHE) > 4096:
-        for k in [k for k, v in _W16_CACHE.items() if v[0]() is None]:
-            del _W16_CACHE[k]
-    _W16_CACHE[key] = (weakref.ref(base), _ver(w), prec, w.shape, out)
-    return out
+    def make() -> torch.Tensor:
+        if transposed:
+            out = torch.empty(w.shape[1], w.shape[0], device=w.device, dtype=_DT16[prec])
+            item = (_lib.CastItem * 1)()
+            item[0].src, item[0].dst, item[0].rows, item[0].cols, item[0].transpose = w.data_ptr(), out.data_ptr(), w.shape[0], w.shape[1], 1
+            _lib.check(_lib.load().cfm_cast16_multi_f32(prec, ctypes.addressof(item), 1, _stream()), "cfm_cast16_multi_f32")
+        else:
+            out = torch.empty(w.shape, device=w.device, dtype=_DT16[prec])
+            _lib.check(_lib.load().cfm_cast16_f32(prec, w.data_ptr(), out.data_ptr(), w.numel(), _stream()), "cfm_cast16_f32")
+        return out
+    # (a freed temporary -- e.g. last step's fused QKV matrix -- can hand its address to a new tensor: the owner's identity tells them apart)
+    return _WEIGHT_COPIES.get((w.data_ptr(), transposed), (w,), make, extra=prec)
 
 
 def refresh_weight16(params) -> int:
@@ -126,18 +112,14 @@ def refresh_weight16(params) -> int:
     rewritten IN PLACE (same addresses: graph-friendly; the previous step's kernels that read them precede the optimizer
     step on the stream).  Returns the number of copies refreshed."""
     by_prec = {}
+    def queue(p, transposed, prec, shape2, out) -> bool:      # shape2: the 2-D view the copy was made from (conv weights arrive reshaped)
+        ok = len(shape2) == 2 and shape2[0] * shape2[1] == p.numel() and p.is_contiguous()
+        if ok:
+            by_prec.setdefault(prec, []).append((p.detach().reshape(shape2), out, transposed))
+        return ok
     for p in params:
-        for transposed in (False, True):
-            key = (p.data_ptr(), transposed)
-            hit = _W16_CACHE.get(key)
-            if hit is None or hit[0]() is not (p._base if p._base is not None else p) or hit[1] == _ver(p):
-                continue
-            shape2 = tuple(hit[3])                     # the 2-D view the copy was made from (conv weights arrive reshaped)
-            if len(shape2) != 2 or shape2[0] * shape2[1] != p.numel() or not p.is_contiguous():
-                continue
-            w2 = p.detach().reshape(shape2)
-            by_prec.setdefault(hit[2], []).append((w2, hit[4], transposed))
-            _W16_CACHE[key] = (hit[0], _ver(p), hit[2], hit[3], hit[4])
+        for t in (False, True):
+            _WEIGHT_COPIES.refresh((p.data_ptr(), t), (p,), lambda prec, shapes, out: queue(p, t, prec, shapes[0], out))
     n = 0
     for prec, items in by_prec.items():
         arr = (_lib.CastItem * len(items))()
@@ -185,26 +167,18 @@ def fp32_matmul() -> str:
     return {v: k for k, v in _FP32_MATMUL.items()}[_fp32_planes]
 
 
-_WSPLIT_CACHE = {}     # data_ptr -> (weakref(base), version, planes, shape, [planes][N][K] bf16)
 def weight_split(w: torch.Tensor, planes: int) -> Optional[torch.Tensor]:
     """Exact bf16 expansion of a (N,K) weight matrix in MFMA fragment order ([row block of 32][K-step of 16][plane][lane][8]),
     cached like weight16.  None when the split path does not apply (K % 16 != 0)."""
     if w.dim() != 2 or w.shape[1] % 16:
         return None
-    key = w.data_ptr()
-    base = w._base if w._base is not None else w
-    hit = _WSPLIT_CACHE.get(key)
-    if hit is not None and hit[0]() is base and hit[1] == _ver(w) and hit[2] == planes and hit[3] == w.shape:
-        return hit[4]
-    lib = _lib.load()
-    n, k = w.shape
-    out = torch.empty(int(lib.cfm_split_pack_elems(planes, n, k)), device=w.device, dtype=torch.bfloat16)
-    _lib.check(lib.cfm_split_pack_bf16_f32(planes, w.data_ptr(), out.data_ptr(), n, k, _stream()), "cfm_split_pack_bf16_f32")
-    if len(_WSPLIT_CACHE) > 4096:
-        for kk in [kk for kk, v in _WSPLIT_CACHE.items() if v[0]() is None]:
-            del _WSPLIT_CACHE[kk]
-    _WSPLIT_CACHE[key] = (weakref.ref(base), _ver(w), planes, w.shape, out)
-    return out
+    def make() -> torch.Tensor:
+        lib = _lib.load()
+        n, k = w.shape
+        out = torch.empty(int(lib.cfm_split_pack_elems(planes, n, k)), device=w.device, dtype=torch.bfloat16)
+        _lib.check(lib.cfm_split_pack_bf16_f32(planes, w.data_ptr(), out.data_ptr(), n, k, _stream()), "cfm_split_pack_bf16_f32")
+        return out
+    return _WEIGHT_COPIES.get((w.data_ptr(), "split"), (w,), make, extra=planes)
 
 
 def unpack_weight_split(packed: torch.Tensor, planes: int, n: int, k: int) -> torch.Tensor:

@@ -183,6 +183,7 @@ class SlotStreamingEncoder(StreamingEncoder):
         """mel_chunk (S, n_mel, Tc): slot b's next frames[b] mel frames are mel_chunk[b, :, :frames[b]] (the rest is ignored).
         Returns the compact new encoder frames (S, k_max, d) and k (host list): rows >= k[b] of slot b are padding."""
         x, ks, new_tails = self.plan(mel_chunk, frames)
+        self._follow_weights()
         frames = [int(f) for f in frames]
         S, Tc, dev = self.S, x.shape[2], x.device
         k_max = max(ks)

@@ -16,7 +16,7 @@ modules are local in time, so they are exact under chunking; relative positions 
 State per layer: the fused Q|K|V projections of every frame so far (B, T'max, 3d) -- new rows are appended in place and
 `cfm_relpos_attention_rows_f32` computes the new query rows only, against the whole cache -- and the last (K-1)/2 GLU
 outputs feeding the depthwise convolution.  Per utterance: the un-consumed tail (3..6 frames) of the mel stream and the
-positional table projected ONCE for T'max.  fp32 inference only.
+positional table projected ONCE for T'max.
 """
 from __future__ import annotations
 
@@ -25,6 +25,7 @@ from typing import Iterable, List, Optional
 import torch
 
 from . import ops
+from ._derived import fingerprint
 from .model.modules.encoder import Encoder
 
 
@@ -60,13 +61,21 @@ class _Stream:
 
 
 class StreamingEncoder:
-    """graphs=True: every distinct chunk step -- keyed on (frames so far, chunk length, buffered tail) -- is captured ONCE as a
-    hipGraph and replayed from then on (the next utterance batch of a streaming service walks through the same keys): one host
-    call per chunk instead of ~420 launches, whose issue cost (not their device time) was what a 7-11 ms chunk step consisted
-    of (profiles/r02_streaming_bench.json vs r03).  All graphs share one memory pool; the state (K/V caches, depthwise state,
-    mel tail) lives in fixed buffers outside it.  The returned frames are a copy (the graph's output buffer is reused)."""
+    """graphs=True: every distinct chunk step -- keyed on (frames so far, chunk length, buffered tail, matrix-pipe precision) -- is
+    captured ONCE as a hipGraph and replayed from then on (the next utterance batch of a streaming service walks through the same
+    keys): one host call per chunk instead of ~420 launches, whose issue cost (not their device time) was what a 7-11 ms chunk
+    step consisted of (profiles/r02_streaming_bench.json vs r03).  All graphs share one memory pool; the state (K/V caches,
+    depthwise state, mel tail) lives in fixed buffers outside it.  The returned frames are a copy (the graph's output buffer is
+    reused).
 
-    def __init__(self, encoder: Encoder, batch: int, max_mel_frames: int, graphs: bool = False) -> None:
+    The projected position table and the graphs hold what was derived from the weights when they were made.  Every step()
+    compares the encoder's fingerprint (epoch, address and in-place version of each parameter and buffer, as GraphedEncoder
+    does) with the recorded one; after an optimizer step, `load_state_dict`, an in-place update or invalidate_weight_caches()
+    the table is projected again and all graphs are dropped, eager path included.  The stream state is NOT touched: the cached
+    K/V rows were computed with the old weights, so a caller who changes weights mid-utterance calls reset().
+    check_weights=False (frozen-weight serving) skips that per-step walk over the encoder's tensors."""
+
+    def __init__(self, encoder: Encoder, batch: int, max_mel_frames: int, graphs: bool = False, check_weights: bool = True) -> None:
         if encoder.training:
             raise RuntimeError("StreamingEncoder: put the encoder in eval() mode (running BatchNorm statistics, no dropout)")
         p = next(encoder.parameters())
@@ -80,9 +89,6 @@ class StreamingEncoder:
             raise ValueError("max_mel_frames must give at least one encoder frame (>= 7)")
         dev = p.device
         layers = list(encoder.layers)
-        with torch.no_grad():
-            self.table = encoder.rel_pe.table(self.t_max)
-            self.pos_all = encoder._projected_positions(self.table)       # (2T'max-1, L*d): every layer's pos_proj, once
         self.qkv = [torch.zeros(self.B, self.t_max, 3 * self.d, device=dev, dtype=torch.float32) for _ in layers]
         self.ctx = torch.zeros(self.B, self.t_max, self.d, device=dev, dtype=torch.float32)     # scratch shared by the layers
         halves = [(l.conv.deepwise_conv.kernel_size[0] - 1) // 2 for l in layers]     # the carried GLU rows: (K-1)/2 per layer
@@ -92,8 +98,24 @@ class StreamingEncoder:
         self.tail_len = 0
         self.frames = 0                                                    # encoder frames produced so far
         self.use_graphs = bool(graphs)
-        self._graphs = {}                                                  # key -> (graph, static input, static output, k, new tail)
+        self.check_weights = bool(check_weights)
+        self._tensors = list(encoder.parameters()) + list(encoder.buffers())     # (walked once, not per step)
+        self._derive()
+
+    @torch.no_grad()
+    def _derive(self) -> None:
+        """Everything this object holds that was made from the weights: the projected table, the graphs and their pool."""
+        self.table = self.enc.rel_pe.table(self.t_max)
+        self.pos_all = self.enc._projected_positions(self.table)          # (2T'max-1, L*d): every layer's pos_proj, once
+        self._graphs = {}                                                  # key -> (graph, static input, static output)
         self._pool = None
+        self._warm = set()                                                 # precisions whose derived weights a warm step built
+        self._fingerprint = fingerprint(self._tensors)
+
+    def _follow_weights(self) -> None:
+        """The top of every step: weights changed since _derive() -- never run on a stale table or replay stale packs."""
+        if self.check_weights and fingerprint(self._tensors) != self._fingerprint:
+            self._derive()
 
     def reset(self) -> None:
         for t in self.conv_state:
@@ -109,6 +131,7 @@ class StreamingEncoder:
     def step(self, mel_chunk: torch.Tensor) -> torch.Tensor:
         """mel_chunk (B, n_mel, Tc): the next Tc log-mel frames of every utterance (any Tc >= 1).  Returns the encoder
         frames that became computable, (B, k, d) with k = ((buffered-1)//2-1)//2 >= 0."""
+        self._follow_weights()
         x_in = ops._req(mel_chunk, "mel_chunk")
         if self.mel_tail_buf is None:
             self.mel_tail_buf = torch.zeros(self.B, x_in.shape[1], 8, device=x_in.device, dtype=torch.float32)
@@ -125,11 +148,14 @@ class StreamingEncoder:
         if not self.use_graphs:
             out = self._step_core(x_in, n0, tail, k)
         else:
-            key = (n0, x_in.shape[2], tail)
+            prec = ops.mfma16_prec()                                      # the capture bakes in the fp32 or the 16-bit kernels
+            key = (n0, x_in.shape[2], tail, prec)
             ent = self._graphs.get(key)
             if ent is None:
                 if self._pool is None:
                     self._pool = torch.cuda.graph_pool_handle()
+                if prec not in self._warm:
+                    self._warm.add(prec)
                     self._step_warm(x_in, n0, tail, k)                    # derived weights / tables are built outside any capture
                 static_in = x_in.clone()
                 g = torch.cuda.CUDAGraph()

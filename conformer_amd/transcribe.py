@@ -54,13 +54,15 @@ def lstm_state(model, who: str, batch: int):
 
 class StreamingTranscriber:
     """model: a Conformer in eval() mode on the HIP device; decoder: the BeamCTCDecoder whose configuration (beam knobs, lm,
-    hotwords) the streamed search takes; batch utterances of at most max_mel_frames mel frames.  graphs: as StreamingEncoder."""
+    hotwords) the streamed search takes; batch utterances of at most max_mel_frames mel frames.  graphs, check_weights: as
+    StreamingEncoder."""
 
-    def __init__(self, model, decoder: BeamCTCDecoder, batch: int, max_mel_frames: int, graphs: bool = False) -> None:
+    def __init__(self, model, decoder: BeamCTCDecoder, batch: int, max_mel_frames: int, graphs: bool = False,
+                 check_weights: bool = True) -> None:
         self.B = int(batch)
         device, self.state = lstm_state(model, "StreamingTranscriber", self.B)
         self.model = model
-        self.encoder = StreamingEncoder(model.encoder, batch, max_mel_frames, graphs=graphs)
+        self.encoder = StreamingEncoder(model.encoder, batch, max_mel_frames, graphs=graphs, check_weights=check_weights)
         self.beam: BeamCTCStream = decoder.stream(self.B, self.encoder.t_max, device)
 
     def reset(self) -> None:

@@ -289,3 +289,18 @@ def test_inference_mode_with_cached_projected_positions(dev):
     with torch.no_grad():                                     # and the same module afterwards outside inference mode
         y3, _ = enc(x, L)
     assert torch.equal(y3, y1)
+
+
+def test_position_table_of_an_inference_mode_module(dev):
+    """A model BUILT under torch.inference_mode() holds inference tensors as parameters: `div_term._version` raises on them,
+    so the table's cache key must not read it."""
+    from conformer_amd import ops
+    from model.utils.position import RelativePositionalEncoding
+    with torch.inference_mode():
+        rel = RelativePositionalEncoding(16).to(dev)
+        assert rel.div_term.is_inference()
+        t9 = rel.table(9)
+        assert t9.shape == (17, 16) and torch.equal(t9, ops.relpos_table(rel.div_term, 9))
+        assert rel.table(9) is t9
+        t5 = rel.table(5)
+        assert t5.shape == (9, 16) and torch.equal(t5, ops.relpos_table(rel.div_term, 5))

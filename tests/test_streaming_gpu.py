@@ -259,3 +259,87 @@ def test_streaming_under_autocast_tracks_fp32_streaming(dev):
         out = StreamingEncoder(enc, 2, 403).run(x, 128)
     assert out.dtype == torch.float32 and out.shape == ref.shape
     assert rel_l2(out, ref) < 1e-2
+
+
+FOLLOW_CHUNKS = [70, 5, 64, 1, 63]                       # 16, 2, 16, 0 (buffered only), 16 encoder frames: four chunk steps
+
+
+def _tiny_stream_case(dev):
+    """The model_tiny golden's encoder (d = 32: folded LayerNorm, 16-bit operands under autocast), B = 2, FOLLOW_CHUNKS."""
+    from model.modules.encoder import Encoder
+    from tests.util import cfg_params, load_golden
+    meta, _ = load_golden("model_tiny")
+    P = cfg_params(meta)
+    enc = Encoder(80, meta["n_blocks"], meta["d"], meta["n_heads"], meta["ksize"], 0.0)
+    enc.load_state_dict({k[len("encoder."):]: v for k, v in P.items() if k.startswith("encoder.")}, strict=True)
+    x = torch.randn(2, 80, sum(FOLLOW_CHUNKS), generator=torch.Generator().manual_seed(21)).to(dev)
+    return enc.to(dev).eval(), x
+
+
+def _steps(st, x):
+    st.reset()
+    outs, t0 = [], 0
+    for c in FOLLOW_CHUNKS:
+        outs.append(st.step(x[:, :, t0:t0 + c]))
+        t0 += c
+    return outs
+
+
+def _update_weights(enc):
+    with torch.no_grad():
+        enc.layers[1].attention.attention.pos_proj.weight.mul_(1.5)      # goes through the stream's projected position table
+        enc.linear.weight.add_(0.01)                                     # goes through the packed input-linear weight
+
+
+def test_eager_stream_follows_an_in_place_weight_update(dev):
+    """The projected position table is made once per StreamingEncoder: after an in-place update of the weights it (and every
+    pack) must be made again, so the same object computes what a StreamingEncoder constructed after the update computes."""
+    from conformer_amd.streaming import StreamingEncoder
+    enc, x = _tiny_stream_case(dev)
+    T = x.shape[2]
+    st = StreamingEncoder(enc, 2, T)
+    first = torch.cat(_steps(st, x), dim=1)
+    assert first.shape == (2, 50, 32) and st.frames == 50
+    _update_weights(enc)
+    again = torch.cat(_steps(st, x), dim=1)
+    fresh = torch.cat(_steps(StreamingEncoder(enc, 2, T), x), dim=1)
+    assert torch.equal(again, fresh)
+    assert not torch.equal(again, first)
+
+
+def test_graphed_stream_follows_precision_and_weight_updates(dev):
+    """One StreamingEncoder(graphs=True) through (a) fp32, (b) bf16 autocast, (c) fp32 after an in-place weight update: every
+    step equals the eager step of the same pass, so no graph of another precision or of stale packs is replayed."""
+    from conformer_amd.streaming import StreamingEncoder
+    enc, x = _tiny_stream_case(dev)
+    T = x.shape[2]
+    eager, graphed = StreamingEncoder(enc, 2, T), StreamingEncoder(enc, 2, T, graphs=True)
+    n_steps = sum(1 for o in _steps(StreamingEncoder(enc, 2, T), x) if o.shape[1])
+    assert n_steps == 4
+
+    def one_pass():
+        eager.reset(); graphed.reset()
+        outs, t0 = [], 0
+        for c in FOLLOW_CHUNKS:
+            a, b = eager.step(x[:, :, t0:t0 + c]), graphed.step(x[:, :, t0:t0 + c])
+            assert a.shape == b.shape and torch.equal(a, b)
+            outs.append(b)
+            t0 += c
+        assert eager.frames == graphed.frames == 50
+        return torch.cat(outs, dim=1)
+
+    ya = one_pass()
+    assert len(graphed._graphs) == n_steps
+    with torch.autocast("cuda", dtype=torch.bfloat16):
+        yb = one_pass()
+    assert not torch.equal(yb, ya)                                       # the bf16 graphs were captured, not the fp32 ones replayed
+    assert len(graphed._graphs) == 2 * n_steps
+    assert torch.equal(one_pass(), ya) and len(graphed._graphs) == 2 * n_steps     # back in fp32: the first graphs, still valid
+    _update_weights(enc)
+    yc = one_pass()
+    assert not torch.equal(yc, ya)
+    assert len(graphed._graphs) == n_steps                               # the old graphs were dropped, not accumulated
+    frozen = StreamingEncoder(enc, 2, T, graphs=True, check_weights=False)       # frozen-weight serving: no per-step walk
+    for _ in range(2):                                                   # capture, then replay
+        assert torch.equal(torch.cat(_steps(frozen, x), dim=1), yc)
+    assert len(frozen._graphs) == n_steps

@@ -184,7 +184,8 @@ def test_block_bf16_within_1e2_of_fp32_oracle(dev):
                                              (1, 300, 2, 64, None)])
 def test_mfma16_attention_forward(dev, B, T, H, dh, lengths, dt16):
     """16-bit-MFMA attention vs the float64 oracle fed the ROUNDED q+u, q+v, k, v and positions (the probabilities are
-    rounded once more inside the kernel for P.V: tolerance 2^-8 / 2^-11) and vs the unrounded oracle (16-bit budget)."""
+    rounded once more inside the kernel for P.V: tolerance 2^-8 / 2^-11) and vs the unrounded oracle (16-bit budget).
+    Local faults (a lost key, a skewed tile) are caught per element by tests/test_attention_probe_gpu.py, not by this rel_l2."""
     from conformer_amd import ops
     d = H * dh
     qkv = rnd(B, T, 3 * d, seed=11) * 0.5
@@ -273,7 +274,8 @@ def test_attention_16bit_projections_and_context_in_inference(dev, dt16):
     """Inference under autocast: the fused q|k|v projection is written in the 16-bit type (what autocast's nn.Linear returns) and
     so is the attention context.  (a) A 16-bit context changes nothing: its only consumer, the out-projection GEMM, rounds an
     fp32 context to that type anyway -- EQUAL outputs.  (b) 16-bit projections: k and v are rounded exactly as the kernel's staging
-    rounds them, q is rounded before the bias add as well as after (the reference's arithmetic) -- within 16-bit distance."""
+    rounds them, q is rounded before the bias add as well as after (the reference's arithmetic) -- within 16-bit distance.
+    Local faults of either route are caught per element by tests/test_attention_probe_gpu.py, not by this rel_l2."""
     from conformer_amd import ops
     from model.utils.attention import MultiHeadSelfAttentionModule
     torch.manual_seed(3)

@@ -220,7 +220,8 @@ def test_block_chain_refuses_a_stream_outside_inference(dev, case):
 @pytest.mark.parametrize("dt", [torch.bfloat16, torch.float16])
 def test_attention_rows_16bit_form_vs_float64(dev, dt):
     """cfm_relpos_attention_rows_mfma16_f32 (streaming under autocast): chunk rows against the cache == the float64 attention core
-    with the prefix rule, at the 16-bit operand-rounding tolerance (1e-2 bf16 / 3e-3 fp16, the autocast bars of tests/test_mfma16_gpu.py)."""
+    with the prefix rule, at the 16-bit operand-rounding tolerance (1e-2 bf16 / 3e-3 fp16, the autocast bars of tests/test_mfma16_gpu.py).
+    Local faults (a chunk start off a tile boundary, a lost key) are caught per element by tests/test_attention_probe_gpu.py."""
     from conformer_amd import ops
     B, T, H, dh = 3, 200, 4, 36
     d = H * dh

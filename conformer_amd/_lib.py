@@ -153,6 +153,8 @@ SIGNATURES = {
     "cfm_ctc_align_f32": (c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, ctypes.c_size_t, _P, _P, _P, _P, _P, _P, _P, _P]),
     "cfm_relpos_attention_rows_f32": (c_int, [_P, _P, _P, _L, _P, _L, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     "cfm_relpos_attention_slots_f32": (c_int, [_P, _P, _P, _L, _P, _L, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "cfm_relpos_attention_slots_mfma16_f32": (c_int, [_I, _P, _P, _P, _I, _L, _P, _L, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _I,
+                                                      _P, _P]),
     "cfm_debug_attention_trace_f32": (c_int, [_P, _P, _P, _L, _P, _L, _P, _P, _P, _P, _L, _I, _I, _I, _I, _P, _P]),
     "cfm_debug_set_bwd_tile": (c_int, [_I]),
     "cfm_debug_set_attention_waves": (c_int, [_I]),

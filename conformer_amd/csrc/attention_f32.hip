@@ -943,3 +943,18 @@ extern "C" int cfm_relpos_attention_slots_f32(const float* q, const float* k, co
     }
     return cfm_launch_status();
 }
+
+// The merge of the slots key split for the 16-bit kernel (attention_mfma16.hip), whose slices fill the same workspace
+// (nsplit*B*q_max*(H*dh + H) floats, ldo == H*dh): attn_merge_splits_kernel<true> on the fields it reads.  Arguments already checked.
+void cfm_attention_slots_merge(const int64_t* q_begin, const int64_t* q_count, const int64_t* lengths, float* ctx, int64_t ldo,
+                               int B, int T, int H, int dh, int q_max, int nsplit, float* workspace, hipStream_t s) {
+    SlotAttnArgs a{};
+    a.lengths = lengths; a.ctx = ctx; a.ldo = ldo;
+    a.B = B; a.T = T; a.H = H; a.dh = dh;
+    a.q_end = q_max; a.nsplit = nsplit;
+    a.part_ctx = workspace;
+    a.part_lse = workspace + (int64_t)nsplit * B * q_max * ldo;
+    a.slot_begin = q_begin; a.slot_count = q_count; a.q_max = q_max;
+    const int64_t total = (int64_t)B * q_max * H * (dh / 4);
+    hipLaunchKernelGGL(attn_merge_splits_kernel<true>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, a);
+}

@@ -16,6 +16,7 @@
 //     registers) and double-buffered K / V tiles: ONE workgroup barrier per key tile instead of two (60 KB LDS, 2 workgroups per CU).
 #include "cfm_common.h"
 #include <math.h>
+#include <type_traits>
 
 namespace {
 
@@ -34,10 +35,22 @@ struct Attn16Args {
     int q_begin, q_end;          // query rows computed: [q_begin, q_end) (the whole utterance, or a streaming chunk against its K/V cache)
 };
 
+// Independent streams (cfm_relpos_attention_slots_mfma16_f32): slot b computes cache rows [slot_begin[b], slot_begin[b] +
+// slot_count[b]) into the COMPACT fp32 rows ctx[b, 0 .. q_max) (rows >= its count written as zeros), its key tiles divided over
+// nsplit workgroups as the fp32 kernel divides them (attention_f32.hip: SlotAttnArgs, whose merge kernel reads the same workspace).
+// The device values are clamped in the kernel, never trusted.
+struct Slot16Args : Attn16Args {
+    const int64_t* slot_begin; const int64_t* slot_count; int q_max;
+    int nsplit; float* part_ctx; float* part_lse;     // nsplit > 1: normalised partial contexts + their log-sum-exps, merged afterwards
+};
+template <bool SLOTS> using Attn16ArgsT = std::conditional_t<SLOTS, Slot16Args, Attn16Args>;
+
 // QKV16: q / k / v are stored in T16 (compile-time: a run-time test around the loads costs their overlap -- the compiler waits
 // for every conditional load at once)
-template <typename T16, bool QKV16>
-__global__ __launch_bounds__(256, 2) void relpos_attn_fwd_mfma16_kernel(const Attn16Args a) {
+// SLOTS: the query rows, the output rows and the key split are per slot (Slot16Args); a workgroup past its slot's rows only
+// zero-fills (key split: the merge does), before reading anything; no dropout, no lse, fp32 context.
+template <typename T16, bool QKV16, bool SLOTS = false>
+__global__ __launch_bounds__(256, 2) void relpos_attn_fwd_mfma16_kernel(const Attn16ArgsT<SLOTS> a) {
     using x8 = typename Lowp<T16>::x8;
     using x4 = typename Lowp<T16>::x4;
     __shared__ __attribute__((aligned(16))) T16 smem16[2 * 32 * KROWH + 2 * 32 * VROWH + RINGH * KROWH];
@@ -51,9 +64,39 @@ __global__ __launch_bounds__(256, 2) void relpos_attn_fwd_mfma16_kernel(const At
     const int li = lane & 31, hf = lane >> 5;
     const int bh = blockIdx.y, b = bh / a.H, h = bh % a.H;
     const int T = a.T, dh = a.dh;
-    const int q0 = a.q_begin + blockIdx.x * 128;
+    int q_begin = a.q_begin, q_end = a.q_end, split = 0;
+    unsigned rowblock = blockIdx.x;
+    if constexpr (SLOTS) {                                           // the clamps of slot_rows() in attention_f32.hip
+        const int64_t qb = min(max(a.slot_begin[b], (int64_t)0), (int64_t)T);
+        const int64_t qn = min(max(a.slot_count[b], (int64_t)0), min((int64_t)a.q_max, (int64_t)T - qb));
+        q_begin = (int)qb;
+        q_end = (int)(qb + qn);
+        if (a.nsplit > 1) { split = (int)(blockIdx.x % (unsigned)a.nsplit); rowblock = blockIdx.x / (unsigned)a.nsplit; }
+    }
+    const int q0 = q_begin + rowblock * 128;
     const int i0 = q0 + wave * 32;
-    const bool active = i0 < a.q_end;
+    const bool active = i0 < q_end;
+    // SLOTS: compact row il = i (query) - q_begin of slot b; rows [q_end - q_begin, q_max) are zeros
+    [[maybe_unused]] auto zero_row = [&]() {
+        if constexpr (SLOTS) {
+            const int il = i0 + li - q_begin;
+            if (il >= a.q_max) return;
+            float* orow = a.ctx + ((int64_t)b * a.q_max + il) * a.ldo + h * dh;
+#pragma unroll
+            for (int n = 0; n < 2; ++n)
+#pragma unroll
+                for (int gq = 0; gq < 4; ++gq) {
+                    const int dd = 32 * n + 8 * gq + 4 * hf;
+                    if (dd < dh) *reinterpret_cast<f32x4*>(orow + dd) = f32x4{0.f, 0.f, 0.f, 0.f};
+                }
+        }
+    };
+    if constexpr (SLOTS) {
+        if (q0 >= q_end) {                                           // no query row of this slot here: Q / K / V / lengths unread
+            if (a.nsplit == 1) zero_row();
+            return;
+        }
+    }
 
     int klen = T;
     bool uniform = false;
@@ -62,7 +105,15 @@ __global__ __launch_bounds__(256, 2) void relpos_attn_fwd_mfma16_kernel(const At
         if (L <= 0) uniform = true;
         else if (L < T) klen = (int)L;
     }
-    const int ntiles = (klen + 31) / 32;
+    // SLOTS: this workgroup's key tiles are [kt_begin, ntiles) of the slot's ntiles_all
+    const int ntiles_all = (klen + 31) / 32;
+    int kt_begin = 0, ntiles = ntiles_all;
+    if constexpr (SLOTS) {
+        const int tiles_per_split = (ntiles_all + a.nsplit - 1) / a.nsplit;
+        kt_begin = split * tiles_per_split;
+        ntiles = min(ntiles_all, kt_begin + tiles_per_split);
+        if (kt_begin >= ntiles) return;                              // an empty slice (short cache): uniform for the workgroup; the
+    }                                                                // merge counts the live slices and never reads this one
 
     const int64_t qkv_off = (int64_t)b * T * a.ld + h * dh;          // element offset of this (utterance, head) in q / k / v
     auto load4 = [&](const float* base, int64_t off) -> f32x4 {      // four consecutive q / k / v values at element offset `off`
@@ -119,8 +170,9 @@ __global__ __launch_bounds__(256, 2) void relpos_attn_fwd_mfma16_kernel(const At
         }
     };
 
-    {   // prologue: ring rows [jlo, jlo+127] of tile 0 (the top 32 rows arrive with prefetch(0))
-        const int jlo = T - 1 - q0 - 128;
+    {   // prologue: ring rows [jlo, jlo+127] of the first tile (the top 32 rows arrive with its prefetch); a key slice starts
+        // its ring at its own first tile
+        const int jlo = T - 1 - q0 - 128 + 32 * kt_begin;
 #pragma unroll
         for (int p = 0; p < 8; ++p) {
             const int r = srow + 16 * p;
@@ -131,9 +183,9 @@ __global__ __launch_bounds__(256, 2) void relpos_attn_fwd_mfma16_kernel(const At
             *reinterpret_cast<x4*>(Pr + slot * KROWH + sch * 4) = Lowp<T16>::cvt4(val);
         }
     }
-    prefetch(0);
-    commit(0);
-    if (ntiles > 1) prefetch(1);
+    prefetch(kt_begin);
+    commit(kt_begin);
+    if (kt_begin + 1 < ntiles) prefetch(kt_begin + 1);
     __syncthreads();
 
     // ---- (Q+u)^T, (Q+v)^T as MFMA B operands: lane (query li, half hf) holds dims 16s + 8hf + {0..7} at step s
@@ -194,14 +246,14 @@ __global__ __launch_bounds__(256, 2) void relpos_attn_fwd_mfma16_kernel(const At
     };
     float skp[16];
     if (active) {                                                   // first key tile: its band tile 1 explicitly
-        spill_band(band(T - 1 - i0 + 31, 1));
+        spill_band(band(T - 1 - i0 + 32 * kt_begin + 31, 1));
         skew_reads(skp);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
     }
-    __syncthreads();                                                // every wave has read its band-1 rows: commit(1) may replace them
+    __syncthreads();                                                // every wave has read its band-1 rows: the next commit may replace them
 
-    for (int kt = 0; kt < ntiles; ++kt) {
+    for (int kt = kt_begin; kt < ntiles; ++kt) {
         const int k0 = kt * 32;
         const T16* Ks = Ksb + (kt & 1) * 32 * KROWH;
         const T16* Vt = Vtb + (kt & 1) * 32 * VROWH;
@@ -258,7 +310,7 @@ __global__ __launch_bounds__(256, 2) void relpos_attn_fwd_mfma16_kernel(const At
             psum += __shfl_xor(psum, 32, 64);
             lrow = lrow * alpha + psum;
             mrow = mnew;
-            if (a.drop_p > 0.f) {
+            if (!SLOTS && a.drop_p > 0.f) {
                 const float inv_keep = 1.0f / (1.0f - a.drop_p);
                 const unsigned long long rowbase = ((unsigned long long)bh * T + (unsigned)(i0 + li)) * (unsigned long long)T;
 #pragma unroll
@@ -297,9 +349,16 @@ __global__ __launch_bounds__(256, 2) void relpos_attn_fwd_mfma16_kernel(const At
         if (kt + 1 < ntiles) __syncthreads();                       // one barrier per key tile
     }
 
-    if (active && i0 + li < a.q_end) {
+    if (active && i0 + li < q_end) {
         const float inv = 1.0f / lrow;
         float* orow = a.ctx + ((int64_t)b * T + i0 + li) * a.ldo + h * dh;
+        if constexpr (SLOTS) {
+            const int il = i0 + li - q_begin;
+            orow = a.nsplit > 1 ? a.part_ctx + (((int64_t)split * a.B + b) * a.q_max + il) * a.ldo + h * dh
+                                : a.ctx + ((int64_t)b * a.q_max + il) * a.ldo + h * dh;
+            if (a.nsplit > 1 && hf == 0)
+                a.part_lse[(((int64_t)split * a.B + b) * a.H + h) * a.q_max + il] = mrow * 0.69314718055994530942f + logf(lrow);
+        }
 #pragma unroll
         for (int n = 0; n < 2; ++n)
 #pragma unroll
@@ -307,13 +366,15 @@ __global__ __launch_bounds__(256, 2) void relpos_attn_fwd_mfma16_kernel(const At
                 const int dd = 32 * n + 8 * gq + 4 * hf;
                 if (dd < dh) {
                     f32x4 out = {o[n][4 * gq] * inv, o[n][4 * gq + 1] * inv, o[n][4 * gq + 2] * inv, o[n][4 * gq + 3] * inv};
-                    if (a.ctx16)
+                    if (!SLOTS && a.ctx16)
                         *reinterpret_cast<typename Lowp<T16>::x4*>(reinterpret_cast<T16*>(a.ctx) + ((int64_t)b * T + i0 + li) * a.ldo + h * dh + dd) =
                             Lowp<T16>::cvt4(out);
                     else *reinterpret_cast<f32x4*>(orow + dd) = out;
                 }
             }
-        if (a.lse && hf == 0) a.lse[((int64_t)b * a.H + h) * T + i0 + li] = mrow * 0.69314718055994530942f + logf(lrow);
+        if (!SLOTS && a.lse && hf == 0) a.lse[((int64_t)b * a.H + h) * T + i0 + li] = mrow * 0.69314718055994530942f + logf(lrow);
+    } else if constexpr (SLOTS) {
+        if (a.nsplit == 1) zero_row();
     }
 }
 
@@ -380,4 +441,47 @@ extern "C" int cfm_relpos_attention_io16_mfma16_f32(int prec, const void* q, con
     return attn16_launch(prec, static_cast<const float*>(q), static_cast<const float*>(k), static_cast<const float*>(v), ld, pos, ldp, u,
                          vbias, lengths_or_null, ctx, ctx_is_16bit ? 1 : 0, ldo, nullptr, B, T, H, dh, 0.f, 0, stream,
                          qkv_is_16bit ? 1 : 0);
+}
+
+// Independent streams under autocast (conformer_amd/slots.py with dtype=): the 16-bit form of cfm_relpos_attention_slots_f32.  q / k / v
+// are the fp32 cache (rounded to `prec` where they enter a product) or, qkv_is_16bit, a cache stored in `prec` (ld in elements,
+// ld % 8 == 0); ctx is the COMPACT fp32 (B, q_max, ldo).  The three device arrays are clamped in the kernel; nsplit > 1 divides every
+// slot's key tiles as the fp32 entry does and shares its workspace layout and its merge kernel.
+extern "C" int cfm_relpos_attention_slots_mfma16_f32(int prec, const void* q, const void* k, const void* v, int qkv_is_16bit, int64_t ld,
+                                                     const float* pos, int64_t ldp, const float* u, const float* vbias,
+                                                     const int64_t* q_begin, const int64_t* q_count, const int64_t* lengths,
+                                                     float* ctx, int64_t ldo, int B, int T, int H, int dh, int q_max, int nsplit,
+                                                     float* workspace_or_null, cfm_stream_t stream) {
+    CFM_REQUIRE(q && k && v && pos && u && vbias && q_begin && q_count && lengths && ctx, CFM_ERR_NULL);
+    CFM_REQUIRE(B > 0 && T > 0 && H > 0 && dh > 0 && (dh & 3) == 0, CFM_ERR_BAD_SHAPE);
+    CFM_REQUIRE((ld & 3) == 0 && (ldp & 3) == 0 && (ldo & 3) == 0 && ldo >= (int64_t)H * dh, CFM_ERR_BAD_SHAPE);
+    CFM_REQUIRE(!qkv_is_16bit || (ld & 7) == 0, CFM_ERR_BAD_SHAPE);
+    CFM_REQUIRE(dh <= 64, CFM_ERR_UNSUPPORTED);
+    CFM_REQUIRE(prec == CFM_PREC_BF16 || prec == CFM_PREC_FP16, CFM_ERR_UNSUPPORTED);
+    CFM_REQUIRE(CFM_ALIGNED16(q) && CFM_ALIGNED16(k) && CFM_ALIGNED16(v) && CFM_ALIGNED16(pos) && CFM_ALIGNED16(u) &&
+                CFM_ALIGNED16(vbias) && CFM_ALIGNED16(ctx) && CFM_ALIGNED16(workspace_or_null), CFM_ERR_ALIGN);
+    CFM_REQUIRE((int64_t)B * H <= 65535 && T < (1 << 28), CFM_ERR_UNSUPPORTED);
+    CFM_REQUIRE(q_max >= 1 && q_max <= T, CFM_ERR_BAD_SHAPE);
+    CFM_REQUIRE(nsplit >= 1 && nsplit <= 16 && (nsplit == 1 || (workspace_or_null && ldo == (int64_t)H * dh)), CFM_ERR_BAD_SHAPE);
+    Slot16Args a{};
+    static_cast<Attn16Args&>(a) = Attn16Args{static_cast<const float*>(q), static_cast<const float*>(k), static_cast<const float*>(v), ld,
+                                             pos, ldp, u, vbias, lengths, ctx, ldo, nullptr, 0, qkv_is_16bit ? 1 : 0, B, T, H, dh,
+                                             1.0f / sqrtf((float)dh), 0.f, 0, 0, q_max};
+    a.slot_begin = q_begin;
+    a.slot_count = q_count;
+    a.q_max = q_max;
+    a.nsplit = nsplit;
+    a.part_ctx = nsplit > 1 ? workspace_or_null : nullptr;
+    a.part_lse = nsplit > 1 ? workspace_or_null + (int64_t)nsplit * B * q_max * ldo : nullptr;
+    const dim3 grid((unsigned)((q_max + 127) / 128) * nsplit, (unsigned)(B * H)), block(256);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (prec == CFM_PREC_BF16) {
+        if (qkv_is_16bit) hipLaunchKernelGGL((relpos_attn_fwd_mfma16_kernel<__bf16, true, true>), grid, block, 0, s, a);
+        else hipLaunchKernelGGL((relpos_attn_fwd_mfma16_kernel<__bf16, false, true>), grid, block, 0, s, a);
+    } else {
+        if (qkv_is_16bit) hipLaunchKernelGGL((relpos_attn_fwd_mfma16_kernel<_Float16, true, true>), grid, block, 0, s, a);
+        else hipLaunchKernelGGL((relpos_attn_fwd_mfma16_kernel<_Float16, false, true>), grid, block, 0, s, a);
+    }
+    if (nsplit > 1) cfm_attention_slots_merge(q_begin, q_count, lengths, ctx, ldo, B, T, H, dh, q_max, nsplit, workspace_or_null, s);
+    return cfm_launch_status();
 }

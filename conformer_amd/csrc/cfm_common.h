@@ -16,6 +16,10 @@ static inline int cfm_launch_status() {
     return hipGetLastError() == hipSuccess ? CFM_OK : CFM_ERR_LAUNCH;
 }
 
+// attention_f32.hip: the merge kernel of the slots key split, shared with the 16-bit slots entry of attention_mfma16.hip
+void cfm_attention_slots_merge(const int64_t* q_begin, const int64_t* q_count, const int64_t* lengths, float* ctx, int64_t ldo,
+                               int B, int T, int H, int dh, int q_max, int nsplit, float* workspace, hipStream_t s);
+
 // full-wave (64 lane) butterfly reductions
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

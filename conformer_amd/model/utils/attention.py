@@ -77,8 +77,10 @@ class RelativeMultiHeadAttention(nn.Module):
 
     def fused(self, x, pos_table, lengths, residual: Optional[torch.Tensor] = None,
               pos_projected: Optional[torch.Tensor] = None, ln_fold=None, emit_stats: bool = False, stream=None):
-        # the context only feeds out_proj; a stream's q|k|v rows go into its fp32 K/V cache: not for_gemm (fused_chain: (1))
-        ctx = self.context(x, pos_table, lengths, pos_projected, for_gemm=stream is None, ln_fold=ln_fold, stream=stream)
+        # the context only feeds out_proj; a stream's q|k|v rows go into its K/V cache: not for_gemm (fused_chain: (1)) unless the
+        # stream keeps that cache in the 16-bit type (stream.qkv16: the projection writes 16-bit rows, as whole-utterance inference)
+        ctx = self.context(x, pos_table, lengths, pos_projected, for_gemm=stream is None or stream.qkv16, ln_fold=ln_fold,
+                           stream=stream)
         if residual is None:
             if emit_stats:
                 return ops.linear(ctx, self.out_proj.weight, self.out_proj.bias, emit_stats=True)

@@ -53,7 +53,8 @@ class ConformerBlock(nn.Module):
         context (instead of pos_proj + ops.relpos_attention: pos_table, lengths and pos_projected are unused), and
         stream.depthwise(conv, g) runs the depthwise kernel over a window that reaches back into its carried GLU rows.
         Deliberately, a stream launches what streaming launched when it had a chain of its own: (1) the LayerNorms in front of
-        the q|k|v projection and of pointwise_conv_1, and that projection, are not `for_gemm` (the K/V caches are fp32); (2) the
+        the q|k|v projection and of pointwise_conv_1, and that projection, are not `for_gemm` (the K/V caches are fp32; a stream
+        whose cache is 16-bit, stream.qkv16, has that one projection write 16-bit rows); (2) the
         depthwise kernel is not `for_gemm`; (3) FFN2 does not absorb the closing LayerNorm, and the row chains, which have no
         seam, are not taken.  Whether a stream should adopt the one-kernel FFN2 + closing LayerNorm at large row counts is an
         open question that needs a measurement."""

@@ -580,6 +580,17 @@ def _key_split(B: int, n_heads: int, q_rows: int, T: int, keys_hint: Optional[in
     return max(1, min(16, tiles // 8, -(-1024 // blocks)))
 
 
+def _key_split16(B: int, n_heads: int, q_rows: int, T: int, keys_hint: Optional[int]) -> int:
+    """Key slices of the 16-bit slots kernel: >= 8 key tiles of 32 per slice, as _key_split, but aiming at 512 workgroups -- one
+    residency of the chip (256 CUs x 2 workgroups of 60 KB LDS).  Its key tile costs about half the fp32 kernel's, so a second
+    round of workgroups buys nothing and every further slice pays its own 128-row positional prologue and a wider merge: at
+    512 row-block workgroups (S = 32, H = 8, 160 rows) any split is slower, at 128 four slices are the fastest and eight lose
+    (DESIGN.md "Independent streams under autocast" has the table)."""
+    tiles = ((T if keys_hint is None else min(int(keys_hint), T)) + 31) // 32
+    blocks = B * n_heads * ((q_rows + 127) // 128)
+    return max(1, min(16, tiles // 8, 512 // blocks))
+
+
 def relpos_attention(qkv: torch.Tensor, pos: torch.Tensor, u: torch.Tensor, v: torch.Tensor,
                      lengths: Optional[torch.Tensor], n_heads: int, for_gemm: bool = False) -> torch.Tensor:
     """qkv: (B,T,3d) fused projections [q|k|v]; pos: (2T-1,d) projected table; returns ctx (B,T,d).
@@ -666,16 +677,24 @@ def relpos_attention_slots(qkv: torch.Tensor, pos: torch.Tensor, u: torch.Tensor
     keys < lengths[b] into the COMPACT rows ctx[b, :q_count[b]] of ctx (S,q_max,d); rows q_count[b]..q_max-1 are zeros.
     q_begin, q_count, lengths: (S) int64 device tensors (nothing synchronises; the kernel clamps them, so no value makes an
     out-of-bounds access).  keys_hint: host-side upper bound of `lengths` (default Tmax) choosing the key split as
-    relpos_attention_rows does.  fp32 only (the 16-bit form is not implemented: refused under autocast)."""
-    qkv = _req(qkv, "qkv"); u = _req(u, "content_bias"); v = _req(v, "position_bias")
+    relpos_attention_rows does.  Under torch.autocast the 16-bit form runs (cfm_relpos_attention_slots_mfma16_f32, with the same
+    key split): qkv is the fp32 cache or a cache stored in the autocast type (d % 8 == 0); ctx stays fp32."""
+    u = _req(u, "content_bias"); v = _req(v, "position_bias")
+    prec = mfma16_prec()
+    q16 = isinstance(qkv, torch.Tensor) and qkv.dtype in (torch.bfloat16, torch.float16)
+    if q16:
+        if not prec or qkv.dtype != _DT16[prec]:
+            raise _lib.ConformerHipError(f"relpos_attention_slots: a {qkv.dtype} cache needs torch.autocast of that type")
+        if not (qkv.is_cuda and qkv.dim() == 3 and qkv.shape[-1] % 24 == 0):
+            raise _lib.ConformerHipError("relpos_attention_slots: 16-bit qkv: expected a (S,T,3d) HIP tensor with d % 8 == 0")
+    else:
+        qkv = _req(qkv, "qkv")
     B, T, d3 = qkv.shape
     d = d3 // 3
     q_max = int(q_max)
     _req_pos(pos, T, d)
     if not qkv.is_contiguous():
         raise _lib.ConformerHipError("relpos_attention_slots: qkv (S,T,3d) must be a contiguous cache buffer")
-    if mfma16_prec() != PREC_F32:
-        raise _lib.ConformerHipError("relpos_attention_slots: fp32 only (no 16-bit form under autocast)")
     if ctx is None:
         ctx = torch.empty(B, q_max, d, device=qkv.device, dtype=torch.float32)
     ctx = _req(ctx, "ctx")
@@ -687,9 +706,18 @@ def relpos_attention_slots(qkv: torch.Tensor, pos: torch.Tensor, u: torch.Tensor
     for name, t in (("lengths", lengths), ("q_begin", q_begin), ("q_count", q_count)):
         if t.shape != (B,) or not t.is_contiguous():
             raise _lib.ConformerHipError(f"relpos_attention_slots: {name} must be a contiguous ({B},) int64 tensor")
-    nsplit = _key_split(B, n_heads, q_max, T, keys_hint)
+    nsplit = (_key_split16 if prec else _key_split)(B, n_heads, q_max, T, keys_hint)
     ws = torch.empty(nsplit * B * q_max * (d + n_heads), device=qkv.device, dtype=torch.float32) if nsplit > 1 else None
     base = qkv.data_ptr()
+    if prec != PREC_F32:
+        esz = 2 if q16 else 4
+        st = _lib.load().cfm_relpos_attention_slots_mfma16_f32(prec, base, base + esz * d, base + 2 * esz * d, int(q16), d3,
+                                                               pos.data_ptr(), pos.stride(0), u.data_ptr(), v.data_ptr(),
+                                                               q_begin.data_ptr(), q_count.data_ptr(), lengths.data_ptr(),
+                                                               ctx.data_ptr(), d, B, T, n_heads, d // n_heads, q_max, nsplit,
+                                                               _p(ws), _stream())
+        _lib.check(st, "cfm_relpos_attention_slots_mfma16_f32")
+        return ctx
     st = _lib.load().cfm_relpos_attention_slots_f32(base, base + 4 * d, base + 8 * d, d3, pos.data_ptr(), pos.stride(0),
                                                     u.data_ptr(), v.data_ptr(), q_begin.data_ptr(), q_count.data_ptr(),
                                                     lengths.data_ptr(), ctx.data_ptr(), d, B, T, n_heads, d // n_heads, q_max,

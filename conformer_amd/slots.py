@@ -14,10 +14,17 @@ nothing synchronises except partial_text() and close().
 
 Semantics: for each slot, the sequence of frame counts it received from open to close is that utterance's own chunking, and
 its results are those of a one-utterance StreamingEncoder / StreamingTranscriber fed the same chunks (to GEMM rounding: the
-compact rows may tile differently).  fp32 inference only.
+compact rows may tile differently).  Inference only.
+
+Precision is fixed at construction (`dtype=`): None / torch.float32 is the fp32 object; torch.bfloat16 / torch.float16 runs every
+step inside its own torch.autocast of that type, keeps the per-layer K/V caches in it (the q|k|v GEMM writes the 16-bit rows the
+attention core would round to anyway: half the cache bytes, no change in arithmetic) and attends with the 16-bit slots kernel
+(cfm_relpos_attention_slots_mfma16_f32).  The depthwise state, the mel tail, the LSTM state and what step() returns stay fp32.  A
+stream must not change precision between chunks, so ambient autocast of another type is refused.
 """
 from __future__ import annotations
 
+import contextlib
 from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -45,9 +52,30 @@ def slot_plan(tails: Sequence[int], frames: Sequence[int]) -> Tuple[List[int], L
     return ks, new_tails
 
 
-def _refuse_autocast(who: str) -> None:
-    if torch.is_autocast_enabled("cuda"):
-        raise RuntimeError(f"{who}: fp32 only; leave torch.autocast before stepping (the 16-bit slot path does not exist)")
+def _slot_dtype(who: str, dtype: Optional[torch.dtype]) -> Optional[torch.dtype]:
+    """The `dtype=` keyword of the slot objects: None for the fp32 object, else the 16-bit type of every stream it carries."""
+    if dtype is None or dtype == torch.float32:
+        return None
+    if dtype not in (torch.bfloat16, torch.float16):
+        raise ValueError(f"{who}: dtype must be None, torch.float32, torch.bfloat16 or torch.float16, got {dtype}")
+    return dtype
+
+
+def _refuse_autocast(who: str, dtype: Optional[torch.dtype] = None) -> None:
+    """The precision of a stream was fixed when the object was made: an fp32 object refuses any ambient autocast, a 16-bit
+    object the other 16-bit type."""
+    if not torch.is_autocast_enabled("cuda"):
+        return
+    if dtype is None:
+        raise RuntimeError(f"{who}: this object is fp32; leave torch.autocast before stepping (construct it with dtype= for the "
+                           "16-bit slot path)")
+    if torch.get_autocast_dtype("cuda") != dtype:
+        raise RuntimeError(f"{who}: this object's streams are {dtype}; it cannot step under torch.autocast of "
+                           f"{torch.get_autocast_dtype('cuda')}")
+
+
+def _autocast(dtype: Optional[torch.dtype]):
+    return contextlib.nullcontext() if dtype is None else torch.autocast("cuda", dtype=dtype)
 
 
 class _Step:
@@ -96,6 +124,7 @@ class _SlotStream:
 
     def __init__(self, st: "SlotStreamingEncoder", cur: _Step) -> None:
         self.st, self.cur, self.i = st, cur, 0
+        self.qkv16 = st.dtype is not None          # the q|k|v GEMM writes the rows in the 16-bit type of the cache (for_gemm)
 
     def attend(self, a, qkv_new: torch.Tensor) -> torch.Tensor:
         """Append every slot's new Q|K|V rows at its own cache row and return the compact context (S, k_max, d)."""
@@ -118,9 +147,17 @@ class _SlotStream:
 class SlotStreamingEncoder(StreamingEncoder):
     """The chunked encoder of StreamingEncoder over `slots` independent streams of at most max_mel_frames mel frames each.
     open(s) starts a stream in a free slot, step(mel, frames) feeds every slot its own number of new frames, close(s) frees the
-    slot.  Returns compact rows: step -> ((S, k_max, d), k) with slot b's new encoder frames in rows 0 .. k[b]-1."""
+    slot.  Returns compact rows: step -> ((S, k_max, d), k) with slot b's new encoder frames in rows 0 .. k[b]-1.
+    dtype: None / torch.float32, or torch.bfloat16 / torch.float16 -- the precision of every stream of this object (module
+    docstring): 16-bit K/V caches (d % 8 == 0), every step under its own autocast."""
 
-    def __init__(self, encoder: Encoder, slots: int, max_mel_frames: int) -> None:
+    def __init__(self, encoder: Encoder, slots: int, max_mel_frames: int, dtype: Optional[torch.dtype] = None) -> None:
+        self.dtype = _slot_dtype("SlotStreamingEncoder", dtype)
+        if self.dtype is not None:
+            d = encoder.linear.out_features
+            if d % 8:
+                raise ValueError(f"SlotStreamingEncoder: a {self.dtype} K/V cache needs d % 8 == 0, got d = {d}")
+            self.cache_dtype = self.dtype                                  # (read by StreamingEncoder.__init__: no fp32 caches)
         super().__init__(encoder, slots, max_mel_frames, graphs=False)
         self.ctx = None                                                    # the compact context is allocated per step
         self.S = self.B
@@ -160,7 +197,7 @@ class SlotStreamingEncoder(StreamingEncoder):
         """Check a step's arguments against the slots (raises before anything is enqueued): (mel, k, new tails)."""
         if self.enc.training:
             raise RuntimeError("SlotStreamingEncoder: put the encoder in eval() mode (running BatchNorm statistics, no dropout)")
-        _refuse_autocast("SlotStreamingEncoder")
+        _refuse_autocast("SlotStreamingEncoder", self.dtype)
         x = ops._req(mel_chunk, "mel_chunk")
         if x.dim() != 3 or x.shape[0] != self.S:
             raise ValueError(f"mel_chunk: expected ({self.S}, n_mel, Tc), got {tuple(x.shape)}")
@@ -185,6 +222,17 @@ class SlotStreamingEncoder(StreamingEncoder):
         x, ks, new_tails = self.plan(mel_chunk, frames)
         self._follow_weights()
         frames = [int(f) for f in frames]
+        with _autocast(self.dtype):
+            out, cur = self._step_device(x, frames, ks)
+        for b in range(self.S):
+            self.n0[b] += ks[b]
+            self.mel_seen[b] += frames[b]
+        self.tails = new_tails
+        self.last_step = cur
+        return out, ks
+
+    def _step_device(self, x: torch.Tensor, frames: List[int], ks: List[int]) -> Tuple[torch.Tensor, _Step]:
+        """The device work of one step (under the object's autocast, if it has one)."""
         S, Tc, dev = self.S, x.shape[2], x.device
         k_max = max(ks)
         if self.mel_tail_buf is None:
@@ -202,12 +250,7 @@ class SlotStreamingEncoder(StreamingEncoder):
             mel = torch.gather(src, 2, cur.mel_index(pos, Tc)[:, None, :].expand(S, n_mel, W))
             out = self._encode(mel, _SlotStream(self, cur), lambda: self.lengths.copy_(cur.lengths))
         self.mel_tail_buf.copy_(new_tail)
-        for b in range(S):
-            self.n0[b] += ks[b]
-            self.mel_seen[b] += frames[b]
-        self.tails = new_tails
-        self.last_step = cur
-        return out, ks
+        return out, cur
 
 
 class SlotTranscriber:
@@ -216,13 +259,16 @@ class SlotTranscriber:
 
         tr.open(s); logits, k = tr.step(mel, frames); tr.partial_text(); text = tr.close(s)
 
-    close(s) returns what decoder(...) returns on that slot's concatenated logits.  fp32 eval mode only."""
+    close(s) returns what decoder(...) returns on that slot's concatenated logits.  Eval mode only; dtype: as
+    SlotStreamingEncoder (the LSTM state and the logits stay fp32; the search consumes the logits the step returned)."""
 
-    def __init__(self, model, decoder: BeamCTCDecoder, slots: int, max_mel_frames: int) -> None:
+    def __init__(self, model, decoder: BeamCTCDecoder, slots: int, max_mel_frames: int,
+                 dtype: Optional[torch.dtype] = None) -> None:
+        self.dtype = _slot_dtype("SlotTranscriber", dtype)
         self.device, self.state = lstm_state(model, "SlotTranscriber", int(slots))
         self.model = model
         self.decoder = decoder
-        self.encoder = SlotStreamingEncoder(model.encoder, slots, max_mel_frames)
+        self.encoder = SlotStreamingEncoder(model.encoder, slots, max_mel_frames, dtype=self.dtype)
         self.S = self.encoder.S
         f = decoder._fusion(self.device)
         self.beam = beam_ctc_stream_init(self.S, self.encoder.t_max, self.device, beam_width=decoder.beam_width,
@@ -256,14 +302,15 @@ class SlotTranscriber:
         its own rows.  Nothing synchronises with the host."""
         if self.model.training:
             raise RuntimeError("SlotTranscriber: the model is in training mode; put it back in eval()")
-        _refuse_autocast("SlotTranscriber")
+        _refuse_autocast("SlotTranscriber", self.dtype)
         n0 = list(self.encoder.n0)
         enc, ks = self.encoder.step(mel_chunk, frames)
         k_max = max(ks)
         if k_max == 0:
             return enc.new_empty(self.S, 0, self.model.decoder.linear.out_features), ks
         k_dev = self.encoder.last_step.k
-        logits = decode_frames(self.model, self.state, enc, k_dev)
+        with _autocast(self.dtype):
+            logits = decode_frames(self.model, self.state, enc, k_dev)
         d = self.decoder
         # the search's bound: the furthest slot after this step, less the chunk (each slot's own frames_b + k_b <= T_max
         # holds: the encoder refused more than max_mel_frames)

@@ -38,6 +38,8 @@ class _Stream:
     """The stream context of ConformerBlock.fused_chain for one lockstep chunk step: the chunk is rows n0 .. n0+k-1 of every
     utterance; `i` is the layer the chain is in (StreamingEncoder._encode sets it)."""
 
+    qkv16 = False              # the K/V cache is fp32: the q|k|v GEMM writes fp32 rows (slots.py: a 16-bit cache sets it)
+
     def __init__(self, st: "StreamingEncoder", n0: int, k: int) -> None:
         self.st, self.n0, self.k, self.i = st, n0, k, 0
 
@@ -75,6 +77,8 @@ class StreamingEncoder:
     K/V rows were computed with the old weights, so a caller who changes weights mid-utterance calls reset().
     check_weights=False (frozen-weight serving) skips that per-step walk over the encoder's tensors."""
 
+    cache_dtype = torch.float32        # storage type of the K/V caches (SlotStreamingEncoder(dtype=...) sets a 16-bit one)
+
     def __init__(self, encoder: Encoder, batch: int, max_mel_frames: int, graphs: bool = False, check_weights: bool = True) -> None:
         if encoder.training:
             raise RuntimeError("StreamingEncoder: put the encoder in eval() mode (running BatchNorm statistics, no dropout)")
@@ -89,7 +93,7 @@ class StreamingEncoder:
             raise ValueError("max_mel_frames must give at least one encoder frame (>= 7)")
         dev = p.device
         layers = list(encoder.layers)
-        self.qkv = [torch.zeros(self.B, self.t_max, 3 * self.d, device=dev, dtype=torch.float32) for _ in layers]
+        self.qkv = [torch.zeros(self.B, self.t_max, 3 * self.d, device=dev, dtype=self.cache_dtype) for _ in layers]
         self.ctx = torch.zeros(self.B, self.t_max, self.d, device=dev, dtype=torch.float32)     # scratch shared by the layers
         halves = [(l.conv.deepwise_conv.kernel_size[0] - 1) // 2 for l in layers]     # the carried GLU rows: (K-1)/2 per layer
         self.conv_state = [torch.zeros(self.B, h, self.d, device=dev, dtype=torch.float32) for h in halves]

@@ -728,6 +728,15 @@ int cfm_relpos_attention_slots_f32(const float* q, const float* k, const float* 
                                    const int64_t* lengths, float* ctx, int64_t ldo, int B, int T, int H, int dh, int q_max,
                                    int nsplit, float* workspace_or_null, cfm_stream_t stream);
 
+/*      the same under torch.autocast (prec = CFM_PREC_BF16 / CFM_PREC_FP16) on the 16-bit matrix pipe: q / k / v are the fp32 cache
+ *      (rounded to `prec` where they enter a product) or, qkv_is_16bit, a cache stored in `prec` (ld in elements, ld % 8 == 0); the
+ *      compact ctx stays fp32.  Clamps, q_max, nsplit and the workspace as cfm_relpos_attention_slots_f32 (the same merge kernel). */
+int cfm_relpos_attention_slots_mfma16_f32(int prec, const void* q, const void* k, const void* v, int qkv_is_16bit, int64_t ld,
+                                          const float* pos, int64_t ldp, const float* u, const float* vbias,
+                                          const int64_t* q_begin, const int64_t* q_count, const int64_t* lengths, float* ctx,
+                                          int64_t ldo, int B, int T, int H, int dh, int q_max, int nsplit,
+                                          float* workspace_or_null, cfm_stream_t stream);
+
 /* diagnostics only: cfm_relpos_attention_fwd_f32 + s_memrealtime stamps of one wave (trace: 16*ceil(T/32) uint64) */
 int cfm_debug_attention_trace_f32(const float* q, const float* k, const float* v, int64_t ld, const float* pos,
                                   int64_t ldp, const float* u, const float* vbias, const int64_t* lengths_or_null,

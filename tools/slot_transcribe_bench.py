@@ -8,10 +8,14 @@ beam search at W=100 with and without a synthetic word n-gram LM.
   lockstep   every slot opened together and given the same frames: StreamingTranscriber (eager) and SlotTranscriber at the
              same S and chunk, per-step latency side by side
   attention  relpos_attention_slots against relpos_attention_rows with identical offsets in every slot (the new rows of a
-             640-frame chunk against caches of growing length), device events after warm-up
+             640-frame chunk against caches of growing length), device events after warm-up; with --dtype bf16 / fp16 both run
+             under that autocast: the 16-bit slots kernel on the fp32 and on the 16-bit cache, with the key split of
+             ops._key_split and with keys_hint=1 (no split), against the 16-bit rows kernel (which has no split)
 
-Random weights, so the logits are not peaky: the beam search runs at its random-logit cost (the upper end)."""
+--dtype bf16 | fp16: the slot objects are built with dtype= (16-bit K/V caches, every step under their own autocast) and the
+lockstep StreamingTranscriber steps under torch.autocast of that type.  Random weights, so the logits are not peaky: the beam search runs at its random-logit cost (the upper end)."""
 import argparse
+import contextlib
 import json
 import os
 import random
@@ -68,17 +72,26 @@ def staggered(tr, S, chunk, steps, max_mel, seed, dev):
             "mel_frames": frames_total}
 
 
-def lockstep(m, dec, S, chunk, steps, dev):
+def _autocast(dt):
+    return contextlib.nullcontext() if dt is None else torch.autocast("cuda", dtype=dt)
+
+
+def lockstep(m, dec, S, chunk, steps, dev, dt=None):
     x = torch.randn(S, 80, chunk, device=dev)
     out = {}
+
+    def stream_step(tr):
+        with _autocast(dt):
+            return tr.step(x)
+
     for name in ("streaming", "slots"):
         best = None
         for _ in range(2):                                     # the first pass warms up (packs, tables)
             if name == "streaming":
                 tr = StreamingTranscriber(m, dec, S, chunk * steps)
-                run = lambda: tr.step(x)                        # noqa: E731
+                run = lambda: stream_step(tr)                   # noqa: E731
             else:
-                tr = SlotTranscriber(m, dec, S, chunk * steps)
+                tr = SlotTranscriber(m, dec, S, chunk * steps, dtype=dt)
                 for s in range(S):
                     tr.open(s)
                 run = lambda: tr.step(x, [chunk] * S)           # noqa: E731
@@ -98,34 +111,40 @@ def lockstep(m, dec, S, chunk, steps, dev):
     return out
 
 
-def attention_ab(S, dev, iters=50):
+def attention_ab(S, dev, dt=None, iters=50):
     H, dh, t_max, k = 8, 64, 4999, 160                          # Conformer-L, T = 20000 mel frames, a 640-frame chunk
     d = H * dh
     qkv = torch.randn(S, t_max, 3 * d, device=dev)
+    qkv16 = None if dt is None else qkv.to(dt)
     pos = torch.randn(2 * t_max - 1, d, device=dev) * 0.5
     u, v = torch.randn(d, device=dev) * 0.3, torch.randn(d, device=dev) * 0.3
     ctx = torch.empty(S, t_max, d, device=dev)
     rows = []
-    for n0 in (640, 2400, t_max - k):
+    for n0 in (640, 2400, t_max - k) if dt is None else (0, 640, 1440, 2400, t_max - k):
         L = torch.full((S,), n0 + k, device=dev, dtype=torch.int64)
         qb = torch.full((S,), n0, device=dev, dtype=torch.int64)
         qc = torch.full((S,), k, device=dev, dtype=torch.int64)
         cc = torch.empty(S, k, d, device=dev)
+        slots = lambda cache, hint: ops.relpos_attention_slots(cache, pos, u, v, L, H, qb, qc, k, cc, keys_hint=hint)  # noqa: E731
         fns = {"rows": lambda: ops.relpos_attention_rows(qkv, pos, u, v, L, H, n0, k, ctx, keys_hint=n0 + k),
-               "slots": lambda: ops.relpos_attention_slots(qkv, pos, u, v, L, H, qb, qc, k, cc, keys_hint=n0 + k)}
-        res = {"keys": n0 + k}
-        for _ in range(2):                                      # alternate the two, keep each one's best
-            for name, fn in fns.items():
-                for _ in range(5):
-                    fn()
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                for _ in range(iters):
-                    fn()
-                e1.record()
-                torch.cuda.synchronize()
-                us = e0.elapsed_time(e1) * 1e3 / iters
-                res[name + "_us"] = min(res.get(name + "_us", us), us)
+               "slots": lambda: slots(qkv, n0 + k)}
+        res = {"keys": n0 + k, "nsplit": (ops._key_split if dt is None else ops._key_split16)(S, H, k, t_max, n0 + k)}
+        if dt is not None:
+            fns.update({"slots_nosplit": lambda: slots(qkv, 1), "slots_cache16": lambda: slots(qkv16, n0 + k),
+                        "slots_cache16_nosplit": lambda: slots(qkv16, 1)})
+        with _autocast(dt):
+            for _ in range(2):                                  # alternate them, keep each one's best
+                for name, fn in fns.items():
+                    for _ in range(5):
+                        fn()
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    for _ in range(iters):
+                        fn()
+                    e1.record()
+                    torch.cuda.synchronize()
+                    us = e0.elapsed_time(e1) * 1e3 / iters
+                    res[name + "_us"] = min(res.get(name + "_us", us), us)
         res["slots_over_rows"] = res["slots_us"] / res["rows_us"]
         rows.append(res)
     return rows
@@ -141,16 +160,24 @@ def main():
     ap.add_argument("--max-mel", type=int, default=20000)
     ap.add_argument("--lm-ngrams", type=int, default=100000, help="n-grams per order (2..5) of the synthetic ARPA model")
     ap.add_argument("--no-lm", action="store_true")
+    ap.add_argument("--dtype", choices=["fp32", "bf16", "fp16"], default="fp32",
+                    help="precision of the slot objects (dtype=) and autocast type of the lockstep and attention comparisons")
+    ap.add_argument("--attention-only", action="store_true", help="only the attention section")
     args = ap.parse_args()
+    dt = {"fp32": None, "bf16": torch.bfloat16, "fp16": torch.float16}[args.dtype]
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
     vocab = ["<pad>"] + [chr(ord("a") + i) for i in range(26)] + ["'", "|", "<unk>"]
     m = Conformer(len(vocab), 80, 16, 512, 8, 31, 640, 1, 0.0).to(dev).eval()
     out = {"what": "independent streams (slots): Conformer-L, 640-frame chunks, beam W=100", "chunk": args.chunk,
-           "beam_width": args.beam, "runs": [], "attention_ab": {}}
+           "beam_width": args.beam, "dtype": args.dtype, "runs": [], "attention_ab": {}}
     with torch.no_grad():
         for S in args.slots:
-            out["attention_ab"][f"S{S}"] = attention_ab(S, dev)
+            out["attention_ab"][f"S{S}"] = attention_ab(S, dev, dt)
+            print(json.dumps({f"attention_ab S{S}": out["attention_ab"][f"S{S}"]}), file=sys.stderr, flush=True)
+    if args.attention_only:
+        print(json.dumps(out))
+        return
     with tempfile.TemporaryDirectory() as tmp:
         lms = [("no_lm", None)]
         if not args.no_lm:
@@ -160,14 +187,14 @@ def main():
         for name, lm in lms:
             dec = BeamCTCDecoder(vocab, blank_id=0, skip_ids=(len(vocab) - 1,), beam_width=args.beam, lm=lm)
             for S in args.slots:
-                tr = SlotTranscriber(m, dec, S, args.max_mel)
+                tr = SlotTranscriber(m, dec, S, args.max_mel, dtype=dt)
                 staggered(tr, S, args.chunk, 3, args.max_mel, 0, dev)          # warm-up
                 del tr
-                tr = SlotTranscriber(m, dec, S, args.max_mel)
+                tr = SlotTranscriber(m, dec, S, args.max_mel, dtype=dt)
                 run = {"decoder": name, "slots": S, "staggered": staggered(tr, S, args.chunk, args.steps, args.max_mel, 1, dev)}
                 del tr
                 torch.cuda.empty_cache()
-                run["lockstep"] = lockstep(m, dec, S, args.chunk, args.lockstep_steps, dev)
+                run["lockstep"] = lockstep(m, dec, S, args.chunk, args.lockstep_steps, dev, dt)
                 out["runs"].append(run)
                 print(json.dumps(run), file=sys.stderr, flush=True)
     print(json.dumps(out))

@@ -166,6 +166,8 @@ SIGNATURES = {
     "cfm_relpos_table_f32": (c_int, [_P, _P, _I, _I, _P]),
     "cfm_relpos_attention_fwd_f32": (c_int, [_P, _P, _P, _L, _P, _L, _P, _P, _P, _P, _L, _P, _I, _I, _I, _I, _P]),
     "cfm_dwconv_bn_swish_fwd_f32": (c_int, [_P, _P, _P, _P, _P, _P, _P, _F, _P, _I, _I, _I, _I, _P]),
+    "cfm_convmod_glu_dwconv_f32": (c_int, [_P, _L, _P, _I, _F, _P, _P, _P, _P, _P, _P, _P, _P, _P, _F, _P, _L, _I, _I, _I, _I, _P]),
+    "cfm_debug_convmod_variant": (c_int, [_I]),
     "cfm_subsample_conv1_relu_f32": (c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "cfm_pack_conv2_weight_f32": (c_int, [_P, _P, _I, _P]),
     "cfm_subsample_conv2_relu_f32": (c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),

@@ -4,7 +4,7 @@ Each of the four residual sub-layers ends in an MFMA GEMM whose epilogue applies
 (alpha = 1/2 for the two FFNs, block.py:19,25), so no stand-alone add/scale kernels run; the closing
 LayerNorm (block.py:27) is the wave-per-row kernel.  16 launches per block in total; 12 on the folded-LayerNorm
 inference path (fused_chain), 9 with the one-kernel feed-forward sub-layers (ops.ffn_fused: FFN2 also applies the closing
-LayerNorm).
+LayerNorm), 8 where the convolution module's GLU GEMM and depthwise kernel are one launch too (ops.convmod_glu_dwconv).
 """
 from typing import Optional
 

@@ -5,6 +5,8 @@ convolution.py:23,31 disappear:
     LN -> pointwise Conv1d(C->2C)+GLU as ONE MFMA GEMM with a GLU epilogue
        -> depthwise Conv1d(K)+BatchNorm1d(eval)+Swish as one register-sliding-window kernel
        -> pointwise Conv1d(C->C) GEMM (+ fused residual when called from ConformerBlock).
+On the folded-LayerNorm inference path the first two are ONE kernel where ops.convmod_fused_ok holds (ops.convmod_glu_dwconv: the
+depthwise conv runs out of LDS in the GLU GEMM's epilogue, same bits).
 ConvolutionSubsampling: conv1+ReLU writes a channel-last activation; conv2+ReLU is an implicit GEMM on the
 MFMA pipe over a re-laid-out (cached) weight; the (B,T',C*F') flattening order of convolution.py:51-52 is
 folded into a cached column permutation of the encoder's input Linear, so no permute copy runs on the
@@ -45,8 +47,9 @@ class ConvolutionModule(nn.Module):
     def fused(self, x: torch.Tensor, residual: Optional[torch.Tensor] = None, stats: Optional[torch.Tensor] = None,
               emit_stats: bool = False, stream=None):
         """stats / emit_stats: see FeedForwardModule.fused (the LayerNorm of convolution.py:22 folds into the pointwise_conv_1 +
-        GLU GEMM; eval-mode BatchNorm only).  stream: from ConformerBlock.fused_chain, which has refused gradients and
-        training-mode BatchNorm: stream.depthwise(self, g) stands in for depthwise_eval(g)."""
+        GLU GEMM; eval-mode BatchNorm only; with ops.convmod_fused_ok that GEMM and the depthwise kernel are one launch).
+        stream: from ConformerBlock.fused_chain, which has refused gradients and training-mode BatchNorm:
+        stream.depthwise(self, g) stands in for depthwise_eval(g)."""
         refuse_dropout(self, "ConvolutionModule")
         bn = self.batch_norm
         train_bn = bn.training or bn.running_mean is None      # nn.BatchNorm1d semantics: the BN sub-module's own flag
@@ -81,12 +84,20 @@ class ConvolutionModule(nn.Module):
             ln, pw1 = self.layer_norm, self.pointwise_conv_1
             wf, bf, cs = self._packs.get("ln_fold", (pw1.weight, pw1.bias, ln.weight, ln.bias),
                                          lambda: ops.fold_layernorm(pw1.weight, pw1.bias, ln.weight, ln.bias))
-            g = ops.linear_lnfold(x, stats, wf, bf, cs, ln.eps, glu=True)
+            dw = self.deepwise_conv
+            if stream is None and x.dim() == 3 and ops.convmod_fused_ok(x.shape[0], x.shape[1], x.shape[2], dw.weight.shape[-1]):
+                # the GLU GEMM and the depthwise kernel as one launch (same bits; the (B,T,C) GLU tensor never leaves the chip)
+                g = None
+                s = ops.convmod_glu_dwconv(x, stats, wf, bf, cs, ln.eps, dw.weight, dw.bias, bn.weight, bn.bias, bn.running_mean,
+                                           bn.running_var, bn.eps)
+            else:
+                g = ops.linear_lnfold(x, stats, wf, bf, cs, ln.eps, glu=True)
         else:
             h = ops.layernorm(x, self.layer_norm.weight, self.layer_norm.bias, self.layer_norm.eps, for_gemm=stream is None)
             g = ops.linear_glu(h, self.pointwise_conv_1.weight, self.pointwise_conv_1.bias)
         # a stream's window reaches back into its carried rows; neither its LayerNorm nor its depthwise kernel is for_gemm
-        s = self.depthwise_eval(g, for_gemm=True) if stream is None else stream.depthwise(self, g)
+        if g is not None:
+            s = self.depthwise_eval(g, for_gemm=True) if stream is None else stream.depthwise(self, g)
         if residual is None:
             if emit_stats:
                 return ops.linear(s, self.pointwise_conv_2.weight, self.pointwise_conv_2.bias, emit_stats=True)

@@ -749,6 +749,65 @@ def dwconv_bn_swish(g, w, b, bn_w, bn_b, bn_mean, bn_var, eps: float = 1e-5, for
     return y
 
 
+# ---- convolution module middle in one kernel (fp32 inference; csrc/convmod_fused_f32.hip) ---------------------------------------
+_CONVMOD_FUSED = __import__("os").environ.get("CONFORMER_AMD_CONVMOD_FUSED", "1") != "0"
+# lowest T / (256 * chunks) at which the fused kernel beat the two kernels in every round of tools/convmod_fused_ab.py (B = 32,
+# C = 512, K = 31; profiles/convmod_fused_ab.txt): it wins at 0.875 (T = 224) and above, loses at 0.75 (T = 192) and below
+_CONVMOD_MIN_ROW_EFF = 0.875
+
+
+def set_convmod_fused(on: bool) -> bool:
+    """Enable / disable the one-kernel pointwise_conv_1 + GLU + depthwise conv + BatchNorm + Swish of the folded-LayerNorm
+    inference path (default on; CONFORMER_AMD_CONVMOD_FUSED=0 disables).  Returns the previous setting.  Off = the GLU GEMM and
+    the depthwise kernel (two launches)."""
+    global _CONVMOD_FUSED
+    prev, _CONVMOD_FUSED = _CONVMOD_FUSED, bool(on)
+    return prev
+
+
+def convmod_chunks(T: int, K: int) -> int:
+    """Time chunks per utterance of the fused kernel: one 256-row GEMM tile up to 256 frames, then 256 - (K-1) output frames each."""
+    return 1 if T <= 256 else 1 + (T - 256 + (256 - K)) // (257 - K)
+
+
+def convmod_fused_ok(B: int, T: int, C: int, K: int) -> bool:
+    """Whether ConvolutionModule takes the fused kernel.  One 256-row workgroup per (utterance, chunk, 64 channels), one per CU:
+    the workgroups must fill whole rounds of the chip's 256 CUs to >= 90 % (the rule of ffn_fused_ok), and the rows a tile
+    computes must mostly be frames of the utterance: T / (256 * chunks) >= the measured break-even."""
+    if not (_CONVMOD_FUSED and ln_fold_ok(C) and C % 64 == 0 and K in (3, 7, 15, 31) and B > 0 and T > 0):
+        return False
+    chunks = convmod_chunks(T, K)
+    blocks = B * chunks * (C // 64)
+    rounds = (blocks + 255) // 256
+    return blocks >= 0.9 * 256 * rounds and T >= _CONVMOD_MIN_ROW_EFF * 256 * chunks
+
+
+def convmod_glu_dwconv(x, stats, wf, bf, cs, ln_eps: float, w, b, bn_w, bn_b, bn_mean, bn_var, bn_eps: float = 1e-5) -> torch.Tensor:
+    """Swish(BN_eval(depthwise(GLU(LN(x) @ W1.T + b1)))) of x (B, T, C) in one kernel: linear_lnfold(..., glu=True) followed by
+    dwconv_bn_swish, bit for bit.  stats / wf / bf / cs: as linear_lnfold; w (C, 1, K), b and the BatchNorm tensors: as
+    dwconv_bn_swish.  Called directly, the shape predicate convmod_fused_ok does not apply (any B, T)."""
+    x = _req(x, "x"); stats = _req(stats, "ln_stats"); wf = _req(wf, "Wf"); bf = _req(bf, "bias_f"); cs = _req(cs, "colsum")
+    w = _req(w, "dw weight"); b = _req(b, "dw bias")
+    if x.dim() != 3:
+        raise _lib.ConformerHipError(f"convmod_glu_dwconv: x must be (B, T, C), got {tuple(x.shape)}")
+    B, T, C = x.shape
+    K = w.shape[-1]
+    if (tuple(wf.shape) != (2 * C, C) or stats.dim() != 3 or stats.shape[0] != B * T or stats.shape[2] != 2 or w.numel() != C * K
+            or bf.numel() != 2 * C or cs.numel() != 2 * C or b.numel() != C):
+        raise _lib.ConformerHipError(f"convmod_glu_dwconv: x{tuple(x.shape)}, Wf{tuple(wf.shape)}, stats{tuple(stats.shape)}, "
+                                     f"dw weight{tuple(w.shape)} do not match")
+    bn = [_req(t, n) for t, n in ((bn_w, "bn_w"), (bn_b, "bn_b"), (bn_mean, "bn_mean"), (bn_var, "bn_var"))]
+    if any(t.numel() != C for t in bn):
+        raise _lib.ConformerHipError(f"convmod_glu_dwconv: the BatchNorm tensors must have {C} values")
+    y = torch.empty(B, T, C, device=x.device, dtype=torch.float32)
+    if B * T:
+        _lib.check(_lib.load().cfm_convmod_glu_dwconv_f32(x.data_ptr(), C, stats.data_ptr(), stats.shape[1], float(ln_eps), wf.data_ptr(),
+                                                          bf.data_ptr(), cs.data_ptr(), w.data_ptr(), b.data_ptr(), bn[0].data_ptr(),
+                                                          bn[1].data_ptr(), bn[2].data_ptr(), bn[3].data_ptr(), float(bn_eps),
+                                                          y.data_ptr(), C, B, T, C, K, _stream()), "cfm_convmod_glu_dwconv_f32")
+    return y
+
+
 def pack_conv2_weight(w2: torch.Tensor) -> torch.Tensor:
     w2 = _req(w2, "conv_2.weight")
     C = w2.shape[0]

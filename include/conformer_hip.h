@@ -170,6 +170,22 @@ int cfm_dwconv_bn_swish_fwd_f32(const float* g, const float* w, const float* bia
                                 const float* bn_mean, const float* bn_var, float bn_eps,
                                 float* y, int B, int T, int C, int K, cfm_stream_t stream);
 
+/* ---- convolution module middle in one kernel (inference, fp32 MFMA; convolution.py:22-28):
+ *        y = Swish(BN_eval(depthwise_K(GLU(LN(x).W1^T + b1))))
+ *      = cfm_gemm_lnfold_f32(epi 3) followed by cfm_dwconv_bn_swish_fwd_f32, bit for bit, without the (B,T,C) GLU tensor: one
+ *      512-thread workgroup per (utterance, time chunk, 64 channels) runs the 256 x 128 GLU GEMM tile and then the depthwise
+ *      conv of its 64 channels out of LDS.  x: (B*T, C) rows at ldx, ln_stats / ln_parts / ln_eps / Wf (2C, C) / bias_f (2C) /
+ *      colsum (2C) as cfm_gemm_lnfold_f32; dw_w (C,K), dw_b and the BatchNorm arguments as cfm_dwconv_bn_swish_fwd_f32;
+ *      y: (B*T, C) rows at ldy.  An utterance longer than 256 frames is cut into 1 + ceil((T - 256) / (256 - (K-1))) chunks
+ *      of 256 - (K-1) output frames that recompute (K-1)/2 GLU rows either side.
+ *      K in {3, 7, 15, 31} and C in {64, 128, 256, 512} (CFM_ERR_UNSUPPORTED otherwise); ln_parts in {1, 2, 4, 8, 16},
+ *      C % ln_parts == 0; ldx % 4 == 0; 16-byte aligned x / Wf / bias_f / colsum / ln_stats (CFM_ERR_ALIGN). */
+int cfm_convmod_glu_dwconv_f32(const float* x, int64_t ldx, const float* ln_stats, int ln_parts, float ln_eps,
+                               const float* Wf, const float* bias_f, const float* colsum, const float* dw_w,
+                               const float* dw_b, const float* bn_w, const float* bn_b, const float* bn_mean,
+                               const float* bn_var, float bn_eps, float* y, int64_t ldy, int B, int T, int C, int K,
+                               cfm_stream_t stream);
+
 /* ---- convolution subsampling stem (ConvolutionSubsampling.forward, convolution.py:42-57)
  *      x: (B, F, T) log-mel (mel axis is the conv "height").  T1=(T-1)/2, F1=(F-1)/2, T2=(T1-1)/2,
  *      F2=(F1-1)/2 (integer division).
@@ -450,6 +466,7 @@ int cfm_debug_gemm_cfg_f32(int cfg, const float* A, const float* W, const float*
                            cfm_stream_t stream);
 int cfm_debug_ffn_trace(void* trace_or_null, int per_slice);   /* 128 x uint64 s_memrealtime stamps of cfm_ffn_fused_f32 (wave 0 of blocks 0 / 128), or NULL */
 int cfm_debug_ffn_variant(int v);               /* 0 | 1 = main loop without weight loads (wrong results: the pure MFMA rate) */
+int cfm_debug_convmod_variant(int v);           /* 0 | 1 = cfm_convmod_glu_dwconv_f32 without its depthwise stage (wrong results: the GEMM alone) */
 int cfm_debug_ffn_layout(int pad_f4, int rotate); /* pad between packed tiles (16-byte units; < 0 keeps it) and the per-workgroup slice rotation: re-pack after changing */
 int cfm_debug_set_conv2_bk(int bk);   /* K-tile of cfm_subsample_conv2_relu_f32: 16 (default) | 32; 0 / 1: K walked in storage order / channel-chunk-major (default); 100: tile by shape (default) | 101: the 128x128 tile only | 102: the 256x256 tile for every row where C % 256 == 0; returns the previous K-tile */
 /*      cfg + 16: bias epilogue; cfg + 32: swish epilogue; cfg + 64: K-tile 32 (a staged row = one whole 128-byte line;

@@ -42,6 +42,14 @@ __device__ __forceinline__ float rcp_fast(float x) { return __builtin_amdgcn_rcp
 __device__ __forceinline__ float sigmoidf_acc(float x) { return rcp_fast(1.0f + exp_fast(-x)); }
 __device__ __forceinline__ float swishf_acc(float x) { return x * sigmoidf_acc(x); }
 
+// An fp32 result on its way into a 16-bit store, kept as an fp32 value of its own.  Without it the compiler folds the last fp32
+// multiply into the conversion to fp16 (v_fma_mixlo_f16: the product rounded once, straight to fp16), and the 16-bit-output form of
+// a kernel no longer writes what its fp32 twin writes, rounded -- which is what "identical results" promises every consumer.
+__device__ __forceinline__ float f32_value(float v) {
+    asm("" : "+v"(v));
+    return v;
+}
+
 // Dropout keep-factor for element `idx` of a tensor under (seed): a counter-based generator, so the backward regenerates exactly
 // the forward's mask from (seed, idx) with no stored mask.  ONE splitmix64 finaliser serves the FOUR elements of an aligned
 // group (idx >> 2); element idx & 3 takes 16 of its 64 bits: a GEMM epilogue's four consecutive columns cost one hash (the

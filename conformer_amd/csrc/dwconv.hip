@@ -2,6 +2,8 @@
 // HBM-bound.  Lanes run along channels (coalesced rows of the (B,T,C) tensor); each wave owns TT
 // consecutive frames of 64 channels and slides over the TT+K-1 input frames with the K taps and the TT
 // accumulators held in registers (both loops fully unrolled => static register indexing).
+#include <type_traits>
+
 #include "cfm_common.h"
 
 namespace {
@@ -41,7 +43,11 @@ __global__ __launch_bounds__(256) void dwconv_bn_swish_kernel(
 #pragma unroll
     for (int o = 0; o < TT; ++o) {
         const int t = t0 + o;
-        if (t < T && cok) yb[(int64_t)t * C] = (TOUT)swishf_acc((acc[o] - mu) * inv * ga + be);
+        if (t < T && cok) {
+            const float v = swishf_acc((acc[o] - mu) * inv * ga + be);
+            if constexpr (std::is_same_v<TOUT, _Float16>) yb[(int64_t)t * C] = (TOUT)f32_value(v);   // (fp16 only: see f32_value)
+            else yb[(int64_t)t * C] = (TOUT)v;
+        }
     }
 }
 

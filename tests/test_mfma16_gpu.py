@@ -224,7 +224,8 @@ def test_mfma16_attention_forward(dev, B, T, H, dh, lengths, dt16):
 @pytest.mark.parametrize("dt16", DT)
 def test_mfma16_stem_inference_keeps_16bit_activations(dev, dt16):
     """Inference under autocast: conv1 writes h1 in the 16-bit type, conv2 consumes it and writes a 16-bit h2 that the
-    input Linear consumes -- against the fp32 path (operand + one output rounding)."""
+    input Linear consumes -- against the fp32 path (operand + one output rounding).
+    (Every tile and operand form of conv2 against float64 at 2e-5: tests/test_property_stem16_gpu.py.)"""
     from conformer_amd import ops
     g = torch.Generator().manual_seed(3)
     C = 64

@@ -430,7 +430,8 @@ def test_stem_train_refuses_channels_off_16(ops):
        prec=st.sampled_from([1, 2]), seed=st.integers(0, 10 ** 6))
 @example(B=1, Fm=7, T=7, C=64, prec=1, seed=0).via("F2 = T2 = 1 under bf16")
 def test_stem_bwd_16bit_any_shape(ops, B, Fm, T, C, prec, seed):
-    """16-bit class-gather stem backward (16-bit h1, dz2, dh1) under bf16 and fp16."""
+    """16-bit class-gather stem backward (16-bit h1, dz2, dh1) under bf16 and fp16.
+    (h2 and dh1 themselves, per window and on every block tile, against float64 at 2e-5: tests/test_property_stem16_gpu.py.)"""
     _check_stem(ops, B, Fm, _stem_budget(B, Fm, T, C), C, prec, seed)
 
 

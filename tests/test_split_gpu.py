@@ -73,6 +73,7 @@ def test_split_gemm_error_vs_native_fp32(dev, shape, mode, bound):
 
 
 def test_split_glu_residual_and_conv2(dev):
+    """(The split-plane conv2 on its 128x64 and 128x128 tiles, K = 2304: tests/test_property_stem16_gpu.py.)"""
     from conformer_amd import ops
     a, w, b = _data(1000, 1024, 512, dev, seed=3)
     res = torch.randn(1000, 512, device=dev)

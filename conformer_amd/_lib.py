@@ -1,186 +1,64 @@
-"""ctypes binding of libconformer_hip.so (the C ABI declared in include/conformer_hip.h).
+"""ctypes binding of libconformer_hip.so, derived from the one statement of its C ABI: include/conformer_hip.h.
 
-The product path has NO fallback: if the shared library is missing, or a call returns a negative status,
-an exception is raised.  Nothing here imports the CPU oracle.
+The header is parsed once at import (no torch needed): SIGNATURES and PARAMS from its declarations, CONSTANTS from its `#define
+CFM_*` lines and `enum cfm_status`.  A type the parser does not know, or a `cfm_*(` it cannot read, is an error, never a guess.
+There is NO fallback: a missing header or library, or a non-zero status, raises.  Nothing here imports the CPU oracle.
 """
 from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import c_char_p, c_float, c_int, c_int64, c_uint64, c_void_p
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # (CONFORMER_AMD_LIB: A/B a differently built library from tools/*, development only)
 LIB_PATH = os.environ.get("CONFORMER_AMD_LIB") or os.path.join(_HERE, "lib", "libconformer_hip.so")
-
-_P, _I, _L, _F, _U = c_void_p, c_int, c_int64, c_float, c_uint64
-ABI_VERSION = 4        # CFM_ABI_VERSION of include/conformer_hip.h (checked in load())
-
-# name -> (restype, argtypes).  Mirrors include/conformer_hip.h one to one (checked by tests/test_abi.py).
-SIGNATURES = {
-    "cfm_version": (c_int, []),
-    "cfm_abi_version": (c_int, []),
-    "cfm_gemm_bias_stats_f32": (c_int, [_P, _P, _P, _P, _P, _L, _I, _I, _L, _L, _P]),
-    "cfm_gemm_bias_residual_stats_f32": (c_int, [_P, _P, _P, _P, _F, _P, _P, _L, _I, _I, _L, _L, _L, _P]),
-    "cfm_gemm_splitk_f32": (c_int, [_I, _P, _P, _P, _P, _F, _P, _P, _I, _L, _I, _I, _L, _L, _L, _P]),
-    "cfm_gemm_lnfold_f32": (c_int, [_I, _P, _P, _I, _F, _P, _P, _P, _P, _L, _I, _I, _L, _L, _P]),
-    "cfm_layernorm_fwd_stats_f32": (c_int, [_P, _P, _P, _P, _P, _L, _I, _F, _P]),
-    "cfm_ffn_pack_elems": (ctypes.c_int64, [_I, _I]),
-    "cfm_ffn_pack_f32": (c_int, [_P, _P, _P, _I, _I, _P]),
-    "cfm_rowgemm_pack_f32": (c_int, [_P, _P, _I, _I, _I, _P]),
-    "cfm_rowchain_f32": (c_int, [_I, _I, _I, _I, _P, _L, _P, _P, _P, _L, _P, _L, _P, _I, _F, _P, _P, _P, _P, _F, _I, _P, _L, _P, _P, _P, _F,
-                                 _P, _P, _P, _F, _P, _L, _L, _I, _P]),
-    "cfm_ffn_tile_stride_f4": (ctypes.c_int64, [_I]),
-    "cfm_ffn_rotate": (c_int, []),
-    "cfm_ffn_fused_f32": (c_int, [_P, _L, _P, _I, _F, _P, _P, _P, _P, _F, _P, _L, _I, _P, _P, _P, _F, _L, _I, _I, _P]),
-    "cfm_strerror": (c_char_p, [_I]),
-    "cfm_device_check": (c_int, []),
-    "cfm_subsampled_length": (c_int64, [_L]),
-    "cfm_subsampled_lengths_i64": (c_int, [_P, _P, _I, _P]),
-    "cfm_layernorm_fwd_f32": (c_int, [_P, _P, _P, _P, _P, _P, _L, _I, _F, _P]),
-    "cfm_gemm_bias_f32": (c_int, [_P, _P, _P, _P, _L, _I, _I, _L, _L, _P]),
-    "cfm_gemm_bias_swish_f32": (c_int, [_P, _P, _P, _P, _L, _I, _I, _L, _L, _P]),
-    "cfm_gemm_bias_relu_f32": (c_int, [_P, _P, _P, _P, _L, _I, _I, _L, _L, _P]),
-    "cfm_gemm_bias_glu_f32": (c_int, [_P, _P, _P, _P, _L, _I, _I, _L, _L, _P]),
-    "cfm_gemm_bias_residual_f32": (c_int, [_P, _P, _P, _P, _F, _P, _L, _I, _I, _L, _L, _L, _P]),
-    "cfm_gemm_mfma16_f32": (c_int, [_I, _I, _P, _I, _P, _I, _P, _P, _F, _P, _I, _P, _I, _L, _I, _I, _L, _L, _L, _F, _U, _P]),
-    "cfm_layernorm_fwd_out16_f32": (c_int, [_I, _P, _P, _P, _P, _P, _P, _L, _I, _F, _P]),
-    "cfm_cast16_f32": (c_int, [_I, _P, _P, _L, _P]),
-    "cfm_cast16_multi_f32": (c_int, [_I, _P, _I, _P]),
-    "cfm_relpos_attention_mfma16_f32": (c_int, [_I, _P, _P, _P, _L, _P, _L, _P, _P, _P, _P, _L, _P, _I, _I, _I, _I, _F, _U, _P]),
-    "cfm_relpos_attention_rows_mfma16_f32": (c_int, [_I, _P, _P, _P, _L, _P, _L, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _P]),
-    "cfm_relpos_attention_io16_mfma16_f32": (c_int, [_I, _P, _P, _P, _I, _L, _P, _L, _P, _P, _P, _P, _I, _L, _I, _I, _I, _I, _P]),
-    "cfm_subsample_conv2_relu_mfma16_f32": (c_int, [_I, _P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _I, _P]),
-    "cfm_subsample_conv1_relu_out16_f32": (c_int, [_I, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
-    "cfm_gemm_bwd_batched_mfma16_f32": (c_int, [_I, _P, _I, _L, _P, _I, _I, _L, _P, _I, _L, _F, _P, _L, _I, _I, _I, _L, _I, _I, _I, _I,
-                                                _L, _L, _L, _L, _L, _L, _F, _U, _I, _P]),
-    "cfm_subsample_conv2_bwd_weight_mfma16_f32": (c_int, [_I, _P, _P, _P, _I, _I, _I, _I, _P]),
-    "cfm_subsample_conv2_bwd_input_mfma16_f32": (c_int, [_I, _P, _P, _P, _I, _I, _I, _I, _P]),
-    "cfm_subsample_conv2_rowtab_elems": (ctypes.c_int64, [_I, _I, _I]),
-    "cfm_subsample_conv2_bwd_weight_h16_mfma16_f32": (c_int, [_I, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
-    "cfm_relu_bwd_out16_f32": (c_int, [_I, _P, _P, _P, _L, _P]),
-    "cfm_dwconv_bn_swish_fwd_out16_f32": (c_int, [_I, _P, _P, _P, _P, _P, _P, _P, _F, _P, _I, _I, _I, _I, _P]),
-    "cfm_glu_bwd_out16_f32": (c_int, [_I, _P, _P, _P, _L, _I, _P]),
-    "cfm_subsample_conv2_bwd_input_fwdkernel_mfma16_f32": (c_int, [_I, _P, _I, _P, _P, _P, _I, _I, _I, _I, _P]),
-    "cfm_subsample_conv2_bwd_input_fwdkernel_out16_mfma16_f32": (c_int, [_I, _P, _I, _P, _P, _P, _I, _I, _I, _I, _P]),
-    "cfm_subsample_conv1_bwd_d16_f32": (c_int, [_I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
-    "cfm_reflect_pad_f32": (c_int, [_P, _P, _I, _L, _I, _L, _P]),
-    "cfm_power_mel_log_f32": (c_int, [_P, _L, _P, _P, _I, _I, _I, _I, _F, _P]),
-    "cfm_power_mel_log_mfma_f32": (c_int, [_P, _L, _P, _P, _I, _I, _I, _I, _I, _F, _P]),
-    "cfm_dft_frames_f32": (c_int, [_P, _P, _P, _L, _I, _I, _I, _P]),
-    "cfm_specaugment_apply_f32": (c_int, [_P, _I, _I, _I, _P, _I, _F, _P]),
-    "cfm_gemm_bias_swish_save_f32": (c_int, [_P, _P, _P, _P, _P, _L, _I, _I, _L, _L, _P]),
-    "cfm_gemm_bwd_f32": (c_int, [_P, _I, _L, _P, _I, _L, _P, _L, _F, _P, _L, _I, _I, _L, _I, _P]),
-    "cfm_gemm_bwd_batched_f32": (c_int, [_P, _I, _L, _P, _I, _L, _P, _L, _F, _P, _L, _I, _I, _L, _I, _I, _I, _I,
-                                         _L, _L, _L, _L, _L, _L, _F, _U, _P]),
-    "cfm_gemm_train_f32": (c_int, [_I, _P, _P, _P, _P, _F, _P, _P, _L, _I, _I, _L, _L, _L, _F, _U, _P]),
-    "cfm_relpos_attention_train_f32": (c_int, [_P, _P, _P, _L, _P, _L, _P, _P, _P, _P, _L, _P, _I, _I, _I, _I, _F, _U, _P]),
-    "cfm_dropout_f32": (c_int, [_P, _P, _L, _F, _U, _P]),
-    "cfm_dropout_out16_f32": (c_int, [_I, _P, _P, _L, _F, _U, _P]),
-    "cfm_layernorm_bwd_dx_f32": (c_int, [_P, _P, _P, _P, _P, _P, _P, _L, _I, _P]),
-    "cfm_layernorm_bwd_params_f32": (c_int, [_P, _P, _P, _P, _P, _P, _L, _I, _P]),
-    "cfm_layernorm_bwd_f32": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _P, ctypes.c_size_t, _P]),
-    "cfm_layernorm_bwd_workspace_bytes": (ctypes.c_size_t, [_L, _I]),
-    "cfm_colsum_f32": (c_int, [_P, _L, _L, _I, _F, _P, _P]),
-    "cfm_glu_fwd_f32": (c_int, [_P, _P, _L, _I, _P]),
-    "cfm_glu_bwd_f32": (c_int, [_P, _P, _P, _L, _I, _P]),
-    "cfm_dwconv_bn_swish_bwd_f32": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _F, _I, _P, _P, _P, _P, _P, _P,
-                                            _I, _I, _I, _I, _P]),
-    "cfm_dwconv_bn_stats_workspace_bytes": (ctypes.c_size_t, [_I, _I, _I]),
-    "cfm_dwconv_bn_stats_f32": (c_int, [_P, _P, _P, _P, _P, _P, _P, _F, _I, _I, _I, _I, _P, ctypes.c_size_t, _P]),
-    "cfm_debug_attention_bwd_trace_f32": (c_int, [_P]),
-    "cfm_debug_attention_bwd_trace_mfma16": (c_int, [_P]),
-    "cfm_debug_gemm_mfma16_trace": (c_int, [_P]),
-    "cfm_debug_gemm_mfma16_force_tile": (c_int, [_I]),
-    "cfm_debug_gemm_last_tile": (c_int, [_I, _P]),
-    "cfm_relpos_attention_bwd_mfma16_f32": (c_int, [_I, _P, _P, _P, _L, _P, _L, _P, _P, _P, _P, _P, _L, _P, _P, _P, _P, _L, _P, _L,
-                                                    _P, _P, _I, _I, _I, _I, _F, _U, _P]),
-    "cfm_relpos_attention_bwd_f32": (c_int, [_P, _P, _P, _L, _P, _L, _P, _P, _P, _P, _P, _L, _P, _P, _P, _P, _L, _P, _L, _P, _P,
-                                             _I, _I, _I, _I, _F, _U, _I, _P]),
-    "cfm_relu_bwd_f32": (c_int, [_P, _P, _P, _L, _P]),
-    "cfm_subsample_conv2_bwd_weight_f32": (c_int, [_P, _P, _P, _I, _I, _I, _I, _P]),
-    "cfm_pack_conv2_weight_t_f32": (c_int, [_P, _P, _I, _P]),
-    "cfm_subsample_conv2_bwd_input_f32": (c_int, [_P, _P, _P, _I, _I, _I, _I, _P]),
-    "cfm_subsample_conv1_bwd_f32": (c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
-    "cfm_adam_step_f32": (c_int, [_P, _I, _F, _F, _F, _F, _F, _F, _P]),
-    "cfm_greedy_ctc_decode_f32": (c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
-    "cfm_ctc_beam_workspace_bytes": (ctypes.c_size_t, [_I, _I, _I, _I]),
-    "cfm_ctc_beam_decode_f32": (c_int, [_P, _P, _I, _I, _I, _I, _I, _I, _F, _F, _I, _P, ctypes.c_size_t, _P, _P, _P, _P, _P]),
-    "cfm_ngram_lm_pack_bytes": (ctypes.c_size_t, [_I, _P, _I, _L, _I, _L]),
-    "cfm_ngram_lm_pack": (c_int, [_I, _P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, ctypes.c_size_t]),
-    "cfm_ngram_lm_score_f64": (c_int, [_P, _P, _P, _I, _I, _P, _P]),
-    "cfm_ctc_beam_lm_workspace_bytes": (ctypes.c_size_t, [_I, _I, _I, _I]),
-    "cfm_ctc_beam_lm_decode_f32": (c_int, [_P, _P, _I, _I, _I, _I, _I, _I, _F, _F, _I, _P, ctypes.c_double, ctypes.c_double,
-                                           ctypes.c_double, _I, _P, ctypes.c_size_t, _P, _P, _P, _P, _P, _P]),
-    "cfm_hotword_pack_bytes": (ctypes.c_size_t, [_I, _L, _I, _L, _I, _L]),
-    "cfm_hotword_pack": (c_int, [_I, _P, _P, _I, _P, _P, _I, _P, _P, _P, _P, ctypes.c_size_t]),
-    "cfm_hotword_count": (c_int, [_P, _P, _P, _I, ctypes.c_double, _P, _P, _P]),
-    "cfm_ctc_beam_hw_workspace_bytes": (ctypes.c_size_t, [_I, _I, _I, _I]),
-    "cfm_ctc_beam_hw_decode_f32": (c_int, [_P, _P, _I, _I, _I, _I, _I, _I, _F, _F, _I, _P, ctypes.c_double, ctypes.c_double,
-                                           ctypes.c_double, _I, _P, ctypes.c_double, _P, ctypes.c_size_t, _P, _P, _P, _P, _P,
-                                           _P]),
-    "cfm_ctc_beam_stream_state_bytes": (ctypes.c_size_t, [_I, _I, _I, _I, _I, _I]),
-    "cfm_ctc_beam_stream_init": (c_int, [_I, _I, _I, _I, _P, _I, _P, _P, ctypes.c_size_t, _P]),
-    "cfm_ctc_beam_stream_step_f32": (c_int, [_P, _P, _I, _I, _I, _I, _I, _I, _F, _F, _I, _P, ctypes.c_double, ctypes.c_double,
-                                             ctypes.c_double, _I, _P, ctypes.c_double, _P, ctypes.c_size_t, _I, _I, _P, _P, _P,
-                                             _P, _P, _P]),
-    "cfm_ctc_beam_stream_finish_f32": (c_int, [_I, _I, _I, _I, _P, ctypes.c_double, ctypes.c_double, ctypes.c_double, _I, _P,
-                                               ctypes.c_double, _P, ctypes.c_size_t, _I, _P, _P, _P, _P, _P, _P]),
-    "cfm_ctc_beam_stream_reset_slots": (c_int, [_I, _I, _I, _I, _P, _I, _P, _P, _I, _P, ctypes.c_size_t, _P]),
-    "cfm_lstm_fwd_carry_f32": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
-    "cfm_lstm_fwd_frag_carry_f32": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
-    "cfm_lstm_fwd_mfma16_carry_f32": (c_int, [_I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
-    "cfm_lstm_fwd_f32": (c_int, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
-    "cfm_lstm_fwd_frag_f32": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
-    "cfm_lstm_bwd_frag_f32": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
-    "cfm_debug_lstm_trace": (c_int, [_P]),
-    "cfm_debug_dw16_trace": (c_int, [_P]),
-    "cfm_linear_bwd_weight_mfma16_f32": (c_int, [_I, _P, _I, _L, _P, _I, _L, _P, _L, _P, _I, _I, _L, _F, _P]),
-    "cfm_lstm_fwd_mfma16_f32": (c_int, [_I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
-    "cfm_lstm_bwd_mfma16_f32": (c_int, [_I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
-    "cfm_lstm_bwd_f32": (c_int, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
-    "cfm_swish_bn_eval_f32": (c_int, [_P, _P, _P, _P, _P, _F, _P, _L, _I, _P]),
-    "cfm_swish_bn_stats_f32": (c_int, [_P, _P, _P, _P, _P, _F, _L, _I, _P]),
-    "cfm_swish_bn_bwd_f32": (c_int, [_P, _P, _P, _P, _P, _F, _I, _P, _P, _P, _L, _I, _P]),
-    "cfm_split_pack_elems": (ctypes.c_int64, [_I, _I, _I]),
-    "cfm_split_pack_bf16_f32": (c_int, [_I, _P, _P, _I, _I, _P]),
-    "cfm_gemm_split_bf16_f32": (c_int, [_I, _I, _P, _P, _P, _P, _F, _P, _L, _I, _I, _L, _L, _L, _P]),
-    "cfm_subsample_conv2_relu_split_bf16_f32": (c_int, [_I, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
-    "cfm_ctc_workspace_floats": (ctypes.c_int64, [_I, _I, _I]),
-    "cfm_ctc_loss_fwd_f32": (c_int, [_P, _P, _P, _L, _L, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
-    "cfm_ctc_loss_bwd_f32": (c_int, [_P, _P, _P, _L, _L, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
-    "cfm_ctc_align_workspace_bytes": (ctypes.c_size_t, [_I, _I, _I]),
-    "cfm_ctc_align_f32": (c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, ctypes.c_size_t, _P, _P, _P, _P, _P, _P, _P, _P]),
-    "cfm_relpos_attention_rows_f32": (c_int, [_P, _P, _P, _L, _P, _L, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
-    "cfm_relpos_attention_slots_f32": (c_int, [_P, _P, _P, _L, _P, _L, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _P, _P]),
-    "cfm_relpos_attention_slots_mfma16_f32": (c_int, [_I, _P, _P, _P, _I, _L, _P, _L, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _I,
-                                                      _P, _P]),
-    "cfm_debug_attention_trace_f32": (c_int, [_P, _P, _P, _L, _P, _L, _P, _P, _P, _P, _L, _I, _I, _I, _I, _P, _P]),
-    "cfm_debug_set_bwd_tile": (c_int, [_I]),
-    "cfm_debug_set_attention_waves": (c_int, [_I]),
-    "cfm_debug_gemm_cfg_f32": (c_int, [_I, _P, _P, _P, _P, _F, _P, _L, _I, _I, _P, _P]),
-    "cfm_debug_set_conv2_bk": (c_int, [_I]),
-    "cfm_debug_ffn_trace": (c_int, [_P, _I]),
-    "cfm_debug_ffn_variant": (c_int, [_I]),
-    "cfm_debug_ffn_layout": (c_int, [_I, _I]),
-    "cfm_relpos_table_f32": (c_int, [_P, _P, _I, _I, _P]),
-    "cfm_relpos_attention_fwd_f32": (c_int, [_P, _P, _P, _L, _P, _L, _P, _P, _P, _P, _L, _P, _I, _I, _I, _I, _P]),
-    "cfm_dwconv_bn_swish_fwd_f32": (c_int, [_P, _P, _P, _P, _P, _P, _P, _F, _P, _I, _I, _I, _I, _P]),
-    "cfm_convmod_glu_dwconv_f32": (c_int, [_P, _L, _P, _I, _F, _P, _P, _P, _P, _P, _P, _P, _P, _P, _F, _P, _L, _I, _I, _I, _I, _P]),
-    "cfm_debug_convmod_variant": (c_int, [_I]),
-    "cfm_subsample_conv1_relu_f32": (c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
-    "cfm_pack_conv2_weight_f32": (c_int, [_P, _P, _I, _P]),
-    "cfm_subsample_conv2_relu_f32": (c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
-    "cfm_pack_linear_weight_f32": (c_int, [_P, _P, _I, _I, _I, _P]),
-    "cfm_conv2_wino_plane_elems": (c_int64, [_I, _I, _I, _I]),
-    "cfm_pack_conv2_wino_weight_f32": (c_int, [_P, _P, _I, _P]),
-    "cfm_subsample_conv2_wino_relu_f32": (c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
-}
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "conformer_hip.h")
+_CTYPES = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "float": ctypes.c_float, "double": ctypes.c_double,
+           "uint64_t": ctypes.c_uint64, "size_t": ctypes.c_size_t, "cfm_stream_t": ctypes.c_void_p}
+_DECL = re.compile(r"^[ \t]*((?:const\s+)?\w+[\s*]+?)(cfm_\w+)\s*\(([^()]*)\)\s*;", re.M)
 
 
 class ConformerHipError(RuntimeError):
     pass
 
+
+def parse_header(text: str):
+    """(SIGNATURES, PARAMS, CONSTANTS) of the header `text`: name -> (restype, [argtypes]), name -> [parameter names]
+    (`arg<i>` where the header names none), and every `#define CFM_X <integer>` / `CFM_X = <integer>` enum member -> int."""
+    def ctype(words, where):            # words: the type without `const`, every `*` glued to the word before it
+        if words[-1].endswith("*"):
+            return ctypes.c_void_p
+        if " ".join(words) not in _CTYPES:
+            raise ConformerHipError(f"{HEADER_PATH}: {where}: no ctypes mapping for the type `{' '.join(words)}`")
+        return _CTYPES[" ".join(words)]
+
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    signatures, params = {}, {}
+    for ret, name, plist in _DECL.findall(text):
+        ret = re.sub(r"\s*\*\s*", "* ", ret).split()
+        restype = ctypes.c_char_p if ret == ["const", "char*"] else ctype(ret, name)
+        argtypes, names = [], []
+        for i, p in enumerate([] if plist.strip() in ("", "void") else plist.split(",")):
+            words = [w for w in re.sub(r"\s*\*\s*", "* ", p).split() if w != "const"]
+            named = len(words) > 1 and re.fullmatch(r"[A-Za-z_]\w*", words[-1]) is not None
+            argtypes.append(ctype(words[:-1] if named else words, f"{name}, parameter {i + 1} `{p.strip()}`"))
+            names.append(words[-1] if named else f"arg{i}")
+        signatures[name], params[name] = (restype, argtypes), names
+    tokens = re.findall(r"cfm_\w+\s*\(", text)
+    if len(tokens) != len(signatures):           # a declaration the pattern above did not read (or read twice)
+        missed = sorted({t.rstrip("( \t\n") for t in tokens} - set(signatures)) or "a duplicate"
+        raise ConformerHipError(f"{HEADER_PATH}: {len(tokens)} `cfm_*(` tokens but {len(signatures)} declarations read: {missed}")
+    constants = re.findall(r"^[ \t]*#[ \t]*define[ \t]+(CFM_\w+)[ \t]+(-?\d+)[ \t]*$", text, flags=re.M)
+    constants += re.findall(r"^[ \t]*(CFM_\w+)[ \t]*=[ \t]*(-?\d+)[ \t]*,?[ \t]*$", text, flags=re.M)
+    return signatures, params, {k: int(v) for k, v in constants}
+
+
+if not os.path.exists(HEADER_PATH):
+    raise ConformerHipError(f"{HEADER_PATH} is missing: the ctypes binding is derived from it")
+with open(HEADER_PATH) as _f:
+    SIGNATURES, PARAMS, CONSTANTS = parse_header(_f.read())
+ABI_VERSION = CONSTANTS["CFM_ABI_VERSION"]        # checked in load()
 
 _lib = None
 
@@ -199,7 +77,7 @@ def load() -> ctypes.CDLL:
     # a library built against another revision of include/conformer_hip.h would take shifted arguments silently (ctypes checks
     # nothing): refuse it before the first call (matters most for the CONFORMER_AMD_LIB override)
     try:
-        lib.cfm_abi_version.restype = c_int
+        lib.cfm_abi_version.restype = ctypes.c_int
         got = int(lib.cfm_abi_version())
     except AttributeError:
         got = 0
@@ -224,7 +102,22 @@ CALLS = [0]          # C-ABI calls checked so far (bench.py reports the count of
 
 
 def check(status: int, what: str) -> None:
+    """Count and check a status that was read from `load()` directly (`call` does both for the package's own calls)."""
     CALLS[0] += 1
-    if status != 0:
+    if status != CONSTANTS["CFM_OK"]:
         msg = load().cfm_strerror(status).decode()
         raise ConformerHipError(f"{what} failed: {msg} (status {status})")
+
+
+def call(name: str, *args) -> None:
+    """Call the status-returning entry point `name` and raise unless it returns CFM_OK.  The entry is looked up on the CDLL at
+    every call (an attribute swapped onto it is what runs); positional arguments only, converted by the header's argtypes."""
+    CALLS[0] += 1
+    lib = _lib or load()
+    try:
+        status = getattr(lib, name)(*args)
+    except ctypes.ArgumentError as e:
+        i = int(re.search(r"argument (\d+)", str(e)).group(1))
+        raise ConformerHipError(f"{name}: argument {i} (`{PARAMS[name][i - 1]}`) has the wrong Python type: {e}") from None
+    if status:
+        raise ConformerHipError(f"{name} failed: {lib.cfm_strerror(status).decode()} (status {status})")

@@ -15,8 +15,8 @@ import torch
 
 from . import _lib, ops
 
-MAX_FRAMES = 16384          # CFM_CTC_ALIGN_MAX_FRAMES of include/conformer_hip.h
-MAX_TARGET = 4096           # CFM_CTC_ALIGN_MAX_TARGET
+MAX_FRAMES = _lib.CONSTANTS["CFM_CTC_ALIGN_MAX_FRAMES"]
+MAX_TARGET = _lib.CONSTANTS["CFM_CTC_ALIGN_MAX_TARGET"]
 
 
 class Alignment(NamedTuple):
@@ -89,11 +89,9 @@ def ctc_forced_align(logits: torch.Tensor, targets: torch.Tensor, blank_id: int,
     token_score = torch.empty(B, lmax, dtype=torch.float32, device=dev)
     score = torch.empty(B, dtype=torch.float64, device=dev)
     ok = torch.empty(B, dtype=torch.bool, device=dev)
-    status = lib.cfm_ctc_align_f32(x.data_ptr(), y.data_ptr(), ops._p(lengths), ops._p(target_lengths), B, T, V, lmax,
-                                   int(blank_id), workspace.data_ptr(), ws_bytes, frame_tokens.data_ptr(),
-                                   frame_index.data_ptr(), token_start.data_ptr(), token_end.data_ptr(),
-                                   token_score.data_ptr(), score.data_ptr(), ok.data_ptr(), ops._stream())
-    _lib.check(status, "cfm_ctc_align_f32")
+    _lib.call("cfm_ctc_align_f32", x.data_ptr(), y.data_ptr(), ops._p(lengths), ops._p(target_lengths), B, T, V, lmax,
+              int(blank_id), workspace.data_ptr(), ws_bytes, frame_tokens.data_ptr(), frame_index.data_ptr(),
+              token_start.data_ptr(), token_end.data_ptr(), token_score.data_ptr(), score.data_ptr(), ok.data_ptr(), ops._stream())
     return Alignment(frame_tokens, frame_index, token_start[:, :L], token_end[:, :L], token_score[:, :L], score, ok)
 
 

@@ -39,9 +39,8 @@ def greedy_ctc_decode(logits: torch.Tensor, pad_id: int, unk_id: int, lengths: O
     counts = torch.empty(B, dtype=torch.int64, device=x.device)
     if lengths is not None:
         lengths = ops._req(lengths, "lengths", torch.int64)
-    st = _lib.load().cfm_greedy_ctc_decode_f32(x.data_ptr(), ops._p(lengths), frame_ids.data_ptr(), tokens.data_ptr(),
-                                               counts.data_ptr(), B, T, V, int(pad_id), int(unk_id), ops._stream())
-    _lib.check(st, "cfm_greedy_ctc_decode_f32")
+    _lib.call("cfm_greedy_ctc_decode_f32", x.data_ptr(), ops._p(lengths), frame_ids.data_ptr(), tokens.data_ptr(),
+              counts.data_ptr(), B, T, V, int(pad_id), int(unk_id), ops._stream())
     return frame_ids, tokens, counts
 
 
@@ -99,8 +98,7 @@ def _beam_search(logits: torch.Tensor, blank_id: int, lengths: Optional[torch.Te
     if lengths is not None:
         lengths = ops._req(lengths, "lengths", torch.int64)
     f = _PLAIN if fusion is None else fusion(x.device)
-    lib = _lib.load()
-    ws_bytes = lib.cfm_ctc_beam_workspace_bytes(B, T, int(beam_width), int(max_candidates))
+    ws_bytes = _lib.load().cfm_ctc_beam_workspace_bytes(B, T, int(beam_width), int(max_candidates))
     workspace = torch.empty(max(int(ws_bytes), 1), dtype=torch.uint8, device=x.device)
     tokens, counts, scores, am_scores, num_hyps = _beam_outputs(B, int(n_best), T, x.device, f.fused)
     search = (x.data_ptr(), ops._p(lengths), B, T, V, int(blank_id), int(beam_width), int(max_candidates),
@@ -112,7 +110,7 @@ def _beam_search(logits: torch.Tensor, blank_id: int, lengths: Optional[torch.Te
         name, args = "cfm_ctc_beam_lm_decode_f32", search + f.args[:5] + out + (am_scores.data_ptr(),)
     else:
         name, args = "cfm_ctc_beam_decode_f32", search + out
-    _lib.check(getattr(lib, name)(*args, num_hyps.data_ptr(), ops._stream()), name)
+    _lib.call(name, *args, num_hyps.data_ptr(), ops._stream())
     if f.fused:
         return tokens, counts, scores, am_scores, num_hyps
     return tokens, counts, scores, num_hyps
@@ -287,10 +285,8 @@ def beam_ctc_stream_init(batch: int, max_frames: int, device, *, beam_width: int
 def beam_ctc_stream_reset(st: _StreamState) -> None:
     """Every utterance back at the empty prefix (enqueues only)."""
     f = st.fusion
-    _lib.check(_lib.load().cfm_ctc_beam_stream_init(st.B, st.t_max, st.beam_width, st.max_candidates, ops._p(f.lm_tables),
-                                                    f.score_boundary, ops._p(f.hw_tables), st.buf.data_ptr(),
-                                                    st.buf.numel(), ops._stream()),
-               "cfm_ctc_beam_stream_init")
+    _lib.call("cfm_ctc_beam_stream_init", st.B, st.t_max, st.beam_width, st.max_candidates, ops._p(f.lm_tables), f.score_boundary,
+              ops._p(f.hw_tables), st.buf.data_ptr(), st.buf.numel(), ops._stream())
     st.t_used = 0
 
 
@@ -301,11 +297,9 @@ def beam_ctc_stream_reset_slots(st: _StreamState, slots: torch.Tensor) -> None:
     if slots.dim() != 1 or not 1 <= slots.numel() <= st.B or not slots.is_contiguous():
         raise ValueError(f"beam_ctc_stream_reset_slots: expected 1..{st.B} slot indices, got shape {tuple(slots.shape)}")
     f = st.fusion
-    _lib.check(_lib.load().cfm_ctc_beam_stream_reset_slots(st.B, st.t_max, st.beam_width, st.max_candidates,
-                                                           ops._p(f.lm_tables), f.score_boundary, ops._p(f.hw_tables),
-                                                           slots.data_ptr(), slots.numel(), st.buf.data_ptr(), st.buf.numel(),
-                                                           ops._stream()),
-               "cfm_ctc_beam_stream_reset_slots")
+    _lib.call("cfm_ctc_beam_stream_reset_slots", st.B, st.t_max, st.beam_width, st.max_candidates, ops._p(f.lm_tables),
+              f.score_boundary, ops._p(f.hw_tables), slots.data_ptr(), slots.numel(), st.buf.data_ptr(), st.buf.numel(),
+              ops._stream())
 
 
 def beam_ctc_stream_step(st: _StreamState, logits: torch.Tensor, blank_id: int, lengths: Optional[torch.Tensor] = None, *,
@@ -330,11 +324,10 @@ def beam_ctc_stream_step(st: _StreamState, logits: torch.Tensor, blank_id: int, 
     if lengths is not None:
         lengths = ops._req(lengths, "lengths", torch.int64)
     tokens, counts, scores, am_scores, num_hyps = _beam_outputs(st.B, int(n_best), st.t_max, x.device, st.fusion.fused)
-    status = _lib.load().cfm_ctc_beam_stream_step_f32(
-        x.data_ptr(), ops._p(lengths), st.B, Tc, V, int(blank_id), st.beam_width, st.max_candidates, float(token_min_logp),
-        float(beam_prune_logp), int(n_best), *st.fusion.args, st.buf.data_ptr(), st.buf.numel(), st.t_max, used,
-        tokens.data_ptr(), counts.data_ptr(), scores.data_ptr(), ops._p(am_scores), num_hyps.data_ptr(), ops._stream())
-    _lib.check(status, "cfm_ctc_beam_stream_step_f32")
+    _lib.call("cfm_ctc_beam_stream_step_f32", x.data_ptr(), ops._p(lengths), st.B, Tc, V, int(blank_id), st.beam_width,
+              st.max_candidates, float(token_min_logp), float(beam_prune_logp), int(n_best), *st.fusion.args, st.buf.data_ptr(),
+              st.buf.numel(), st.t_max, used, tokens.data_ptr(), counts.data_ptr(), scores.data_ptr(), ops._p(am_scores),
+              num_hyps.data_ptr(), ops._stream())
     if t_used is None:
         st.t_used += Tc
     return tokens, counts, scores, am_scores, num_hyps
@@ -345,10 +338,9 @@ def beam_ctc_stream_finish(st: _StreamState, n_best: int = 1):
     without LM and hotwords, num_hyps), equal bit for bit to one-shot decoding of the consumed frames (with T = max_frames)."""
     tokens, counts, scores, am_scores, num_hyps = _beam_outputs(st.B, int(n_best), st.t_max, st.buf.device,
                                                                 st.fusion.fused)
-    status = _lib.load().cfm_ctc_beam_stream_finish_f32(
-        st.B, st.beam_width, st.max_candidates, int(n_best), *st.fusion.args, st.buf.data_ptr(), st.buf.numel(), st.t_max,
-        tokens.data_ptr(), counts.data_ptr(), scores.data_ptr(), ops._p(am_scores), num_hyps.data_ptr(), ops._stream())
-    _lib.check(status, "cfm_ctc_beam_stream_finish_f32")
+    _lib.call("cfm_ctc_beam_stream_finish_f32", st.B, st.beam_width, st.max_candidates, int(n_best), *st.fusion.args,
+              st.buf.data_ptr(), st.buf.numel(), st.t_max, tokens.data_ptr(), counts.data_ptr(), scores.data_ptr(),
+              ops._p(am_scores), num_hyps.data_ptr(), ops._stream())
     return tokens, counts, scores, am_scores, num_hyps
 
 

@@ -77,24 +77,23 @@ class ConformerAudioFrontend:
         hop = self.hop_length
         rpu = T + (self.n_fft + hop - 1) // hop                       # rows per utterance: pitch rpu * hop >= L + n_fft
         Lp = rpu * hop
-        lib = _lib.load()
         # (B, Lp) padded waves back to back + n_fft floats of slack: the junk frames behind the last utterance read into it (rows are
         # independent: whatever those floats hold only reaches spectrum rows nobody reads)
         xbuf = torch.empty(B * Lp + self.n_fft, device=x.device, dtype=torch.float32)
         xp = xbuf[:B * Lp].view(B, Lp)
-        _lib.check(lib.cfm_reflect_pad_f32(x.data_ptr(), xp.data_ptr(), B, L, pad, Lp, ops._stream()), "cfm_reflect_pad_f32")
+        _lib.call("cfm_reflect_pad_f32", x.data_ptr(), xp.data_ptr(), B, L, pad, Lp, ops._stream())
         nb2 = self.basis.shape[0]                                                    # 2 * nk = 416 DFT columns (Re | Im, zero-padded)
         spec = torch.empty(B * rpu, nb2, device=x.device, dtype=torch.float32)
         if hop % 4 == 0:
             # frames = overlapping rows of the padded waves (row b * rpu + t); the tuned forward GEMM with lda = hop
-            _lib.check(lib.cfm_dft_frames_f32(xp.data_ptr(), self.basis.data_ptr(), spec.data_ptr(), B * rpu, nb2, self.n_fft, hop,
-                                              ops._stream()), "cfm_dft_frames_f32")
+            _lib.call("cfm_dft_frames_f32", xp.data_ptr(), self.basis.data_ptr(), spec.data_ptr(), B * rpu, nb2, self.n_fft, hop,
+                      ops._stream())
         else:
             ops.gemm_bwd(xp, False, self.basis, False, T, nb2, self.n_fft, out=spec, lda=hop, ldb=self.n_fft,
                          ldc=nb2, nbatch=B, nb1=1, sa=(Lp, 0), sb=(0, 0), sc=(rpu * nb2, 0))
         out = torch.empty(B, self.n_mels, T, device=x.device, dtype=torch.float32)
-        _lib.check(lib.cfm_power_mel_log_mfma_f32(spec.data_ptr(), nb2, self.fbT.data_ptr(), out.data_ptr(), B, T, rpu,
-                                                  self.n_fft // 2 + 1, self.n_mels, 1e-5, ops._stream()), "cfm_power_mel_log_mfma_f32")
+        _lib.call("cfm_power_mel_log_mfma_f32", spec.data_ptr(), nb2, self.fbT.data_ptr(), out.data_ptr(), B, T, rpu,
+                  self.n_fft // 2 + 1, self.n_mels, 1e-5, ops._stream())
         return out
 
     def __call__(self, audios: Sequence[torch.Tensor], augment: Optional["ConformerAugment"] = None) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -146,6 +145,5 @@ class ConformerAugment:
         else:
             value = float(x.mean())                                  # torchaudio: mask_value = specgram.mean() (one sync)
         bt = torch.tensor(bands, dtype=torch.int32, device=x.device)
-        _lib.check(_lib.load().cfm_specaugment_apply_f32(x.data_ptr(), B, F, T, bt.data_ptr(), len(bands), value,
-                                                         ops._stream()), "cfm_specaugment_apply_f32")
+        _lib.call("cfm_specaugment_apply_f32", x.data_ptr(), B, F, T, bt.data_ptr(), len(bands), value, ops._stream())
         return x

@@ -92,11 +92,9 @@ class Hotwords(PackedTables):
         if not nbytes:
             raise ValueError("the hotwords or the vocabulary are out of the packer's range")
         blob = np.empty(int(nbytes), dtype=np.uint8)
-        st = lib.cfm_hotword_pack(len(self.unigrams), uni_off.ctypes.data_as(ctypes.c_void_p), p(uni_cp), len(self.phrase_ids),
-                                  ph_off.ctypes.data_as(ctypes.c_void_p), p(ph_words), len(vocab),
-                                  tok_off.ctypes.data_as(ctypes.c_void_p), p(tok_cp), kinds.ctypes.data_as(ctypes.c_void_p),
-                                  blob.ctypes.data_as(ctypes.c_void_p), blob.nbytes)
-        _lib.check(st, "cfm_hotword_pack")
+        _lib.call("cfm_hotword_pack", len(self.unigrams), uni_off.ctypes.data_as(ctypes.c_void_p), p(uni_cp), len(self.phrase_ids),
+                  ph_off.ctypes.data_as(ctypes.c_void_p), p(ph_words), len(vocab), tok_off.ctypes.data_as(ctypes.c_void_p),
+                  p(tok_cp), kinds.ctypes.data_as(ctypes.c_void_p), blob.ctypes.data_as(ctypes.c_void_p), blob.nbytes)
         return blob
 
     def count(self, sequences: Sequence[Sequence[int]], vocab: Sequence[str], delim_token: str = "|",
@@ -112,12 +110,10 @@ class Hotwords(PackedTables):
         counts = np.zeros(max(flat.size, 1), dtype=np.int32)
         bonus = np.zeros(max(flat.size, 1), dtype=np.float64)
         final = np.zeros(len(sequences), dtype=np.int32)
-        st = _lib.load().cfm_hotword_count(blob.ctypes.data_as(ctypes.c_void_p),
-                                           flat.ctypes.data_as(ctypes.c_void_p) if flat.size else None,
-                                           off.ctypes.data_as(ctypes.c_void_p), len(sequences), float(weight),
-                                           counts.ctypes.data_as(ctypes.c_void_p), bonus.ctypes.data_as(ctypes.c_void_p),
-                                           final.ctypes.data_as(ctypes.c_void_p))
-        _lib.check(st, "cfm_hotword_count")
+        _lib.call("cfm_hotword_count", blob.ctypes.data_as(ctypes.c_void_p),
+                  flat.ctypes.data_as(ctypes.c_void_p) if flat.size else None, off.ctypes.data_as(ctypes.c_void_p), len(sequences),
+                  float(weight), counts.ctypes.data_as(ctypes.c_void_p), bonus.ctypes.data_as(ctypes.c_void_p),
+                  final.ctypes.data_as(ctypes.c_void_p))
         return [(counts[off[s]:off[s + 1]].tolist(), bonus[off[s]:off[s + 1]].tolist(), int(final[s]))
                 for s in range(len(sequences))]
 

@@ -229,11 +229,10 @@ class NgramLanguageModel(PackedTables):
         if not nbytes:
             raise ValueError("the language model or the vocabulary is out of the packer's range")
         blob = np.empty(int(nbytes), dtype=np.uint8)
-        st = lib.cfm_ngram_lm_pack(self.order, counts.ctypes.data_as(ctypes.c_void_p), p(ids), p(logp), p(backoff),
-                                   len(self.words), word_off.ctypes.data_as(ctypes.c_void_p), p(word_cp), self.bos, self.eos,
-                                   self.unk, len(vocab), tok_off.ctypes.data_as(ctypes.c_void_p), p(tok_cp),
-                                   kinds.ctypes.data_as(ctypes.c_void_p), blob.ctypes.data_as(ctypes.c_void_p), blob.nbytes)
-        _lib.check(st, "cfm_ngram_lm_pack")
+        _lib.call("cfm_ngram_lm_pack", self.order, counts.ctypes.data_as(ctypes.c_void_p), p(ids), p(logp), p(backoff),
+                  len(self.words), word_off.ctypes.data_as(ctypes.c_void_p), p(word_cp), self.bos, self.eos, self.unk, len(vocab),
+                  tok_off.ctypes.data_as(ctypes.c_void_p), p(tok_cp), kinds.ctypes.data_as(ctypes.c_void_p),
+                  blob.ctypes.data_as(ctypes.c_void_p), blob.nbytes)
         return blob
 
     def score_sentences(self, sentences: Sequence[Sequence[Union[str, int]]], boundary: bool = True, device=None):
@@ -248,9 +247,8 @@ class NgramLanguageModel(PackedTables):
         words = torch.tensor(flat if flat else [0], dtype=torch.int32).to(tables.device)
         offsets = torch.from_numpy(off).to(tables.device)
         out = torch.empty(len(sentences), dtype=torch.float64, device=tables.device)
-        st = _lib.load().cfm_ngram_lm_score_f64(tables.data_ptr(), words.data_ptr(), offsets.data_ptr(), len(sentences),
-                                                1 if boundary else 0, out.data_ptr(), ops._stream())
-        _lib.check(st, "cfm_ngram_lm_score_f64")
+        _lib.call("cfm_ngram_lm_score_f64", tables.data_ptr(), words.data_ptr(), offsets.data_ptr(), len(sentences),
+                  1 if boundary else 0, out.data_ptr(), ops._stream())
         return out
 
 

@@ -40,7 +40,7 @@ def _f32_like(t: torch.Tensor) -> torch.Tensor:
     return torch.empty(t.shape, device=t.device, dtype=torch.float32)
 
 
-PREC_F32, PREC_BF16, PREC_FP16 = 0, 1, 2          # CFM_PREC_* of include/conformer_hip.h (0 = the fp32 MFMA path)
+PREC_F32, PREC_BF16, PREC_FP16 = (_lib.CONSTANTS[f"CFM_PREC_{p}"] for p in ("F32", "BF16", "FP16"))     # (F32: the fp32 MFMA path)
 _DT16 = {PREC_BF16: torch.bfloat16, PREC_FP16: torch.float16}
 _tls = threading.local()       # .forced: precision pinned by `precision(...)` for the current thread (autograd runs the
                                # backward on its own device thread: a process-global would race between threads)
@@ -96,10 +96,10 @@ def weight16(w: torch.Tensor, prec: int, transposed: bool = False) -> Optional[t
             out = torch.empty(w.shape[1], w.shape[0], device=w.device, dtype=_DT16[prec])
             item = (_lib.CastItem * 1)()
             item[0].src, item[0].dst, item[0].rows, item[0].cols, item[0].transpose = w.data_ptr(), out.data_ptr(), w.shape[0], w.shape[1], 1
-            _lib.check(_lib.load().cfm_cast16_multi_f32(prec, ctypes.addressof(item), 1, _stream()), "cfm_cast16_multi_f32")
+            _lib.call("cfm_cast16_multi_f32", prec, ctypes.addressof(item), 1, _stream())
         else:
             out = torch.empty(w.shape, device=w.device, dtype=_DT16[prec])
-            _lib.check(_lib.load().cfm_cast16_f32(prec, w.data_ptr(), out.data_ptr(), w.numel(), _stream()), "cfm_cast16_f32")
+            _lib.call("cfm_cast16_f32", prec, w.data_ptr(), out.data_ptr(), w.numel(), _stream())
         return out
     # (a freed temporary -- e.g. last step's fused QKV matrix -- can hand its address to a new tensor: the owner's identity tells them apart)
     return _WEIGHT_COPIES.get((w.data_ptr(), transposed), (w,), make, extra=prec)
@@ -126,7 +126,7 @@ def refresh_weight16(params) -> int:
         for i, (w2, out, transposed) in enumerate(items):
             arr[i].src, arr[i].dst = w2.data_ptr(), out.data_ptr()
             arr[i].rows, arr[i].cols, arr[i].transpose = w2.shape[0], w2.shape[1], int(transposed)
-        _lib.check(_lib.load().cfm_cast16_multi_f32(prec, ctypes.addressof(arr), len(items), _stream()), "cfm_cast16_multi_f32")
+        _lib.call("cfm_cast16_multi_f32", prec, ctypes.addressof(arr), len(items), _stream())
         n += len(items)
     return n
 
@@ -176,7 +176,7 @@ def weight_split(w: torch.Tensor, planes: int) -> Optional[torch.Tensor]:
         lib = _lib.load()
         n, k = w.shape
         out = torch.empty(int(lib.cfm_split_pack_elems(planes, n, k)), device=w.device, dtype=torch.bfloat16)
-        _lib.check(lib.cfm_split_pack_bf16_f32(planes, w.data_ptr(), out.data_ptr(), n, k, _stream()), "cfm_split_pack_bf16_f32")
+        _lib.call("cfm_split_pack_bf16_f32", planes, w.data_ptr(), out.data_ptr(), n, k, _stream())
         return out
     return _WEIGHT_COPIES.get((w.data_ptr(), "split"), (w,), make, extra=planes)
 
@@ -195,8 +195,8 @@ def _split_gemm(epi: int, a, w2, b, c, m, n, k, res=None, alpha: float = 1.0):
     ws = weight_split(w2, _fp32_planes) if (epi != 3 or n % 32 == 0) else None
     if ws is None:
         return None
-    _lib.check(_lib.load().cfm_gemm_split_bf16_f32(_fp32_planes, epi, a.data_ptr(), ws.data_ptr(), b.data_ptr(), _p(res), alpha,
-                                                   c.data_ptr(), m, n, k, k, n, n, _stream()), "cfm_gemm_split_bf16_f32")
+    _lib.call("cfm_gemm_split_bf16_f32", _fp32_planes, epi, a.data_ptr(), ws.data_ptr(), b.data_ptr(), _p(res), alpha, c.data_ptr(),
+              m, n, k, k, n, n, _stream())
     return c
 
 
@@ -212,11 +212,9 @@ def _mfma16_gemm(prec: int, epi: int, a, w2, b, c, m, n, k, res=None, alpha: flo
     a16 = a.dtype != torch.float32
     if a16 and (w16 is None or a.dtype != _DT16[prec]):
         raise _lib.ConformerHipError(f"16-bit A operand ({a.dtype}) does not match the precision mode / weight shape")
-    st = _lib.load().cfm_gemm_mfma16_f32(prec, epi, a.data_ptr(), int(a16), (w2 if w16 is None else w16).data_ptr(),
-                                         int(w16 is not None), b.data_ptr(), _p(res), alpha, c.data_ptr(),
-                                         int(c.dtype != torch.float32), _p(z), int(z is not None and z.dtype != torch.float32),
-                                         m, n, k, k, n, n, float(drop_p), int(seed), _stream())
-    _lib.check(st, "cfm_gemm_mfma16_f32")
+    _lib.call("cfm_gemm_mfma16_f32", prec, epi, a.data_ptr(), int(a16), (w2 if w16 is None else w16).data_ptr(),
+              int(w16 is not None), b.data_ptr(), _p(res), alpha, c.data_ptr(), int(c.dtype != torch.float32), _p(z),
+              int(z is not None and z.dtype != torch.float32), m, n, k, k, n, n, float(drop_p), int(seed), _stream())
     return c
 
 
@@ -229,8 +227,7 @@ def subsampled_lengths(lengths: torch.Tensor) -> torch.Tensor:
     lengths = _req(lengths, "lengths", torch.int64)
     out = torch.empty(lengths.shape, device=lengths.device, dtype=torch.int64)
     if lengths.numel():
-        _lib.check(_lib.load().cfm_subsampled_lengths_i64(lengths.data_ptr(), out.data_ptr(), lengths.numel(), _stream()),
-                   "cfm_subsampled_lengths_i64")
+        _lib.call("cfm_subsampled_lengths_i64", lengths.data_ptr(), out.data_ptr(), lengths.numel(), _stream())
     return out
 
 
@@ -274,9 +271,8 @@ def linear_lnfold(a, stats, wf, bf, cs, eps: float, act: str = "none", glu: bool
         raise _lib.ConformerHipError(f"linear_lnfold: A(...,{k}), Wf{tuple(wf.shape)}, stats{tuple(stats.shape)} do not match")
     c = torch.empty(*a.shape[:-1], n, device=a.device, dtype=torch.float32)
     epi = 3 if glu else {"none": 0, "swish": 1}[act]
-    _lib.check(_lib.load().cfm_gemm_lnfold_f32(epi, a.data_ptr(), stats.data_ptr(), stats.shape[1], float(eps), wf.data_ptr(),
-                                               bf.data_ptr(), cs.data_ptr(), c.data_ptr(), m, n, k, k, n, _stream()),
-               "cfm_gemm_lnfold_f32")
+    _lib.call("cfm_gemm_lnfold_f32", epi, a.data_ptr(), stats.data_ptr(), stats.shape[1], float(eps), wf.data_ptr(), bf.data_ptr(),
+              cs.data_ptr(), c.data_ptr(), m, n, k, k, n, _stream())
     return c
 
 
@@ -317,7 +313,7 @@ def ffn_pack(w1f: torch.Tensor, w2: torch.Tensor) -> torch.Tensor:
     if _FFN_LAYOUT_ENV is not None:
         lib.cfm_debug_ffn_layout(-1, int(_FFN_LAYOUT_ENV))
     wp = torch.zeros(int(lib.cfm_ffn_pack_elems(d, hidden)), device=w1f.device, dtype=torch.float32)   # (pads between tiles: zero)
-    _lib.check(lib.cfm_ffn_pack_f32(w1f.data_ptr(), w2.data_ptr(), wp.data_ptr(), d, hidden, _stream()), "cfm_ffn_pack_f32")
+    _lib.call("cfm_ffn_pack_f32", w1f.data_ptr(), w2.data_ptr(), wp.data_ptr(), d, hidden, _stream())
     return wp
 
 
@@ -342,11 +338,9 @@ def ffn_fused(x: torch.Tensor, stats: torch.Tensor, wp: torch.Tensor, b1f: torch
     elif emit_stats:
         mode = 1
         st_out = torch.empty(rows, d // 32, 2, device=x.device, dtype=torch.float32)
-    _lib.check(_lib.load().cfm_ffn_fused_f32(x.data_ptr(), d, stats.data_ptr(), stats.shape[1], float(eps), wp.data_ptr(),
-                                             b1f.data_ptr(), cs.data_ptr(), b2.data_ptr(), float(alpha), y.data_ptr(), d, mode,
-                                             None if st_out is None else st_out.data_ptr(),
-                                             None if g2 is None else g2.data_ptr(), None if bt2 is None else bt2.data_ptr(),
-                                             eps2, rows, d, hidden, _stream()), "cfm_ffn_fused_f32")
+    _lib.call("cfm_ffn_fused_f32", x.data_ptr(), d, stats.data_ptr(), stats.shape[1], float(eps), wp.data_ptr(), b1f.data_ptr(),
+              cs.data_ptr(), b2.data_ptr(), float(alpha), y.data_ptr(), d, mode, None if st_out is None else st_out.data_ptr(),
+              None if g2 is None else g2.data_ptr(), None if bt2 is None else bt2.data_ptr(), eps2, rows, d, hidden, _stream())
     return (y, st_out) if emit_stats else y
 
 
@@ -374,7 +368,7 @@ def rowgemm_pack(w: torch.Tensor, glu: bool = False) -> torch.Tensor:
     w = _req(w.reshape(w.shape[0], -1), "W")
     n, d = w.shape
     wp = torch.empty(n * d, device=w.device, dtype=torch.float32)
-    _lib.check(_lib.load().cfm_rowgemm_pack_f32(w.data_ptr(), wp.data_ptr(), n, d, 1 if glu else 0, _stream()), "cfm_rowgemm_pack_f32")
+    _lib.call("cfm_rowgemm_pack_f32", w.data_ptr(), wp.data_ptr(), n, d, 1 if glu else 0, _stream())
     return wp
 
 
@@ -385,12 +379,10 @@ def _rowchain(pre, core, post, mode, x, d, *, wpre=None, bpre=None, res=None, y1
     wp, b1f, cs1 = ffn if ffn is not None else (None, None, None)
     hidden = 0 if b1f is None else b1f.numel()
     g2, bt2, eps2 = ln2 if ln2 is not None else (None, None, 0.0)
-    st = _lib.load().cfm_rowchain_f32(pre, core, post, mode, x.data_ptr(), d, ptr(wpre), ptr(bpre), ptr(res), d, ptr(y1), d,
-                                      ptr(stats), 0 if stats is None else stats.shape[1], float(ln_eps), ptr(wp), ptr(b1f), ptr(cs1),
-                                      ptr(b2), float(alpha), hidden, ptr(y), d, ptr(stats_out), ptr(g2), ptr(bt2), float(eps2),
-                                      ptr(wpost), ptr(bpost), ptr(cspost), float(post_eps), ptr(z), 0 if z is None else z.shape[-1],
-                                      rows, d, _stream())
-    _lib.check(st, "cfm_rowchain_f32")
+    _lib.call("cfm_rowchain_f32", pre, core, post, mode, x.data_ptr(), d, ptr(wpre), ptr(bpre), ptr(res), d, ptr(y1), d, ptr(stats),
+              0 if stats is None else stats.shape[1], float(ln_eps), ptr(wp), ptr(b1f), ptr(cs1), ptr(b2), float(alpha), hidden,
+              ptr(y), d, ptr(stats_out), ptr(g2), ptr(bt2), float(eps2), ptr(wpost), ptr(bpost), ptr(cspost), float(post_eps),
+              ptr(z), 0 if z is None else z.shape[-1], rows, d, _stream())
 
 
 def rowchain_ffn_qkv(x, stats, ffn, b2, alpha: float, ffn_eps: float, wqkv_p, bqkv_f, csqkv, att_eps: float):
@@ -439,21 +431,20 @@ def layernorm(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, eps: fl
     if emit_stats:
         y = torch.empty(x.shape, device=x.device, dtype=torch.float32)
         stats = torch.empty(rows, 1, 2, device=x.device, dtype=torch.float32)
-        _lib.check(_lib.load().cfm_layernorm_fwd_stats_f32(x.data_ptr(), weight.data_ptr(), bias.data_ptr(), y.data_ptr(),
-                                                           stats.data_ptr(), rows, d, eps, _stream()), "cfm_layernorm_fwd_stats_f32")
+        _lib.call("cfm_layernorm_fwd_stats_f32", x.data_ptr(), weight.data_ptr(), bias.data_ptr(), y.data_ptr(), stats.data_ptr(),
+                  rows, d, eps, _stream())
         return y, stats
     p16 = out16_ok(d) if for_gemm and out is None else 0
     if p16:
         y = torch.empty(x.shape, device=x.device, dtype=_DT16[p16])
-        _lib.check(_lib.load().cfm_layernorm_fwd_out16_f32(p16, x.data_ptr(), weight.data_ptr(), bias.data_ptr(), y.data_ptr(),
-                                                           None, None, rows, d, eps, _stream()), "cfm_layernorm_fwd_out16_f32")
+        _lib.call("cfm_layernorm_fwd_out16_f32", p16, x.data_ptr(), weight.data_ptr(), bias.data_ptr(), y.data_ptr(), None, None,
+                  rows, d, eps, _stream())
         return y
     y = _f32_like(x) if out is None else _req(out, "out")
     if y.shape != x.shape:
         raise _lib.ConformerHipError(f"layernorm: out{tuple(y.shape)} does not match x{tuple(x.shape)}")
-    st = _lib.load().cfm_layernorm_fwd_f32(x.data_ptr(), weight.data_ptr(), bias.data_ptr(), y.data_ptr(),
-                                           None, None, rows, d, eps, _stream())
-    _lib.check(st, "cfm_layernorm_fwd_f32")
+    _lib.call("cfm_layernorm_fwd_f32", x.data_ptr(), weight.data_ptr(), bias.data_ptr(), y.data_ptr(), None, None, rows, d, eps,
+              _stream())
     return y
 
 
@@ -483,8 +474,8 @@ def _splitk_gemm(epi: int, a, w2, b, c, m, n, k, res=None, alpha: float = 1.0):
     if not sp or a.dtype != torch.float32 or c.dtype != torch.float32 or _fp32_planes or mfma16_prec():
         return None
     ws = torch.empty(sp * m * n, device=a.device, dtype=torch.float32)
-    _lib.check(_lib.load().cfm_gemm_splitk_f32(epi, a.data_ptr(), w2.data_ptr(), b.data_ptr(), _p(res), alpha, c.data_ptr(),
-                                               ws.data_ptr(), sp, m, n, k, k, n, n, _stream()), "cfm_gemm_splitk_f32")
+    _lib.call("cfm_gemm_splitk_f32", epi, a.data_ptr(), w2.data_ptr(), b.data_ptr(), _p(res), alpha, c.data_ptr(), ws.data_ptr(),
+              sp, m, n, k, k, n, n, _stream())
     return c
 
 
@@ -497,8 +488,8 @@ def linear(a, w, b, act: str = "none", for_gemm: bool = False, emit_stats: bool 
             raise _lib.ConformerHipError("linear(emit_stats=True) needs the native fp32 path, act='none' and ln_fold_ok(N)")
         c = torch.empty(*a.shape[:-1], n, device=a.device, dtype=torch.float32)
         stats = torch.empty(m, n // 32, 2, device=a.device, dtype=torch.float32)
-        _lib.check(_lib.load().cfm_gemm_bias_stats_f32(a.data_ptr(), w2.data_ptr(), b.data_ptr(), c.data_ptr(), stats.data_ptr(),
-                                                       m, n, k, k, n, _stream()), "cfm_gemm_bias_stats_f32")
+        _lib.call("cfm_gemm_bias_stats_f32", a.data_ptr(), w2.data_ptr(), b.data_ptr(), c.data_ptr(), stats.data_ptr(), m, n, k, k,
+                  n, _stream())
         return c, stats
     prec = mfma16_prec()
     p16 = out16_ok(n) if for_gemm else 0
@@ -510,8 +501,7 @@ def linear(a, w, b, act: str = "none", for_gemm: bool = False, emit_stats: bool 
     if act != "relu" and _splitk_gemm({"none": 0, "swish": 1}[act], a, w2, b, c, m, n, k) is not None:
         return c
     fn = {"none": "cfm_gemm_bias_f32", "swish": "cfm_gemm_bias_swish_f32", "relu": "cfm_gemm_bias_relu_f32"}[act]
-    st = getattr(_lib.load(), fn)(a.data_ptr(), w2.data_ptr(), b.data_ptr(), c.data_ptr(), m, n, k, k, n, _stream())
-    _lib.check(st, fn)
+    _lib.call(fn, a.data_ptr(), w2.data_ptr(), b.data_ptr(), c.data_ptr(), m, n, k, k, n, _stream())
     return c
 
 
@@ -525,9 +515,7 @@ def linear_glu(a, w, b) -> torch.Tensor:
         return _mfma16_gemm(prec, 3, a, w2, b, c, m, n, k)
     if _split_gemm(3, a, w2, b, c, m, n, k) is not None:
         return c
-    st = _lib.load().cfm_gemm_bias_glu_f32(a.data_ptr(), w2.data_ptr(), b.data_ptr(), c.data_ptr(), m, n, k, k, n,
-                                           _stream())
-    _lib.check(st, "cfm_gemm_bias_glu_f32")
+    _lib.call("cfm_gemm_bias_glu_f32", a.data_ptr(), w2.data_ptr(), b.data_ptr(), c.data_ptr(), m, n, k, k, n, _stream())
     return c
 
 
@@ -540,9 +528,8 @@ def linear_residual(a, w, b, res: torch.Tensor, alpha: float = 1.0, emit_stats: 
             raise _lib.ConformerHipError("linear_residual(emit_stats=True) needs the native fp32 path and ln_fold_ok(N)")
         c = torch.empty(*a.shape[:-1], n, device=a.device, dtype=torch.float32)
         stats = torch.empty(m, n // 32, 2, device=a.device, dtype=torch.float32)
-        _lib.check(_lib.load().cfm_gemm_bias_residual_stats_f32(a.data_ptr(), w2.data_ptr(), b.data_ptr(), res.data_ptr(), alpha,
-                                                                c.data_ptr(), stats.data_ptr(), m, n, k, k, n, n, _stream()),
-                   "cfm_gemm_bias_residual_stats_f32")
+        _lib.call("cfm_gemm_bias_residual_stats_f32", a.data_ptr(), w2.data_ptr(), b.data_ptr(), res.data_ptr(), alpha,
+                  c.data_ptr(), stats.data_ptr(), m, n, k, k, n, n, _stream())
         return c, stats
     c = torch.empty(*a.shape[:-1], n, device=a.device, dtype=torch.float32)
     prec = mfma16_prec()
@@ -552,9 +539,8 @@ def linear_residual(a, w, b, res: torch.Tensor, alpha: float = 1.0, emit_stats: 
         return c
     if _splitk_gemm(4, a, w2, b, c, m, n, k, res, alpha) is not None:
         return c
-    st = _lib.load().cfm_gemm_bias_residual_f32(a.data_ptr(), w2.data_ptr(), b.data_ptr(), res.data_ptr(), alpha,
-                                                c.data_ptr(), m, n, k, k, n, n, _stream())
-    _lib.check(st, "cfm_gemm_bias_residual_f32")
+    _lib.call("cfm_gemm_bias_residual_f32", a.data_ptr(), w2.data_ptr(), b.data_ptr(), res.data_ptr(), alpha, c.data_ptr(), m, n, k,
+              k, n, n, _stream())
     return c
 
 
@@ -562,8 +548,7 @@ def relpos_table(div_term: torch.Tensor, t: int) -> torch.Tensor:
     dt = _req(div_term, "div_term").reshape(-1)
     d = 2 * dt.numel()
     pe = torch.empty(2 * t - 1, d, device=dt.device, dtype=torch.float32)
-    st = _lib.load().cfm_relpos_table_f32(dt.data_ptr(), pe.data_ptr(), t, d, _stream())
-    _lib.check(st, "cfm_relpos_table_f32")
+    _lib.call("cfm_relpos_table_f32", dt.data_ptr(), pe.data_ptr(), t, d, _stream())
     return pe
 
 
@@ -616,22 +601,17 @@ def relpos_attention(qkv: torch.Tensor, pos: torch.Tensor, u: torch.Tensor, v: t
     if q16 or c16:
         esz = 2 if q16 else 4
         ctx = torch.empty(B, T, d, device=qkv.device, dtype=_DT16[prec] if c16 else torch.float32)
-        st = _lib.load().cfm_relpos_attention_io16_mfma16_f32(prec, base, base + esz * d, base + 2 * esz * d, int(q16), d3,
-                                                              pos.data_ptr(), ldp, u.data_ptr(), v.data_ptr(), _p(lengths),
-                                                              ctx.data_ptr(), int(c16), d, B, T, n_heads, dh, _stream())
-        _lib.check(st, "cfm_relpos_attention_io16_mfma16_f32")
+        _lib.call("cfm_relpos_attention_io16_mfma16_f32", prec, base, base + esz * d, base + 2 * esz * d, int(q16), d3,
+                  pos.data_ptr(), ldp, u.data_ptr(), v.data_ptr(), _p(lengths), ctx.data_ptr(), int(c16), d, B, T, n_heads, dh,
+                  _stream())
         return ctx
     ctx = torch.empty(B, T, d, device=qkv.device, dtype=torch.float32)
     if prec:
-        st = _lib.load().cfm_relpos_attention_mfma16_f32(prec, base, base + 4 * d, base + 8 * d, d3, pos.data_ptr(), ldp,
-                                                         u.data_ptr(), v.data_ptr(), _p(lengths), ctx.data_ptr(), d, None,
-                                                         B, T, n_heads, dh, 0.0, 0, _stream())
-        _lib.check(st, "cfm_relpos_attention_mfma16_f32")
+        _lib.call("cfm_relpos_attention_mfma16_f32", prec, base, base + 4 * d, base + 8 * d, d3, pos.data_ptr(), ldp, u.data_ptr(),
+                  v.data_ptr(), _p(lengths), ctx.data_ptr(), d, None, B, T, n_heads, dh, 0.0, 0, _stream())
         return ctx
-    st = _lib.load().cfm_relpos_attention_fwd_f32(base, base + 4 * d, base + 8 * d, d3, pos.data_ptr(), ldp,
-                                                  u.data_ptr(), v.data_ptr(), _p(lengths), ctx.data_ptr(), d, None,
-                                                  B, T, n_heads, dh, _stream())
-    _lib.check(st, "cfm_relpos_attention_fwd_f32")
+    _lib.call("cfm_relpos_attention_fwd_f32", base, base + 4 * d, base + 8 * d, d3, pos.data_ptr(), ldp, u.data_ptr(), v.data_ptr(),
+              _p(lengths), ctx.data_ptr(), d, None, B, T, n_heads, dh, _stream())
     return ctx
 
 
@@ -654,18 +634,16 @@ def relpos_attention_rows(qkv: torch.Tensor, pos: torch.Tensor, u: torch.Tensor,
     if prec != PREC_F32:
         # under autocast: the 16-bit matrix-pipe form (fp32 cache, operands rounded where they enter a product; no key split)
         base = qkv.data_ptr()
-        st = _lib.load().cfm_relpos_attention_rows_mfma16_f32(prec, base, base + 4 * d, base + 8 * d, d3, pos.data_ptr(), pos.stride(0),
-                                                              u.data_ptr(), v.data_ptr(), lengths.data_ptr(), ctx.data_ptr(), d, B, T,
-                                                              n_heads, d // n_heads, int(q_begin), int(q_count), _stream())
-        _lib.check(st, "cfm_relpos_attention_rows_mfma16_f32")
+        _lib.call("cfm_relpos_attention_rows_mfma16_f32", prec, base, base + 4 * d, base + 8 * d, d3, pos.data_ptr(), pos.stride(0),
+                  u.data_ptr(), v.data_ptr(), lengths.data_ptr(), ctx.data_ptr(), d, B, T, n_heads, d // n_heads, int(q_begin),
+                  int(q_count), _stream())
         return ctx
     nsplit = _key_split(B, n_heads, q_count, T, keys_hint)
     ws = torch.empty(nsplit * B * q_count * (d + n_heads), device=qkv.device, dtype=torch.float32) if nsplit > 1 else None
     base = qkv.data_ptr()
-    st = _lib.load().cfm_relpos_attention_rows_f32(base, base + 4 * d, base + 8 * d, d3, pos.data_ptr(), pos.stride(0),
-                                                   u.data_ptr(), v.data_ptr(), lengths.data_ptr(), ctx.data_ptr(), d, B, T,
-                                                   n_heads, d // n_heads, int(q_begin), int(q_count), nsplit, _p(ws), _stream())
-    _lib.check(st, "cfm_relpos_attention_rows_f32")
+    _lib.call("cfm_relpos_attention_rows_f32", base, base + 4 * d, base + 8 * d, d3, pos.data_ptr(), pos.stride(0), u.data_ptr(),
+              v.data_ptr(), lengths.data_ptr(), ctx.data_ptr(), d, B, T, n_heads, d // n_heads, int(q_begin), int(q_count), nsplit,
+              _p(ws), _stream())
     return ctx
 
 
@@ -711,18 +689,13 @@ def relpos_attention_slots(qkv: torch.Tensor, pos: torch.Tensor, u: torch.Tensor
     base = qkv.data_ptr()
     if prec != PREC_F32:
         esz = 2 if q16 else 4
-        st = _lib.load().cfm_relpos_attention_slots_mfma16_f32(prec, base, base + esz * d, base + 2 * esz * d, int(q16), d3,
-                                                               pos.data_ptr(), pos.stride(0), u.data_ptr(), v.data_ptr(),
-                                                               q_begin.data_ptr(), q_count.data_ptr(), lengths.data_ptr(),
-                                                               ctx.data_ptr(), d, B, T, n_heads, d // n_heads, q_max, nsplit,
-                                                               _p(ws), _stream())
-        _lib.check(st, "cfm_relpos_attention_slots_mfma16_f32")
+        _lib.call("cfm_relpos_attention_slots_mfma16_f32", prec, base, base + esz * d, base + 2 * esz * d, int(q16), d3,
+                  pos.data_ptr(), pos.stride(0), u.data_ptr(), v.data_ptr(), q_begin.data_ptr(), q_count.data_ptr(),
+                  lengths.data_ptr(), ctx.data_ptr(), d, B, T, n_heads, d // n_heads, q_max, nsplit, _p(ws), _stream())
         return ctx
-    st = _lib.load().cfm_relpos_attention_slots_f32(base, base + 4 * d, base + 8 * d, d3, pos.data_ptr(), pos.stride(0),
-                                                    u.data_ptr(), v.data_ptr(), q_begin.data_ptr(), q_count.data_ptr(),
-                                                    lengths.data_ptr(), ctx.data_ptr(), d, B, T, n_heads, d // n_heads, q_max,
-                                                    nsplit, _p(ws), _stream())
-    _lib.check(st, "cfm_relpos_attention_slots_f32")
+    _lib.call("cfm_relpos_attention_slots_f32", base, base + 4 * d, base + 8 * d, d3, pos.data_ptr(), pos.stride(0), u.data_ptr(),
+              v.data_ptr(), q_begin.data_ptr(), q_count.data_ptr(), lengths.data_ptr(), ctx.data_ptr(), d, B, T, n_heads,
+              d // n_heads, q_max, nsplit, _p(ws), _stream())
     return ctx
 
 
@@ -734,18 +707,14 @@ def dwconv_bn_swish(g, w, b, bn_w, bn_b, bn_mean, bn_var, eps: float = 1e-5, for
     p16 = out16_ok(C) if for_gemm and K in (3, 7, 15, 31) else 0
     if p16:
         y = torch.empty(g.shape, device=g.device, dtype=_DT16[p16])
-        st = _lib.load().cfm_dwconv_bn_swish_fwd_out16_f32(p16, g.data_ptr(), w.data_ptr(), b.data_ptr(), _req(bn_w, "bn_w").data_ptr(),
-                                                           _req(bn_b, "bn_b").data_ptr(), _req(bn_mean, "bn_mean").data_ptr(),
-                                                           _req(bn_var, "bn_var").data_ptr(), eps, y.data_ptr(), B, T, C, K,
-                                                           _stream())
-        _lib.check(st, "cfm_dwconv_bn_swish_fwd_out16_f32")
+        _lib.call("cfm_dwconv_bn_swish_fwd_out16_f32", p16, g.data_ptr(), w.data_ptr(), b.data_ptr(), _req(bn_w, "bn_w").data_ptr(),
+                  _req(bn_b, "bn_b").data_ptr(), _req(bn_mean, "bn_mean").data_ptr(), _req(bn_var, "bn_var").data_ptr(), eps,
+                  y.data_ptr(), B, T, C, K, _stream())
         return y
     y = _f32_like(g)
-    st = _lib.load().cfm_dwconv_bn_swish_fwd_f32(g.data_ptr(), w.data_ptr(), b.data_ptr(), _req(bn_w, "bn_w").data_ptr(),
-                                                 _req(bn_b, "bn_b").data_ptr(), _req(bn_mean, "bn_mean").data_ptr(),
-                                                 _req(bn_var, "bn_var").data_ptr(), eps, y.data_ptr(), B, T, C, K,
-                                                 _stream())
-    _lib.check(st, "cfm_dwconv_bn_swish_fwd_f32")
+    _lib.call("cfm_dwconv_bn_swish_fwd_f32", g.data_ptr(), w.data_ptr(), b.data_ptr(), _req(bn_w, "bn_w").data_ptr(),
+              _req(bn_b, "bn_b").data_ptr(), _req(bn_mean, "bn_mean").data_ptr(), _req(bn_var, "bn_var").data_ptr(), eps,
+              y.data_ptr(), B, T, C, K, _stream())
     return y
 
 
@@ -801,10 +770,9 @@ def convmod_glu_dwconv(x, stats, wf, bf, cs, ln_eps: float, w, b, bn_w, bn_b, bn
         raise _lib.ConformerHipError(f"convmod_glu_dwconv: the BatchNorm tensors must have {C} values")
     y = torch.empty(B, T, C, device=x.device, dtype=torch.float32)
     if B * T:
-        _lib.check(_lib.load().cfm_convmod_glu_dwconv_f32(x.data_ptr(), C, stats.data_ptr(), stats.shape[1], float(ln_eps), wf.data_ptr(),
-                                                          bf.data_ptr(), cs.data_ptr(), w.data_ptr(), b.data_ptr(), bn[0].data_ptr(),
-                                                          bn[1].data_ptr(), bn[2].data_ptr(), bn[3].data_ptr(), float(bn_eps),
-                                                          y.data_ptr(), C, B, T, C, K, _stream()), "cfm_convmod_glu_dwconv_f32")
+        _lib.call("cfm_convmod_glu_dwconv_f32", x.data_ptr(), C, stats.data_ptr(), stats.shape[1], float(ln_eps), wf.data_ptr(),
+                  bf.data_ptr(), cs.data_ptr(), w.data_ptr(), b.data_ptr(), bn[0].data_ptr(), bn[1].data_ptr(), bn[2].data_ptr(),
+                  bn[3].data_ptr(), float(bn_eps), y.data_ptr(), C, B, T, C, K, _stream())
     return y
 
 
@@ -812,7 +780,7 @@ def pack_conv2_weight(w2: torch.Tensor) -> torch.Tensor:
     w2 = _req(w2, "conv_2.weight")
     C = w2.shape[0]
     out = torch.empty(C, 9 * C, device=w2.device, dtype=torch.float32)
-    _lib.check(_lib.load().cfm_pack_conv2_weight_f32(w2.data_ptr(), out.data_ptr(), C, _stream()), "cfm_pack_conv2_weight_f32")
+    _lib.call("cfm_pack_conv2_weight_f32", w2.data_ptr(), out.data_ptr(), C, _stream())
     return out
 
 
@@ -839,16 +807,14 @@ def pack_conv2_wino_weight(w2: torch.Tensor) -> torch.Tensor:
     w2 = _req(w2, "conv_2.weight")
     C = w2.shape[0]
     out = torch.empty(25 * C * C, device=w2.device, dtype=torch.float32)
-    _lib.check(_lib.load().cfm_pack_conv2_wino_weight_f32(w2.data_ptr(), out.data_ptr(), C, _stream()),
-               "cfm_pack_conv2_wino_weight_f32")
+    _lib.call("cfm_pack_conv2_wino_weight_f32", w2.data_ptr(), out.data_ptr(), C, _stream())
     return out
 
 
 def pack_linear_weight(wl: torch.Tensor, C: int, F2: int) -> torch.Tensor:
     wl = _req(wl, "linear.weight")
     out = _f32_like(wl)
-    _lib.check(_lib.load().cfm_pack_linear_weight_f32(wl.data_ptr(), out.data_ptr(), wl.shape[0], C, F2, _stream()),
-               "cfm_pack_linear_weight_f32")
+    _lib.call("cfm_pack_linear_weight_f32", wl.data_ptr(), out.data_ptr(), wl.shape[0], C, F2, _stream())
     return out
 
 
@@ -865,40 +831,36 @@ def subsample_stem(x: torch.Tensor, w1, b1, w2p, b2, w2w=None) -> torch.Tensor:
     p16 = out16_ok(C) if C % 64 == 0 else 0       # inference under autocast: h1 and h2 only feed 16-bit GEMM operands
     if p16:
         h1 = torch.empty(B, T1, F1, C, device=x.device, dtype=_DT16[p16])
-        _lib.check(lib.cfm_subsample_conv1_relu_out16_f32(p16, x.data_ptr(), w1.data_ptr(), b1.data_ptr(), h1.data_ptr(), B, F,
-                                                          T, C, _stream()), "cfm_subsample_conv1_relu_out16_f32")
+        _lib.call("cfm_subsample_conv1_relu_out16_f32", p16, x.data_ptr(), w1.data_ptr(), b1.data_ptr(), h1.data_ptr(), B, F, T, C,
+                  _stream())
         h2 = torch.empty(B, T2, F2 * C, device=x.device, dtype=_DT16[p16])
     else:
         h1 = torch.empty(B, T1, F1, C, device=x.device, dtype=torch.float32)
-        _lib.check(lib.cfm_subsample_conv1_relu_f32(x.data_ptr(), w1.data_ptr(), b1.data_ptr(), h1.data_ptr(), B, F, T, C,
-                                                    _stream()), "cfm_subsample_conv1_relu_f32")
+        _lib.call("cfm_subsample_conv1_relu_f32", x.data_ptr(), w1.data_ptr(), b1.data_ptr(), h1.data_ptr(), B, F, T, C, _stream())
         h2 = torch.empty(B, T2, F2 * C, device=x.device, dtype=torch.float32)
         if w2w is not None and conv2_winograd_ok(C):
             planes = torch.empty(int(lib.cfm_conv2_wino_plane_elems(B, F1, T1, C)), device=x.device, dtype=torch.float32)
-            _lib.check(lib.cfm_subsample_conv2_wino_relu_f32(h1.data_ptr(), _req(w2w, "Winograd conv_2.weight").data_ptr(),
-                                                             b2.data_ptr(), planes.data_ptr(), h2.data_ptr(), B, F1, T1, C,
-                                                             _stream()), "cfm_subsample_conv2_wino_relu_f32")
+            _lib.call("cfm_subsample_conv2_wino_relu_f32", h1.data_ptr(), _req(w2w, "Winograd conv_2.weight").data_ptr(),
+                      b2.data_ptr(), planes.data_ptr(), h2.data_ptr(), B, F1, T1, C, _stream())
             return h2
-    _conv2_relu(lib, h1, w2p, b2, h2, B, F1, T1, C)
+    _conv2_relu(h1, w2p, b2, h2, B, F1, T1, C)
     return h2
 
 
-def _conv2_relu(lib, h1, w2p, b2, h2, B, F1, T1, C):
+def _conv2_relu(h1, w2p, b2, h2, B, F1, T1, C):
     prec = mfma16_prec()
     if prec and C % 64 == 0:
         w16 = weight16(w2p, prec)
-        _lib.check(lib.cfm_subsample_conv2_relu_mfma16_f32(prec, h1.data_ptr(), int(h1.dtype != torch.float32),
-                                                           (w2p if w16 is None else w16).data_ptr(), int(w16 is not None),
-                                                           b2.data_ptr(), h2.data_ptr(), int(h2.dtype != torch.float32), B, F1,
-                                                           T1, C, _stream()), "cfm_subsample_conv2_relu_mfma16_f32")
+        _lib.call("cfm_subsample_conv2_relu_mfma16_f32", prec, h1.data_ptr(), int(h1.dtype != torch.float32),
+                  (w2p if w16 is None else w16).data_ptr(), int(w16 is not None), b2.data_ptr(), h2.data_ptr(),
+                  int(h2.dtype != torch.float32), B, F1, T1, C, _stream())
     elif _fp32_planes and C % 64 == 0:
         ws = weight_split(w2p.view(C, 9 * C), _fp32_planes)
-        _lib.check(lib.cfm_subsample_conv2_relu_split_bf16_f32(_fp32_planes, h1.data_ptr(), ws.data_ptr(), b2.data_ptr(),
-                                                               h2.data_ptr(), B, F1, T1, C, _stream()),
-                   "cfm_subsample_conv2_relu_split_bf16_f32")
+        _lib.call("cfm_subsample_conv2_relu_split_bf16_f32", _fp32_planes, h1.data_ptr(), ws.data_ptr(), b2.data_ptr(),
+                  h2.data_ptr(), B, F1, T1, C, _stream())
     else:
-        _lib.check(lib.cfm_subsample_conv2_relu_f32(h1.data_ptr(), w2p.data_ptr(), b2.data_ptr(), h2.data_ptr(), B, F1, T1,
-                                                    C, _stream()), "cfm_subsample_conv2_relu_f32")
+        _lib.call("cfm_subsample_conv2_relu_f32", h1.data_ptr(), w2p.data_ptr(), b2.data_ptr(), h2.data_ptr(), B, F1, T1, C,
+                  _stream())
 
 
 # ======================================================================================================
@@ -944,14 +906,12 @@ def layernorm_train(x, weight, bias, eps: float = 1e-5, for_gemm: bool = False):
     p16 = out16_ok(d) if for_gemm else 0
     if p16:
         y = torch.empty(x.shape, device=x.device, dtype=_DT16[p16])
-        _lib.check(_lib.load().cfm_layernorm_fwd_out16_f32(p16, x.data_ptr(), weight.data_ptr(), bias.data_ptr(), y.data_ptr(),
-                                                           mean.data_ptr(), rstd.data_ptr(), rows, d, eps, _stream()),
-                   "cfm_layernorm_fwd_out16_f32")
+        _lib.call("cfm_layernorm_fwd_out16_f32", p16, x.data_ptr(), weight.data_ptr(), bias.data_ptr(), y.data_ptr(),
+                  mean.data_ptr(), rstd.data_ptr(), rows, d, eps, _stream())
         return y, mean, rstd
     y = _f32_like(x)
-    st = _lib.load().cfm_layernorm_fwd_f32(x.data_ptr(), weight.data_ptr(), bias.data_ptr(), y.data_ptr(),
-                                           mean.data_ptr(), rstd.data_ptr(), rows, d, eps, _stream())
-    _lib.check(st, "cfm_layernorm_fwd_f32")
+    _lib.call("cfm_layernorm_fwd_f32", x.data_ptr(), weight.data_ptr(), bias.data_ptr(), y.data_ptr(), mean.data_ptr(),
+              rstd.data_ptr(), rows, d, eps, _stream())
     return y, mean, rstd
 
 
@@ -968,17 +928,13 @@ def layernorm_bwd(x, weight, dy, mean, rstd, dres=None):
     if d <= 2048:                                  # one pass over x and dy: input and parameter gradients together
         nws = int(lib.cfm_layernorm_bwd_workspace_bytes(rows, d))
         ws = torch.empty(nws // 4, device=x.device, dtype=torch.float32)
-        _lib.check(lib.cfm_layernorm_bwd_f32(x.data_ptr(), weight.data_ptr(), dy.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
-                                             _p(dres), dx.data_ptr(), dw.data_ptr(), db.data_ptr(), rows, d, ws.data_ptr(), nws,
-                                             _stream()),
-                   "cfm_layernorm_bwd_f32")
+        _lib.call("cfm_layernorm_bwd_f32", x.data_ptr(), weight.data_ptr(), dy.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
+                  _p(dres), dx.data_ptr(), dw.data_ptr(), db.data_ptr(), rows, d, ws.data_ptr(), nws, _stream())
         return dx, dw, db
-    _lib.check(lib.cfm_layernorm_bwd_dx_f32(x.data_ptr(), weight.data_ptr(), dy.data_ptr(), mean.data_ptr(),
-                                            rstd.data_ptr(), _p(dres), dx.data_ptr(), rows, d, _stream()),
-               "cfm_layernorm_bwd_dx_f32")
-    _lib.check(lib.cfm_layernorm_bwd_params_f32(x.data_ptr(), dy.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
-                                                dw.data_ptr(), db.data_ptr(), rows, d, _stream()),
-               "cfm_layernorm_bwd_params_f32")
+    _lib.call("cfm_layernorm_bwd_dx_f32", x.data_ptr(), weight.data_ptr(), dy.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
+              _p(dres), dx.data_ptr(), rows, d, _stream())
+    _lib.call("cfm_layernorm_bwd_params_f32", x.data_ptr(), dy.data_ptr(), mean.data_ptr(), rstd.data_ptr(), dw.data_ptr(),
+              db.data_ptr(), rows, d, _stream())
     return dx, dw, db
 
 
@@ -987,9 +943,8 @@ def linear_swish_save(a, w, b):
     a, w2, b, m, n, k = _gemm_common(a, w, b)
     c = torch.empty(*a.shape[:-1], n, device=a.device, dtype=torch.float32)
     z = _f32_like(c)
-    st = _lib.load().cfm_gemm_bias_swish_save_f32(a.data_ptr(), w2.data_ptr(), b.data_ptr(), c.data_ptr(), z.data_ptr(),
-                                                  m, n, k, k, n, _stream())
-    _lib.check(st, "cfm_gemm_bias_swish_save_f32")
+    _lib.call("cfm_gemm_bias_swish_save_f32", a.data_ptr(), w2.data_ptr(), b.data_ptr(), c.data_ptr(), z.data_ptr(), m, n, k, k, n,
+              _stream())
     return c, z
 
 
@@ -1047,9 +1002,8 @@ def linear_train(epi: str, a, w, b, *, residual=None, alpha: float = 1.0, drop_p
     if prec:
         _mfma16_gemm(prec, code, a, w2, b, c, m, n, k, residual, alpha, z, drop_p, seed)
         return (c, z) if save_z else c
-    st = _lib.load().cfm_gemm_train_f32(code, a.data_ptr(), w2.data_ptr(), b.data_ptr(), _p(residual), alpha, c.data_ptr(),
-                                        _p(z), m, n, k, k, n, n, float(drop_p), int(seed), _stream())
-    _lib.check(st, "cfm_gemm_train_f32")
+    _lib.call("cfm_gemm_train_f32", code, a.data_ptr(), w2.data_ptr(), b.data_ptr(), _p(residual), alpha, c.data_ptr(), _p(z), m, n,
+              k, k, n, n, float(drop_p), int(seed), _stream())
     return (c, z) if save_z else c
 
 
@@ -1062,14 +1016,13 @@ def dropout_apply(x, drop_p: float, seed: int, for_gemm: bool = False):
     prec = mfma16_prec() if for_gemm else 0
     if prec and x.numel() % 8 == 0 and x.shape[-1] % 8 == 0:
         y = torch.empty(x.shape, device=x.device, dtype=_DT16[prec])
-        _lib.check(_lib.load().cfm_dropout_out16_f32(prec, x.data_ptr(), y.data_ptr(), x.numel(), float(max(drop_p, 0.0)), int(seed),
-                                                     _stream()), "cfm_dropout_out16_f32")
+        _lib.call("cfm_dropout_out16_f32", prec, x.data_ptr(), y.data_ptr(), x.numel(), float(max(drop_p, 0.0)), int(seed),
+                  _stream())
         return y
     if drop_p <= 0.0:
         return x
     y = _f32_like(x)
-    _lib.check(_lib.load().cfm_dropout_f32(x.data_ptr(), y.data_ptr(), x.numel(), float(drop_p), int(seed), _stream()),
-               "cfm_dropout_f32")
+    _lib.call("cfm_dropout_f32", x.data_ptr(), y.data_ptr(), x.numel(), float(drop_p), int(seed), _stream())
     return y
 
 
@@ -1078,7 +1031,7 @@ def glu_fwd(z):
     n = z.shape[-1] // 2
     rows = z.numel() // (2 * n)
     y = torch.empty(*z.shape[:-1], n, device=z.device, dtype=torch.float32)
-    _lib.check(_lib.load().cfm_glu_fwd_f32(z.data_ptr(), y.data_ptr(), rows, n, _stream()), "cfm_glu_fwd_f32")
+    _lib.call("cfm_glu_fwd_f32", z.data_ptr(), y.data_ptr(), rows, n, _stream())
     return y
 
 
@@ -1091,12 +1044,10 @@ def glu_bwd(z, dy, for_gemm: bool = False):
     p16 = out16_ok(2 * n) if for_gemm and n % 8 == 0 else 0
     if p16:
         dz = torch.empty(z.shape, device=z.device, dtype=_DT16[p16])
-        _lib.check(_lib.load().cfm_glu_bwd_out16_f32(p16, z.data_ptr(), dy.data_ptr(), dz.data_ptr(), rows, n, _stream()),
-                   "cfm_glu_bwd_out16_f32")
+        _lib.call("cfm_glu_bwd_out16_f32", p16, z.data_ptr(), dy.data_ptr(), dz.data_ptr(), rows, n, _stream())
         return dz
     dz = _f32_like(z)
-    _lib.check(_lib.load().cfm_glu_bwd_f32(z.data_ptr(), dy.data_ptr(), dz.data_ptr(), rows, n, _stream()),
-               "cfm_glu_bwd_f32")
+    _lib.call("cfm_glu_bwd_f32", z.data_ptr(), dy.data_ptr(), dz.data_ptr(), rows, n, _stream())
     return dz
 
 
@@ -1107,8 +1058,7 @@ def colsum(x2d, alpha: float = 1.0, rows=None, cols=None, ld=None, out=None):
     ld = x2d.stride(0) if ld is None else ld
     if out is None:
         out = torch.zeros(cols, device=x2d.device, dtype=x2d.dtype)
-    _lib.check(_lib.load().cfm_colsum_f32(x2d.data_ptr(), ld, rows, cols, alpha, out.data_ptr(), _stream()),
-               "cfm_colsum_f32")
+    _lib.call("cfm_colsum_f32", x2d.data_ptr(), ld, rows, cols, alpha, out.data_ptr(), _stream())
     return out
 
 
@@ -1134,12 +1084,11 @@ def gemm_bwd(A, a_col: bool, B, b_col: bool, I: int, J: int, Kc: int, *, alpha: 
     tail = (ldb, _p(Z), int(z16), ldz, alpha, out.data_ptr() if c_ptr is None else c_ptr, ldc, int(c16), I, J, Kc, int(allow_split),
             int(accumulate), nbatch, nb1, sa[0], sa[1], sb[0], sb[1], sc[0], sc[1], float(drop_p), int(drop_seed))
     if prec:
-        _lib.check(_lib.load().cfm_gemm_bwd_batched_mfma16_f32(prec, *head, int(b16), *tail, int(pad4), _stream()),
-                   "cfm_gemm_bwd_batched_mfma16_f32")
+        _lib.call("cfm_gemm_bwd_batched_mfma16_f32", prec, *head, int(b16), *tail, int(pad4), _stream())
     else:
         if b16 or c16 or z16:
             raise _lib.ConformerHipError("16-bit operands / results need a 16-bit precision mode")
-        _lib.check(_lib.load().cfm_gemm_bwd_batched_f32(*head, *tail[:2], *tail[3:7], *tail[8:], _stream()), "cfm_gemm_bwd_batched_f32")
+        _lib.call("cfm_gemm_bwd_batched_f32", *head, *tail[:2], *tail[3:7], *tail[8:], _stream())
     return out
 
 
@@ -1178,17 +1127,16 @@ def linear_bwd(x2d, w, dy2d, *, alpha: float = 1.0, Z=None, need_dx: bool = True
         # dX = dY.W with a 16-bit dY: the forward kernel (row-major 16-bit A operand) on the cached transposed 16-bit weight
         wt16 = weight16(w2, prec, transposed=True)
         dx = torch.empty(m, k, device=dy2d.device, dtype=torch.float32)
-        _lib.check(_lib.load().cfm_gemm_mfma16_f32(prec, 0, dy2d.data_ptr(), 1, wt16.data_ptr(), 1, _zero_bias(k, dy2d.device).data_ptr(),
-                                                   None, 1.0, dx.data_ptr(), 0, None, 0, m, k, n, dy2d.stride(0), k, k, 0.0, 0, _stream()),
-                   "cfm_gemm_mfma16_f32")
+        _lib.call("cfm_gemm_mfma16_f32", prec, 0, dy2d.data_ptr(), 1, wt16.data_ptr(), 1, _zero_bias(k, dy2d.device).data_ptr(),
+                  None, 1.0, dx.data_ptr(), 0, None, 0, m, k, n, dy2d.stride(0), k, k, 0.0, 0, _stream())
     elif need_dx and prec and z_ok:
         # d(pre-activation) = alpha * (dY.W) * swish'(Z) [* dropout mask]: forward kernel (big tiles, deep prefetch) on the
         # cached transposed 16-bit weight, swish' fused in its row-major epilogue
         wt16 = weight16(w2, prec, transposed=True)
         dx = torch.empty(m, k, device=dy2d.device, dtype=_DT16[prec] if dx16 else torch.float32)
-        _lib.check(_lib.load().cfm_gemm_mfma16_f32(prec, 5, dy2d.data_ptr(), int(dy16), wt16.data_ptr(), 1, None, None, alpha, dx.data_ptr(),
-                                                   int(dx16), Z.data_ptr(), int(Z.dtype != torch.float32), m, k, n, dy2d.stride(0),
-                                                   Z.stride(0), k, float(drop_p), int(drop_seed), _stream()), "cfm_gemm_mfma16_f32")
+        _lib.call("cfm_gemm_mfma16_f32", prec, 5, dy2d.data_ptr(), int(dy16), wt16.data_ptr(), 1, None, None, alpha, dx.data_ptr(),
+                  int(dx16), Z.data_ptr(), int(Z.dtype != torch.float32), m, k, n, dy2d.stride(0), Z.stride(0), k, float(drop_p),
+                  int(drop_seed), _stream())
     elif need_dx:
         w16 = weight16(w2, prec) if prec else None              # the cast the forward made (same parameter version)
         # (a 16-bit dx feeds linear_bwd of the layer below, whose weight is (k, n'): it takes a 16-bit dY only when both k and
@@ -1202,9 +1150,8 @@ def linear_bwd(x2d, w, dy2d, *, alpha: float = 1.0, Z=None, need_dx: bool = True
             and x2d.stride(0) % (8 if x16 else 4) == 0 and dy2d.stride(0) % (8 if dy16 else 4) == 0
             and x2d.data_ptr() % 16 == 0 and dy2d.data_ptr() % 16 == 0):
         # weight and bias gradient in one kernel (gemm_dw16_impl.h): dY is read once
-        _lib.check(_lib.load().cfm_linear_bwd_weight_mfma16_f32(prec, dy2d.data_ptr(), int(dy16), dy2d.stride(0), x2d.data_ptr(),
-                                                                int(x16), x2d.stride(0), dw.data_ptr(), k, db.data_ptr(), n, k, m,
-                                                                alpha, _stream()), "cfm_linear_bwd_weight_mfma16_f32")
+        _lib.call("cfm_linear_bwd_weight_mfma16_f32", prec, dy2d.data_ptr(), int(dy16), dy2d.stride(0), x2d.data_ptr(), int(x16),
+                  x2d.stride(0), dw.data_ptr(), k, db.data_ptr(), n, k, m, alpha, _stream())
     else:
         if dy16:
             raise _lib.ConformerHipError("a 16-bit dY needs the aligned 16-bit weight-gradient kernel (N % 8 == 0, K % 8 == 0)")
@@ -1223,9 +1170,8 @@ def dwconv_bn_batch_stats(g, w, b, running_mean, running_var, momentum: float = 
     nws = int(lib.cfm_dwconv_bn_stats_workspace_bytes(B, T, C))
     buf = torch.empty(2 * C + (nws + 3) // 4, device=g.device, dtype=torch.float32)     # mean | var | per-workgroup partials
     mean, var, ws = buf[:C], buf[C:2 * C], buf[2 * C:]
-    st = lib.cfm_dwconv_bn_stats_f32(g.data_ptr(), w.data_ptr(), b.data_ptr(), mean.data_ptr(), var.data_ptr(),
-                                     _p(running_mean), _p(running_var), momentum, B, T, C, K, ws.data_ptr(), nws, _stream())
-    _lib.check(st, "cfm_dwconv_bn_stats_f32")
+    _lib.call("cfm_dwconv_bn_stats_f32", g.data_ptr(), w.data_ptr(), b.data_ptr(), mean.data_ptr(), var.data_ptr(),
+              _p(running_mean), _p(running_var), momentum, B, T, C, K, ws.data_ptr(), nws, _stream())
     return mean, var
 
 
@@ -1237,11 +1183,9 @@ def dwconv_bn_swish_bwd(g, dy, w, b, bn_w, bn_b, bn_mean, bn_var, eps: float = 1
     dc = _f32_like(g)
     dg = _f32_like(g)
     dw, db, dga, dbe = _zeros_split(g.device, g.dtype, tuple(w.shape), (C,), (C,), (C,))
-    st = _lib.load().cfm_dwconv_bn_swish_bwd_f32(g.data_ptr(), dy.data_ptr(), w.data_ptr(), b.data_ptr(), bn_w.data_ptr(),
-                                                 bn_b.data_ptr(), bn_mean.data_ptr(), bn_var.data_ptr(), eps,
-                                                 int(train_stats), dc.data_ptr(), dg.data_ptr(), dw.data_ptr(), db.data_ptr(),
-                                                 dga.data_ptr(), dbe.data_ptr(), B, T, C, K, _stream())
-    _lib.check(st, "cfm_dwconv_bn_swish_bwd_f32")
+    _lib.call("cfm_dwconv_bn_swish_bwd_f32", g.data_ptr(), dy.data_ptr(), w.data_ptr(), b.data_ptr(), bn_w.data_ptr(),
+              bn_b.data_ptr(), bn_mean.data_ptr(), bn_var.data_ptr(), eps, int(train_stats), dc.data_ptr(), dg.data_ptr(),
+              dw.data_ptr(), db.data_ptr(), dga.data_ptr(), dbe.data_ptr(), B, T, C, K, _stream())
     return dg, dw, db, dga, dbe
 
 
@@ -1264,16 +1208,12 @@ def relpos_attention_train(qkv, pos, u, v, lengths, n_heads, drop_p: float = 0.0
     base = qkv.data_ptr()
     prec = mfma16_prec()
     if prec:
-        st = _lib.load().cfm_relpos_attention_mfma16_f32(prec, base, base + 4 * d, base + 8 * d, d3, pos.data_ptr(),
-                                                         pos.stride(0), u.data_ptr(), v.data_ptr(), _p(lengths),
-                                                         ctx.data_ptr(), d, lse.data_ptr(), B, T, n_heads, dh, float(drop_p),
-                                                         int(seed), _stream())
-        _lib.check(st, "cfm_relpos_attention_mfma16_f32")
+        _lib.call("cfm_relpos_attention_mfma16_f32", prec, base, base + 4 * d, base + 8 * d, d3, pos.data_ptr(), pos.stride(0),
+                  u.data_ptr(), v.data_ptr(), _p(lengths), ctx.data_ptr(), d, lse.data_ptr(), B, T, n_heads, dh, float(drop_p),
+                  int(seed), _stream())
         return ctx, lse
-    st = _lib.load().cfm_relpos_attention_train_f32(base, base + 4 * d, base + 8 * d, d3, pos.data_ptr(), pos.stride(0),
-                                                    u.data_ptr(), v.data_ptr(), _p(lengths), ctx.data_ptr(), d,
-                                                    lse.data_ptr(), B, T, n_heads, dh, float(drop_p), int(seed), _stream())
-    _lib.check(st, "cfm_relpos_attention_train_f32")
+    _lib.call("cfm_relpos_attention_train_f32", base, base + 4 * d, base + 8 * d, d3, pos.data_ptr(), pos.stride(0), u.data_ptr(),
+              v.data_ptr(), _p(lengths), ctx.data_ptr(), d, lse.data_ptr(), B, T, n_heads, dh, float(drop_p), int(seed), _stream())
     return ctx, lse
 
 
@@ -1306,11 +1246,11 @@ def relpos_attention_bwd(qkv, pos, u, v, lengths, n_heads, ctx, lse, dctx, drop_
             du.data_ptr(), dvb.data_ptr(), B, T, n_heads, dh, float(drop_p), int(seed))
     prec = mfma16_prec()
     if prec and dh > 16:
-        _lib.check(_lib.load().cfm_relpos_attention_bwd_mfma16_f32(prec, *args, _stream()), "cfm_relpos_attention_bwd_mfma16_f32")
+        _lib.call("cfm_relpos_attention_bwd_mfma16_f32", prec, *args, _stream())
     else:
         # fp32 products; under autocast with heads of <= 16 dims (too few contraction terms for 16-bit products to average
         # out, and no matrix work worth saving) still the fp32 kernel, replaying the forward's operand rounding (`prec`)
-        _lib.check(_lib.load().cfm_relpos_attention_bwd_f32(*args, prec, _stream()), "cfm_relpos_attention_bwd_f32")
+        _lib.call("cfm_relpos_attention_bwd_f32", *args, prec, _stream())
     return dqkv, dpos, du, dvb
 
 
@@ -1323,19 +1263,17 @@ def subsample_stem_train(x, w1, b1, w2p, b2):
     C = w1.shape[0]
     F1, T1 = (F - 1) // 2, (T - 1) // 2
     F2, T2 = (F1 - 1) // 2, (T1 - 1) // 2
-    lib = _lib.load()
     p16 = out16_ok(C) if C % 64 == 0 and B * T1 * F1 * C < 2 ** 31 else 0
     if p16:
         # under autocast h1 only feeds the 16-bit conv2 GEMM (forward) and its weight-gradient GEMM (backward): stored in that type
         h1 = torch.empty(B, T1, F1, C, device=x.device, dtype=_DT16[p16])
-        _lib.check(lib.cfm_subsample_conv1_relu_out16_f32(p16, x.data_ptr(), w1.data_ptr(), b1.data_ptr(), h1.data_ptr(), B, F,
-                                                          T, C, _stream()), "cfm_subsample_conv1_relu_out16_f32")
+        _lib.call("cfm_subsample_conv1_relu_out16_f32", p16, x.data_ptr(), w1.data_ptr(), b1.data_ptr(), h1.data_ptr(), B, F, T, C,
+                  _stream())
     else:
         h1 = torch.empty(B, T1, F1, C, device=x.device, dtype=torch.float32)
-        _lib.check(lib.cfm_subsample_conv1_relu_f32(x.data_ptr(), w1.data_ptr(), b1.data_ptr(), h1.data_ptr(), B, F, T, C,
-                                                    _stream()), "cfm_subsample_conv1_relu_f32")
+        _lib.call("cfm_subsample_conv1_relu_f32", x.data_ptr(), w1.data_ptr(), b1.data_ptr(), h1.data_ptr(), B, F, T, C, _stream())
     h2 = torch.empty(B, T2, F2 * C, device=x.device, dtype=torch.float32)
-    _conv2_relu(lib, h1, w2p, b2, h2, B, F1, T1, C)
+    _conv2_relu(h1, w2p, b2, h2, B, F1, T1, C)
     return h2, h1
 
 
@@ -1356,25 +1294,21 @@ def subsample_stem_bwd(x, w1, b1, w2, h1, h2, dh2):
         # the all-16-bit stem backward of the autocast path: dz2 = relu'(h2) * dh2 only feeds the two conv2 gradient GEMMs (and
         # the bias gradient, which the weight-gradient kernel sums from the dz2 values it stages)
         dz2 = torch.empty(dh2.shape, device=x.device, dtype=_DT16[prec])
-        _lib.check(lib.cfm_relu_bwd_out16_f32(prec, h2.data_ptr(), dh2.data_ptr(), dz2.data_ptr(), dz2.numel(), _stream()),
-                   "cfm_relu_bwd_out16_f32")
+        _lib.call("cfm_relu_bwd_out16_f32", prec, h2.data_ptr(), dh2.data_ptr(), dz2.data_ptr(), dz2.numel(), _stream())
         rowtab = torch.empty(int(lib.cfm_subsample_conv2_rowtab_elems(B, F1, T1)), device=x.device, dtype=torch.int32)
-        _lib.check(lib.cfm_subsample_conv2_bwd_weight_h16_mfma16_f32(prec, dz2.data_ptr(), 1, h1.data_ptr(), rowtab.data_ptr(),
-                                                                     dw2p.data_ptr(), db2.data_ptr(), B, F1, T1, C, _stream()),
-                   "cfm_subsample_conv2_bwd_weight_h16_mfma16_f32")
+        _lib.call("cfm_subsample_conv2_bwd_weight_h16_mfma16_f32", prec, dz2.data_ptr(), 1, h1.data_ptr(), rowtab.data_ptr(),
+                  dw2p.data_ptr(), db2.data_ptr(), B, F1, T1, C, _stream())
     else:
         dz2 = _f32_like(dh2)
-        _lib.check(lib.cfm_relu_bwd_f32(h2.data_ptr(), dh2.data_ptr(), dz2.data_ptr(), dz2.numel(), _stream()),
-                   "cfm_relu_bwd_f32")
+        _lib.call("cfm_relu_bwd_f32", h2.data_ptr(), dh2.data_ptr(), dz2.data_ptr(), dz2.numel(), _stream())
         colsum(dz2.view(-1, C), out=db2)
         if prec:
-            _lib.check(lib.cfm_subsample_conv2_bwd_weight_mfma16_f32(prec, dz2.data_ptr(), h1.data_ptr(), dw2p.data_ptr(), B, F1,
-                                                                     T1, C, _stream()), "cfm_subsample_conv2_bwd_weight_mfma16_f32")
+            _lib.call("cfm_subsample_conv2_bwd_weight_mfma16_f32", prec, dz2.data_ptr(), h1.data_ptr(), dw2p.data_ptr(), B, F1, T1,
+                      C, _stream())
         else:
-            _lib.check(lib.cfm_subsample_conv2_bwd_weight_f32(dz2.data_ptr(), h1.data_ptr(), dw2p.data_ptr(), B, F1, T1, C,
-                                                              _stream()), "cfm_subsample_conv2_bwd_weight_f32")
+            _lib.call("cfm_subsample_conv2_bwd_weight_f32", dz2.data_ptr(), h1.data_ptr(), dw2p.data_ptr(), B, F1, T1, C, _stream())
     w2c = torch.empty(9 * C * C, device=x.device, dtype=torch.float32)
-    _lib.check(lib.cfm_pack_conv2_weight_t_f32(w2.data_ptr(), w2c.data_ptr(), C, _stream()), "cfm_pack_conv2_weight_t_f32")
+    _lib.call("cfm_pack_conv2_weight_t_f32", w2.data_ptr(), w2c.data_ptr(), C, _stream())
     # dh1: fp32, or -- all-16-bit stem of the autocast path -- in the 16-bit type: its only consumer is the conv1 parameter-gradient
     # reduction, and under torch.autocast conv1's incoming gradient is a 16-bit tensor.  (Never empty_like(h1) for the fp32 case:
     # h1 itself may be stored in the 16-bit type.)
@@ -1383,19 +1317,18 @@ def subsample_stem_bwd(x, w1, b1, w2, h1, h2, dh2):
     if prec:
         # transposed conv as four parity-class implicit GEMMs on the FORWARD 16-bit kernel (two-tile prefetch, row-major epilogue)
         w2c16 = torch.empty(9 * C * C, device=x.device, dtype=_DT16[prec])
-        _lib.check(lib.cfm_cast16_f32(prec, w2c.data_ptr(), w2c16.data_ptr(), w2c.numel(), _stream()), "cfm_cast16_f32")
-        fn = lib.cfm_subsample_conv2_bwd_input_fwdkernel_out16_mfma16_f32 if d16 else lib.cfm_subsample_conv2_bwd_input_fwdkernel_mfma16_f32
-        _lib.check(fn(prec, dz2.data_ptr(), int(dz2.dtype != torch.float32), w2c16.data_ptr(), _zero_bias(C, x.device).data_ptr(),
-                      dh1.data_ptr(), B, F1, T1, C, _stream()), "cfm_subsample_conv2_bwd_input_fwdkernel_mfma16_f32")
+        _lib.call("cfm_cast16_f32", prec, w2c.data_ptr(), w2c16.data_ptr(), w2c.numel(), _stream())
+        _lib.call("cfm_subsample_conv2_bwd_input_fwdkernel_out16_mfma16_f32" if d16 else "cfm_subsample_conv2_bwd_input_fwdkernel_mfma16_f32",
+                  prec, dz2.data_ptr(), int(dz2.dtype != torch.float32), w2c16.data_ptr(), _zero_bias(C, x.device).data_ptr(),
+                  dh1.data_ptr(), B, F1, T1, C, _stream())
     else:
-        _lib.check(lib.cfm_subsample_conv2_bwd_input_f32(dz2.data_ptr(), w2c.data_ptr(), dh1.data_ptr(), B, F1, T1, C,
-                                                         _stream()), "cfm_subsample_conv2_bwd_input_f32")
+        _lib.call("cfm_subsample_conv2_bwd_input_f32", dz2.data_ptr(), w2c.data_ptr(), dh1.data_ptr(), B, F1, T1, C, _stream())
     if d16:
-        _lib.check(lib.cfm_subsample_conv1_bwd_d16_f32(prec, x.data_ptr(), w1.data_ptr(), b1.data_ptr(), dh1.data_ptr(), dw1.data_ptr(),
-                                                       db1.data_ptr(), B, F, T, C, _stream()), "cfm_subsample_conv1_bwd_d16_f32")
+        _lib.call("cfm_subsample_conv1_bwd_d16_f32", prec, x.data_ptr(), w1.data_ptr(), b1.data_ptr(), dh1.data_ptr(),
+                  dw1.data_ptr(), db1.data_ptr(), B, F, T, C, _stream())
     else:
-        _lib.check(lib.cfm_subsample_conv1_bwd_f32(x.data_ptr(), w1.data_ptr(), b1.data_ptr(), dh1.data_ptr(), dw1.data_ptr(),
-                                                   db1.data_ptr(), B, F, T, C, _stream()), "cfm_subsample_conv1_bwd_f32")
+        _lib.call("cfm_subsample_conv1_bwd_f32", x.data_ptr(), w1.data_ptr(), b1.data_ptr(), dh1.data_ptr(), dw1.data_ptr(),
+                  db1.data_ptr(), B, F, T, C, _stream())
     dw2 = dw2p.view(C, 3, 3, C).permute(0, 3, 1, 2).contiguous()        # packed (co,kf,kt,ci) -> (co,ci,kf,kt): tiny glue
     return dw1, db1, dw2, db2
 
@@ -1439,13 +1372,11 @@ def lstm_recurrence(gx, w_hh, lengths=None, save: bool = False, state=None):
         # W_hh in MFMA fragment order (H/8, H/16, 2, 32, 8): one contiguous 1 KB block per workgroup and contraction step
         w16 = w16.view(4, H // 8, 8, H // 16, 2, 8).permute(1, 3, 4, 0, 2, 5).contiguous()
         if hs is not None:
-            _lib.check(_lib.load().cfm_lstm_fwd_mfma16_carry_f32(prec, gx.data_ptr(), w16.data_ptr(), _p(lengths), y.data_ptr(),
-                                                                 hs.data_ptr(), c.data_ptr(), h16.data_ptr(), _p(gates), _p(cells),
-                                                                 B, T, H, _stream()), "cfm_lstm_fwd_mfma16_carry_f32")
+            _lib.call("cfm_lstm_fwd_mfma16_carry_f32", prec, gx.data_ptr(), w16.data_ptr(), _p(lengths), y.data_ptr(),
+                      hs.data_ptr(), c.data_ptr(), h16.data_ptr(), _p(gates), _p(cells), B, T, H, _stream())
             return (y, gates, cells) if save else y
-        _lib.check(_lib.load().cfm_lstm_fwd_mfma16_f32(prec, gx.data_ptr(), w16.data_ptr(), _p(lengths), y.data_ptr(), c.data_ptr(),
-                                                       h16.data_ptr(), _p(gates), _p(cells), B, T, H, _stream()),
-                   "cfm_lstm_fwd_mfma16_f32")
+        _lib.call("cfm_lstm_fwd_mfma16_f32", prec, gx.data_ptr(), w16.data_ptr(), _p(lengths), y.data_ptr(), c.data_ptr(),
+                  h16.data_ptr(), _p(gates), _p(cells), B, T, H, _stream())
         return (y, gates, cells) if save else y
     if H % 16 == 0:
         # fp32 recurrence with both operands in MFMA fragment order (bit-identical to the row-major kernel, fewer cache
@@ -1453,20 +1384,18 @@ def lstm_recurrence(gx, w_hh, lengths=None, save: bool = False, state=None):
         wf = w_hh.view(4, H // 4, 4, H // 16, 4, 4).permute(1, 3, 4, 0, 2, 5).contiguous()
         hf = torch.empty(2 * ((B + 15) // 16) * 16 * H, device=gx.device, dtype=torch.float32)
         if hs is not None:
-            _lib.check(_lib.load().cfm_lstm_fwd_frag_carry_f32(gx.data_ptr(), wf.data_ptr(), _p(lengths), y.data_ptr(), hs.data_ptr(),
-                                                               c.data_ptr(), hf.data_ptr(), _p(gates), _p(cells), B, T, H, _stream()),
-                       "cfm_lstm_fwd_frag_carry_f32")
+            _lib.call("cfm_lstm_fwd_frag_carry_f32", gx.data_ptr(), wf.data_ptr(), _p(lengths), y.data_ptr(), hs.data_ptr(),
+                      c.data_ptr(), hf.data_ptr(), _p(gates), _p(cells), B, T, H, _stream())
             return (y, gates, cells) if save else y
-        _lib.check(_lib.load().cfm_lstm_fwd_frag_f32(gx.data_ptr(), wf.data_ptr(), _p(lengths), y.data_ptr(), c.data_ptr(),
-                                                     hf.data_ptr(), _p(gates), _p(cells), B, T, H, _stream()),
-                   "cfm_lstm_fwd_frag_f32")
+        _lib.call("cfm_lstm_fwd_frag_f32", gx.data_ptr(), wf.data_ptr(), _p(lengths), y.data_ptr(), c.data_ptr(), hf.data_ptr(),
+                  _p(gates), _p(cells), B, T, H, _stream())
         return (y, gates, cells) if save else y
     if hs is not None:
-        _lib.check(_lib.load().cfm_lstm_fwd_carry_f32(gx.data_ptr(), w_hh.data_ptr(), _p(lengths), y.data_ptr(), hs.data_ptr(),
-                                                      c.data_ptr(), _p(gates), _p(cells), B, T, H, _stream()), "cfm_lstm_fwd_carry_f32")
+        _lib.call("cfm_lstm_fwd_carry_f32", gx.data_ptr(), w_hh.data_ptr(), _p(lengths), y.data_ptr(), hs.data_ptr(), c.data_ptr(),
+                  _p(gates), _p(cells), B, T, H, _stream())
         return (y, gates, cells) if save else y
-    _lib.check(_lib.load().cfm_lstm_fwd_f32(gx.data_ptr(), w_hh.data_ptr(), _p(lengths), y.data_ptr(), c.data_ptr(), _p(gates),
-                                            _p(cells), B, T, H, _stream()), "cfm_lstm_fwd_f32")
+    _lib.call("cfm_lstm_fwd_f32", gx.data_ptr(), w_hh.data_ptr(), _p(lengths), y.data_ptr(), c.data_ptr(), _p(gates), _p(cells), B,
+              T, H, _stream())
     return (y, gates, cells) if save else y
 
 
@@ -1474,17 +1403,15 @@ def swish_bn_eval(h, bn_mean, bn_var, bn_weight, bn_bias, eps: float = 1e-5):
     h = _req(h, "h")
     C = h.shape[-1]
     out = _f32_like(h)
-    _lib.check(_lib.load().cfm_swish_bn_eval_f32(h.data_ptr(), _req(bn_mean, "bn_mean").data_ptr(),
-                                                 _req(bn_var, "bn_var").data_ptr(), _req(bn_weight, "bn_weight").data_ptr(),
-                                                 _req(bn_bias, "bn_bias").data_ptr(), eps, out.data_ptr(), h.numel() // C, C,
-                                                 _stream()), "cfm_swish_bn_eval_f32")
+    _lib.call("cfm_swish_bn_eval_f32", h.data_ptr(), _req(bn_mean, "bn_mean").data_ptr(), _req(bn_var, "bn_var").data_ptr(),
+              _req(bn_weight, "bn_weight").data_ptr(), _req(bn_bias, "bn_bias").data_ptr(), eps, out.data_ptr(), h.numel() // C, C,
+              _stream())
     return out
 
 
 def lstm_backward(x, w_ih, w_hh, y, gates, cells, dy, lengths=None, need_dx: bool = True):
     """Backward of lstm_forward(save=True): returns (dx or None, dw_ih, dw_hh, dbias) with dbias = d/d(b_ih) = d/d(b_hh).
     The time recursion yields dG (B,T,4H); the weight / input gradients are dense GEMMs over all frames."""
-    lib = _lib.load()
     B, T, D = x.shape
     H = w_hh.shape[1]
     dy = _req(dy, "dy")
@@ -1496,20 +1423,18 @@ def lstm_backward(x, w_ih, w_hh, y, gates, cells, dy, lengths=None, need_dx: boo
         # W_hh^T (H,4H) in MFMA fragment order (H/16, 4H/16, 2, 16, 8); dG_t exchanged between steps in the same order
         wt16 = wt16.view(H // 16, 16, 4 * H // 16, 2, 8).permute(0, 2, 3, 1, 4).contiguous()
         dg16 = torch.empty(2 * ((B + 15) // 16) * 16 * 4 * H, device=x.device, dtype=_DT16[prec])
-        _lib.check(lib.cfm_lstm_bwd_mfma16_f32(prec, dy.data_ptr(), gates.data_ptr(), cells.data_ptr(), wt16.data_ptr(), _p(lengths),
-                                               dG.data_ptr(), dc.data_ptr(), dg16.data_ptr(), B, T, H, _stream()),
-                   "cfm_lstm_bwd_mfma16_f32")
+        _lib.call("cfm_lstm_bwd_mfma16_f32", prec, dy.data_ptr(), gates.data_ptr(), cells.data_ptr(), wt16.data_ptr(), _p(lengths),
+                  dG.data_ptr(), dc.data_ptr(), dg16.data_ptr(), B, T, H, _stream())
     elif H % 16 == 0:
         # fp32: W_hh^T (H,4H) -> (H/16, 4H/16, kq 4, unit 16, 4); dG_t exchanged between steps in the same order
         wtf = w_hh.t().reshape(H // 16, 16, 4 * H // 16, 4, 4).permute(0, 2, 3, 1, 4).contiguous()
         dgf = torch.empty(2 * ((B + 15) // 16) * 16 * 4 * H, device=x.device, dtype=torch.float32)
-        _lib.check(lib.cfm_lstm_bwd_frag_f32(dy.data_ptr(), gates.data_ptr(), cells.data_ptr(), wtf.data_ptr(), _p(lengths),
-                                             dG.data_ptr(), dc.data_ptr(), dgf.data_ptr(), B, T, H, _stream()),
-                   "cfm_lstm_bwd_frag_f32")
+        _lib.call("cfm_lstm_bwd_frag_f32", dy.data_ptr(), gates.data_ptr(), cells.data_ptr(), wtf.data_ptr(), _p(lengths),
+                  dG.data_ptr(), dc.data_ptr(), dgf.data_ptr(), B, T, H, _stream())
     else:
         whh_t = w_hh.t().contiguous()                                 # (H,4H): 6.5 MB of glue per step
-        _lib.check(lib.cfm_lstm_bwd_f32(dy.data_ptr(), gates.data_ptr(), cells.data_ptr(), whh_t.data_ptr(), _p(lengths),
-                                        dG.data_ptr(), dc.data_ptr(), B, T, H, _stream()), "cfm_lstm_bwd_f32")
+        _lib.call("cfm_lstm_bwd_f32", dy.data_ptr(), gates.data_ptr(), cells.data_ptr(), whh_t.data_ptr(), _p(lengths),
+                  dG.data_ptr(), dc.data_ptr(), B, T, H, _stream())
     dG2, x2 = dG.view(B * T, 4 * H), x.reshape(B * T, D)
     h_prev = torch.zeros(y.shape, device=y.device, dtype=torch.float32)                                      # h_{t-1}: y shifted by one frame per utterance
     h_prev[:, 1:] = y[:, :-1]
@@ -1527,9 +1452,8 @@ def swish_bn_batch_stats(h, running_mean, running_var, momentum: float = 0.1):
     C = h.shape[-1]
     mean = torch.empty(C, device=h.device, dtype=torch.float32)
     var = torch.empty(C, device=h.device, dtype=torch.float32)
-    _lib.check(_lib.load().cfm_swish_bn_stats_f32(h.data_ptr(), mean.data_ptr(), var.data_ptr(), _p(running_mean),
-                                                  _p(running_var), momentum, h.numel() // C, C, _stream()),
-               "cfm_swish_bn_stats_f32")
+    _lib.call("cfm_swish_bn_stats_f32", h.data_ptr(), mean.data_ptr(), var.data_ptr(), _p(running_mean), _p(running_var), momentum,
+              h.numel() // C, C, _stream())
     return mean, var
 
 
@@ -1539,14 +1463,13 @@ def swish_bn_bwd(h, dz, bn_mean, bn_var, bn_weight, eps: float = 1e-5, train_sta
     C = h.shape[-1]
     dh = _f32_like(h)
     dga, dbe = _zeros_split(h.device, h.dtype, (C,), (C,))
-    _lib.check(_lib.load().cfm_swish_bn_bwd_f32(h.data_ptr(), dz.data_ptr(), bn_mean.data_ptr(), bn_var.data_ptr(),
-                                                bn_weight.data_ptr(), eps, int(train_stats), dh.data_ptr(), dga.data_ptr(),
-                                                dbe.data_ptr(), h.numel() // C, C, _stream()), "cfm_swish_bn_bwd_f32")
+    _lib.call("cfm_swish_bn_bwd_f32", h.data_ptr(), dz.data_ptr(), bn_mean.data_ptr(), bn_var.data_ptr(), bn_weight.data_ptr(), eps,
+              int(train_stats), dh.data_ptr(), dga.data_ptr(), dbe.data_ptr(), h.numel() // C, C, _stream())
     return dh, dga, dbe
 
 
 # ---- N1 loss: CTC over the logits (log-softmax folded in), evaluation.py:12-16 ------------------------------------------------
-CTC_MAX_TARGET = 1023            # CFM_CTC_MAX_TARGET
+CTC_MAX_TARGET = _lib.CONSTANTS["CFM_CTC_MAX_TARGET"]
 
 
 def _ctc_geometry(logits, targets, input_lengths, target_lengths):
@@ -1582,9 +1505,8 @@ def ctc_loss_forward(logits, targets, input_lengths, target_lengths, blank: int 
     lib = _lib.load()
     ws = torch.empty(int(lib.cfm_ctc_workspace_floats(B, T, lmax)), device=logits.device, dtype=torch.float32)
     loss = torch.empty((), device=logits.device, dtype=torch.float32)
-    _lib.check(lib.cfm_ctc_loss_fwd_f32(logits.data_ptr(), targets.data_ptr(), _p(off), stride, targets.numel(),
-                                        in_len.data_ptr(), tg_len.data_ptr(), B, T, V, lmax, int(blank), ws.data_ptr(),
-                                        loss.data_ptr(), _stream()), "cfm_ctc_loss_fwd_f32")
+    _lib.call("cfm_ctc_loss_fwd_f32", logits.data_ptr(), targets.data_ptr(), _p(off), stride, targets.numel(), in_len.data_ptr(),
+              tg_len.data_ptr(), B, T, V, lmax, int(blank), ws.data_ptr(), loss.data_ptr(), _stream())
     return loss, (logits, targets, off, stride, in_len, tg_len, lmax, int(blank), ws)
 
 
@@ -1593,9 +1515,8 @@ def ctc_loss_backward(ctx, grad_out):
     B, T, V = logits.shape
     g = _req(grad_out.reshape(1), "grad_out")
     dlogits = _f32_like(logits)
-    _lib.check(_lib.load().cfm_ctc_loss_bwd_f32(logits.data_ptr(), targets.data_ptr(), _p(off), stride, targets.numel(),
-                                                in_len.data_ptr(), tg_len.data_ptr(), B, T, V, lmax, blank, ws.data_ptr(),
-                                                g.data_ptr(), dlogits.data_ptr(), _stream()), "cfm_ctc_loss_bwd_f32")
+    _lib.call("cfm_ctc_loss_bwd_f32", logits.data_ptr(), targets.data_ptr(), _p(off), stride, targets.numel(), in_len.data_ptr(),
+              tg_len.data_ptr(), B, T, V, lmax, blank, ws.data_ptr(), g.data_ptr(), dlogits.data_ptr(), _stream())
     return dlogits
 
 

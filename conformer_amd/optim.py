@@ -14,8 +14,8 @@ import torch
 from . import _lib, ops
 
 class _AdamTensor(ctypes.Structure):      # cfm_adam_tensor, include/conformer_hip.h
-    _fields_ = [("p", ctypes.c_void_p), ("g", ctypes.c_void_p), ("m", ctypes.c_void_p), ("v", ctypes.c_void_p),
-                ("n", ctypes.c_int64)]
+    _fields_ = [("param", ctypes.c_void_p), ("grad", ctypes.c_void_p), ("exp_avg", ctypes.c_void_p),
+                ("exp_avg_sq", ctypes.c_void_p), ("numel", ctypes.c_int64)]
 
 
 class FusedAdam(torch.optim.Optimizer):
@@ -39,8 +39,8 @@ class FusedAdam(torch.optim.Optimizer):
             self._tables[group_idx] = hit
         arr = hit[1]
         for i, p in enumerate(plist):
-            arr[i].g = p.grad.data_ptr()
-            arr[i].p = p.data_ptr()
+            arr[i].grad = p.grad.data_ptr()
+            arr[i].param = p.data_ptr()
         return arr
 
     @torch.no_grad()
@@ -69,9 +69,8 @@ class FusedAdam(torch.optim.Optimizer):
             step = self._steps[gi] = self._steps[gi] + 1
             b1, b2 = group["betas"]
             arr = self._table(gi, plist)
-            _lib.check(_lib.load().cfm_adam_step_f32(ctypes.addressof(arr), len(plist), float(group["lr"]), b1, b2, group["eps"],
-                                                     1.0 - b1 ** step, math.sqrt(1.0 - b2 ** step), ops._stream()),
-                       "cfm_adam_step_f32")
+            _lib.call("cfm_adam_step_f32", ctypes.addressof(arr), len(plist), float(group["lr"]), b1, b2, group["eps"],
+                      1.0 - b1 ** step, math.sqrt(1.0 - b2 ** step), ops._stream())
             # the kernel wrote through raw pointers: tell autograd (and every cache keyed on `_version`: the packed / fused /
             # 16-bit weight copies of the modules and of ops.weight16) that the parameters changed in place
             torch.autograd.graph.increment_version(plist)

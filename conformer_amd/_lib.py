@@ -14,6 +14,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # (CONFORMER_AMD_LIB: A/B a differently built library from tools/*, development only)
 LIB_PATH = os.environ.get("CONFORMER_AMD_LIB") or os.path.join(_HERE, "lib", "libconformer_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "conformer_hip.h")
+# entries added to the library without touching the main header (no existing signature moves, so the ABI revision stays)
+EXT_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "conformer_hip_window.h")
 _CTYPES = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "float": ctypes.c_float, "double": ctypes.c_double,
            "uint64_t": ctypes.c_uint64, "size_t": ctypes.c_size_t, "cfm_stream_t": ctypes.c_void_p}
 _DECL = re.compile(r"^[ \t]*((?:const\s+)?\w+[\s*]+?)(cfm_\w+)\s*\(([^()]*)\)\s*;", re.M)
@@ -59,6 +61,13 @@ if not os.path.exists(HEADER_PATH):
 with open(HEADER_PATH) as _f:
     SIGNATURES, PARAMS, CONSTANTS = parse_header(_f.read())
 ABI_VERSION = CONSTANTS["CFM_ABI_VERSION"]        # checked in load()
+if not os.path.exists(EXT_HEADER_PATH):
+    raise ConformerHipError(f"{EXT_HEADER_PATH} is missing: the ctypes binding is derived from it")
+with open(EXT_HEADER_PATH) as _f:
+    EXT_SIGNATURES, _ext_params, _ = parse_header(_f.read())
+if set(EXT_SIGNATURES) & set(SIGNATURES):
+    raise ConformerHipError(f"{EXT_HEADER_PATH} declares again: {sorted(set(EXT_SIGNATURES) & set(SIGNATURES))}")
+PARAMS.update(_ext_params)                        # (`call` names a parameter of either header)
 
 _lib = None
 
@@ -86,6 +95,14 @@ def load() -> ctypes.CDLL:
                                 "`python -m conformer_amd.build`")
     for name, (res, args) in SIGNATURES.items():
         fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    for name, (res, args) in EXT_SIGNATURES.items():
+        # same ABI revision, newer entry: a library built before include/conformer_hip_window.h existed passes the check above
+        fn = getattr(lib, name, None)
+        if fn is None:
+            raise ConformerHipError(f"{LIB_PATH} lacks {name} (include/conformer_hip_window.h): rebuild it with "
+                                    "`python -m conformer_amd.build`")
         fn.restype = res
         fn.argtypes = args
     _lib = lib

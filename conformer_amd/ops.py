@@ -699,6 +699,55 @@ def relpos_attention_slots(qkv: torch.Tensor, pos: torch.Tensor, u: torch.Tensor
     return ctx
 
 
+def relpos_attention_window(qkv: torch.Tensor, pos: torch.Tensor, u: torch.Tensor, v: torch.Tensor, n_heads: int,
+                            q_begin: torch.Tensor, q_count: torch.Tensor, q_max: int, left: int,
+                            ctx: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Windowed attention of independent streams over RING caches (bounded-history streaming): qkv (S,R,3d) holds frame n of
+    slot b in row n mod R; pos (2P-1, d) is the projected table, row P-1-r for the relative position r.  Slot b computes the
+    queries i = q_begin[b] + il, il < q_count[b], against the keys max(0, i-left) <= j < q_begin[b]+q_count[b] into the COMPACT
+    rows ctx[b, :q_count[b]] of ctx (S,q_max,d); rows q_count[b]..q_max-1 are zeros.  q_begin (absolute frame index, unbounded),
+    q_count: (S) int64 device tensors (nothing synchronises; the kernel clamps them).  R % 32 == 0, R >= left + q_max,
+    P >= max(left+1, q_max).  fp32 only: under torch.autocast this raises (no 16-bit window kernel)."""
+    if mfma16_prec() != PREC_F32:
+        raise NotImplementedError("relpos_attention_window: fp32 only; there is no 16-bit window kernel (leave torch.autocast)")
+    u = _req(u, "content_bias"); v = _req(v, "position_bias")
+    qkv = _req(qkv, "qkv")
+    if qkv.dim() != 3 or qkv.shape[-1] % 3:
+        raise _lib.ConformerHipError(f"relpos_attention_window: qkv: expected a (S,R,3d) ring, got {tuple(qkv.shape)}")
+    B, R, d3 = qkv.shape
+    d = d3 // 3
+    q_max, left = int(q_max), int(left)
+    if not qkv.is_contiguous():
+        raise _lib.ConformerHipError("relpos_attention_window: qkv (S,R,3d) must be a contiguous ring buffer")
+    if not (isinstance(pos, torch.Tensor) and pos.is_cuda and pos.dtype == torch.float32 and pos.dim() == 2
+            and pos.stride(1) == 1 and pos.shape[1] == d and pos.shape[0] % 2 == 1):
+        raise _lib.ConformerHipError(f"pos: expected a (2P-1,{d}) fp32 HIP tensor with unit column stride")
+    P = (pos.shape[0] + 1) // 2
+    if left < 0 or q_max < 1:
+        raise _lib.ConformerHipError(f"relpos_attention_window: left = {left} (>= 0) and q_max = {q_max} (>= 1)")
+    if R % 32 or R < left + q_max:
+        raise _lib.ConformerHipError(f"relpos_attention_window: a ring of R = {R} rows: R % 32 == 0 and R >= left + q_max = "
+                                     f"{left + q_max}")
+    if P < max(left + 1, q_max):
+        raise _lib.ConformerHipError(f"relpos_attention_window: a table for P = {P} positions: P >= max(left + 1, q_max) = "
+                                     f"{max(left + 1, q_max)}")
+    if ctx is None:
+        ctx = torch.empty(B, q_max, d, device=qkv.device, dtype=torch.float32)
+    ctx = _req(ctx, "ctx")
+    if ctx.shape != (B, q_max, d) or not ctx.is_contiguous():
+        raise _lib.ConformerHipError(f"relpos_attention_window: ctx must be a contiguous ({B},{q_max},{d}) tensor")
+    q_begin = _req(q_begin, "q_begin", torch.int64)
+    q_count = _req(q_count, "q_count", torch.int64)
+    for name, t in (("q_begin", q_begin), ("q_count", q_count)):
+        if t.shape != (B,) or not t.is_contiguous():
+            raise _lib.ConformerHipError(f"relpos_attention_window: {name} must be a contiguous ({B},) int64 tensor")
+    base = qkv.data_ptr()
+    _lib.call("cfm_relpos_attention_window_f32", base, base + 4 * d, base + 8 * d, d3, pos.data_ptr(), pos.stride(0), P,
+              u.data_ptr(), v.data_ptr(), q_begin.data_ptr(), q_count.data_ptr(), ctx.data_ptr(), d, B, R, n_heads, d // n_heads,
+              q_max, left, _stream())
+    return ctx
+
+
 def dwconv_bn_swish(g, w, b, bn_w, bn_b, bn_mean, bn_var, eps: float = 1e-5, for_gemm: bool = False) -> torch.Tensor:
     """for_gemm: see layernorm (the result feeds the pointwise_conv_2 GEMM of contraction length C)."""
     g = _req(g, "g"); w = _req(w, "dw weight"); b = _req(b, "dw bias")

@@ -21,6 +21,10 @@ step inside its own torch.autocast of that type, keeps the per-layer K/V caches 
 attention core would round to anyway: half the cache bytes, no change in arithmetic) and attends with the 16-bit slots kernel
 (cfm_relpos_attention_slots_mfma16_f32).  The depthwise state, the mel tail, the LSTM state and what step() returns stay fp32.  A
 stream must not change precision between chunks, so ambient autocast of another type is refused.
+
+Bounded history (`left_context=`, `max_chunk_mel_frames=`: streaming.py): every slot's caches are rings (S, R, 3d) and the window
+kernel attends; a reopened slot starts again at frame 0 over whatever its ring still holds, which the kernel never reads (rows
+outside a query's window are selected away at staging).  fp32 only.
 """
 from __future__ import annotations
 
@@ -34,7 +38,7 @@ from . import ops
 from .decode import BeamCTCDecoder, beam_ctc_stream_finish, beam_ctc_stream_init, beam_ctc_stream_reset_slots, \
     beam_ctc_stream_step
 from .model.modules.encoder import Encoder
-from .streaming import StreamingEncoder, encoder_frames
+from .streaming import StreamingEncoder, _refuse_window_autocast, encoder_frames
 from .transcribe import decode_frames, lstm_state
 
 _TAIL = 8                  # mel-tail buffer width: a slot carries 0..6 un-consumed frames
@@ -50,6 +54,19 @@ def slot_plan(tails: Sequence[int], frames: Sequence[int]) -> Tuple[List[int], L
         ks.append(k)
         new_tails.append(total - 4 * k)
     return ks, new_tails
+
+
+def append_rows(n0: Sequence[int], ks: Sequence[int], k_max: int, t_max: Optional[int],
+                ring: Optional[int] = None) -> Tuple[List[int], List[int]]:
+    """The cache append of one step as flat row indices: compact row b*k_max + r of the new (S, k_max, .) rows goes to row
+    n0[b] + r of slot b's linear cache (S, t_max, .), or, ring caches (S, ring, .), to row (n0[b] + r) mod ring."""
+    S = len(ks)
+    src = [b * k_max + r for b in range(S) for r in range(ks[b])]
+    if ring is None:
+        dst = [b * t_max + n0[b] + r for b in range(S) for r in range(ks[b])]
+    else:
+        dst = [b * ring + (n0[b] + r) % ring for b in range(S) for r in range(ks[b])]
+    return src, dst
 
 
 def _slot_dtype(who: str, dtype: Optional[torch.dtype]) -> Optional[torch.dtype]:
@@ -81,10 +98,9 @@ def _autocast(dtype: Optional[torch.dtype]):
 class _Step:
     """Device views of one step's per-slot offsets (one pinned host buffer, one non-blocking copy)."""
 
-    def __init__(self, dev: torch.device, tails, totals, n0, ks, k_max: int, t_max: int) -> None:
+    def __init__(self, dev: torch.device, tails, totals, n0, ks, k_max: int, t_max: int, ring: Optional[int] = None) -> None:
         S = len(ks)
-        src = [b * k_max + r for b in range(S) for r in range(ks[b])]          # compact row -> cache row of the append
-        dst = [b * t_max + n0[b] + r for b in range(S) for r in range(ks[b])]
+        src, dst = append_rows(n0, ks, k_max, t_max, ring)
         nk = len(src)
         host = torch.empty(5 * S + 2 * nk, dtype=torch.int64, pin_memory=True)
         h = host.numpy()
@@ -95,7 +111,7 @@ class _Step:
         self.tail, self.total, self.q_begin, self.k, self.lengths = (d[j * S:(j + 1) * S] for j in range(5))
         self.src, self.dst = d[5 * S:5 * S + nk], d[5 * S + nk:]
         self.nk, self.k_max = nk, k_max
-        self.keys_hint = max(a + b for a, b in zip(n0, ks))
+        self.keys_hint = max(a + b for a, b in zip(n0, ks))                    # (windowed: unused, and no bound on it)
         self._keep: Dict[int, torch.Tensor] = {}
         self._mask: Optional[torch.Tensor] = None
 
@@ -131,6 +147,9 @@ class _SlotStream:
         st, cur, i, d = self.st, self.cur, self.i, self.st.d
         if cur.nk:
             st.qkv[i].view(-1, 3 * d).index_copy_(0, cur.dst, qkv_new.reshape(-1, 3 * d).index_select(0, cur.src))
+        if st.left is not None:
+            return ops.relpos_attention_window(st.qkv[i], st.pos_all[:, i * d:(i + 1) * d], a.content_bias, a.position_bias,
+                                               a.n_heads, cur.q_begin, cur.k, cur.k_max, st.left)
         return ops.relpos_attention_slots(st.qkv[i], st.pos_all[:, i * d:(i + 1) * d], a.content_bias, a.position_bias,
                                           st.lengths, a.n_heads, cur.q_begin, cur.k, cur.k_max, keys_hint=cur.keys_hint)
 
@@ -149,19 +168,25 @@ class SlotStreamingEncoder(StreamingEncoder):
     open(s) starts a stream in a free slot, step(mel, frames) feeds every slot its own number of new frames, close(s) frees the
     slot.  Returns compact rows: step -> ((S, k_max, d), k) with slot b's new encoder frames in rows 0 .. k[b]-1.
     dtype: None / torch.float32, or torch.bfloat16 / torch.float16 -- the precision of every stream of this object (module
-    docstring): 16-bit K/V caches (d % 8 == 0), every step under its own autocast."""
+    docstring): 16-bit K/V caches (d % 8 == 0), every step under its own autocast.
+    left_context, max_chunk_mel_frames: bounded history over ring caches as StreamingEncoder (a slot may then bring at most
+    max_chunk_mel_frames mel frames per step, and max_mel_frames=None lifts the limit per stream); fp32 only."""
 
-    def __init__(self, encoder: Encoder, slots: int, max_mel_frames: int, dtype: Optional[torch.dtype] = None) -> None:
+    def __init__(self, encoder: Encoder, slots: int, max_mel_frames: Optional[int] = None, dtype: Optional[torch.dtype] = None, *,
+                 left_context: Optional[int] = None, max_chunk_mel_frames: Optional[int] = None) -> None:
         self.dtype = _slot_dtype("SlotStreamingEncoder", dtype)
+        if self.dtype is not None and left_context is not None:
+            raise NotImplementedError(f"SlotStreamingEncoder: left_context with dtype={self.dtype} (no 16-bit window kernel yet)")
         if self.dtype is not None:
             d = encoder.linear.out_features
             if d % 8:
                 raise ValueError(f"SlotStreamingEncoder: a {self.dtype} K/V cache needs d % 8 == 0, got d = {d}")
             self.cache_dtype = self.dtype                                  # (read by StreamingEncoder.__init__: no fp32 caches)
-        super().__init__(encoder, slots, max_mel_frames, graphs=False)
+        super().__init__(encoder, slots, max_mel_frames, graphs=False, left_context=left_context,
+                         max_chunk_mel_frames=max_chunk_mel_frames)
         self.ctx = None                                                    # the compact context is allocated per step
         self.S = self.B
-        self.max_mel = int(max_mel_frames)
+        self.max_mel = None if max_mel_frames is None else int(max_mel_frames)
         self.is_open = [False] * self.S
         self.n0 = [0] * self.S                                             # encoder frames per slot so far
         self.tails = [0] * self.S                                          # buffered mel frames per slot (0..6)
@@ -197,6 +222,8 @@ class SlotStreamingEncoder(StreamingEncoder):
         """Check a step's arguments against the slots (raises before anything is enqueued): (mel, k, new tails)."""
         if self.enc.training:
             raise RuntimeError("SlotStreamingEncoder: put the encoder in eval() mode (running BatchNorm statistics, no dropout)")
+        if self.left is not None:
+            _refuse_window_autocast("SlotStreamingEncoder")
         _refuse_autocast("SlotStreamingEncoder", self.dtype)
         x = ops._req(mel_chunk, "mel_chunk")
         if x.dim() != 3 or x.shape[0] != self.S:
@@ -210,7 +237,9 @@ class SlotStreamingEncoder(StreamingEncoder):
                 raise ValueError(f"frames[{b}] = {f} outside [0, {Tc}]")
             if f and not self.is_open[b]:
                 raise RuntimeError(f"frames given for free slot {b}: open() it first")
-            if self.mel_seen[b] + f > self.max_mel:
+            if self.left is not None and f > self.max_chunk:
+                raise ValueError(f"frames[{b}] = {f}: the ring was sized for max_chunk_mel_frames={self.max_chunk}")
+            if self.max_mel is not None and self.mel_seen[b] + f > self.max_mel:
                 raise RuntimeError(f"slot {b}: {self.mel_seen[b] + f} mel frames would pass max_mel_frames={self.max_mel}")
         ks, new_tails = slot_plan(self.tails, frames)
         return x, ks, new_tails
@@ -238,7 +267,7 @@ class SlotStreamingEncoder(StreamingEncoder):
         if self.mel_tail_buf is None:
             self.mel_tail_buf = torch.zeros(S, x.shape[1], _TAIL, device=dev, dtype=torch.float32)
         totals = [t + f for t, f in zip(self.tails, frames)]
-        cur = _Step(dev, self.tails, totals, self.n0, ks, k_max, self.t_max)
+        cur = _Step(dev, self.tails, totals, self.n0, ks, k_max, self.t_max, self.ring)
         src = torch.cat([self.mel_tail_buf, x, x.new_zeros(S, x.shape[1], 1)], dim=2)   # [tail | chunk | zero column]
         n_mel = x.shape[1]
         keep = cur.k[:, None] * 4 + torch.arange(_TAIL, device=dev)[None, :]
@@ -263,12 +292,16 @@ class SlotTranscriber:
     SlotStreamingEncoder (the LSTM state and the logits stay fp32; the search consumes the logits the step returned)."""
 
     def __init__(self, model, decoder: BeamCTCDecoder, slots: int, max_mel_frames: int,
-                 dtype: Optional[torch.dtype] = None) -> None:
+                 dtype: Optional[torch.dtype] = None, *, left_context: Optional[int] = None,
+                 max_chunk_mel_frames: Optional[int] = None) -> None:
         self.dtype = _slot_dtype("SlotTranscriber", dtype)
+        if self.dtype is not None and left_context is not None:
+            raise NotImplementedError(f"SlotTranscriber: left_context with dtype={self.dtype} (no 16-bit window kernel yet)")
         self.device, self.state = lstm_state(model, "SlotTranscriber", int(slots))
         self.model = model
         self.decoder = decoder
-        self.encoder = SlotStreamingEncoder(model.encoder, slots, max_mel_frames, dtype=self.dtype)
+        self.encoder = SlotStreamingEncoder(model.encoder, slots, max_mel_frames, dtype=self.dtype, left_context=left_context,
+                                            max_chunk_mel_frames=max_chunk_mel_frames)
         self.S = self.encoder.S
         f = decoder._fusion(self.device)
         self.beam = beam_ctc_stream_init(self.S, self.encoder.t_max, self.device, beam_width=decoder.beam_width,
@@ -302,6 +335,8 @@ class SlotTranscriber:
         its own rows.  Nothing synchronises with the host."""
         if self.model.training:
             raise RuntimeError("SlotTranscriber: the model is in training mode; put it back in eval()")
+        if self.encoder.left is not None:
+            _refuse_window_autocast("SlotTranscriber")
         _refuse_autocast("SlotTranscriber", self.dtype)
         n0 = list(self.encoder.n0)
         enc, ks = self.encoder.step(mel_chunk, frames)

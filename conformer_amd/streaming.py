@@ -17,6 +17,12 @@ State per layer: the fused Q|K|V projections of every frame so far (B, T'max, 3d
 `cfm_relpos_attention_rows_f32` computes the new query rows only, against the whole cache -- and the last (K-1)/2 GLU
 outputs feeding the depthwise convolution.  Per utterance: the un-consumed tail (3..6 frames) of the mel stream and the
 positional table projected ONCE for T'max.
+
+Bounded history (`left_context=L`, INTEGRATION.md "Bounded history"): the windowed prefix rule -- query frame i of a chunk that
+ends at frame e attends to the keys max(0, i-L) <= j < e; everything else above stays.  The per-layer caches are then RINGS
+(B, R, 3d), frame n in row n mod R, R = 32 ceil((L + k_cap)/32) with k_cap the most encoder frames one step can make; the table is
+projected for P = max(L+1, k_cap) positions and `cfm_relpos_attention_window_f32` attends.  Memory and the cost of a chunk no
+longer depend on the stream position, and max_mel_frames may be None: a stream without an end.
 """
 from __future__ import annotations
 
@@ -27,6 +33,45 @@ import torch
 from . import ops
 from ._derived import fingerprint
 from .model.modules.encoder import Encoder
+
+
+def ring_plan(left_context: int, max_chunk_mel_frames: int):
+    """(R, P, k_cap) of a windowed stream: a step buffers at most 6 + max_chunk_mel_frames mel frames, so it makes at most k_cap
+    encoder frames; the ring keeps the L frames a query may look back on next to the step's own rows, in whole key tiles of 32;
+    the table covers the relative positions -(k_cap-1) .. L.  Host arithmetic."""
+    L, mc = int(left_context), int(max_chunk_mel_frames)
+    if L < 0:
+        raise ValueError(f"left_context must be >= 0 encoder frames, got {L}")
+    if mc < 1:
+        raise ValueError(f"max_chunk_mel_frames must be >= 1, got {mc}")
+    k_cap = encoder_frames(mc + 6)
+    return 32 * ((L + k_cap + 31) // 32), max(L + 1, k_cap), k_cap
+
+
+def ring_rows(n0: int, k: int, R: int):
+    """Ring rows of frames n0 .. n0+k-1 (k <= R) as one or two (ring start, source start, count) runs."""
+    s = n0 % R
+    first = min(k, R - s)
+    return [(s, 0, first)] + ([(0, first, k - first)] if first < k else [])
+
+
+def _window_args(who: str, left_context, max_chunk_mel_frames, max_mel_frames):
+    """The three sizing keywords of the streaming objects, checked on the host: (L, max chunk) or (None, None)."""
+    if left_context is None:
+        if max_chunk_mel_frames is not None:
+            raise ValueError(f"{who}: max_chunk_mel_frames sizes the ring of a windowed stream: give left_context too")
+        if max_mel_frames is None:
+            raise ValueError(f"{who}: max_mel_frames=None (a stream without an end) needs left_context")
+        return None, None
+    if max_chunk_mel_frames is None:
+        raise ValueError(f"{who}: left_context needs max_chunk_mel_frames (the ring is sized for the largest step)")
+    ring_plan(left_context, max_chunk_mel_frames)
+    return int(left_context), int(max_chunk_mel_frames)
+
+
+def _refuse_window_autocast(who: str) -> None:
+    if torch.is_autocast_enabled("cuda"):
+        raise NotImplementedError(f"{who}: left_context is fp32 only (no 16-bit window kernel yet); leave torch.autocast")
 
 
 def encoder_frames(mel_frames: int) -> int:
@@ -42,10 +87,20 @@ class _Stream:
 
     def __init__(self, st: "StreamingEncoder", n0: int, k: int) -> None:
         self.st, self.n0, self.k, self.i = st, n0, k, 0
+        self._pos = None           # windowed: (q_begin, q_count) on the device, made once per step
 
     def attend(self, a, qkv_new: torch.Tensor) -> torch.Tensor:
         """Append the chunk's Q|K|V rows to the layer's cache and return the attention context of the new rows (B, k, d)."""
         st, i, n0, k = self.st, self.i, self.n0, self.k
+        if st.left is not None:                                            # ring: rows (n0 + r) mod R, then the window kernel
+            for dst, src, n in ring_rows(n0, k, st.ring):
+                st.qkv[i][:, dst:dst + n].copy_(qkv_new[:, src:src + n])
+            if self._pos is None:
+                dev = qkv_new.device
+                self._pos = (torch.full((st.B,), n0, dtype=torch.int64, device=dev),
+                             torch.full((st.B,), k, dtype=torch.int64, device=dev))
+            return ops.relpos_attention_window(st.qkv[i], st.pos_all[:, i * st.d:(i + 1) * st.d], a.content_bias, a.position_bias,
+                                               a.n_heads, self._pos[0], self._pos[1], k, st.left)
         st.qkv[i][:, n0:n0 + k].copy_(qkv_new)
         ops.relpos_attention_rows(st.qkv[i], st.pos_all[:, i * st.d:(i + 1) * st.d], a.content_bias, a.position_bias,
                                   st.lengths, a.n_heads, n0, k, st.ctx, keys_hint=n0 + k)
@@ -75,11 +130,21 @@ class StreamingEncoder:
     does) with the recorded one; after an optimizer step, `load_state_dict`, an in-place update or invalidate_weight_caches()
     the table is projected again and all graphs are dropped, eager path included.  The stream state is NOT touched: the cached
     K/V rows were computed with the old weights, so a caller who changes weights mid-utterance calls reset().
-    check_weights=False (frozen-weight serving) skips that per-step walk over the encoder's tensors."""
+    check_weights=False (frozen-weight serving) skips that per-step walk over the encoder's tensors.
+
+    left_context=L (encoder frames, with max_chunk_mel_frames: the most mel frames one step() may bring): bounded history, the
+    module docstring's windowed rule over ring caches; max_mel_frames may then be None (no end).  fp32 and eager only: graphs=True
+    or a step under torch.autocast raises NotImplementedError."""
 
     cache_dtype = torch.float32        # storage type of the K/V caches (SlotStreamingEncoder(dtype=...) sets a 16-bit one)
 
-    def __init__(self, encoder: Encoder, batch: int, max_mel_frames: int, graphs: bool = False, check_weights: bool = True) -> None:
+    def __init__(self, encoder: Encoder, batch: int, max_mel_frames: Optional[int] = None, graphs: bool = False,
+                 check_weights: bool = True, *, left_context: Optional[int] = None,
+                 max_chunk_mel_frames: Optional[int] = None) -> None:
+        self.left, self.max_chunk = _window_args("StreamingEncoder", left_context, max_chunk_mel_frames, max_mel_frames)
+        if self.left is not None and graphs:
+            raise NotImplementedError("StreamingEncoder: graphs=True with left_context (a graph key still holds the stream "
+                                      "position, so an endless stream would capture without end)")
         if encoder.training:
             raise RuntimeError("StreamingEncoder: put the encoder in eval() mode (running BatchNorm statistics, no dropout)")
         p = next(encoder.parameters())
@@ -88,13 +153,19 @@ class StreamingEncoder:
         self.enc = encoder
         self.B = int(batch)
         self.d = encoder.linear.out_features
-        self.t_max = encoder_frames(int(max_mel_frames))
-        if self.t_max < 1:
+        self.t_max = None if max_mel_frames is None else encoder_frames(int(max_mel_frames))     # None: a stream without an end
+        if self.t_max is not None and self.t_max < 1:
             raise ValueError("max_mel_frames must give at least one encoder frame (>= 7)")
         dev = p.device
         layers = list(encoder.layers)
-        self.qkv = [torch.zeros(self.B, self.t_max, 3 * self.d, device=dev, dtype=self.cache_dtype) for _ in layers]
-        self.ctx = torch.zeros(self.B, self.t_max, self.d, device=dev, dtype=torch.float32)     # scratch shared by the layers
+        if self.left is None:
+            self.ring = self.n_pos = None
+            self.qkv = [torch.zeros(self.B, self.t_max, 3 * self.d, device=dev, dtype=self.cache_dtype) for _ in layers]
+            self.ctx = torch.zeros(self.B, self.t_max, self.d, device=dev, dtype=torch.float32)     # scratch shared by the layers
+        else:
+            self.ring, self.n_pos, _ = ring_plan(self.left, self.max_chunk)
+            self.qkv = [torch.zeros(self.B, self.ring, 3 * self.d, device=dev, dtype=torch.float32) for _ in layers]
+            self.ctx = None                                                # the window kernel's context is compact, per step
         halves = [(l.conv.deepwise_conv.kernel_size[0] - 1) // 2 for l in layers]     # the carried GLU rows: (K-1)/2 per layer
         self.conv_state = [torch.zeros(self.B, h, self.d, device=dev, dtype=torch.float32) for h in halves]
         self.lengths = torch.zeros(self.B, dtype=torch.int64, device=dev)
@@ -109,8 +180,8 @@ class StreamingEncoder:
     @torch.no_grad()
     def _derive(self) -> None:
         """Everything this object holds that was made from the weights: the projected table, the graphs and their pool."""
-        self.table = self.enc.rel_pe.table(self.t_max)
-        self.pos_all = self.enc._projected_positions(self.table)          # (2T'max-1, L*d): every layer's pos_proj, once
+        self.table = self.enc.rel_pe.table(self.t_max if self.left is None else self.n_pos)
+        self.pos_all = self.enc._projected_positions(self.table)          # (2T'max-1 | 2P-1, L*d): every layer's pos_proj, once
         self._graphs = {}                                                  # key -> (graph, static input, static output)
         self._pool = None
         self._warm = set()                                                 # precisions whose derived weights a warm step built
@@ -135,6 +206,11 @@ class StreamingEncoder:
     def step(self, mel_chunk: torch.Tensor) -> torch.Tensor:
         """mel_chunk (B, n_mel, Tc): the next Tc log-mel frames of every utterance (any Tc >= 1).  Returns the encoder
         frames that became computable, (B, k, d) with k = ((buffered-1)//2-1)//2 >= 0."""
+        if self.left is not None:                                          # refusals first: nothing enqueued, no state touched
+            _refuse_window_autocast("StreamingEncoder")
+            if mel_chunk.shape[2] > self.max_chunk:
+                raise ValueError(f"StreamingEncoder: a step of {mel_chunk.shape[2]} mel frames, the ring was sized for "
+                                 f"max_chunk_mel_frames={self.max_chunk}")
         self._follow_weights()
         x_in = ops._req(mel_chunk, "mel_chunk")
         if self.mel_tail_buf is None:
@@ -147,7 +223,7 @@ class StreamingEncoder:
             self.mel_tail_buf[:, :, tail:total].copy_(x_in)
             self.tail_len = total
             return x_in.new_empty(self.B, 0, self.d)
-        if n0 + k > self.t_max:
+        if self.t_max is not None and n0 + k > self.t_max:
             raise RuntimeError(f"StreamingEncoder: stream longer than max_mel_frames (T'max = {self.t_max})")
         if not self.use_graphs:
             out = self._step_core(x_in, n0, tail, k)

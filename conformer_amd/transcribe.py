@@ -54,15 +54,18 @@ def lstm_state(model, who: str, batch: int):
 
 class StreamingTranscriber:
     """model: a Conformer in eval() mode on the HIP device; decoder: the BeamCTCDecoder whose configuration (beam knobs, lm,
-    hotwords) the streamed search takes; batch utterances of at most max_mel_frames mel frames.  graphs, check_weights: as
-    StreamingEncoder."""
+    hotwords) the streamed search takes; batch utterances of at most max_mel_frames mel frames.  graphs, check_weights,
+    left_context, max_chunk_mel_frames: as StreamingEncoder (max_mel_frames still sizes the beam search's buffers; with
+    left_context the encoder no longer allocates by it)."""
 
     def __init__(self, model, decoder: BeamCTCDecoder, batch: int, max_mel_frames: int, graphs: bool = False,
-                 check_weights: bool = True) -> None:
+                 check_weights: bool = True, *, left_context: Optional[int] = None,
+                 max_chunk_mel_frames: Optional[int] = None) -> None:
         self.B = int(batch)
         device, self.state = lstm_state(model, "StreamingTranscriber", self.B)
         self.model = model
-        self.encoder = StreamingEncoder(model.encoder, batch, max_mel_frames, graphs=graphs, check_weights=check_weights)
+        self.encoder = StreamingEncoder(model.encoder, batch, max_mel_frames, graphs=graphs, check_weights=check_weights,
+                                        left_context=left_context, max_chunk_mel_frames=max_chunk_mel_frames)
         self.beam: BeamCTCStream = decoder.stream(self.B, self.encoder.t_max, device)
 
     def reset(self) -> None:

@@ -16,6 +16,8 @@ LIB_PATH = os.environ.get("CONFORMER_AMD_LIB") or os.path.join(_HERE, "lib", "li
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "conformer_hip.h")
 # entries added to the library without touching the main header (no existing signature moves, so the ABI revision stays)
 EXT_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "conformer_hip_window.h")
+# the committed-prefix streaming search, added the same way (its own table: EXT_SIGNATURES stays the window header's)
+COMMIT_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "conformer_hip_commit.h")
 _CTYPES = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "float": ctypes.c_float, "double": ctypes.c_double,
            "uint64_t": ctypes.c_uint64, "size_t": ctypes.c_size_t, "cfm_stream_t": ctypes.c_void_p}
 _DECL = re.compile(r"^[ \t]*((?:const\s+)?\w+[\s*]+?)(cfm_\w+)\s*\(([^()]*)\)\s*;", re.M)
@@ -68,6 +70,14 @@ with open(EXT_HEADER_PATH) as _f:
 if set(EXT_SIGNATURES) & set(SIGNATURES):
     raise ConformerHipError(f"{EXT_HEADER_PATH} declares again: {sorted(set(EXT_SIGNATURES) & set(SIGNATURES))}")
 PARAMS.update(_ext_params)                        # (`call` names a parameter of either header)
+if not os.path.exists(COMMIT_HEADER_PATH):
+    raise ConformerHipError(f"{COMMIT_HEADER_PATH} is missing: the ctypes binding is derived from it")
+with open(COMMIT_HEADER_PATH) as _f:
+    COMMIT_SIGNATURES, _commit_params, _ = parse_header(_f.read())
+if set(COMMIT_SIGNATURES) & (set(SIGNATURES) | set(EXT_SIGNATURES)):
+    raise ConformerHipError(f"{COMMIT_HEADER_PATH} declares again: "
+                            f"{sorted(set(COMMIT_SIGNATURES) & (set(SIGNATURES) | set(EXT_SIGNATURES)))}")
+PARAMS.update(_commit_params)
 
 _lib = None
 
@@ -97,14 +107,15 @@ def load() -> ctypes.CDLL:
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
-    for name, (res, args) in EXT_SIGNATURES.items():
-        # same ABI revision, newer entry: a library built before include/conformer_hip_window.h existed passes the check above
-        fn = getattr(lib, name, None)
-        if fn is None:
-            raise ConformerHipError(f"{LIB_PATH} lacks {name} (include/conformer_hip_window.h): rebuild it with "
-                                    "`python -m conformer_amd.build`")
-        fn.restype = res
-        fn.argtypes = args
+    for header, table in ((EXT_HEADER_PATH, EXT_SIGNATURES), (COMMIT_HEADER_PATH, COMMIT_SIGNATURES)):
+        for name, (res, args) in table.items():
+            # same ABI revision, newer entry: a library built before the extension header existed passes the check above
+            fn = getattr(lib, name, None)
+            if fn is None:
+                raise ConformerHipError(f"{LIB_PATH} lacks {name} (include/{os.path.basename(header)}): rebuild it with "
+                                        "`python -m conformer_amd.build`")
+            fn.restype = res
+            fn.argtypes = args
     _lib = lib
     return lib
 

@@ -32,6 +32,7 @@ def _newest_dep():
     deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
     deps.append(os.path.join(ROOT, "include", "conformer_hip.h"))
     deps.append(os.path.join(ROOT, "include", "conformer_hip_window.h"))
+    deps.append(os.path.join(ROOT, "include", "conformer_hip_commit.h"))
     return max(os.path.getmtime(d) for d in deps)
 
 

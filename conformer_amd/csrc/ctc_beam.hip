@@ -37,6 +37,7 @@
 #include <float.h>
 #include <type_traits>
 #include "cfm_common.h"
+#include "../../include/conformer_hip_commit.h"
 #include "hotword.h"
 #include "ngram_lm.h"
 
@@ -914,6 +915,162 @@ __global__ void beam_stream_reset_slots_kernel(BeamWs ws, StreamParams<true> sp,
     beam_stream_init_one<LM, HW>(ws, sp, (int)b, W, lm_tables, score_boundary);
 }
 
+// Committed-prefix streaming (INTEGRATION.md "Committed-prefix streaming (max_pending)"): the step after a resumable step.  One
+// workgroup per utterance on the SAVED state, thread r owns saved hypothesis r.  The search kernel numbers new nodes by
+// sp.frames and bounds its walks by the saved lengths, and it compares sequences token by token (same_sequence, the
+// traceback), never by node identity: so this kernel may cut the shared prefix off every chain, give each survivor a private
+// chain at the bottom of the tree and leave lengths, nodes and the frame count relative to the committed prefix.
+//   1. thread 0 walks y_0's chain once into y0 (token, node) per position -- global scratch, not LDS: |y_0| is bounded by
+//      max_pending + max_chunk_frames, which no LDS array is
+//   2. every thread walks its own chain against y0 for the length of its common prefix with y_0 (it stops where both chains
+//      reach the same node: the rest is shared); block-min -> lcp; nb; survivors; their ranks by a ballot scan in rank order
+//   3. each survivor copies its pending suffix (<= max_pending tokens) to its own scratch row and reads its saved values
+//   4. after the barrier (no thread reads the old tree or the old values any more): the private chains, the values at the
+//      survivors' ranks, nh, frames, the commit log and its total
+struct CommitParams {
+    int2* y0;                            // (B, T_tree) scratch
+    int* suf;                            // (B, W, M) scratch
+    int* log;                            // (B, L) ring of committed tokens
+    int64_t* total;                      // (B) tokens committed so far
+    int* committed;                      // (B) tokens committed by this call, or null
+    const int64_t* lengths;              // the step's lengths, or null
+    int M, L;
+};
+
+__global__ __launch_bounds__(BEAM_MAX_W) void beam_commit_kernel(BeamWs ws, StreamParams<true> sp, CommitParams cp, int W) {
+    __shared__ int red_min[4], red_cnt[4], red_max[4];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int TT = sp.t_max, M = cp.M;
+    const int nh = min(sp.nh[b], W);
+    if ((cp.lengths && cp.lengths[b] <= 0) || nh < 1) {                  // no frame consumed: nothing changed (block-uniform)
+        if (tid == 0 && cp.committed) cp.committed[b] = 0;
+        return;
+    }
+    const int nn = 1 + TT * W;                                            // nodes of one utterance's tree
+    int2* nd = ws.nodes + (int64_t)b * nn;
+    int2* y0 = cp.y0 + (int64_t)b * TT;
+    const int64_t o = (int64_t)b * W + tid;
+    const int64_t tot = cp.total[b];
+    const int len0 = min(max(sp.len[(int64_t)b * W], 0), TT);
+    // ---- 1: y_0's pending tokens and their nodes
+    if (tid == 0) {
+        int x = sp.node[(int64_t)b * W];
+        for (int p = len0 - 1; p >= 0 && x > 0 && x < nn; --p) {
+            const int2 e = nd[x];
+            y0[p] = make_int2(e.y, x);
+            x = e.x;
+        }
+    }
+    __syncthreads();
+    // ---- 2: common prefix with y_0
+    const bool own = tid < nh;
+    int len = 0, node = 0, lc = INT_MAX;
+    if (own) {
+        len = min(max(sp.len[o], 0), TT);
+        node = sp.node[o];
+        lc = min(len, len0);
+        int x = node;
+        for (int p = len - 1; p >= 0 && x > 0 && x < nn; --p) {
+            const int2 e = nd[x];
+            if (p < len0) {
+                const int2 y = y0[p];
+                if (y.y == x) break;                                      // the same node: both chains are one from here down
+                if (y.x != e.y) lc = p;
+            }
+            x = e.x;
+        }
+    }
+    int m = lc;
+#pragma unroll
+    for (int q = 32; q > 0; q >>= 1) m = min(m, __shfl_xor(m, q, 64));
+    if (lane == 0) red_min[wv] = m;
+    __syncthreads();
+    const int lcp = min(min(red_min[0], red_min[1]), min(red_min[2], red_min[3]));
+    const int nb = max(lcp, len0 - M);                                    // 0 <= nb <= len0 (thread 0 holds lc = len0)
+    const bool surv = own && lc >= nb && len - nb <= M;                   // (lc >= nb: y_r starts with y_0[:nb])
+    const int slen = surv ? len - nb : 0;
+    const unsigned long long bal = __ballot(surv);
+    const int pre = __popcll(bal & ((1ull << lane) - 1ull));
+    int mx = slen;
+#pragma unroll
+    for (int q = 32; q > 0; q >>= 1) mx = max(mx, __shfl_xor(mx, q, 64));
+    if (lane == 0) { red_cnt[wv] = __popcll(bal); red_max[wv] = mx; }
+    // ---- 3: the survivor's suffix to its scratch row, its saved values to registers
+    int* suf = cp.suf + o * M;
+    double pb = 0, pnb = 0, s = 0, lm = 0;
+    unsigned long long hash = 0;
+    int last = 0, tn = 0, pl = 0, hn = 0, hd = 0, hwl = 0, hc = 0;
+    int ctx[LM_CTX];
+    short hw[HW_WIN];
+    if (surv) {
+        int x = node;
+        for (int p = slen - 1; p >= 0 && x > 0 && x < nn; --p) {
+            const int2 e = nd[x];
+            suf[p] = e.y;
+            x = e.x;
+        }
+        pb = sp.pb[o]; pnb = sp.pnb[o]; s = sp.s[o]; hash = sp.hash[o]; last = sp.last[o];
+        if (sp.lm) {
+            lm = sp.lm[o]; tn = sp.tn[o]; pl = sp.pl[o];
+            for (int i = 0; i < LM_CTX; ++i) ctx[i] = sp.ctx[((int64_t)b * LM_CTX + i) * W + tid];
+        }
+        if (sp.hn) {
+            hn = sp.hn[o]; hd = sp.hd[o]; hwl = sp.hwl[o]; hc = sp.hc[o];
+            for (int u = 0; u < HW_WIN; ++u) hw[u] = sp.hw[((int64_t)b * HW_WIN + u) * W + tid];
+        }
+    }
+    __syncthreads();
+    // ---- 4: private chains and the compacted state
+    int q = pre;
+    for (int w = 0; w < wv; ++w) q += red_cnt[w];
+    if (surv) {
+        for (int p = 0; p < slen; ++p) nd[1 + p * W + q] = make_int2(p ? 1 + (p - 1) * W + q : 0, suf[p]);
+        const int64_t oq = (int64_t)b * W + q;
+        sp.pb[oq] = pb; sp.pnb[oq] = pnb; sp.s[oq] = s; sp.hash[oq] = hash; sp.last[oq] = last;
+        sp.node[oq] = slen ? 1 + (slen - 1) * W + q : 0;
+        sp.len[oq] = slen;
+        if (sp.lm) {
+            sp.lm[oq] = lm; sp.tn[oq] = tn; sp.pl[oq] = pl;
+            for (int i = 0; i < LM_CTX; ++i) sp.ctx[((int64_t)b * LM_CTX + i) * W + q] = ctx[i];
+        }
+        if (sp.hn) {
+            sp.hn[oq] = hn; sp.hd[oq] = hd; sp.hwl[oq] = hwl; sp.hc[oq] = hc;
+            for (int u = 0; u < HW_WIN; ++u) sp.hw[((int64_t)b * HW_WIN + u) * W + q] = hw[u];
+        }
+    }
+    for (int p = tid; p < nb; p += BEAM_MAX_W) cp.log[(int64_t)b * cp.L + (int)(((tot + p) % cp.L + cp.L) % cp.L)] = y0[p].x;
+    if (tid == 0) {
+        sp.nh[b] = red_cnt[0] + red_cnt[1] + red_cnt[2] + red_cnt[3];
+        sp.frames[b] = max(max(red_max[0], red_max[1]), max(red_max[2], red_max[3]));
+        cp.total[b] = tot + nb;
+        if (cp.committed) cp.committed[b] = nb;
+    }
+}
+
+__global__ void beam_commit_reset_slots_kernel(int64_t* total, int B, const int64_t* slots, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int64_t b = slots[i];
+    if (b >= 0 && b < B) total[b] = 0;
+}
+
+// the commit buffer: the stream state for T_tree = M + k_cap frames, then the commit step's scratch
+inline size_t commit_carve(int B, int M, int k_cap, int W, int K, bool lm, bool hw, char* base, BeamWs* ws, StreamParams<true>* sp,
+                           CommitParams* cp) {
+    const int TT = M + k_cap;
+    size_t off = stream_carve(B, TT, W, K, lm, hw, base, ws, sp);
+    auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += beam_align(bytes); return p; };
+    char* y0 = take((size_t)B * TT * sizeof(int2));
+    char* suf = take((size_t)B * W * M * sizeof(int));
+    if (cp) { cp->y0 = (int2*)y0; cp->suf = (int*)suf; cp->M = M; }
+    return off;
+}
+
+inline bool commit_args_ok(int B, int M, int k_cap, int W, int K) {
+    return B > 0 && M >= 1 && k_cap >= 1 && W >= 1 && W <= BEAM_MAX_W && K >= 1 && K <= BEAM_MAX_K &&
+           ((int64_t)M + k_cap) * W < INT32_MAX;
+}
+
 // ---- host side ---------------------------------------------------------------------------------------------------------
 
 #define CFM_CHECK(call) do { const int st_ = (call); if (st_ != CFM_OK) return st_; } while (0)
@@ -1144,4 +1301,41 @@ extern "C" int cfm_ctc_beam_stream_finish_f32(int B, int beam_width, int max_can
     // traceback (plain search)
     return beam_launch(nullptr, nullptr, ws, sp, B, 0, 2, 0, beam_width, max_candidates, 0.f, 0.f, n_best, fz, tokens, counts,
                        scores, am_scores_or_null, num_hyps, stream);
+}
+
+// ---- committed-prefix streaming (include/conformer_hip_commit.h) ----------------------------------------------------------------
+
+extern "C" size_t cfm_ctc_beam_commit_state_bytes(int B, int max_pending, int max_chunk_frames, int W, int K, int lm, int hw) {
+    if (!commit_args_ok(B, max_pending, max_chunk_frames, W, K)) return 0;
+    return commit_carve(B, max_pending, max_chunk_frames, W, K, lm != 0, hw != 0, nullptr, nullptr, nullptr, nullptr);
+}
+
+extern "C" int cfm_ctc_beam_stream_commit(int B, int max_pending, int max_chunk_frames, int beam_width, int max_candidates, int lm,
+                                          int hw, const int64_t* lengths_or_null, void* state, size_t state_bytes, int* log, int L,
+                                          int64_t* total, int* committed_or_null, cfm_stream_t stream) {
+    CFM_REQUIRE(state && log && total, CFM_ERR_NULL);
+    CFM_REQUIRE(B > 0 && max_pending >= 1 && max_chunk_frames >= 1, CFM_ERR_BAD_SHAPE);
+    CFM_REQUIRE((int64_t)max_pending + max_chunk_frames < INT32_MAX, CFM_ERR_UNSUPPORTED);
+    const int TT = max_pending + max_chunk_frames;
+    CFM_CHECK(beam_check(B, TT, 2, beam_width, max_candidates, 1, 0, 0.f, 0.f));
+    CFM_REQUIRE(L >= TT, CFM_ERR_BAD_SHAPE);
+    BeamWs ws;
+    StreamParams<true> sp;
+    CommitParams cp{};
+    CFM_REQUIRE(state_bytes >= commit_carve(B, max_pending, max_chunk_frames, beam_width, max_candidates, lm != 0, hw != 0, nullptr,
+                                            nullptr, nullptr, nullptr), CFM_ERR_BAD_SHAPE);
+    commit_carve(B, max_pending, max_chunk_frames, beam_width, max_candidates, lm != 0, hw != 0, static_cast<char*>(state), &ws,
+                 &sp, &cp);
+    cp.log = log; cp.L = L; cp.total = total; cp.committed = committed_or_null; cp.lengths = lengths_or_null;
+    hipLaunchKernelGGL(beam_commit_kernel, dim3((unsigned)B), dim3(BEAM_MAX_W), 0, static_cast<hipStream_t>(stream), ws, sp, cp,
+                       beam_width);
+    return cfm_launch_status();
+}
+
+extern "C" int cfm_ctc_beam_commit_reset_slots(int B, const int64_t* slots, int n_slots, int64_t* total, cfm_stream_t stream) {
+    CFM_REQUIRE(slots && total, CFM_ERR_NULL);
+    CFM_REQUIRE(B > 0 && n_slots >= 1 && n_slots <= B, CFM_ERR_BAD_SHAPE);
+    hipLaunchKernelGGL(beam_commit_reset_slots_kernel, dim3((unsigned)((n_slots + 255) / 256)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), total, B, slots, n_slots);
+    return cfm_launch_status();
 }

@@ -15,7 +15,9 @@ Hotword boosting, with or without the language model (`conformer_amd.hotwords`):
 `BeamCTCDecoder(hotwords=...)`, semantics in INTEGRATION.md "Hotword boosting".
 
 The same search resumed chunk by chunk over a stream, in every mode: `beam_ctc_stream_init/step/finish` and
-`BeamCTCDecoder.stream`, semantics in INTEGRATION.md "Streaming (resumable) search"."""
+`BeamCTCDecoder.stream`, semantics in INTEGRATION.md "Streaming (resumable) search".  With `max_pending` the stream has no end:
+after every step the prefix no live hypothesis can change is committed and the prefix tree re-rooted there, INTEGRATION.md
+"Committed-prefix streaming (max_pending)"."""
 from __future__ import annotations
 
 import math
@@ -208,10 +210,13 @@ class BeamCTCDecoder:
             raise ValueError(f"hotword_weight must be finite, got {hotword_weight}")
         self.hotword_weight = hotword_weight
 
-    def stream(self, batch: int, max_frames: int, device=None) -> "BeamCTCStream":
+    def stream(self, batch: int, max_frames: Optional[int], device=None, *, max_pending: Optional[int] = None,
+               max_chunk_frames: Optional[int] = None, commit_log: int = 4096) -> "BeamCTCStream":
         """A resumable search configured like this decoder (beam knobs, lm, hotwords) over `batch` utterances of at most
-        `max_frames` frames in all: BeamCTCStream."""
-        return BeamCTCStream(self, batch, max_frames, device)
+        `max_frames` frames in all: BeamCTCStream.  max_pending (tokens) with max_chunk_frames (logit frames per step) and
+        max_frames=None: a stream without an end in commit mode (beam_ctc_stream_init)."""
+        return BeamCTCStream(self, batch, max_frames, device, max_pending=max_pending, max_chunk_frames=max_chunk_frames,
+                             commit_log=commit_log)
 
     def text(self, ids: Sequence[int]) -> str:
         joined = "".join(self.vocab[i] for i in ids if i not in self.skip_ids)
@@ -259,25 +264,67 @@ class _StreamState:
         self.beam_width, self.max_candidates = beam_width, max_candidates
         self.fusion = fusion
         self.t_used = 0                    # chunk frames stepped since the init: a bound on what any utterance consumed
+        # commit mode (beam_ctc_stream_init(max_pending=...)): t_max is the tree's max_pending + max_chunk_frames frames
+        self.max_pending: Optional[int] = None
+        self.max_chunk_frames: Optional[int] = None
+        self.log: Optional[torch.Tensor] = None          # (B, L) int32 ring of committed tokens
+        self.total: Optional[torch.Tensor] = None        # (B) int64 tokens committed since the init / the slot's reset
+        self.committed: Optional[torch.Tensor] = None    # (B) int32 tokens the latest step committed
 
 
-def beam_ctc_stream_init(batch: int, max_frames: int, device, *, beam_width: int = 100, max_candidates: int = 16,
+def _commit_args(who: str, max_frames, max_pending, max_chunk_frames, commit_log=4096):
+    """The sizing arguments of a search, checked on the host: None (the search ends at max_frames) or (M, k_cap)."""
+    if max_pending is None and max_chunk_frames is None:
+        if max_frames is None:
+            raise ValueError(f"{who}: max_frames=None (a stream without an end) needs max_pending and max_chunk_frames")
+        return None
+    if max_pending is None:
+        raise ValueError(f"{who}: max_chunk_frames sizes the tree of commit mode: give max_pending too")
+    if max_chunk_frames is None:
+        raise ValueError(f"{who}: max_pending needs max_chunk_frames (the tree is sized for the largest step)")
+    if max_frames is not None:
+        raise ValueError(f"{who}: max_frames={max_frames} together with max_pending: a committing search has no end, pass "
+                         "max_frames=None")
+    M, k_cap = int(max_pending), int(max_chunk_frames)
+    if M < 1 or k_cap < 1:
+        raise ValueError(f"{who}: max_pending and max_chunk_frames must be >= 1, got {M} and {k_cap}")
+    if int(commit_log) < 1:
+        raise ValueError(f"{who}: commit_log must be >= 1 token, got {commit_log}")
+    return M, k_cap
+
+
+def beam_ctc_stream_init(batch: int, max_frames: Optional[int], device, *, beam_width: int = 100, max_candidates: int = 16,
                          lm_tables: Optional[torch.Tensor] = None, hw_tables: Optional[torch.Tensor] = None,
                          alpha: float = 2.1, beta: float = 9.2, unk_score_offset: float = -10.0, score_boundary: bool = True,
-                         hotword_weight: float = 9.0) -> _StreamState:
+                         hotword_weight: float = 9.0, max_pending: Optional[int] = None,
+                         max_chunk_frames: Optional[int] = None, commit_log: int = 4096) -> _StreamState:
     """Allocate and initialise the state of a resumable CTC prefix beam search over `batch` utterances of at most
     `max_frames` frames, every utterance at the empty prefix.  `lm_tables` / `hw_tables`: the device blobs of
-    NgramLanguageModel.device_tables / Hotwords.device_tables (None: not used).  Enqueues only."""
-    B, Tm = int(batch), int(max_frames)
+    NgramLanguageModel.device_tables / Hotwords.device_tables (None: not used).  Enqueues only.
+    Commit mode: max_pending = M tokens with max_chunk_frames = k_cap logit frames per step and max_frames=None.  The state is
+    then sized by (B, M, k_cap, W, K, lm, hw) alone and the stream has no end; the committed tokens go to a ring of
+    max(commit_log, M + k_cap) tokens per utterance (beam_ctc_stream_committed reads it)."""
+    commit = _commit_args("beam_ctc_stream_init", max_frames, max_pending, max_chunk_frames, commit_log)
+    B = int(batch)
     W, K = int(beam_width), int(max_candidates)
     lib = _lib.load()
-    nbytes = int(lib.cfm_ctc_beam_stream_state_bytes(B, Tm, W, K, int(lm_tables is not None), int(hw_tables is not None)))
+    lm, hw = int(lm_tables is not None), int(hw_tables is not None)
+    if commit is None:
+        Tm = int(max_frames)
+        nbytes = int(lib.cfm_ctc_beam_stream_state_bytes(B, Tm, W, K, lm, hw))
+    else:
+        Tm = commit[0] + commit[1]
+        nbytes = int(lib.cfm_ctc_beam_commit_state_bytes(B, commit[0], commit[1], W, K, lm, hw))
     if nbytes == 0:
-        raise ValueError(f"beam_ctc_stream_init: unsupported arguments (B={B}, max_frames={Tm}, beam_width={W}, "
-                         f"max_candidates={K})")
+        raise ValueError(f"beam_ctc_stream_init: unsupported arguments (B={B}, max_frames={max_frames}, beam_width={W}, "
+                         f"max_candidates={K}, max_pending={max_pending}, max_chunk_frames={max_chunk_frames})")
     buf = torch.empty(nbytes, dtype=torch.uint8, device=device)
     st = _StreamState(buf, B, Tm, W, K,
                       _Fusion(lm_tables, hw_tables, alpha, beta, unk_score_offset, score_boundary, hotword_weight))
+    if commit is not None:
+        st.max_pending, st.max_chunk_frames = commit
+        st.log = torch.zeros(B, max(int(commit_log), Tm), dtype=torch.int32, device=device)
+        st.total = torch.zeros(B, dtype=torch.int64, device=device)
     beam_ctc_stream_reset(st)
     return st
 
@@ -288,6 +335,9 @@ def beam_ctc_stream_reset(st: _StreamState) -> None:
     _lib.call("cfm_ctc_beam_stream_init", st.B, st.t_max, st.beam_width, st.max_candidates, ops._p(f.lm_tables), f.score_boundary,
               ops._p(f.hw_tables), st.buf.data_ptr(), st.buf.numel(), ops._stream())
     st.t_used = 0
+    if st.max_pending is not None:
+        st.total.zero_()
+        st.committed = None
 
 
 def beam_ctc_stream_reset_slots(st: _StreamState, slots: torch.Tensor) -> None:
@@ -300,6 +350,8 @@ def beam_ctc_stream_reset_slots(st: _StreamState, slots: torch.Tensor) -> None:
     _lib.call("cfm_ctc_beam_stream_reset_slots", st.B, st.t_max, st.beam_width, st.max_candidates, ops._p(f.lm_tables),
               f.score_boundary, ops._p(f.hw_tables), slots.data_ptr(), slots.numel(), st.buf.data_ptr(), st.buf.numel(),
               ops._stream())
+    if st.max_pending is not None:         # (the slots' committed prefixes are empty again; the other slots' logs stay)
+        _lib.call("cfm_ctc_beam_commit_reset_slots", st.B, slots.data_ptr(), slots.numel(), st.total.data_ptr(), ops._stream())
 
 
 def beam_ctc_stream_step(st: _StreamState, logits: torch.Tensor, blank_id: int, lengths: Optional[torch.Tensor] = None, *,
@@ -310,7 +362,11 @@ def beam_ctc_stream_step(st: _StreamState, logits: torch.Tensor, blank_id: int, 
     without end-of-utterance terms, am_scores (B,N) fp32 or None without LM and hotwords, num_hyps (B)), device tensors;
     nothing synchronises with the host.  t_used: the caller's own bound on the frames any utterance consumed before this
     step (independent streams pass max_b(frames_b + lengths_b) - Tc, having checked frames_b + lengths_b <= max_frames);
-    None: the chunk frames stepped since the init, which this call then advances."""
+    None: the chunk frames stepped since the init, which this call then advances.
+    Commit mode: Tc <= max_chunk_frames; the step is followed by the commit, the returned tokens are (B,N,max_pending +
+    max_chunk_frames) and relative to the committed prefix as it was BEFORE this step (st.committed: the (B) int32 tokens this
+    step then committed, so the pending best is tokens[b, r, st.committed[b]:counts[b, r]]); t_used is taken as a bound on
+    the frames stepped and capped at max_pending, which bounds what the tree holds after a commit."""
     x = _logits(logits)
     if x.dim() != 3 or x.shape[0] != st.B:
         raise ValueError(f"logits: expected ({st.B},Tc,V), got {tuple(x.shape)}")
@@ -318,6 +374,11 @@ def beam_ctc_stream_step(st: _StreamState, logits: torch.Tensor, blank_id: int, 
     if Tc < 1:
         raise ValueError("beam_ctc_stream_step: the chunk has no frames")
     used = st.t_used if t_used is None else int(t_used)
+    if st.max_pending is not None:
+        if Tc > st.max_chunk_frames:
+            raise ValueError(f"beam_ctc_stream_step: a chunk of {Tc} frames, the tree was sized for max_chunk_frames="
+                             f"{st.max_chunk_frames}")
+        used = min(used, st.max_pending)
     if used < 0 or Tc > st.t_max - used:
         raise ValueError(f"beam_ctc_stream_step: {Tc} more frames would pass max_frames={st.t_max} "
                          f"({used} stepped so far)")
@@ -330,12 +391,40 @@ def beam_ctc_stream_step(st: _StreamState, logits: torch.Tensor, blank_id: int, 
               num_hyps.data_ptr(), ops._stream())
     if t_used is None:
         st.t_used += Tc
+    if st.max_pending is not None:
+        st.committed = torch.empty(st.B, dtype=torch.int32, device=x.device)
+        f = st.fusion
+        _lib.call("cfm_ctc_beam_stream_commit", st.B, st.max_pending, st.max_chunk_frames, st.beam_width, st.max_candidates,
+                  int(f.lm_tables is not None), int(f.hw_tables is not None), ops._p(lengths), st.buf.data_ptr(), st.buf.numel(),
+                  st.log.data_ptr(), st.log.shape[1], st.total.data_ptr(), st.committed.data_ptr(), ops._stream())
     return tokens, counts, scores, am_scores, num_hyps
+
+
+def beam_ctc_stream_committed(st: _StreamState, popped: Sequence[int], only: Optional[Sequence[int]] = None
+                              ) -> Tuple[List[List[int]], List[int]]:
+    """Commit mode: per utterance the committed tokens from position popped[b] on, and the totals.  Synchronises.  `only`: the
+    utterances to read (the others get an empty list and are not checked; only their rows of the log are copied).  RuntimeError
+    naming the utterances, before anything is copied, where more than the ring holds were committed since popped[b] (the
+    oldest are overwritten)."""
+    rows = list(range(st.B)) if only is None else [int(b) for b in only]
+    total = st.total.cpu().tolist()
+    L = st.log.shape[1]
+    over = [b for b in rows if total[b] - popped[b] > L]
+    if over:
+        raise RuntimeError(f"utterance(s) {over}: {[total[b] - popped[b] for b in over]} tokens committed since the last pop, the "
+                           f"commit log holds {L}: pop more often, give a larger commit_log, or discard them")
+    out: List[List[int]] = [[] for _ in range(st.B)]
+    if rows:
+        log = st.log.cpu() if only is None else st.log[torch.tensor(rows, device=st.log.device)].cpu()
+        for i, b in enumerate(rows):
+            out[b] = log[i, torch.arange(popped[b], total[b]) % L].tolist()
+    return out, total
 
 
 def beam_ctc_stream_finish(st: _StreamState, n_best: int = 1):
     """The end-of-utterance step over the consumed frames: (tokens (B,N,max_frames), counts, scores, am_scores or None
-    without LM and hotwords, num_hyps), equal bit for bit to one-shot decoding of the consumed frames (with T = max_frames)."""
+    without LM and hotwords, num_hyps), equal bit for bit to one-shot decoding of the consumed frames (with T = max_frames).
+    Commit mode: the tokens are (B,N,max_pending + max_chunk_frames) and follow the committed prefix (st.log / st.total)."""
     tokens, counts, scores, am_scores, num_hyps = _beam_outputs(st.B, int(n_best), st.t_max, st.buf.device,
                                                                 st.fusion.fused)
     _lib.call("cfm_ctc_beam_stream_finish_f32", st.B, st.beam_width, st.max_candidates, int(n_best), *st.fusion.args,
@@ -347,18 +436,25 @@ def beam_ctc_stream_finish(st: _StreamState, n_best: int = 1):
 class BeamCTCStream:
     """A BeamCTCDecoder's search over a stream of logits chunks (BeamCTCDecoder.stream).  `step` enqueues the chunk and returns
     the interim best as device tensors; `partial_text` is the one call that synchronises; `finish` returns the strings
-    BeamCTCDecoder.__call__ returns on the concatenated logits; `reset` starts a new batch of utterances."""
+    BeamCTCDecoder.__call__ returns on the concatenated logits; `reset` starts a new batch of utterances.
+    Commit mode (max_pending, max_chunk_frames, max_frames=None): the stream has no end.  `pop_committed` hands out the tokens
+    that have become final since the previous pop; `committed_text`, `partial_text` and `finish` speak of the text from the
+    last pop on: (unpopped committed) [+ pending best | + final tokens], joined as token ids before `decoder.text`."""
 
-    def __init__(self, decoder: "BeamCTCDecoder", batch: int, max_frames: int, device=None) -> None:
+    def __init__(self, decoder: "BeamCTCDecoder", batch: int, max_frames: Optional[int], device=None, *,
+                 max_pending: Optional[int] = None, max_chunk_frames: Optional[int] = None, commit_log: int = 4096) -> None:
+        self.commit = _commit_args("BeamCTCStream", max_frames, max_pending, max_chunk_frames, commit_log) is not None
         self.decoder = decoder
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         d, f = decoder, decoder._fusion(self.device)
         self.state = beam_ctc_stream_init(batch, max_frames, self.device, beam_width=d.beam_width,
                                           max_candidates=d.max_candidates, lm_tables=f.lm_tables, hw_tables=f.hw_tables,
                                           alpha=d.alpha, beta=d.beta, unk_score_offset=d.unk_score_offset,
-                                          score_boundary=d.score_boundary, hotword_weight=d.hotword_weight)
+                                          score_boundary=d.score_boundary, hotword_weight=d.hotword_weight,
+                                          max_pending=max_pending, max_chunk_frames=max_chunk_frames, commit_log=commit_log)
         self.finished = False
         self.last = None                   # interim outputs of the latest step
+        self.popped = [0] * int(batch)     # commit mode: committed tokens handed out by pop_committed, per utterance
 
     def step(self, logits_chunk: torch.Tensor, lengths: Optional[torch.Tensor] = None):
         """logits_chunk (B,Tc,V): the next frames of every utterance; `lengths` (B) int64: frames of the chunk to consume per
@@ -370,24 +466,61 @@ class BeamCTCStream:
             lengths = torch.as_tensor(lengths, dtype=torch.int64).reshape(-1).to(self.device)
         out = beam_ctc_stream_step(self.state, logits_chunk, d.blank_id, lengths, n_best=1, token_min_logp=d.token_min_logp,
                                    beam_prune_logp=d.beam_prune_logp)
-        self.last = out
+        self.last = out + (self.state.committed,) if self.commit else out
         return out[0], out[1], out[2]
 
+    def _need_commit(self, what: str) -> None:
+        if not self.commit:
+            raise RuntimeError(f"BeamCTCStream.{what}: the stream was made without max_pending, nothing is committed before "
+                               "finish()")
+
+    def _unpopped(self) -> Tuple[List[List[int]], List[int]]:
+        return beam_ctc_stream_committed(self.state, self.popped)
+
+    def pop_committed(self) -> List[List[int]]:
+        """Commit mode: per utterance the token ids committed since the previous pop (they will never change), which are then
+        forgotten.  Synchronises.  RuntimeError, with nothing popped, if more than commit_log tokens were committed in between."""
+        self._need_commit("pop_committed")
+        ids, self.popped = self._unpopped()
+        return ids
+
+    def discard_committed(self) -> None:
+        """Commit mode: forget every committed token not yet popped (the way out after pop_committed raised: the ring was
+        lapped and those tokens cannot all be read any more).  Synchronises."""
+        self._need_commit("discard_committed")
+        self.popped = self.state.total.cpu().tolist()
+
+    def committed_text(self) -> List[str]:
+        """Commit mode: the text of the committed tokens not yet popped."""
+        self._need_commit("committed_text")
+        return [self.decoder.text(ids) for ids in self._unpopped()[0]]
+
     def partial_text(self) -> List[str]:
-        """The interim best transcript of every utterance after the latest step (empty strings before the first)."""
+        """The interim best transcript of every utterance after the latest step (empty strings before the first).  Commit
+        mode: from the last pop on, the committed tokens and then the pending best."""
         if self.last is None:
             return [""] * self.state.B
-        return self.decoder._texts(self.last[0], self.last[1])
+        if not self.commit:
+            return self.decoder._texts(self.last[0], self.last[1])
+        ids = self._unpopped()[0]
+        tk, ct, nc = self.last[0][:, 0].cpu().tolist(), self.last[1][:, 0].cpu().tolist(), self.last[5].cpu().tolist()
+        return [self.decoder.text(ids[b] + tk[b][nc[b]:ct[b]]) for b in range(self.state.B)]
 
     def finish(self, decode_func: Optional[Callable[[str], str]] = None) -> List[str]:
         if self.finished:
             raise RuntimeError("BeamCTCStream.finish() called twice: call reset() to start a new stream")
         tokens, counts, _, _, _ = beam_ctc_stream_finish(self.state, n_best=1)
         self.finished = True
-        return self.decoder._texts(tokens, counts, decode_func)
+        if not self.commit:
+            return self.decoder._texts(tokens, counts, decode_func)
+        ids = self._unpopped()[0]
+        tk, ct = tokens[:, 0].cpu().tolist(), counts[:, 0].cpu().tolist()
+        texts = [self.decoder.text(ids[b] + tk[b][:ct[b]]) for b in range(self.state.B)]
+        return [decode_func(t) for t in texts] if decode_func is not None else texts
 
     def reset(self) -> None:
         beam_ctc_stream_reset(self.state)
         self.finished = False
         self.last = None
+        self.popped = [0] * len(self.popped)
 

@@ -35,11 +35,11 @@ import numpy as np
 import torch
 
 from . import ops
-from .decode import BeamCTCDecoder, beam_ctc_stream_finish, beam_ctc_stream_init, beam_ctc_stream_reset_slots, \
-    beam_ctc_stream_step
+from .decode import BeamCTCDecoder, beam_ctc_stream_committed, beam_ctc_stream_finish, beam_ctc_stream_init, \
+    beam_ctc_stream_reset_slots, beam_ctc_stream_step
 from .model.modules.encoder import Encoder
 from .streaming import StreamingEncoder, _refuse_window_autocast, encoder_frames
-from .transcribe import decode_frames, lstm_state
+from .transcribe import decode_frames, lstm_state, search_plan
 
 _TAIL = 8                  # mel-tail buffer width: a slot carries 0..6 un-consumed frames
 
@@ -289,14 +289,20 @@ class SlotTranscriber:
         tr.open(s); logits, k = tr.step(mel, frames); tr.partial_text(); text = tr.close(s)
 
     close(s) returns what decoder(...) returns on that slot's concatenated logits.  Eval mode only; dtype: as
-    SlotStreamingEncoder (the LSTM state and the logits stay fp32; the search consumes the logits the step returned)."""
+    SlotStreamingEncoder (the LSTM state and the logits stay fp32; the search consumes the logits the step returned).
+    max_pending=M (tokens; needs left_context): every slot's search commits the prefix that can no longer change after each
+    of its steps (INTEGRATION.md "Committed-prefix streaming (max_pending)"); the search buffers are sized by M and the largest
+    step alone and max_mel_frames may be None.  pop_committed() hands out each open slot's final tokens as they come;
+    partial_text() and close(s) then speak of the slot's text from its last pop on."""
 
-    def __init__(self, model, decoder: BeamCTCDecoder, slots: int, max_mel_frames: int,
+    def __init__(self, model, decoder: BeamCTCDecoder, slots: int, max_mel_frames: Optional[int],
                  dtype: Optional[torch.dtype] = None, *, left_context: Optional[int] = None,
-                 max_chunk_mel_frames: Optional[int] = None) -> None:
+                 max_chunk_mel_frames: Optional[int] = None, max_pending: Optional[int] = None,
+                 commit_log: int = 4096) -> None:
         self.dtype = _slot_dtype("SlotTranscriber", dtype)
         if self.dtype is not None and left_context is not None:
             raise NotImplementedError(f"SlotTranscriber: left_context with dtype={self.dtype} (no 16-bit window kernel yet)")
+        self.commit = search_plan("SlotTranscriber", max_mel_frames, left_context, max_chunk_mel_frames, max_pending)
         self.device, self.state = lstm_state(model, "SlotTranscriber", int(slots))
         self.model = model
         self.decoder = decoder
@@ -304,10 +310,14 @@ class SlotTranscriber:
                                             max_chunk_mel_frames=max_chunk_mel_frames)
         self.S = self.encoder.S
         f = decoder._fusion(self.device)
-        self.beam = beam_ctc_stream_init(self.S, self.encoder.t_max, self.device, beam_width=decoder.beam_width,
-                                         max_candidates=decoder.max_candidates, lm_tables=f.lm_tables, hw_tables=f.hw_tables,
-                                         alpha=decoder.alpha, beta=decoder.beta, unk_score_offset=decoder.unk_score_offset,
-                                         score_boundary=decoder.score_boundary, hotword_weight=decoder.hotword_weight)
+        M, k_cap = self.commit or (None, None)
+        self.beam = beam_ctc_stream_init(self.S, None if self.commit else self.encoder.t_max, self.device,
+                                         beam_width=decoder.beam_width, max_candidates=decoder.max_candidates,
+                                         lm_tables=f.lm_tables, hw_tables=f.hw_tables, alpha=decoder.alpha, beta=decoder.beta,
+                                         unk_score_offset=decoder.unk_score_offset, score_boundary=decoder.score_boundary,
+                                         hotword_weight=decoder.hotword_weight, max_pending=M, max_chunk_frames=k_cap,
+                                         commit_log=commit_log)
+        self.popped = [0] * self.S         # commit mode: committed tokens handed out by pop_committed, per slot
         self._last = None                  # interim outputs of the latest beam step
         self._fresh = set()                # slots opened since it
 
@@ -317,7 +327,8 @@ class SlotTranscriber:
 
     def _reset_beam(self, s: int) -> None:
         idx = torch.tensor([s], dtype=torch.int64).pin_memory().to(self.device, non_blocking=True)
-        beam_ctc_stream_reset_slots(self.beam, idx)
+        beam_ctc_stream_reset_slots(self.beam, idx)        # (commit mode: the slot's committed total too)
+        self.popped[s] = 0
 
     def open(self, s: int) -> None:
         """Start an utterance in free slot s (enqueues only)."""
@@ -350,8 +361,10 @@ class SlotTranscriber:
         # the search's bound: the furthest slot after this step, less the chunk (each slot's own frames_b + k_b <= T_max
         # holds: the encoder refused more than max_mel_frames)
         t_used = max(a + b for a, b in zip(n0, ks)) - k_max
+        if self.commit:                    # after a commit a slot's tree holds at most min(max_pending, its frames) frames
+            t_used = min(self.commit[0], max(n0))
         self._last = beam_ctc_stream_step(self.beam, logits, d.blank_id, k_dev, n_best=1, token_min_logp=d.token_min_logp,
-                                          beam_prune_logp=d.beam_prune_logp, t_used=t_used)
+                                          beam_prune_logp=d.beam_prune_logp, t_used=t_used) + (self.beam.committed,)
         self._fresh.clear()
         return logits, ks
 
@@ -360,17 +373,48 @@ class SlotTranscriber:
         open_slots = [s for s in range(self.S) if self.encoder.is_open[s]]
         if self._last is None:
             return {s: "" for s in open_slots}
+        if self.commit:                    # from the slot's last pop on: the committed tokens, then the pending best
+            ids = beam_ctc_stream_committed(self.beam, self.popped, open_slots)[0]
+            tk, ct, nc = self._last[0][:, 0].cpu().tolist(), self._last[1][:, 0].cpu().tolist(), self._last[5].cpu().tolist()
+            return {s: "" if s in self._fresh else self.decoder.text(ids[s] + tk[s][nc[s]:ct[s]]) for s in open_slots}
         texts = self.decoder._texts(self._last[0], self._last[1])
         return {s: "" if s in self._fresh else texts[s] for s in open_slots}
+
+    def pop_committed(self) -> Dict[int, List[int]]:
+        """With max_pending: per open slot the token ids that became final since its previous pop, which are then forgotten
+        (synchronises).  RuntimeError, with nothing popped, if a slot committed more than commit_log tokens in between."""
+        if not self.commit:
+            raise RuntimeError("SlotTranscriber.pop_committed: made without max_pending, nothing is committed before close()")
+        open_slots = [s for s in range(self.S) if self.encoder.is_open[s]]
+        ids, total = beam_ctc_stream_committed(self.beam, self.popped, open_slots)
+        for s in open_slots:
+            self.popped[s] = total[s]
+        return {s: ids[s] for s in open_slots}
+
+    def discard_committed(self, s: int) -> None:
+        """With max_pending: forget slot s's committed tokens that were not popped (the way out when the slot committed more
+        than commit_log tokens between pops, after which partial_text and pop_committed raise for it; close(s) also frees it)."""
+        if not self.commit:
+            raise RuntimeError("SlotTranscriber.discard_committed: made without max_pending")
+        s = self.encoder._check_slot(s, want_open=True)
+        self.popped[s] = int(self.beam.total[s])
 
     def close(self, s: int, decode_func: Optional[Callable[[str], str]] = None) -> str:
         """End slot s's utterance: its final transcript (BeamCTCDecoder on its logits); the slot becomes free.  The finish
         saves no search state, so the other slots go on untouched."""
         s = self.encoder._check_slot(s, want_open=True)
         tokens, counts, _, _, _ = beam_ctc_stream_finish(self.beam, n_best=1)
-        text = self.decoder._texts(tokens[s:s + 1], counts[s:s + 1], decode_func)[0]
-        self._reset_beam(s)
-        self.encoder.close(s)
+        try:
+            if self.commit:                # the slot's whole unpopped text: its committed tokens, then the final ones; only
+                # slot s is read, and a lapped ring raises for s alone, after the slot was freed all the same
+                ids = beam_ctc_stream_committed(self.beam, self.popped, [s])[0][s]
+                text = self.decoder.text(ids + tokens[s, 0, :int(counts[s, 0])].tolist())
+                text = decode_func(text) if decode_func is not None else text
+            else:
+                text = self.decoder._texts(tokens[s:s + 1], counts[s:s + 1], decode_func)[0]
+        finally:
+            self._reset_beam(s)
+            self.encoder.close(s)
         return text
 
     def reset(self) -> None:

@@ -16,7 +16,7 @@ import torch
 
 from . import ops
 from .decode import BeamCTCDecoder, BeamCTCStream
-from .streaming import StreamingEncoder
+from .streaming import StreamingEncoder, ring_plan
 
 
 @torch.no_grad()
@@ -33,6 +33,25 @@ def decode_frames(model, state, enc: torch.Tensor, lengths: Optional[torch.Tenso
     n = dec.norm
     z = ops.swish_bn_eval(h, n.running_mean, n.running_var, n.weight.detach(), n.bias.detach(), n.eps)
     return ops.linear(z, dec.linear.weight.detach(), dec.linear.bias.detach())
+
+
+def search_plan(who: str, max_mel_frames, left_context, max_chunk_mel_frames, max_pending):
+    """The transcribers' sizing of the beam search, checked on the host before anything else: None (the search ends with
+    max_mel_frames) or (max_pending, k_cap), k_cap = ring_plan's encoder frames per step."""
+    if max_mel_frames is None and left_context is None:
+        raise ValueError(f"{who}: max_mel_frames=None (a stream without an end) needs left_context")
+    if max_pending is None:
+        if max_mel_frames is None:
+            raise ValueError(f"{who}: max_mel_frames=None (a stream without an end) needs max_pending: without it the beam "
+                             "search's buffers are sized by the stream's length")
+        return None
+    if left_context is None or max_chunk_mel_frames is None:
+        missing = "left_context" if left_context is None else "max_chunk_mel_frames"
+        raise ValueError(f"{who}: max_pending needs {missing} (the search's tree is sized for the largest step of a windowed "
+                         "stream)")
+    if int(max_pending) < 1:
+        raise ValueError(f"{who}: max_pending must be >= 1 token, got {max_pending}")
+    return int(max_pending), ring_plan(left_context, max_chunk_mel_frames)[2]
 
 
 def lstm_state(model, who: str, batch: int):
@@ -55,18 +74,27 @@ def lstm_state(model, who: str, batch: int):
 class StreamingTranscriber:
     """model: a Conformer in eval() mode on the HIP device; decoder: the BeamCTCDecoder whose configuration (beam knobs, lm,
     hotwords) the streamed search takes; batch utterances of at most max_mel_frames mel frames.  graphs, check_weights,
-    left_context, max_chunk_mel_frames: as StreamingEncoder (max_mel_frames still sizes the beam search's buffers; with
-    left_context the encoder no longer allocates by it)."""
+    left_context, max_chunk_mel_frames: as StreamingEncoder (without max_pending, max_mel_frames still sizes the beam search's
+    buffers; with left_context the encoder no longer allocates by it).
+    max_pending=M (tokens; needs left_context): the search commits the prefix that can no longer change after every step
+    (INTEGRATION.md "Committed-prefix streaming (max_pending)"), its buffers are sized by M and the largest step alone, and
+    max_mel_frames may be None: a stream without an end.  pop_committed() hands out the final tokens as they come."""
 
-    def __init__(self, model, decoder: BeamCTCDecoder, batch: int, max_mel_frames: int, graphs: bool = False,
+    def __init__(self, model, decoder: BeamCTCDecoder, batch: int, max_mel_frames: Optional[int], graphs: bool = False,
                  check_weights: bool = True, *, left_context: Optional[int] = None,
-                 max_chunk_mel_frames: Optional[int] = None) -> None:
+                 max_chunk_mel_frames: Optional[int] = None, max_pending: Optional[int] = None,
+                 commit_log: int = 4096) -> None:
+        plan = search_plan("StreamingTranscriber", max_mel_frames, left_context, max_chunk_mel_frames, max_pending)
         self.B = int(batch)
         device, self.state = lstm_state(model, "StreamingTranscriber", self.B)
         self.model = model
         self.encoder = StreamingEncoder(model.encoder, batch, max_mel_frames, graphs=graphs, check_weights=check_weights,
                                         left_context=left_context, max_chunk_mel_frames=max_chunk_mel_frames)
-        self.beam: BeamCTCStream = decoder.stream(self.B, self.encoder.t_max, device)
+        if plan is None:
+            self.beam: BeamCTCStream = decoder.stream(self.B, self.encoder.t_max, device)
+        else:
+            self.beam = decoder.stream(self.B, None, device, max_pending=plan[0], max_chunk_frames=plan[1],
+                                       commit_log=commit_log)
 
     def reset(self) -> None:
         self.encoder.reset()
@@ -93,6 +121,13 @@ class StreamingTranscriber:
 
     def partial_text(self) -> List[str]:
         return self.beam.partial_text()
+
+    def pop_committed(self) -> List[List[int]]:
+        """With max_pending: per utterance the token ids that became final since the previous pop (BeamCTCStream)."""
+        return self.beam.pop_committed()
+
+    def committed_text(self) -> List[str]:
+        return self.beam.committed_text()
 
     def finish(self, decode_func: Optional[Callable[[str], str]] = None) -> List[str]:
         return self.beam.finish(decode_func)

@@ -13,7 +13,9 @@ beam search at W=100 with and without a synthetic word n-gram LM.
              ops._key_split and with keys_hint=1 (no split), against the 16-bit rows kernel (which has no split)
 
 --dtype bf16 | fp16: the slot objects are built with dtype= (16-bit K/V caches, every step under their own autocast) and the
-lockstep StreamingTranscriber steps under torch.autocast of that type.  Random weights, so the logits are not peaky: the beam search runs at its random-logit cost (the upper end)."""
+lockstep StreamingTranscriber steps under torch.autocast of that type.
+--left-context L: bounded history (ring K/V caches sized for --chunk); --max-pending M (with it; L defaults to 256): the search
+commits after every step and its buffers no longer scale with --max-mel (fp32 only).  Random weights, so the logits are not peaky: the beam search runs at its random-logit cost (the upper end)."""
 import argparse
 import contextlib
 import json
@@ -76,7 +78,8 @@ def _autocast(dt):
     return contextlib.nullcontext() if dt is None else torch.autocast("cuda", dtype=dt)
 
 
-def lockstep(m, dec, S, chunk, steps, dev, dt=None):
+def lockstep(m, dec, S, chunk, steps, dev, dt=None, kw=None):
+    kw = kw or {}
     x = torch.randn(S, 80, chunk, device=dev)
     out = {}
 
@@ -88,10 +91,10 @@ def lockstep(m, dec, S, chunk, steps, dev, dt=None):
         best = None
         for _ in range(2):                                     # the first pass warms up (packs, tables)
             if name == "streaming":
-                tr = StreamingTranscriber(m, dec, S, chunk * steps)
+                tr = StreamingTranscriber(m, dec, S, chunk * steps, **kw)
                 run = lambda: stream_step(tr)                   # noqa: E731
             else:
-                tr = SlotTranscriber(m, dec, S, chunk * steps, dtype=dt)
+                tr = SlotTranscriber(m, dec, S, chunk * steps, dtype=dt, **kw)
                 for s in range(S):
                     tr.open(s)
                 run = lambda: tr.step(x, [chunk] * S)           # noqa: E731
@@ -163,16 +166,28 @@ def main():
     ap.add_argument("--dtype", choices=["fp32", "bf16", "fp16"], default="fp32",
                     help="precision of the slot objects (dtype=) and autocast type of the lockstep and attention comparisons")
     ap.add_argument("--attention-only", action="store_true", help="only the attention section")
+    ap.add_argument("--no-attention", action="store_true", help="skip the attention section")
+    ap.add_argument("--left-context", type=int, default=None, help="bounded history: encoder frames a query looks back on")
+    ap.add_argument("--max-pending", type=int, default=None,
+                    help="commit mode: uncommitted tokens the best hypothesis may hold (left context 256 unless given)")
     args = ap.parse_args()
+    if args.max_pending is not None and args.left_context is None:
+        args.left_context = 256
+    kw = {}
+    if args.left_context is not None:
+        kw = dict(left_context=args.left_context, max_chunk_mel_frames=args.chunk)
+        if args.max_pending is not None:
+            kw["max_pending"] = args.max_pending
     dt = {"fp32": None, "bf16": torch.bfloat16, "fp16": torch.float16}[args.dtype]
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
     vocab = ["<pad>"] + [chr(ord("a") + i) for i in range(26)] + ["'", "|", "<unk>"]
     m = Conformer(len(vocab), 80, 16, 512, 8, 31, 640, 1, 0.0).to(dev).eval()
     out = {"what": "independent streams (slots): Conformer-L, 640-frame chunks, beam W=100", "chunk": args.chunk,
-           "beam_width": args.beam, "dtype": args.dtype, "runs": [], "attention_ab": {}}
+           "beam_width": args.beam, "dtype": args.dtype, "left_context": args.left_context, "max_pending": args.max_pending,
+           "runs": [], "attention_ab": {}}
     with torch.no_grad():
-        for S in args.slots:
+        for S in [] if args.no_attention else args.slots:
             out["attention_ab"][f"S{S}"] = attention_ab(S, dev, dt)
             print(json.dumps({f"attention_ab S{S}": out["attention_ab"][f"S{S}"]}), file=sys.stderr, flush=True)
     if args.attention_only:
@@ -187,14 +202,14 @@ def main():
         for name, lm in lms:
             dec = BeamCTCDecoder(vocab, blank_id=0, skip_ids=(len(vocab) - 1,), beam_width=args.beam, lm=lm)
             for S in args.slots:
-                tr = SlotTranscriber(m, dec, S, args.max_mel, dtype=dt)
+                tr = SlotTranscriber(m, dec, S, args.max_mel, dtype=dt, **kw)
                 staggered(tr, S, args.chunk, 3, args.max_mel, 0, dev)          # warm-up
                 del tr
-                tr = SlotTranscriber(m, dec, S, args.max_mel, dtype=dt)
+                tr = SlotTranscriber(m, dec, S, args.max_mel, dtype=dt, **kw)
                 run = {"decoder": name, "slots": S, "staggered": staggered(tr, S, args.chunk, args.steps, args.max_mel, 1, dev)}
                 del tr
                 torch.cuda.empty_cache()
-                run["lockstep"] = lockstep(m, dec, S, args.chunk, args.lockstep_steps, dev, dt)
+                run["lockstep"] = lockstep(m, dec, S, args.chunk, args.lockstep_steps, dev, dt, kw)
                 out["runs"].append(run)
                 print(json.dumps(run), file=sys.stderr, flush=True)
     print(json.dumps(out))

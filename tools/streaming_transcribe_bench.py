@@ -2,7 +2,9 @@
 """BASELINE cfg-5 with text out: streaming transcription (conformer_amd.transcribe.StreamingTranscriber), B=8, T=20000 mel
 frames in 640-frame chunks, Conformer-L, resumable CTC beam search at W=100, with and without a word n-gram LM.  Reports the
 per-chunk latency split into encoder step, decoder LSTM + projection, and beam step (each part synchronised and timed on its
-own), the whole-stream time with the parts back to back, and the real-time factor per stream.  Random weights, so the
+own), the whole-stream time with the parts back to back, and the real-time factor per stream.  --left-context L: bounded
+history; --max-pending M (with it; L defaults to 256): the beam step commits, its buffers no longer scale with --frames.
+Random weights, so the
 logits are not peaky: the beam search runs at its random-logit cost (the upper end)."""
 import argparse
 import json
@@ -64,7 +66,17 @@ def main():
     ap.add_argument("--beam", type=int, default=100)
     ap.add_argument("--repeats", type=int, default=2)
     ap.add_argument("--lm-ngrams", type=int, default=200000, help="n-grams per order (2..5) of the synthetic ARPA model")
+    ap.add_argument("--left-context", type=int, default=None, help="bounded history: encoder frames a query looks back on")
+    ap.add_argument("--max-pending", type=int, default=None,
+                    help="commit mode: uncommitted tokens the best hypothesis may hold (left context 256 unless given)")
     args = ap.parse_args()
+    if args.max_pending is not None and args.left_context is None:
+        args.left_context = 256
+    kw = {}
+    if args.left_context is not None:
+        kw = dict(left_context=args.left_context, max_chunk_mel_frames=args.chunk)
+        if args.max_pending is not None:
+            kw["max_pending"] = args.max_pending
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
     vocab = ["<pad>"] + [chr(ord("a") + i) for i in range(26)] + ["'", "|", "<unk>"]
@@ -72,13 +84,14 @@ def main():
     x = torch.randn(args.batch, 80, args.frames, device=dev)
     audio_s = args.frames * 0.010
     out = {"what": "cfg-5 streaming transcription: encoder step + carried-state decoder + resumable beam step",
-           "batch": args.batch, "mel_frames": args.frames, "chunk": args.chunk, "beam_width": args.beam, "runs": []}
+           "batch": args.batch, "mel_frames": args.frames, "chunk": args.chunk, "beam_width": args.beam,
+           "left_context": args.left_context, "max_pending": args.max_pending, "runs": []}
     with tempfile.TemporaryDirectory() as tmp:
         arpa = os.path.join(tmp, "bench.arpa")
         write_synthetic_arpa(arpa, vocab[1:28], 20000, [0] + [args.lm_ngrams] * 4, seed=1, max_tokens_per_word=6)
         for name, lm in (("no_lm", None), ("lm_5gram", arpa)):
             dec = BeamCTCDecoder(vocab, blank_id=0, skip_ids=(len(vocab) - 1,), beam_width=args.beam, lm=lm)
-            tr = StreamingTranscriber(m, dec, args.batch, args.frames)
+            tr = StreamingTranscriber(m, dec, args.batch, args.frames, **kw)
             total, enc_ms, dec_ms, beam_ms = run(tr, x, args.chunk, args.repeats)
             out["runs"].append({"decoder": name, "stream_ms": total * 1e3, "chunks": len(enc_ms),
                                 "realtime_factor_per_stream": audio_s / total,

@@ -6,7 +6,7 @@ MelSpectrogram(16 kHz, n_fft 400, win 400 periodic Hann, hop 160, centre reflect
 bins 0-8000 Hz) -> log(clamp(., 1e-5)):
     cfm_reflect_pad_f32 -> ONE batched MFMA GEMM (frames are overlapping rows of the padded wave, lda = hop; the window is
     folded into the (416, 400) [cos; 0; -sin; 0] basis) -> cfm_power_mel_log_mfma_f32 (mel products on the matrix pipe) writes
-    (B, 80, T) directly.
+    (B, 80, T) directly.  A hop that is no multiple of 4 samples runs the same GEMM over a contiguous copy of the frames.
 The DFT basis and the mel filterbank are built once on the host in float64 (they are constants of the configuration).
 Parity: torchaudio is not available to pin against -> "parity unpinned" (DESIGN.md); tests compare with an fp64 DFT.
 """
@@ -83,14 +83,19 @@ class ConformerAudioFrontend:
         xp = xbuf[:B * Lp].view(B, Lp)
         _lib.call("cfm_reflect_pad_f32", x.data_ptr(), xp.data_ptr(), B, L, pad, Lp, ops._stream())
         nb2 = self.basis.shape[0]                                                    # 2 * nk = 416 DFT columns (Re | Im, zero-padded)
-        spec = torch.empty(B * rpu, nb2, device=x.device, dtype=torch.float32)
         if hop % 4 == 0:
             # frames = overlapping rows of the padded waves (row b * rpu + t); the tuned forward GEMM with lda = hop
+            spec = torch.empty(B * rpu, nb2, device=x.device, dtype=torch.float32)
             _lib.call("cfm_dft_frames_f32", xp.data_ptr(), self.basis.data_ptr(), spec.data_ptr(), B * rpu, nb2, self.n_fft, hop,
                       ops._stream())
         else:
-            ops.gemm_bwd(xp, False, self.basis, False, T, nb2, self.n_fft, out=spec, lda=hop, ldb=self.n_fft,
-                         ldc=nb2, nbatch=B, nb1=1, sa=(Lp, 0), sb=(0, 0), sc=(rpu * nb2, 0))
+            # a hop that is no multiple of 4 floats leaves the overlapping rows off the 16-byte grid the GEMM loads on: copy the
+            # T frames of every utterance out (row b * T + t) and run the same GEMM over rows that no longer overlap
+            frames = xp.as_strided((B, T, self.n_fft), (Lp, hop, 1)).contiguous()
+            rpu = T
+            spec = torch.empty(B * T, nb2, device=x.device, dtype=torch.float32)
+            _lib.call("cfm_dft_frames_f32", frames.data_ptr(), self.basis.data_ptr(), spec.data_ptr(), B * T, nb2, self.n_fft,
+                      self.n_fft, ops._stream())
         out = torch.empty(B, self.n_mels, T, device=x.device, dtype=torch.float32)
         _lib.call("cfm_power_mel_log_mfma_f32", spec.data_ptr(), nb2, self.fbT.data_ptr(), out.data_ptr(), B, T, rpu,
                   self.n_fft // 2 + 1, self.n_mels, 1e-5, ops._stream())

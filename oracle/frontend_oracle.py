@@ -49,35 +49,62 @@ def mel_filterbank(n_freqs: int = N_FFT // 2 + 1, n_mels: int = N_MELS, sample_r
     return fb * enorm.unsqueeze(0)
 
 
-def log_mel(wave: torch.Tensor) -> torch.Tensor:
-    """ConformerProcessor.mel_spectrogram (processor.py:155-158): (B, L) -> (B, 80, L//160 + 1)."""
+def log_mel(wave: torch.Tensor, n_mels: int = N_MELS, hop: int = HOP, f_min: float = F_MIN, f_max: float = F_MAX,
+            sample_rate: int = SAMPLE_RATE) -> torch.Tensor:
+    """ConformerProcessor.mel_spectrogram (processor.py:155-158): (B, L) -> (B, n_mels, L//hop + 1)."""
     win = torch.hann_window(WIN, periodic=True, dtype=wave.dtype)
-    spec = torch.stft(wave, N_FFT, hop_length=HOP, win_length=WIN, window=win, center=True, pad_mode="reflect",
+    spec = torch.stft(wave, N_FFT, hop_length=hop, win_length=WIN, window=win, center=True, pad_mode="reflect",
                       normalized=False, onesided=True, return_complex=True)
     power = spec.abs().pow(2.0)                                        # (B, 201, T)
-    mel = torch.matmul(power.transpose(-1, -2), mel_filterbank(dtype=wave.dtype)).transpose(-1, -2)
+    fb = mel_filterbank(n_mels=n_mels, sample_rate=sample_rate, f_min=f_min, f_max=f_max, dtype=wave.dtype)
+    mel = torch.matmul(power.transpose(-1, -2), fb).transpose(-1, -2)
     return torch.log(torch.clamp(mel, min=LOG_FLOOR))
 
 
-def log_mel_numpy64(wave: np.ndarray) -> np.ndarray:
-    """Independent float64 restatement (explicit reflect padding, explicit DFT matrix) used to cross-check log_mel."""
+def _frames_and_basis(wave: np.ndarray, hop: int):
+    """Float64 (B, T, 400) frames of the reflect-padded waves and the (402, 400) windowed basis [cos; -sin]."""
     wave = np.asarray(wave, dtype=np.float64)
     pad = N_FFT // 2
     xp = np.pad(wave, ((0, 0), (pad, pad)), mode="reflect")
-    T = wave.shape[1] // HOP + 1
+    T = wave.shape[1] // hop + 1
     n = np.arange(N_FFT)
     win = 0.5 - 0.5 * np.cos(2 * np.pi * n / WIN)                     # periodic Hann
     k = np.arange(N_FFT // 2 + 1)[:, None]
-    basis = np.exp(-2j * np.pi * k * n[None, :] / N_FFT) * win[None, :]
-    frames = np.stack([xp[:, t * HOP:t * HOP + N_FFT] for t in range(T)], axis=1)   # (B, T, 400)
-    power = np.abs(frames @ basis.T) ** 2                              # (B, T, 201)
-    fb = mel_filterbank(dtype=torch.float64).numpy()
+    ang = 2 * np.pi * k * n[None, :] / N_FFT
+    basis = np.concatenate([np.cos(ang) * win[None, :], -np.sin(ang) * win[None, :]])
+    frames = np.stack([xp[:, t * hop:t * hop + N_FFT] for t in range(T)], axis=1)   # (B, T, 400)
+    return frames, basis
+
+
+def log_mel_numpy64(wave: np.ndarray, n_mels: int = N_MELS, hop: int = HOP, f_min: float = F_MIN, f_max: float = F_MAX,
+                    sample_rate: int = SAMPLE_RATE) -> np.ndarray:
+    """Independent float64 restatement (explicit reflect padding, explicit DFT matrix) used to cross-check log_mel."""
+    frames, basis = _frames_and_basis(wave, hop)
+    nb = N_FFT // 2 + 1
+    spec = frames @ basis.T                                            # (B, T, 402) = [Re | Im]
+    power = spec[..., :nb] ** 2 + spec[..., nb:] ** 2                  # (B, T, 201)
+    fb = mel_filterbank(n_mels=n_mels, sample_rate=sample_rate, f_min=f_min, f_max=f_max, dtype=torch.float64).numpy()
     return np.log(np.maximum(power @ fb, LOG_FLOOR)).transpose(0, 2, 1)
 
 
-def batch_lengths(sample_lengths: Sequence[int]) -> List[int]:
+def log_mel_f32(wave: np.ndarray, n_mels: int = N_MELS, hop: int = HOP, f_min: float = F_MIN, f_max: float = F_MAX,
+                sample_rate: int = SAMPLE_RATE) -> np.ndarray:
+    """The pipeline of log_mel_numpy64 in float32 numpy: the window folded into a basis that is built in float64 and rounded
+    to float32, a float32 product, float32 power and mel (filterbank built in float64, rounded), the float32 log.  It measures
+    what float32 rounding alone costs (the yardstick of the tight end-to-end bound); log_mel_numpy64 stays the reference."""
+    frames, basis = _frames_and_basis(wave, hop)
+    nb = N_FFT // 2 + 1
+    spec = frames.astype(np.float32) @ basis.astype(np.float32).T
+    power = spec[..., :nb] * spec[..., :nb] + spec[..., nb:] * spec[..., nb:]
+    fb = mel_filterbank(n_mels=n_mels, sample_rate=sample_rate, f_min=f_min, f_max=f_max, dtype=torch.float64).numpy()
+    mel = power @ fb.astype(np.float32)
+    assert mel.dtype == np.float32
+    return np.log(np.maximum(mel, np.float32(LOG_FLOOR))).transpose(0, 2, 1)
+
+
+def batch_lengths(sample_lengths: Sequence[int], hop: int = HOP) -> List[int]:
     """processor.py:392: frames = samples // hop + 1."""
-    return [n // HOP + 1 for n in sample_lengths]
+    return [n // hop + 1 for n in sample_lengths]
 
 
 def specaugment_bands(n_frames: int, n_freq: int, n_time_masks: int, time_mask_param: int, n_freq_masks: int,
@@ -100,8 +127,11 @@ def specaugment_bands(n_frames: int, n_freq: int, n_time_masks: int, time_mask_p
 
 
 def specaugment_apply(spec: torch.Tensor, bands, value: float = 0.0) -> torch.Tensor:
+    """Fill position p of `axis` where s <= p < e (torchaudio builds the mask by comparison: with p = 1 and a mask_param above
+    the axis length a start can be negative, which masks from 0, not from the end as a Python slice would)."""
     out = spec.clone()
     for axis, s, e in bands:
+        s, e = max(int(s), 0), max(int(e), 0)
         if axis == 2:
             out[..., s:e] = value
         else:

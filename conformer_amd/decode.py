@@ -439,7 +439,9 @@ class BeamCTCStream:
     BeamCTCDecoder.__call__ returns on the concatenated logits; `reset` starts a new batch of utterances.
     Commit mode (max_pending, max_chunk_frames, max_frames=None): the stream has no end.  `pop_committed` hands out the tokens
     that have become final since the previous pop; `committed_text`, `partial_text` and `finish` speak of the text from the
-    last pop on: (unpopped committed) [+ pending best | + final tokens], joined as token ids before `decoder.text`."""
+    last pop on: (unpopped committed) [+ pending best | + final tokens], joined as token ids before `decoder.text`.
+    Independent utterances (conformer_amd/slots.py): `step(t_used=)` takes the caller's bound, `reset_slots` starts some again
+    and `only=` reads (`finish`: ends) those utterances alone; the returned lists keep length B, "" or [] for the others."""
 
     def __init__(self, decoder: "BeamCTCDecoder", batch: int, max_frames: Optional[int], device=None, *,
                  max_pending: Optional[int] = None, max_chunk_frames: Optional[int] = None, commit_log: int = 4096) -> None:
@@ -455,72 +457,101 @@ class BeamCTCStream:
         self.finished = False
         self.last = None                   # interim outputs of the latest step
         self.popped = [0] * int(batch)     # commit mode: committed tokens handed out by pop_committed, per utterance
+        self.fresh = set(range(int(batch)))    # utterances reset since the latest step: `last` holds no row of theirs
 
-    def step(self, logits_chunk: torch.Tensor, lengths: Optional[torch.Tensor] = None):
+    def step(self, logits_chunk: torch.Tensor, lengths: Optional[torch.Tensor] = None, *, t_used: Optional[int] = None):
         """logits_chunk (B,Tc,V): the next frames of every utterance; `lengths` (B) int64: frames of the chunk to consume per
-        utterance (None: all).  Returns (tokens (B,1,max_frames), counts (B,1), scores (B,1)) of the interim best."""
+        utterance (None: all); t_used: beam_ctc_stream_step.  Returns (tokens (B,1,max_frames), counts (B,1), scores (B,1))."""
         if self.finished:
             raise RuntimeError("BeamCTCStream.step after finish(): call reset() to start a new stream")
         d = self.decoder
         if lengths is not None and not (isinstance(lengths, torch.Tensor) and lengths.is_cuda):
             lengths = torch.as_tensor(lengths, dtype=torch.int64).reshape(-1).to(self.device)
         out = beam_ctc_stream_step(self.state, logits_chunk, d.blank_id, lengths, n_best=1, token_min_logp=d.token_min_logp,
-                                   beam_prune_logp=d.beam_prune_logp)
+                                   beam_prune_logp=d.beam_prune_logp, t_used=t_used)
         self.last = out + (self.state.committed,) if self.commit else out
+        self.fresh.clear()
         return out[0], out[1], out[2]
+
+    def reset_slots(self, slots: Sequence[int]) -> None:
+        """The utterances `slots` (host ints) back at the empty prefix with nothing committed and nothing popped, the others
+        untouched; until the next step their partial text is empty.  Enqueues only.  `finished` stays as it is."""
+        slots = [int(b) for b in slots]
+        idx = torch.tensor(slots, dtype=torch.int64)
+        if self.device.type == "cuda":
+            idx = idx.pin_memory().to(self.device, non_blocking=True)
+        beam_ctc_stream_reset_slots(self.state, idx)       # (commit mode: the utterances' committed totals too)
+        for b in slots:
+            self.popped[b] = 0
+        self.fresh.update(slots)
 
     def _need_commit(self, what: str) -> None:
         if not self.commit:
             raise RuntimeError(f"BeamCTCStream.{what}: the stream was made without max_pending, nothing is committed before "
                                "finish()")
 
-    def _unpopped(self) -> Tuple[List[List[int]], List[int]]:
-        return beam_ctc_stream_committed(self.state, self.popped)
+    def _rows(self, only: Optional[Sequence[int]]) -> List[int]:
+        return list(range(len(self.popped))) if only is None else [int(b) for b in only]
 
-    def pop_committed(self) -> List[List[int]]:
+    def _unpopped(self, only: Optional[Sequence[int]] = None) -> Tuple[List[List[int]], List[int]]:
+        if not self.commit:                # nothing is committed before the end
+            return [[] for _ in self.popped], self.popped
+        return beam_ctc_stream_committed(self.state, self.popped, only)
+
+    def pop_committed(self, only: Optional[Sequence[int]] = None) -> List[List[int]]:
         """Commit mode: per utterance the token ids committed since the previous pop (they will never change), which are then
         forgotten.  Synchronises.  RuntimeError, with nothing popped, if more than commit_log tokens were committed in between."""
         self._need_commit("pop_committed")
-        ids, self.popped = self._unpopped()
+        ids, total = self._unpopped(only)
+        for b in self._rows(only):
+            self.popped[b] = total[b]
         return ids
 
-    def discard_committed(self) -> None:
+    def discard_committed(self, only: Optional[Sequence[int]] = None) -> None:
         """Commit mode: forget every committed token not yet popped (the way out after pop_committed raised: the ring was
         lapped and those tokens cannot all be read any more).  Synchronises."""
         self._need_commit("discard_committed")
-        self.popped = self.state.total.cpu().tolist()
+        total = self.state.total.cpu().tolist()
+        for b in self._rows(only):
+            self.popped[b] = total[b]
 
-    def committed_text(self) -> List[str]:
+    def committed_text(self, only: Optional[Sequence[int]] = None) -> List[str]:
         """Commit mode: the text of the committed tokens not yet popped."""
         self._need_commit("committed_text")
-        return [self.decoder.text(ids) for ids in self._unpopped()[0]]
+        return [self.decoder.text(ids) for ids in self._unpopped(only)[0]]
 
-    def partial_text(self) -> List[str]:
-        """The interim best transcript of every utterance after the latest step (empty strings before the first).  Commit
-        mode: from the last pop on, the committed tokens and then the pending best."""
-        if self.last is None:
-            return [""] * self.state.B
-        if not self.commit:
-            return self.decoder._texts(self.last[0], self.last[1])
-        ids = self._unpopped()[0]
-        tk, ct, nc = self.last[0][:, 0].cpu().tolist(), self.last[1][:, 0].cpu().tolist(), self.last[5].cpu().tolist()
-        return [self.decoder.text(ids[b] + tk[b][nc[b]:ct[b]]) for b in range(self.state.B)]
+    def partial_text(self, only: Optional[Sequence[int]] = None) -> List[str]:
+        """The interim best transcript of every utterance after the latest step (empty strings before the first, and for an
+        utterance reset since).  Commit mode: from the last pop on, the committed tokens and then the pending best."""
+        texts = [""] * len(self.popped)
+        rows = [b for b in self._rows(only) if b not in self.fresh]
+        if not rows:
+            return texts
+        ids = self._unpopped(only)[0]
+        tk, ct = self.last[0][:, 0].cpu().tolist(), self.last[1][:, 0].cpu().tolist()
+        nc = self.last[5].cpu().tolist() if self.commit else [0] * len(ct)     # the best is relative to the prefix before the step
+        for b in rows:
+            texts[b] = self.decoder.text(ids[b] + tk[b][nc[b]:ct[b]])
+        return texts
 
-    def finish(self, decode_func: Optional[Callable[[str], str]] = None) -> List[str]:
+    def finish(self, decode_func: Optional[Callable[[str], str]] = None, only: Optional[Sequence[int]] = None) -> List[str]:
+        """only=[...]: those utterances' end alone (no search state is saved: the others go on); only their rows are copied."""
         if self.finished:
             raise RuntimeError("BeamCTCStream.finish() called twice: call reset() to start a new stream")
         tokens, counts, _, _, _ = beam_ctc_stream_finish(self.state, n_best=1)
-        self.finished = True
-        if not self.commit:
-            return self.decoder._texts(tokens, counts, decode_func)
-        ids = self._unpopped()[0]
-        tk, ct = tokens[:, 0].cpu().tolist(), counts[:, 0].cpu().tolist()
-        texts = [self.decoder.text(ids[b] + tk[b][:ct[b]]) for b in range(self.state.B)]
-        return [decode_func(t) for t in texts] if decode_func is not None else texts
+        self.finished = only is None
+        ids = self._unpopped(only)[0]
+        if only is None:
+            tk, ct = tokens[:, 0].cpu().tolist(), counts[:, 0].cpu().tolist()
+        texts = [""] * len(self.popped)
+        for b in self._rows(only):
+            row = tk[b][:ct[b]] if only is None else tokens[b, 0, :int(counts[b, 0])].tolist()
+            text = self.decoder.text(ids[b] + row)
+            texts[b] = decode_func(text) if decode_func is not None else text
+        return texts
 
     def reset(self) -> None:
         beam_ctc_stream_reset(self.state)
         self.finished = False
-        self.last = None
         self.popped = [0] * len(self.popped)
-
+        self.fresh = set(range(len(self.popped)))

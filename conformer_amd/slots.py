@@ -35,11 +35,10 @@ import numpy as np
 import torch
 
 from . import ops
-from .decode import BeamCTCDecoder, beam_ctc_stream_committed, beam_ctc_stream_finish, beam_ctc_stream_init, \
-    beam_ctc_stream_reset_slots, beam_ctc_stream_step
+from .decode import BeamCTCDecoder
 from .model.modules.encoder import Encoder
-from .streaming import StreamingEncoder, _refuse_window_autocast, encoder_frames
-from .transcribe import decode_frames, lstm_state, search_plan
+from .streaming import ChunkedEncoder, _refuse_window_autocast, encoder_frames
+from .transcribe import decode_frames, lstm_state, search_plan, search_stream
 
 _TAIL = 8                  # mel-tail buffer width: a slot carries 0..6 un-consumed frames
 
@@ -136,7 +135,7 @@ class _Step:
 
 class _SlotStream:
     """The stream context of ConformerBlock.fused_chain for one slot step: slot b's new rows are the compact rows 0 .. k_b-1,
-    `cur` holds the step's device offsets; `i` is the layer the chain is in (StreamingEncoder._encode sets it)."""
+    `cur` holds the step's device offsets; `i` is the layer the chain is in (ChunkedEncoder._encode sets it)."""
 
     def __init__(self, st: "SlotStreamingEncoder", cur: _Step) -> None:
         self.st, self.cur, self.i = st, cur, 0
@@ -163,7 +162,7 @@ class _SlotStream:
         return s[:, half:].contiguous()
 
 
-class SlotStreamingEncoder(StreamingEncoder):
+class SlotStreamingEncoder(ChunkedEncoder):
     """The chunked encoder of StreamingEncoder over `slots` independent streams of at most max_mel_frames mel frames each.
     open(s) starts a stream in a free slot, step(mel, frames) feeds every slot its own number of new frames, close(s) frees the
     slot.  Returns compact rows: step -> ((S, k_max, d), k) with slot b's new encoder frames in rows 0 .. k[b]-1.
@@ -177,14 +176,10 @@ class SlotStreamingEncoder(StreamingEncoder):
         self.dtype = _slot_dtype("SlotStreamingEncoder", dtype)
         if self.dtype is not None and left_context is not None:
             raise NotImplementedError(f"SlotStreamingEncoder: left_context with dtype={self.dtype} (no 16-bit window kernel yet)")
-        if self.dtype is not None:
-            d = encoder.linear.out_features
-            if d % 8:
-                raise ValueError(f"SlotStreamingEncoder: a {self.dtype} K/V cache needs d % 8 == 0, got d = {d}")
-            self.cache_dtype = self.dtype                                  # (read by StreamingEncoder.__init__: no fp32 caches)
-        super().__init__(encoder, slots, max_mel_frames, graphs=False, left_context=left_context,
-                         max_chunk_mel_frames=max_chunk_mel_frames)
-        self.ctx = None                                                    # the compact context is allocated per step
+        if self.dtype is not None and encoder.linear.out_features % 8:
+            raise ValueError(f"SlotStreamingEncoder: a {self.dtype} K/V cache needs d % 8 == 0, got {encoder.linear.out_features}")
+        super().__init__("SlotStreamingEncoder", encoder, slots, max_mel_frames, cache_dtype=self.dtype or torch.float32,
+                         left_context=left_context, max_chunk_mel_frames=max_chunk_mel_frames)
         self.S = self.B
         self.max_mel = None if max_mel_frames is None else int(max_mel_frames)
         self.is_open = [False] * self.S
@@ -305,30 +300,20 @@ class SlotTranscriber:
         self.commit = search_plan("SlotTranscriber", max_mel_frames, left_context, max_chunk_mel_frames, max_pending)
         self.device, self.state = lstm_state(model, "SlotTranscriber", int(slots))
         self.model = model
-        self.decoder = decoder
         self.encoder = SlotStreamingEncoder(model.encoder, slots, max_mel_frames, dtype=self.dtype, left_context=left_context,
                                             max_chunk_mel_frames=max_chunk_mel_frames)
         self.S = self.encoder.S
-        f = decoder._fusion(self.device)
-        M, k_cap = self.commit or (None, None)
-        self.beam = beam_ctc_stream_init(self.S, None if self.commit else self.encoder.t_max, self.device,
-                                         beam_width=decoder.beam_width, max_candidates=decoder.max_candidates,
-                                         lm_tables=f.lm_tables, hw_tables=f.hw_tables, alpha=decoder.alpha, beta=decoder.beta,
-                                         unk_score_offset=decoder.unk_score_offset, score_boundary=decoder.score_boundary,
-                                         hotword_weight=decoder.hotword_weight, max_pending=M, max_chunk_frames=k_cap,
-                                         commit_log=commit_log)
-        self.popped = [0] * self.S         # commit mode: committed tokens handed out by pop_committed, per slot
-        self._last = None                  # interim outputs of the latest beam step
-        self._fresh = set()                # slots opened since it
+        self.beam = search_stream(decoder, self.commit, self.S, self.encoder.t_max, self.device, commit_log)
 
     @property
     def is_open(self) -> List[bool]:
         return list(self.encoder.is_open)
 
-    def _reset_beam(self, s: int) -> None:
-        idx = torch.tensor([s], dtype=torch.int64).pin_memory().to(self.device, non_blocking=True)
-        beam_ctc_stream_reset_slots(self.beam, idx)        # (commit mode: the slot's committed total too)
-        self.popped[s] = 0
+    def _open_slots(self, read) -> dict:
+        """{open slot: its entry of read(only=the open slots)}, `read` a reading method of the search."""
+        open_slots = [s for s in range(self.S) if self.encoder.is_open[s]]
+        out = read(only=open_slots)
+        return {s: out[s] for s in open_slots}
 
     def open(self, s: int) -> None:
         """Start an utterance in free slot s (enqueues only)."""
@@ -336,8 +321,7 @@ class SlotTranscriber:
         for h, c in self.state:
             h[s].zero_()
             c[s].zero_()
-        self._reset_beam(s)
-        self._fresh.add(int(s))
+        self.beam.reset_slots([s])
 
     @torch.no_grad()
     def step(self, mel_chunk: torch.Tensor, frames: Sequence[int]) -> Tuple[torch.Tensor, List[int]]:
@@ -357,68 +341,38 @@ class SlotTranscriber:
         k_dev = self.encoder.last_step.k
         with _autocast(self.dtype):
             logits = decode_frames(self.model, self.state, enc, k_dev)
-        d = self.decoder
         # the search's bound: the furthest slot after this step, less the chunk (each slot's own frames_b + k_b <= T_max
         # holds: the encoder refused more than max_mel_frames)
         t_used = max(a + b for a, b in zip(n0, ks)) - k_max
         if self.commit:                    # after a commit a slot's tree holds at most min(max_pending, its frames) frames
             t_used = min(self.commit[0], max(n0))
-        self._last = beam_ctc_stream_step(self.beam, logits, d.blank_id, k_dev, n_best=1, token_min_logp=d.token_min_logp,
-                                          beam_prune_logp=d.beam_prune_logp, t_used=t_used) + (self.beam.committed,)
-        self._fresh.clear()
+        self.beam.step(logits, k_dev, t_used=t_used)
         return logits, ks
 
     def partial_text(self) -> Dict[int, str]:
         """The interim best transcript of every open slot (the one step-side call that synchronises)."""
-        open_slots = [s for s in range(self.S) if self.encoder.is_open[s]]
-        if self._last is None:
-            return {s: "" for s in open_slots}
-        if self.commit:                    # from the slot's last pop on: the committed tokens, then the pending best
-            ids = beam_ctc_stream_committed(self.beam, self.popped, open_slots)[0]
-            tk, ct, nc = self._last[0][:, 0].cpu().tolist(), self._last[1][:, 0].cpu().tolist(), self._last[5].cpu().tolist()
-            return {s: "" if s in self._fresh else self.decoder.text(ids[s] + tk[s][nc[s]:ct[s]]) for s in open_slots}
-        texts = self.decoder._texts(self._last[0], self._last[1])
-        return {s: "" if s in self._fresh else texts[s] for s in open_slots}
+        return self._open_slots(self.beam.partial_text)
 
     def pop_committed(self) -> Dict[int, List[int]]:
         """With max_pending: per open slot the token ids that became final since its previous pop, which are then forgotten
         (synchronises).  RuntimeError, with nothing popped, if a slot committed more than commit_log tokens in between."""
-        if not self.commit:
-            raise RuntimeError("SlotTranscriber.pop_committed: made without max_pending, nothing is committed before close()")
-        open_slots = [s for s in range(self.S) if self.encoder.is_open[s]]
-        ids, total = beam_ctc_stream_committed(self.beam, self.popped, open_slots)
-        for s in open_slots:
-            self.popped[s] = total[s]
-        return {s: ids[s] for s in open_slots}
+        return self._open_slots(self.beam.pop_committed)
 
     def discard_committed(self, s: int) -> None:
         """With max_pending: forget slot s's committed tokens that were not popped (the way out when the slot committed more
         than commit_log tokens between pops, after which partial_text and pop_committed raise for it; close(s) also frees it)."""
-        if not self.commit:
-            raise RuntimeError("SlotTranscriber.discard_committed: made without max_pending")
-        s = self.encoder._check_slot(s, want_open=True)
-        self.popped[s] = int(self.beam.total[s])
+        self.beam.discard_committed(only=[self.encoder._check_slot(s, want_open=True)])
 
     def close(self, s: int, decode_func: Optional[Callable[[str], str]] = None) -> str:
         """End slot s's utterance: its final transcript (BeamCTCDecoder on its logits); the slot becomes free.  The finish
-        saves no search state, so the other slots go on untouched."""
+        saves no search state, so the other slots go on; a lapped commit log raises for s alone, the slot freed all the same."""
         s = self.encoder._check_slot(s, want_open=True)
-        tokens, counts, _, _, _ = beam_ctc_stream_finish(self.beam, n_best=1)
         try:
-            if self.commit:                # the slot's whole unpopped text: its committed tokens, then the final ones; only
-                # slot s is read, and a lapped ring raises for s alone, after the slot was freed all the same
-                ids = beam_ctc_stream_committed(self.beam, self.popped, [s])[0][s]
-                text = self.decoder.text(ids + tokens[s, 0, :int(counts[s, 0])].tolist())
-                text = decode_func(text) if decode_func is not None else text
-            else:
-                text = self.decoder._texts(tokens[s:s + 1], counts[s:s + 1], decode_func)[0]
+            return self.beam.finish(decode_func, only=[s])[s]
         finally:
-            self._reset_beam(s)
+            self.beam.reset_slots([s])
             self.encoder.close(s)
-        return text
 
     def reset(self) -> None:
-        """Every slot free (their states are reset when they are opened again)."""
+        """Every slot free (their states, the search's included, are reset when they are opened again)."""
         self.encoder.reset()
-        self._last = None
-        self._fresh.clear()

@@ -81,7 +81,7 @@ def encoder_frames(mel_frames: int) -> int:
 
 class _Stream:
     """The stream context of ConformerBlock.fused_chain for one lockstep chunk step: the chunk is rows n0 .. n0+k-1 of every
-    utterance; `i` is the layer the chain is in (StreamingEncoder._encode sets it)."""
+    utterance; `i` is the layer the chain is in (ChunkedEncoder._encode sets it)."""
 
     qkv16 = False              # the K/V cache is fp32: the q|k|v GEMM writes fp32 rows (slots.py: a 16-bit cache sets it)
 
@@ -117,7 +117,67 @@ class _Stream:
         return s[:, half:].contiguous()
 
 
-class StreamingEncoder:
+class ChunkedEncoder:
+    """What StreamingEncoder and slots.SlotStreamingEncoder share (`who`: the one the messages name): the checks, the ring
+    sizing, the K/V caches (linear (B, T'max, 3d) or rings (B, R, 3d), stored as `cache_dtype`), depthwise state, key limits,
+    mel tail buffer, what is derived from the weights and the chain over the blocks.  How a step places its rows is theirs."""
+
+    def __init__(self, who: str, encoder: Encoder, batch: int, max_mel_frames: Optional[int], check_weights: bool = True,
+                 cache_dtype: torch.dtype = torch.float32, *, left_context: Optional[int] = None,
+                 max_chunk_mel_frames: Optional[int] = None) -> None:
+        self.left, self.max_chunk = _window_args(who, left_context, max_chunk_mel_frames, max_mel_frames)
+        if encoder.training:
+            raise RuntimeError(f"{who}: put the encoder in eval() mode (running BatchNorm statistics, no dropout)")
+        p = next(encoder.parameters())
+        if not p.is_cuda or p.dtype != torch.float32:
+            raise RuntimeError(f"{who}: the encoder must live on the HIP device in fp32 (no CPU fallback)")
+        self.enc = encoder
+        self.B = int(batch)
+        self.d = encoder.linear.out_features
+        self.t_max = None if max_mel_frames is None else encoder_frames(int(max_mel_frames))     # None: a stream without an end
+        if self.t_max is not None and self.t_max < 1:
+            raise ValueError("max_mel_frames must give at least one encoder frame (>= 7)")
+        dev = p.device
+        layers = list(encoder.layers)
+        self.ring, self.n_pos, _ = (None, None, None) if self.left is None else ring_plan(self.left, self.max_chunk)
+        self.qkv = [torch.zeros(self.B, self.ring or self.t_max, 3 * self.d, device=dev, dtype=cache_dtype) for _ in layers]
+        halves = [(l.conv.deepwise_conv.kernel_size[0] - 1) // 2 for l in layers]     # the carried GLU rows: (K-1)/2 per layer
+        self.conv_state = [torch.zeros(self.B, h, self.d, device=dev, dtype=torch.float32) for h in halves]
+        self.lengths = torch.zeros(self.B, dtype=torch.int64, device=dev)
+        self.mel_tail_buf: Optional[torch.Tensor] = None                   # (B, n_mel, 8): the un-consumed 0..6 mel frames
+        self.check_weights = bool(check_weights)
+        self._tensors = list(encoder.parameters()) + list(encoder.buffers())     # (walked once, not per step)
+        self._derive()
+
+    @torch.no_grad()
+    def _derive(self) -> None:
+        """Everything this object holds that was made from the weights (a subclass that holds more extends this)."""
+        self.table = self.enc.rel_pe.table(self.t_max if self.left is None else self.n_pos)
+        self.pos_all = self.enc._projected_positions(self.table)          # (2T'max-1 | 2P-1, L*d): every layer's pos_proj, once
+        self._fingerprint = fingerprint(self._tensors)
+
+    def _follow_weights(self) -> None:
+        """The top of every step: weights changed since _derive() -- never run on a stale table or replay stale packs."""
+        if self.check_weights and fingerprint(self._tensors) != self._fingerprint:
+            self._derive()
+
+    def _encode(self, mel: torch.Tensor, stream, set_lengths) -> torch.Tensor:
+        """Stem, input Linear and the blocks on the mel frames of a step's new encoder frames (the stem is local in time);
+        `stream` takes the new rows through the two seams of every block (ConformerBlock.fused_chain); set_lengths() enqueues
+        the step's key limits (self.lengths) in front of the blocks."""
+        enc = self.enc
+        h = enc.downsampling_conv.channel_last(mel.contiguous())           # (B, k, F'*C)
+        wlp = enc._packs.get("wlp", (enc.linear.weight,), lambda: ops.pack_linear_weight(enc.linear.weight, self.d, enc.n_freq_out))
+        h = ops.linear(h, wlp, enc.linear.bias)
+        set_lengths()
+        stats = None
+        for i, blk in enumerate(enc.layers):
+            stream.i = i
+            h, stats = blk.fused_chain(h, None, None, x_stats=stats, want_stats=i + 1 < len(enc.layers), stream=stream)
+        return h
+
+
+class StreamingEncoder(ChunkedEncoder):
     """graphs=True: every distinct chunk step -- keyed on (frames so far, chunk length, buffered tail, matrix-pipe precision) -- is
     captured ONCE as a hipGraph and replayed from then on (the next utterance batch of a streaming service walks through the same
     keys): one host call per chunk instead of ~420 launches, whose issue cost (not their device time) was what a 7-11 ms chunk
@@ -136,61 +196,26 @@ class StreamingEncoder:
     module docstring's windowed rule over ring caches; max_mel_frames may then be None (no end).  fp32 and eager only: graphs=True
     or a step under torch.autocast raises NotImplementedError."""
 
-    cache_dtype = torch.float32        # storage type of the K/V caches (SlotStreamingEncoder(dtype=...) sets a 16-bit one)
-
     def __init__(self, encoder: Encoder, batch: int, max_mel_frames: Optional[int] = None, graphs: bool = False,
                  check_weights: bool = True, *, left_context: Optional[int] = None,
                  max_chunk_mel_frames: Optional[int] = None) -> None:
-        self.left, self.max_chunk = _window_args("StreamingEncoder", left_context, max_chunk_mel_frames, max_mel_frames)
-        if self.left is not None and graphs:
+        if left_context is not None and graphs:
             raise NotImplementedError("StreamingEncoder: graphs=True with left_context (a graph key still holds the stream "
                                       "position, so an endless stream would capture without end)")
-        if encoder.training:
-            raise RuntimeError("StreamingEncoder: put the encoder in eval() mode (running BatchNorm statistics, no dropout)")
-        p = next(encoder.parameters())
-        if not p.is_cuda or p.dtype != torch.float32:
-            raise RuntimeError("StreamingEncoder: the encoder must live on the HIP device in fp32 (no CPU fallback)")
-        self.enc = encoder
-        self.B = int(batch)
-        self.d = encoder.linear.out_features
-        self.t_max = None if max_mel_frames is None else encoder_frames(int(max_mel_frames))     # None: a stream without an end
-        if self.t_max is not None and self.t_max < 1:
-            raise ValueError("max_mel_frames must give at least one encoder frame (>= 7)")
-        dev = p.device
-        layers = list(encoder.layers)
+        super().__init__("StreamingEncoder", encoder, batch, max_mel_frames, check_weights, left_context=left_context,
+                         max_chunk_mel_frames=max_chunk_mel_frames)
+        self.ctx = None                    # the rows kernel's scratch, shared by the layers (windowed: compact, per step)
         if self.left is None:
-            self.ring = self.n_pos = None
-            self.qkv = [torch.zeros(self.B, self.t_max, 3 * self.d, device=dev, dtype=self.cache_dtype) for _ in layers]
-            self.ctx = torch.zeros(self.B, self.t_max, self.d, device=dev, dtype=torch.float32)     # scratch shared by the layers
-        else:
-            self.ring, self.n_pos, _ = ring_plan(self.left, self.max_chunk)
-            self.qkv = [torch.zeros(self.B, self.ring, 3 * self.d, device=dev, dtype=torch.float32) for _ in layers]
-            self.ctx = None                                                # the window kernel's context is compact, per step
-        halves = [(l.conv.deepwise_conv.kernel_size[0] - 1) // 2 for l in layers]     # the carried GLU rows: (K-1)/2 per layer
-        self.conv_state = [torch.zeros(self.B, h, self.d, device=dev, dtype=torch.float32) for h in halves]
-        self.lengths = torch.zeros(self.B, dtype=torch.int64, device=dev)
-        self.mel_tail_buf: Optional[torch.Tensor] = None                   # (B, n_mel, 6): the un-consumed 0..6 mel frames
+            self.ctx = torch.zeros(self.B, self.t_max, self.d, device=self.lengths.device, dtype=torch.float32)
         self.tail_len = 0
         self.frames = 0                                                    # encoder frames produced so far
         self.use_graphs = bool(graphs)
-        self.check_weights = bool(check_weights)
-        self._tensors = list(encoder.parameters()) + list(encoder.buffers())     # (walked once, not per step)
-        self._derive()
 
-    @torch.no_grad()
-    def _derive(self) -> None:
-        """Everything this object holds that was made from the weights: the projected table, the graphs and their pool."""
-        self.table = self.enc.rel_pe.table(self.t_max if self.left is None else self.n_pos)
-        self.pos_all = self.enc._projected_positions(self.table)          # (2T'max-1 | 2P-1, L*d): every layer's pos_proj, once
+    def _derive(self) -> None:                                             # and the graphs and their pool: they replay the weights
+        super()._derive()
         self._graphs = {}                                                  # key -> (graph, static input, static output)
         self._pool = None
         self._warm = set()                                                 # precisions whose derived weights a warm step built
-        self._fingerprint = fingerprint(self._tensors)
-
-    def _follow_weights(self) -> None:
-        """The top of every step: weights changed since _derive() -- never run on a stale table or replay stale packs."""
-        if self.check_weights and fingerprint(self._tensors) != self._fingerprint:
-            self._derive()
 
     def reset(self) -> None:
         for t in self.conv_state:
@@ -268,21 +293,6 @@ class StreamingEncoder:
         rest = x.shape[2] - 4 * k
         self.mel_tail_buf[:, :, :rest].copy_(x[:, :, 4 * k:])
         return self._encode(x, _Stream(self, n0, k), lambda: self.lengths.fill_(n0 + k))
-
-    def _encode(self, mel: torch.Tensor, stream, set_lengths) -> torch.Tensor:
-        """Stem, input Linear and the blocks on the mel frames of a step's new encoder frames (the stem is local in time);
-        `stream` takes the new rows through the two seams of every block (ConformerBlock.fused_chain); set_lengths() enqueues
-        the step's key limits (self.lengths) in front of the blocks."""
-        enc = self.enc
-        h = enc.downsampling_conv.channel_last(mel.contiguous())           # (B, k, F'*C)
-        wlp = enc._packs.get("wlp", (enc.linear.weight,), lambda: ops.pack_linear_weight(enc.linear.weight, self.d, enc.n_freq_out))
-        h = ops.linear(h, wlp, enc.linear.bias)
-        set_lengths()
-        stats = None
-        for i, blk in enumerate(enc.layers):
-            stream.i = i
-            h, stats = blk.fused_chain(h, None, None, x_stats=stats, want_stats=i + 1 < len(enc.layers), stream=stream)
-        return h
 
     def run(self, mel: torch.Tensor, chunk_frames: int = 640) -> torch.Tensor:
         """Feeds mel (B, n_mel, T) in chunks of `chunk_frames` and returns the concatenated (B, T', d) output."""

@@ -54,6 +54,13 @@ def search_plan(who: str, max_mel_frames, left_context, max_chunk_mel_frames, ma
     return int(max_pending), ring_plan(left_context, max_chunk_mel_frames)[2]
 
 
+def search_stream(decoder: BeamCTCDecoder, plan, batch: int, t_max: Optional[int], device, commit_log: int) -> BeamCTCStream:
+    """The transcribers' search for a search_plan: one that ends with the encoder's t_max frames, or a committing one."""
+    if plan is None:
+        return decoder.stream(batch, t_max, device)
+    return decoder.stream(batch, None, device, max_pending=plan[0], max_chunk_frames=plan[1], commit_log=commit_log)
+
+
 def lstm_state(model, who: str, batch: int):
     """Refuses what the streaming transcribers (`who`: the class the message names) cannot run; returns the model's device and
     the zero LSTM state, [(h, c)] per layer, (batch, H) each."""
@@ -90,11 +97,7 @@ class StreamingTranscriber:
         self.model = model
         self.encoder = StreamingEncoder(model.encoder, batch, max_mel_frames, graphs=graphs, check_weights=check_weights,
                                         left_context=left_context, max_chunk_mel_frames=max_chunk_mel_frames)
-        if plan is None:
-            self.beam: BeamCTCStream = decoder.stream(self.B, self.encoder.t_max, device)
-        else:
-            self.beam = decoder.stream(self.B, None, device, max_pending=plan[0], max_chunk_frames=plan[1],
-                                       commit_log=commit_log)
+        self.beam = search_stream(decoder, plan, self.B, self.encoder.t_max, device, commit_log)
 
     def reset(self) -> None:
         self.encoder.reset()

@@ -240,21 +240,23 @@ def test_a_lapped_slot_raises_for_itself_alone_and_close_still_frees_it(monkeypa
         def close(self, s):
             self.is_open[s] = False
 
+    reset = []
+    monkeypatch.setattr(decode, "beam_ctc_stream_init", lambda *a, **kw: _log_state([3, 45]))
+    monkeypatch.setattr(decode, "beam_ctc_stream_reset_slots", lambda st, idx: reset.extend(idx.tolist()))
+    dec = decode.BeamCTCDecoder(["_", "a", "b", "|"] + ["c"] * 36, blank_id=0, beam_width=4)
     tr = object.__new__(slots.SlotTranscriber)
-    tr.S, tr.commit, tr.popped, tr.encoder = 2, (4, 16), [0, 0], Enc()
-    tr.decoder = decode.BeamCTCDecoder(["_", "a", "b", "|"] + ["c"] * 36, blank_id=0, beam_width=4)
-    tr.beam = _log_state([3, 45])
-    tr._last, tr._fresh, reset = None, set(), []
-    tr._reset_beam = lambda s: (reset.append(s), tr.popped.__setitem__(s, 0))
+    tr.S, tr.encoder = 2, Enc()
+    tr.beam = dec.stream(2, None, "cpu", max_pending=4, max_chunk_frames=16)
+    assert isinstance(tr.beam, decode.BeamCTCStream)
     tokens = torch.tensor([[[1, 2, -1]], [[2, -1, -1]]])
-    monkeypatch.setattr(slots, "beam_ctc_stream_finish", lambda st, n_best=1: (tokens, torch.tensor([[2], [1]]), None, None, None))
+    monkeypatch.setattr(decode, "beam_ctc_stream_finish", lambda st, n_best=1: (tokens, torch.tensor([[2], [1]]), None, None, None))
     with pytest.raises(RuntimeError, match=r"utterance\(s\) \[1\]"):
         tr.pop_committed()
-    assert tr.popped == [0, 0]                                     # nothing popped
+    assert tr.beam.popped == [0, 0]                                # nothing popped
     tr.discard_committed(1)                                        # the way out that keeps the slot open
-    assert tr.popped == [0, 45] and tr.pop_committed() == {0: [0, 1, 2], 1: []}
-    tr.popped = [0, 0]
-    assert tr.close(0) == tr.decoder.text([0, 1, 2, 1, 2]) and reset == [0]       # slot 0 is not held up by slot 1
+    assert tr.beam.popped == [0, 45] and tr.pop_committed() == {0: [0, 1, 2], 1: []}
+    tr.beam.popped = [0, 0]
+    assert tr.close(0) == dec.text([0, 1, 2, 1, 2]) and reset == [0]              # slot 0 is not held up by slot 1
     with pytest.raises(RuntimeError, match=r"utterance\(s\) \[1\]"):
         tr.close(1)
     assert reset == [0, 1] and tr.encoder.is_open == [False, False]               # freed all the same

@@ -11,7 +11,7 @@ import pytest
 import torch
 
 from conformer_amd import _lib
-from conformer_amd.decode import (BeamCTCDecoder, beam_ctc_decode, beam_ctc_hotword_decode, beam_ctc_lm_decode,
+from conformer_amd.decode import (BeamCTCDecoder, BeamCTCStream, beam_ctc_decode, beam_ctc_hotword_decode, beam_ctc_lm_decode,
                                   beam_ctc_stream_finish, beam_ctc_stream_init, beam_ctc_stream_step)
 from conformer_amd.hotwords import Hotwords
 from conformer_amd.lm import NgramLanguageModel, write_synthetic_arpa
@@ -276,7 +276,7 @@ def test_slots_commit_per_slot_and_outlive_max_mel_frames(dev):
     S, M = 3, 4
     tr = SlotTranscriber(m, dec, S, None, max_pending=M, **kw)
     k_cap = tr.commit[1]
-    assert tr.beam.buf.numel() == _lib.load().cfm_ctc_beam_commit_state_bytes(S, M, k_cap, 16, 16, 0, 0)
+    assert isinstance(tr.beam, BeamCTCStream) and tr.beam.state.buf.numel() == _lib.load().cfm_ctc_beam_commit_state_bytes(S, M, k_cap, 16, 16, 0, 0)
     # every step: closes, then opens, then mel frames per slot; slot 1 is closed and reopened mid-run
     schedule = [dict(open=[0, 1], frames={0: 64, 1: 5}), dict(frames={0: 33, 1: 3}), dict(open=[2], frames={0: 64, 1: 60, 2: 6}),
                 dict(frames={0: 1, 1: 64, 2: 64}), dict(close=[1], open=[1], frames={0: 64, 1: 64, 2: 0}),
@@ -289,10 +289,11 @@ def test_slots_commit_per_slot_and_outlive_max_mel_frames(dev):
             fed[s] = []
         for s in stp.get("open", []):
             others = [o for o in range(S) if o != s]
-            before = (tr.beam.total.cpu()[others].clone(), tr.beam.log.cpu()[others].clone())
+            before = (tr.beam.state.total.cpu()[others].clone(), tr.beam.state.log.cpu()[others].clone())
             tr.open(s)
-            assert int(tr.beam.total[s]) == 0 and tr.popped[s] == 0
-            assert torch.equal(tr.beam.total.cpu()[others], before[0]) and torch.equal(tr.beam.log.cpu()[others], before[1])
+            assert int(tr.beam.state.total[s]) == 0 and tr.beam.popped[s] == 0
+            assert torch.equal(tr.beam.state.total.cpu()[others], before[0])
+            assert torch.equal(tr.beam.state.log.cpu()[others], before[1])
             mel_seen[s] = 0
         fr = [stp["frames"].get(s, 0) for s in range(S)]
         logits, k = tr.step(torch.randn(S, 80, max(fr), generator=g).mul(3.0).to(dev), fr)
@@ -304,7 +305,7 @@ def test_slots_commit_per_slot_and_outlive_max_mel_frames(dev):
     for s in range(S):
         if tr.is_open[s]:
             texts.append((tr.close(s), fed[s]))
-    assert len(texts) == 4 and int(tr.beam.total.sum()) == 0          # every closed slot's total is reset
+    assert len(texts) == 4 and int(tr.beam.state.total.sum()) == 0          # every closed slot's total is reset
     committed_any = False
     for text, chunks in texts:
         ref = dec.stream(1, None, dev, max_pending=M, max_chunk_frames=k_cap)
@@ -321,6 +322,53 @@ def test_slots_commit_per_slot_and_outlive_max_mel_frames(dev):
     with pytest.raises(RuntimeError, match="max_mel_frames"):
         short.step(torch.randn(S, 80, 64, generator=g).to(dev), [64, 0, 0])
     assert mel_seen[0] > 200 + 64
+
+
+# the slot semantics at the search level: (chunk frames, frames each of the 3 utterances takes); after step 4 utterance 2 ends
+# and its row is given to a new utterance, which takes nothing in its first step
+SLOT_STEPS = [(5, [5, 3, 0]), (3, [3, 0, 3]), (7, [7, 7, 4]), (4, [0, 4, 4]), (6, [6, 2, 0]), (7, [5, 0, 7]), (3, [3, 3, 3]),
+              (5, [5, 5, 1])]
+
+
+@pytest.mark.parametrize("commit", [False, True], ids=["max_frames", "max_pending"])
+def test_stream_rows_are_independent_utterances(dev, commit):
+    """One BeamCTCStream over B = 3 rows against one-utterance streams fed the same frames: the step's tokens and counts
+    (torch.equal), every partial_text and every final text, through finish(only=[2]) + reset_slots([2]) and a second
+    utterance in row 2.  V = 4 (blank, two letters, the delimiter: the fewest tokens with which decoder.text still joins and
+    splits words); the frames of a chunk past an utterance's length hold noise."""
+    Vs, total = 4, sum(tc for tc, _ in SLOT_STEPS)
+    dec = BeamCTCDecoder(["<pad>", "A", "B", "|"], BLANK, beam_width=4, max_candidates=4)
+    x = torch.from_numpy(peaky_logits(17, B=4, T=total, V=Vs)).to(dev)        # utterances 0..2, and 3: the second one of row 2
+    noise = torch.randn(3, 8, Vs, generator=torch.Generator().manual_seed(3)).mul(3.0).to(dev)
+
+    def stream(B):
+        return dec.stream(B, None, dev, max_pending=4, max_chunk_frames=8) if commit else dec.stream(B, total, dev)
+
+    s, refs = stream(3), [stream(1) for _ in range(3)]
+    utt, pos, finals = [0, 1, 2], [0] * 4, {}
+    for i, (tc, L) in enumerate(SLOT_STEPS):
+        if i == 4:
+            finals[2] = (s.finish(only=[2]), refs[2].finish())
+            assert finals[2][0] == ["", "", finals[2][1][0]] and not s.finished
+            s.reset_slots([2])
+            utt[2], refs[2] = 3, stream(1)
+            assert s.partial_text()[2] == "" and s.popped[2] == 0
+            assert s.partial_text(only=[0, 1])[:2] == [r.partial_text()[0] for r in refs[:2]]
+        chunk = noise[:, :tc].clone()
+        for b in range(3):
+            chunk[b, :L[b]] = x[utt[b], pos[utt[b]]:pos[utt[b]] + L[b]]
+            pos[utt[b]] += L[b]
+        tk, ct, _ = s.step(chunk, torch.tensor(L))
+        for b in range(3):
+            if L[b]:
+                rtk, rct, _ = refs[b].step(chunk[b:b + 1, :L[b]].contiguous())
+                assert torch.equal(tk[b:b + 1], rtk) and torch.equal(ct[b:b + 1], rct), (i, b)
+        assert s.partial_text() == [r.partial_text()[0] for r in refs], i
+    assert pos == [34, 24, 11, 11]
+    want = [r.finish()[0] for r in refs]
+    assert s.finish() == want and s.finished
+    # the references alone say that the case is not vacuous: no empty text, and row 0 committed on the way
+    assert all(want) and finals[2][1][0] and (not commit or int(refs[0].state.total[0]) > 0)
 
 
 # ---- 6. pop_committed ----------------------------------------------------------------------------------------------------------

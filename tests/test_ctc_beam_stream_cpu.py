@@ -163,3 +163,96 @@ def test_stream_life_cycle(monkeypatch):
     s.step(torch.zeros(2, 3, 4))
     assert s.finish(decode_func=str.upper) == ["AB", ""]
     assert calls == ["init", "step", "finish", "reset", "step", "finish"]
+
+
+# ---- per-utterance operation (independent streams): the device calls replaced as above, B = 3 --------------------------------
+VOCAB4 = ["_", "a", "b", "|"]
+
+
+@pytest.fixture
+def stream3(monkeypatch):
+    """(stream, calls): a BeamCTCStream over 3 utterances whose step n returns, for every utterance, n tokens `a` (step 1: "a",
+    step 2: "aa") and whose finish returns "ab", "b", "ba"; calls records (name, what the stand-in was given)."""
+    import types
+    calls = []
+
+    def fake_step(st, x, blank, lengths, **kw):
+        calls.append(("step", kw))
+        n = sum(1 for c in calls if c[0] == "step")
+        tokens = torch.full((3, 1, 10), -1, dtype=torch.int64)
+        tokens[:, 0, :n] = 1
+        return tokens, torch.full((3, 1), n, dtype=torch.int64), torch.zeros(3, 1), None, torch.ones(3, dtype=torch.int64)
+
+    def fake_finish(st, n_best=1):
+        calls.append(("finish", None))
+        tokens = torch.tensor([[[1, 2, -1]], [[2, -1, -1]], [[2, 1, -1]]])
+        return tokens, torch.tensor([[2], [1], [2]]), torch.zeros(3, 1), None, torch.ones(3, dtype=torch.int64)
+
+    monkeypatch.setattr(decode, "beam_ctc_stream_init", lambda *a, **kw: types.SimpleNamespace(B=3, t_max=10, t_used=0))
+    monkeypatch.setattr(decode, "beam_ctc_stream_reset", lambda st: calls.append(("reset", None)))
+    monkeypatch.setattr(decode, "beam_ctc_stream_reset_slots", lambda st, idx: calls.append(("reset_slots", idx.tolist())))
+    monkeypatch.setattr(decode, "beam_ctc_stream_step", fake_step)
+    monkeypatch.setattr(decode, "beam_ctc_stream_finish", fake_finish)
+    return decode.BeamCTCDecoder(VOCAB4, blank_id=0, beam_width=4).stream(3, 10, device="cpu"), calls
+
+
+def test_reset_slots_marks_fresh_until_the_next_step(stream3):
+    s, calls = stream3
+    s.popped = [5, 6, 7]
+    s.step(torch.zeros(3, 2, 4))
+    assert s.partial_text() == ["a", "a", "a"]
+    s.reset_slots([1])
+    assert calls[-1] == ("reset_slots", [1])
+    assert s.partial_text() == ["a", "", "a"]                     # `last` still holds the previous occupant's row 1
+    assert s.partial_text(only=[1, 2]) == ["", "", "a"]
+    assert s.popped == [5, 0, 7]
+    s.step(torch.zeros(3, 2, 4))
+    assert s.partial_text() == ["aa", "aa", "aa"] and s.popped == [5, 0, 7]
+    s.reset()                                                      # every utterance fresh, as before the first step
+    assert s.partial_text() == ["", "", ""] and s.popped == [0, 0, 0]
+
+
+def test_finish_of_some_utterances_does_not_end_the_stream(stream3):
+    s, calls = stream3
+    s.step(torch.zeros(3, 2, 4))
+    assert s.finish(only=[2]) == ["", "", "ba"] and not s.finished
+    assert s.finish(decode_func=str.upper, only=[0, 1]) == ["AB", "B", ""]
+    s.step(torch.zeros(3, 2, 4))                                   # does not raise
+    assert s.finish() == ["ab", "b", "ba"] and s.finished
+    with pytest.raises(RuntimeError, match="twice"):
+        s.finish()
+    with pytest.raises(RuntimeError, match="twice"):
+        s.finish(only=[0])
+    with pytest.raises(RuntimeError, match="after finish"):
+        s.step(torch.zeros(3, 2, 4))
+    assert [c[0] for c in calls] == ["step", "finish", "finish", "step", "finish"]
+
+
+def test_step_passes_t_used_through(stream3):
+    s, calls = stream3
+    s.step(torch.zeros(3, 2, 4))
+    s.step(torch.zeros(3, 2, 4), torch.tensor([2, 0, 1]), t_used=7)
+    assert [kw["t_used"] for name, kw in calls if name == "step"] == [None, 7]
+
+
+def test_pop_committed_of_some_utterances(monkeypatch):
+    """Commit mode over a state of three commit logs (the stand-in of tests/test_ctc_beam_commit_cpu.py): utterance 1 lapped
+    its ring of 20."""
+    import types
+    log = torch.arange(60, dtype=torch.int32).reshape(3, 20)
+    state = types.SimpleNamespace(B=3, log=log, total=torch.tensor([3, 45, 23]))
+    monkeypatch.setattr(decode, "beam_ctc_stream_init", lambda *a, **kw: state)
+    s = decode.BeamCTCDecoder(VOCAB4, blank_id=0, beam_width=4).stream(3, None, "cpu", max_pending=4, max_chunk_frames=16)
+    s.popped = [0, 0, 5]
+    with pytest.raises(RuntimeError, match=r"utterance\(s\) \[1\]"):
+        s.pop_committed()
+    assert s.popped == [0, 0, 5]
+    assert s.pop_committed(only=[0, 2]) == [[0, 1, 2], [], [40 + p % 20 for p in range(5, 23)]]
+    assert s.popped == [3, 0, 23]
+    assert s.pop_committed(only=[0, 2]) == [[], [], []] and s.committed_text(only=[0]) == ["", "", ""]
+    s.discard_committed(only=[1])
+    assert s.popped == [3, 45, 23] and s.pop_committed() == [[], [], []]
+    plain = decode.BeamCTCDecoder(VOCAB4, blank_id=0, beam_width=4).stream(3, 10, "cpu")
+    for call in (plain.pop_committed, plain.discard_committed, plain.committed_text):
+        with pytest.raises(RuntimeError, match="without max_pending"):
+            call(only=[0])

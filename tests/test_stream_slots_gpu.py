@@ -215,10 +215,13 @@ def _single_stream_encoder(enc, x, chunks, dev):
 @pytest.mark.parametrize("d,heads", [(32, 4), (48, 4), (512, 8)], ids=["small", "unfolded", "cfg5_width"])  # 48: not ln_fold_ok
 def test_slot_encoder_matches_chunked_oracle(dev, d, heads):
     from conformer_amd.slots import SlotStreamingEncoder
-    from conformer_amd.streaming import chunk_ends
+    from conformer_amd.streaming import StreamingEncoder, chunk_ends
     m, P = _model(d, heads, 61, dev, hidden=8)
     utts = _utts(UTT_LEN, 3)
     enc = SlotStreamingEncoder(m.encoder, 4, 800)
+    # it shares a base with the lockstep encoder but is not one: no (S, T'max, d) context scratch, no lockstep position, no graphs
+    assert not isinstance(enc, StreamingEncoder)
+    assert not any(hasattr(enc, name) for name in ("ctx", "frames", "tail_len", "use_graphs", "_graphs"))
     chunks, rows, _ = _drive(enc, 4, utts, SCHEDULE, dev)
     for u, x in enumerate(utts):
         assert sum(chunks[u]) == x.shape[1]

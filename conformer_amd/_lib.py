@@ -78,6 +78,16 @@ if set(COMMIT_SIGNATURES) & (set(SIGNATURES) | set(EXT_SIGNATURES)):
     raise ConformerHipError(f"{COMMIT_HEADER_PATH} declares again: "
                             f"{sorted(set(COMMIT_SIGNATURES) & (set(SIGNATURES) | set(EXT_SIGNATURES)))}")
 PARAMS.update(_commit_params)
+# token timestamps from the resumable beam search, added the same way
+TIMES_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "conformer_hip_times.h")
+if not os.path.exists(TIMES_HEADER_PATH):
+    raise ConformerHipError(f"{TIMES_HEADER_PATH} is missing: the ctypes binding is derived from it")
+with open(TIMES_HEADER_PATH) as _f:
+    TIMES_SIGNATURES, _times_params, _ = parse_header(_f.read())
+_earlier = set(SIGNATURES) | set(EXT_SIGNATURES) | set(COMMIT_SIGNATURES)
+if set(TIMES_SIGNATURES) & _earlier:
+    raise ConformerHipError(f"{TIMES_HEADER_PATH} declares again: {sorted(set(TIMES_SIGNATURES) & _earlier)}")
+PARAMS.update(_times_params)
 
 _lib = None
 
@@ -107,7 +117,8 @@ def load() -> ctypes.CDLL:
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
-    for header, table in ((EXT_HEADER_PATH, EXT_SIGNATURES), (COMMIT_HEADER_PATH, COMMIT_SIGNATURES)):
+    for header, table in ((EXT_HEADER_PATH, EXT_SIGNATURES), (COMMIT_HEADER_PATH, COMMIT_SIGNATURES),
+                          (TIMES_HEADER_PATH, TIMES_SIGNATURES)):
         for name, (res, args) in table.items():
             # same ABI revision, newer entry: a library built before the extension header existed passes the check above
             fn = getattr(lib, name, None)

@@ -33,6 +33,7 @@ def _newest_dep():
     deps.append(os.path.join(ROOT, "include", "conformer_hip.h"))
     deps.append(os.path.join(ROOT, "include", "conformer_hip_window.h"))
     deps.append(os.path.join(ROOT, "include", "conformer_hip_commit.h"))
+    deps.append(os.path.join(ROOT, "include", "conformer_hip_times.h"))
     return max(os.path.getmtime(d) for d in deps)
 
 

@@ -34,10 +34,15 @@
 // otherwise the LM penalty P(p) (0 without the LM).  Each hypothesis also carries the hotword-trie node of p, its decided
 // matches, its window of undecided words and its count (the window rule of hotword.h); the node each extension reaches is
 // kept in LDS (x_hn), and the window step a delimiter takes is done once per thread (x_hc, x_hd, x_hwl, x_hw).
+//
+// Timestamps (beam_search_kernel<LM, HW, true, true>, beam_commit_kernel<true>, INTEGRATION.md "Beam-search timestamps"): the
+// resumable search also records, per created tree node, the absolute frame and the log-probability of its extension
+// (TimesParams), the tracebacks return them beside the tokens and the commit carries them along (CommitTimes).
 #include <float.h>
 #include <type_traits>
 #include "cfm_common.h"
 #include "../../include/conformer_hip_commit.h"
+#include "../../include/conformer_hip_times.h"
 #include "hotword.h"
 #include "ngram_lm.h"
 
@@ -84,6 +89,19 @@ template <> struct StreamParams<true> {
     float* am_out;                       // interim acoustic scores (B, N) or null
     int t_max;                           // frames the tree has room for
     int finish;                          // 0: save the state and write the interim best; 1: end-of-utterance outputs
+};
+
+// Beam-search timestamps (beam_search_kernel<LM, HW, true, true>, INTEGRATION.md "Beam-search timestamps"): a caller-owned buffer
+// beside the stream state.  Per utterance the absolute frame count since the utterance was opened (the stream state's own count
+// becomes relative in commit mode), and per prefix-tree node the (frame, log-probability) of the extension that created it,
+// parallel to BeamWs::nodes.  A stay keeps its node, so it keeps its record: the record of a token is its ENTRY on the lineage
+// that survived.  The search adds one 8-byte global store per created node and no LDS.
+template <bool TM> struct TimesParams {};
+template <> struct TimesParams<true> {
+    int64_t* count;                      // (B) frames consumed since the utterance was opened
+    int2* rec;                           // (B, 1 + T*W) (frame, bits of the fp32 log-probability) per tree node
+    int64_t* token_frames;               // (B, N, TO) beside `tokens`, padded with -1
+    float* token_logp;                   // (B, N, TO) padded with -inf
 };
 
 // P(p): 0 for an empty partial word or one that spells a prefix of some unigram (node >= 0)
@@ -239,11 +257,12 @@ __device__ bool same_sequence(const int2* nd, int a, int b, int len) {
 
 typedef unsigned __int128 u128;
 
-template <bool LM, bool HW, bool ST = false>
+template <bool LM, bool HW, bool ST = false, bool TM = false>
 __global__ __launch_bounds__(BEAM_MAX_W) void beam_search_kernel(
         const float* __restrict__ logits, const int64_t* __restrict__ lengths, BeamWs ws, int T, int V, int blank, int W,
         int K, double prune, int N, int64_t* __restrict__ tokens, int64_t* __restrict__ counts, float* __restrict__ scores,
-        int64_t* __restrict__ num_hyps, LmParams<LM, HW> lp, StreamParams<ST> sp = {}) {
+        int64_t* __restrict__ num_hyps, LmParams<LM, HW> lp, StreamParams<ST> sp = {}, TimesParams<TM> tp = {}) {
+    static_assert(ST || !TM, "timestamps are recorded by the resumable search");
     // hypotheses in rank order, double-buffered across frames
     __shared__ double h_pb[2][BEAM_MAX_W], h_pnb[2][BEAM_MAX_W], h_s[2][BEAM_MAX_W];
     __shared__ unsigned long long h_hash[2][BEAM_MAX_W];
@@ -286,6 +305,13 @@ __global__ __launch_bounds__(BEAM_MAX_W) void beam_search_kernel(
         n = min(n, TO - t0);                                 // (the host refuses a chunk that could pass t_max)
     }
     int2* nd = ws.nodes + (int64_t)b * (1 + (int64_t)TO * W);
+    // TM: the records of this utterance's nodes and the absolute index of the chunk's frame 0
+    [[maybe_unused]] int2* tr = nullptr;
+    [[maybe_unused]] int64_t a0 = 0;
+    if constexpr (TM) {
+        tr = tp.rec + (int64_t)b * (1 + (int64_t)TO * W);
+        a0 = tp.count[b];
+    }
     const unsigned V1 = (unsigned)V + 1u;
     [[maybe_unused]] LmView lmv;
     if constexpr (LM) lmv = lm_view(lp.tables);
@@ -704,6 +730,7 @@ __global__ __launch_bounds__(BEAM_MAX_W) void beam_search_kernel(
             } else {
                 const int c = c_tok[k], id = 1 + (t0 + t) * W + q;
                 nd[id] = make_int2(h_node[cur][i], c);
+                if constexpr (TM) tr[id] = make_int2((int)(a0 + t), __float_as_int((float)c_lp[k]));
                 qh = seq_hash(h_hash[cur][i], c);
                 h_node[nxt][q] = id; h_par[nxt][q] = h_node[cur][i]; h_last[nxt][q] = c; h_len[nxt][q] = h_len[cur][i] + 1;
             }
@@ -768,6 +795,8 @@ __global__ __launch_bounds__(BEAM_MAX_W) void beam_search_kernel(
                 if constexpr (LM || HW) f = f + lmp;
             }
             if (tid == 0) { sp.frames[b] = t0 + n; sp.nh[b] = nh; }
+            if constexpr (TM)
+                if (tid == 0 && n > 0) tp.count[b] = a0 + n;     // (every thread read a0 before the first frame's barriers)
             if (tid < N) {
                 const int64_t r = (int64_t)b * N + tid;
                 int64_t* out = tokens + r * TO;
@@ -778,6 +807,11 @@ __global__ __launch_bounds__(BEAM_MAX_W) void beam_search_kernel(
                     for (int p = len - 1; p >= 0 && x > 0; --p) {
                         const int2 e = nd[x];
                         out[p] = e.y;
+                        if constexpr (TM) {
+                            const int2 w = tr[x];
+                            tp.token_frames[r * TO + p] = w.x;
+                            tp.token_logp[r * TO + p] = __int_as_float(w.y);
+                        }
                         x = e.x;
                     }
                 }
@@ -785,6 +819,8 @@ __global__ __launch_bounds__(BEAM_MAX_W) void beam_search_kernel(
                 if (sp.am_out) sp.am_out[r] = tid < nh ? (float)h_s[cur][tid] : -INFINITY;
                 counts[r] = len;
                 for (int p = len; p < TO; ++p) out[p] = -1;
+                if constexpr (TM)
+                    for (int p = len; p < TO; ++p) { tp.token_frames[r * TO + p] = -1; tp.token_logp[r * TO + p] = -INFINITY; }
             }
             if (tid == 0) num_hyps[b] = min(nh, N);
             return;
@@ -839,6 +875,11 @@ __global__ __launch_bounds__(BEAM_MAX_W) void beam_search_kernel(
                 for (int p = len - 1; p >= 0 && x > 0; --p) {
                     const int2 e = nd[x];
                     out[p] = e.y;
+                    if constexpr (TM) {
+                        const int2 w = tr[x];
+                        tp.token_frames[o * TO + p] = w.x;
+                        tp.token_logp[o * TO + p] = __int_as_float(w.y);
+                    }
                     x = e.x;
                 }
                 scores[o] = (float)m_val[tid];
@@ -849,6 +890,8 @@ __global__ __launch_bounds__(BEAM_MAX_W) void beam_search_kernel(
             }
             counts[o] = len;
             for (int p = len; p < TO; ++p) out[p] = -1;
+            if constexpr (TM)
+                for (int p = len; p < TO; ++p) { tp.token_frames[o * TO + p] = -1; tp.token_logp[o * TO + p] = -INFINITY; }
         }
         if (tid == 0) num_hyps[b] = min(nh, N);
         return;
@@ -864,6 +907,11 @@ __global__ __launch_bounds__(BEAM_MAX_W) void beam_search_kernel(
             for (int p = len - 1; p >= 0 && x > 0; --p) {
                 const int2 e = nd[x];
                 out[p] = e.y;
+                if constexpr (TM) {
+                    const int2 w = tr[x];
+                    tp.token_frames[o * TO + p] = w.x;
+                    tp.token_logp[o * TO + p] = __int_as_float(w.y);
+                }
                 x = e.x;
             }
             scores[o] = (float)h_s[cur][tid];
@@ -872,6 +920,8 @@ __global__ __launch_bounds__(BEAM_MAX_W) void beam_search_kernel(
         }
         counts[o] = len;
         for (int p = len; p < TO; ++p) out[p] = -1;
+        if constexpr (TM)
+            for (int p = len; p < TO; ++p) { tp.token_frames[o * TO + p] = -1; tp.token_logp[o * TO + p] = -INFINITY; }
     }
     if (tid == 0) num_hyps[b] = min(nh, N);
 }
@@ -937,7 +987,21 @@ struct CommitParams {
     int M, L;
 };
 
-__global__ __launch_bounds__(BEAM_MAX_W) void beam_commit_kernel(BeamWs ws, StreamParams<true> sp, CommitParams cp, int W) {
+// TM: the nodes' records (TimesParams::rec) go where their tokens go: y_0's into y0r beside y0, a survivor's pending suffix
+// into sufr beside suf and from there into its private chain, and y_0[:nb]'s into the rings log_frames / log_logp at the
+// positions of `log`.  The absolute frame count is not touched: a commit consumes no frame.
+template <bool TM> struct CommitTimes {};
+template <> struct CommitTimes<true> {
+    int2* rec;                           // (B, 1 + T_tree*W)
+    int2* y0r;                           // (B, T_tree) scratch
+    int2* sufr;                          // (B, W, M) scratch
+    int64_t* log_frames;                 // (B, L)
+    float* log_logp;                     // (B, L)
+};
+
+template <bool TM>
+__global__ __launch_bounds__(BEAM_MAX_W) void beam_commit_kernel(BeamWs ws, StreamParams<true> sp, CommitParams cp, int W,
+                                                                 CommitTimes<TM> ct = {}) {
     __shared__ int red_min[4], red_cnt[4], red_max[4];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int TT = sp.t_max, M = cp.M;
@@ -952,12 +1016,19 @@ __global__ __launch_bounds__(BEAM_MAX_W) void beam_commit_kernel(BeamWs ws, Stre
     const int64_t o = (int64_t)b * W + tid;
     const int64_t tot = cp.total[b];
     const int len0 = min(max(sp.len[(int64_t)b * W], 0), TT);
+    [[maybe_unused]] int2 *tr = nullptr, *y0r = nullptr, *sufr = nullptr;
+    if constexpr (TM) {
+        tr = ct.rec + (int64_t)b * nn;
+        y0r = ct.y0r + (int64_t)b * TT;
+        sufr = ct.sufr + o * M;
+    }
     // ---- 1: y_0's pending tokens and their nodes
     if (tid == 0) {
         int x = sp.node[(int64_t)b * W];
         for (int p = len0 - 1; p >= 0 && x > 0 && x < nn; --p) {
             const int2 e = nd[x];
             y0[p] = make_int2(e.y, x);
+            if constexpr (TM) y0r[p] = tr[x];
             x = e.x;
         }
     }
@@ -1007,6 +1078,7 @@ __global__ __launch_bounds__(BEAM_MAX_W) void beam_commit_kernel(BeamWs ws, Stre
         for (int p = slen - 1; p >= 0 && x > 0 && x < nn; --p) {
             const int2 e = nd[x];
             suf[p] = e.y;
+            if constexpr (TM) sufr[p] = tr[x];
             x = e.x;
         }
         pb = sp.pb[o]; pnb = sp.pnb[o]; s = sp.s[o]; hash = sp.hash[o]; last = sp.last[o];
@@ -1025,6 +1097,8 @@ __global__ __launch_bounds__(BEAM_MAX_W) void beam_commit_kernel(BeamWs ws, Stre
     for (int w = 0; w < wv; ++w) q += red_cnt[w];
     if (surv) {
         for (int p = 0; p < slen; ++p) nd[1 + p * W + q] = make_int2(p ? 1 + (p - 1) * W + q : 0, suf[p]);
+        if constexpr (TM)
+            for (int p = 0; p < slen; ++p) tr[1 + p * W + q] = sufr[p];
         const int64_t oq = (int64_t)b * W + q;
         sp.pb[oq] = pb; sp.pnb[oq] = pnb; sp.s[oq] = s; sp.hash[oq] = hash; sp.last[oq] = last;
         sp.node[oq] = slen ? 1 + (slen - 1) * W + q : 0;
@@ -1039,6 +1113,12 @@ __global__ __launch_bounds__(BEAM_MAX_W) void beam_commit_kernel(BeamWs ws, Stre
         }
     }
     for (int p = tid; p < nb; p += BEAM_MAX_W) cp.log[(int64_t)b * cp.L + (int)(((tot + p) % cp.L + cp.L) % cp.L)] = y0[p].x;
+    if constexpr (TM)
+        for (int p = tid; p < nb; p += BEAM_MAX_W) {
+            const int64_t at = (int64_t)b * cp.L + (int)(((tot + p) % cp.L + cp.L) % cp.L);
+            ct.log_frames[at] = y0r[p].x;
+            ct.log_logp[at] = __int_as_float(y0r[p].y);
+        }
     if (tid == 0) {
         sp.nh[b] = red_cnt[0] + red_cnt[1] + red_cnt[2] + red_cnt[3];
         sp.frames[b] = max(max(red_max[0], red_max[1]), max(red_max[2], red_max[3]));
@@ -1064,6 +1144,39 @@ inline size_t commit_carve(int B, int M, int k_cap, int W, int K, bool lm, bool 
     char* suf = take((size_t)B * W * M * sizeof(int));
     if (cp) { cp->y0 = (int2*)y0; cp->suf = (int*)suf; cp->M = M; }
     return off;
+}
+
+// the frame counts of every utterance (slots null) or of the utterances slots[0 .. n) back at 0; entries outside [0, B) are skipped
+__global__ void beam_times_reset_kernel(int64_t* count, int B, const int64_t* slots, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int64_t b = slots ? slots[i] : i;
+    if (b >= 0 && b < B) count[b] = 0;
+}
+
+// the times buffer: the frame counts and the node records of a tree of T frames, then (M > 0: commit mode) the commit step's
+// record scratch.  The search entries need the first two only, so a buffer sized with M serves them too.
+struct TimesBuf {
+    int64_t* count;
+    int2 *rec, *y0r, *sufr;
+};
+
+inline size_t times_carve(int B, int T, int W, int M, char* base, TimesBuf* tb) {
+    size_t off = 0;
+    auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += beam_align(bytes); return p; };
+    char* count = take((size_t)B * sizeof(int64_t));
+    char* rec = take((size_t)B * (1 + (size_t)T * W) * sizeof(int2));
+    char *y0r = nullptr, *sufr = nullptr;
+    if (M > 0) {
+        y0r = take((size_t)B * T * sizeof(int2));
+        sufr = take((size_t)B * W * M * sizeof(int2));
+    }
+    if (tb) *tb = TimesBuf{(int64_t*)count, (int2*)rec, (int2*)y0r, (int2*)sufr};
+    return off;
+}
+
+inline bool times_args_ok(int B, int T, int W, int M) {
+    return B > 0 && T > 0 && W >= 1 && W <= BEAM_MAX_W && (int64_t)T * W < INT32_MAX && M >= 0 && (M == 0 || M < T);
 }
 
 inline bool commit_args_ok(int B, int M, int k_cap, int W, int K) {
@@ -1125,10 +1238,11 @@ template <bool LM, bool HW> LmParams<LM, HW> lm_params(const Fusion& fz, float* 
 
 // The candidate rows of the T frames (none for T = 0: the finish), then the search in the mode fz selects; ST: the resumable
 // search on the stream state sp.
-template <bool ST>
+template <bool ST, bool TM = false>
 int beam_launch(const float* logits, const int64_t* lengths, const BeamWs& ws, StreamParams<ST> sp, int B, int T, int V,
                 int blank, int W, int K, float token_min_logp, float beam_prune_logp, int N, const Fusion& fz, int64_t* tokens,
-                int64_t* counts, float* scores, float* am_scores, int64_t* num_hyps, cfm_stream_t stream) {
+                int64_t* counts, float* scores, float* am_scores, int64_t* num_hyps, cfm_stream_t stream,
+                TimesParams<TM> tp = {}) {
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (T > 0) {
         const int64_t rows = (int64_t)B * T;
@@ -1137,9 +1251,9 @@ int beam_launch(const float* logits, const int64_t* lengths, const BeamWs& ws, S
     }
     beam_mode(fz, [&](auto lm, auto hw) {
         constexpr bool LM = decltype(lm)::value, HW = decltype(hw)::value;
-        hipLaunchKernelGGL((beam_search_kernel<LM, HW, ST>), dim3((unsigned)B), dim3(BEAM_MAX_W), 0, s, logits, lengths, ws, T,
-                           V, blank, W, K, (double)beam_prune_logp, N, tokens, counts, scores, num_hyps,
-                           lm_params<LM, HW>(fz, am_scores), sp);
+        hipLaunchKernelGGL((beam_search_kernel<LM, HW, ST, TM>), dim3((unsigned)B), dim3(BEAM_MAX_W), 0, s, logits, lengths, ws,
+                           T, V, blank, W, K, (double)beam_prune_logp, N, tokens, counts, scores, num_hyps,
+                           lm_params<LM, HW>(fz, am_scores), sp, tp);
     });
     return cfm_launch_status();
 }
@@ -1260,36 +1374,57 @@ extern "C" int cfm_ctc_beam_stream_reset_slots(int B, int T_max, int beam_width,
     return cfm_launch_status();
 }
 
-extern "C" int cfm_ctc_beam_stream_step_f32(const float* logits, const int64_t* lengths_or_null, int B, int Tc, int V,
-                                            int blank_id, int beam_width, int max_candidates, float token_min_logp,
-                                            float beam_prune_logp, int n_best, const void* lm_tables_or_null, double alpha,
-                                            double beta, double unk_score_offset, int score_boundary,
-                                            const void* hw_tables_or_null, double hotword_weight, void* state,
-                                            size_t state_bytes, int T_max, int t_used, int64_t* tokens, int64_t* counts,
-                                            float* scores, float* am_scores_or_null, int64_t* num_hyps, cfm_stream_t stream) {
-    CFM_REQUIRE(logits && state && tokens && counts && scores && num_hyps, CFM_ERR_NULL);
+namespace {
+
+// the times arguments of the *_times entries (include/conformer_hip_times.h); a null TimesArgs is the entry without them
+struct TimesArgs {
+    void* times;
+    size_t bytes;
+    int64_t* token_frames;
+    float* token_logp;
+    bool null() const { return !times || !token_frames || !token_logp; }
+};
+
+// the search's view of a times buffer over a tree of T frames (BAD_SHAPE when it is too small)
+int times_params(const TimesArgs& ta, int B, int T, int W, TimesParams<true>* tp) {
+    CFM_REQUIRE(times_args_ok(B, T, W, 0) && ta.bytes >= times_carve(B, T, W, 0, nullptr, nullptr), CFM_ERR_BAD_SHAPE);
+    TimesBuf tb;
+    times_carve(B, T, W, 0, static_cast<char*>(ta.times), &tb);
+    *tp = TimesParams<true>{tb.count, tb.rec, ta.token_frames, ta.token_logp};
+    return CFM_OK;
+}
+
+int stream_step(const float* logits, const int64_t* lengths_or_null, int B, int Tc, int V, int blank_id, int beam_width,
+                int max_candidates, float token_min_logp, float beam_prune_logp, int n_best, const Fusion& fz, void* state,
+                size_t state_bytes, int T_max, int t_used, int64_t* tokens, int64_t* counts, float* scores,
+                float* am_scores_or_null, int64_t* num_hyps, cfm_stream_t stream, const TimesArgs* ta) {
+    CFM_REQUIRE(logits && state && tokens && counts && scores && num_hyps && !(ta && ta->null()), CFM_ERR_NULL);
     CFM_REQUIRE(Tc > 0, CFM_ERR_BAD_SHAPE);
     CFM_CHECK(beam_check(B, T_max, V, beam_width, max_candidates, n_best, blank_id, token_min_logp, beam_prune_logp));
     // t_used: chunk frames passed to the earlier steps since the init, a bound on what any utterance consumed
     CFM_REQUIRE(t_used >= 0 && t_used <= T_max && Tc <= T_max - t_used, CFM_ERR_BAD_SHAPE);
-    const Fusion fz{lm_tables_or_null, alpha, beta, unk_score_offset, score_boundary, hw_tables_or_null, hotword_weight};
     CFM_REQUIRE(fz.finite(), CFM_ERR_BAD_SHAPE);
     BeamWs ws;
     StreamParams<true> sp;
     CFM_CHECK(stream_state(B, T_max, beam_width, max_candidates, fz, state, state_bytes, &ws, &sp));
     sp.am_out = am_scores_or_null;
     sp.finish = 0;
+    if (ta) {
+        TimesParams<true> tp;
+        CFM_CHECK(times_params(*ta, B, T_max, beam_width, &tp));
+        return beam_launch<true, true>(logits, lengths_or_null, ws, sp, B, Tc, V, blank_id, beam_width, max_candidates,
+                                       token_min_logp, beam_prune_logp, n_best, fz, tokens, counts, scores, am_scores_or_null,
+                                       num_hyps, stream, tp);
+    }
     return beam_launch(logits, lengths_or_null, ws, sp, B, Tc, V, blank_id, beam_width, max_candidates, token_min_logp,
                        beam_prune_logp, n_best, fz, tokens, counts, scores, am_scores_or_null, num_hyps, stream);
 }
 
-extern "C" int cfm_ctc_beam_stream_finish_f32(int B, int beam_width, int max_candidates, int n_best, const void* lm_tables_or_null,
-                                              double alpha, double beta, double unk_score_offset, int score_boundary,
-                                              const void* hw_tables_or_null, double hotword_weight, void* state,
-                                              size_t state_bytes, int T_max, int64_t* tokens, int64_t* counts, float* scores,
-                                              float* am_scores_or_null, int64_t* num_hyps, cfm_stream_t stream) {
-    const Fusion fz{lm_tables_or_null, alpha, beta, unk_score_offset, score_boundary, hw_tables_or_null, hotword_weight};
-    CFM_REQUIRE(state && tokens && counts && scores && num_hyps && (am_scores_or_null || !fz.on()), CFM_ERR_NULL);
+int stream_finish(int B, int beam_width, int max_candidates, int n_best, const Fusion& fz, void* state, size_t state_bytes,
+                  int T_max, int64_t* tokens, int64_t* counts, float* scores, float* am_scores_or_null, int64_t* num_hyps,
+                  cfm_stream_t stream, const TimesArgs* ta) {
+    CFM_REQUIRE(state && tokens && counts && scores && num_hyps && (am_scores_or_null || !fz.on()) && !(ta && ta->null()),
+                CFM_ERR_NULL);
     CFM_CHECK(beam_check(B, T_max, 2, beam_width, max_candidates, n_best, 0, 0.f, 0.f));
     CFM_REQUIRE(fz.finite(), CFM_ERR_BAD_SHAPE);
     BeamWs ws;
@@ -1299,8 +1434,39 @@ extern "C" int cfm_ctc_beam_stream_finish_f32(int B, int beam_width, int max_can
     sp.finish = 1;
     // no frames: the kernel resumes the saved state and goes straight to the end-of-utterance step (LM / hotwords) or the
     // traceback (plain search)
+    if (ta) {
+        TimesParams<true> tp;
+        CFM_CHECK(times_params(*ta, B, T_max, beam_width, &tp));
+        return beam_launch<true, true>(nullptr, nullptr, ws, sp, B, 0, 2, 0, beam_width, max_candidates, 0.f, 0.f, n_best, fz,
+                                       tokens, counts, scores, am_scores_or_null, num_hyps, stream, tp);
+    }
     return beam_launch(nullptr, nullptr, ws, sp, B, 0, 2, 0, beam_width, max_candidates, 0.f, 0.f, n_best, fz, tokens, counts,
                        scores, am_scores_or_null, num_hyps, stream);
+}
+
+}  // namespace
+
+extern "C" int cfm_ctc_beam_stream_step_f32(const float* logits, const int64_t* lengths_or_null, int B, int Tc, int V,
+                                            int blank_id, int beam_width, int max_candidates, float token_min_logp,
+                                            float beam_prune_logp, int n_best, const void* lm_tables_or_null, double alpha,
+                                            double beta, double unk_score_offset, int score_boundary,
+                                            const void* hw_tables_or_null, double hotword_weight, void* state,
+                                            size_t state_bytes, int T_max, int t_used, int64_t* tokens, int64_t* counts,
+                                            float* scores, float* am_scores_or_null, int64_t* num_hyps, cfm_stream_t stream) {
+    const Fusion fz{lm_tables_or_null, alpha, beta, unk_score_offset, score_boundary, hw_tables_or_null, hotword_weight};
+    return stream_step(logits, lengths_or_null, B, Tc, V, blank_id, beam_width, max_candidates, token_min_logp, beam_prune_logp,
+                       n_best, fz, state, state_bytes, T_max, t_used, tokens, counts, scores, am_scores_or_null, num_hyps, stream,
+                       nullptr);
+}
+
+extern "C" int cfm_ctc_beam_stream_finish_f32(int B, int beam_width, int max_candidates, int n_best, const void* lm_tables_or_null,
+                                              double alpha, double beta, double unk_score_offset, int score_boundary,
+                                              const void* hw_tables_or_null, double hotword_weight, void* state,
+                                              size_t state_bytes, int T_max, int64_t* tokens, int64_t* counts, float* scores,
+                                              float* am_scores_or_null, int64_t* num_hyps, cfm_stream_t stream) {
+    const Fusion fz{lm_tables_or_null, alpha, beta, unk_score_offset, score_boundary, hw_tables_or_null, hotword_weight};
+    return stream_finish(B, beam_width, max_candidates, n_best, fz, state, state_bytes, T_max, tokens, counts, scores,
+                         am_scores_or_null, num_hyps, stream, nullptr);
 }
 
 // ---- committed-prefix streaming (include/conformer_hip_commit.h) ----------------------------------------------------------------
@@ -1310,10 +1476,13 @@ extern "C" size_t cfm_ctc_beam_commit_state_bytes(int B, int max_pending, int ma
     return commit_carve(B, max_pending, max_chunk_frames, W, K, lm != 0, hw != 0, nullptr, nullptr, nullptr, nullptr);
 }
 
-extern "C" int cfm_ctc_beam_stream_commit(int B, int max_pending, int max_chunk_frames, int beam_width, int max_candidates, int lm,
-                                          int hw, const int64_t* lengths_or_null, void* state, size_t state_bytes, int* log, int L,
-                                          int64_t* total, int* committed_or_null, cfm_stream_t stream) {
-    CFM_REQUIRE(state && log && total, CFM_ERR_NULL);
+namespace {
+
+// ta: the times buffer and, in its output fields, the rings log_frames / log_logp (null: the commit without them)
+int stream_commit(int B, int max_pending, int max_chunk_frames, int beam_width, int max_candidates, int lm, int hw,
+                  const int64_t* lengths_or_null, void* state, size_t state_bytes, int* log, int L, int64_t* total,
+                  int* committed_or_null, cfm_stream_t stream, const TimesArgs* ta) {
+    CFM_REQUIRE(state && log && total && !(ta && ta->null()), CFM_ERR_NULL);
     CFM_REQUIRE(B > 0 && max_pending >= 1 && max_chunk_frames >= 1, CFM_ERR_BAD_SHAPE);
     CFM_REQUIRE((int64_t)max_pending + max_chunk_frames < INT32_MAX, CFM_ERR_UNSUPPORTED);
     const int TT = max_pending + max_chunk_frames;
@@ -1327,9 +1496,28 @@ extern "C" int cfm_ctc_beam_stream_commit(int B, int max_pending, int max_chunk_
     commit_carve(B, max_pending, max_chunk_frames, beam_width, max_candidates, lm != 0, hw != 0, static_cast<char*>(state), &ws,
                  &sp, &cp);
     cp.log = log; cp.L = L; cp.total = total; cp.committed = committed_or_null; cp.lengths = lengths_or_null;
-    hipLaunchKernelGGL(beam_commit_kernel, dim3((unsigned)B), dim3(BEAM_MAX_W), 0, static_cast<hipStream_t>(stream), ws, sp, cp,
-                       beam_width);
+    if (ta) {
+        CFM_REQUIRE(times_args_ok(B, TT, beam_width, max_pending) &&
+                    ta->bytes >= times_carve(B, TT, beam_width, max_pending, nullptr, nullptr), CFM_ERR_BAD_SHAPE);
+        TimesBuf tb;
+        times_carve(B, TT, beam_width, max_pending, static_cast<char*>(ta->times), &tb);
+        const CommitTimes<true> ct{tb.rec, tb.y0r, tb.sufr, ta->token_frames, ta->token_logp};
+        hipLaunchKernelGGL(beam_commit_kernel<true>, dim3((unsigned)B), dim3(BEAM_MAX_W), 0, static_cast<hipStream_t>(stream), ws,
+                           sp, cp, beam_width, ct);
+        return cfm_launch_status();
+    }
+    hipLaunchKernelGGL(beam_commit_kernel<false>, dim3((unsigned)B), dim3(BEAM_MAX_W), 0, static_cast<hipStream_t>(stream), ws, sp,
+                       cp, beam_width, CommitTimes<false>{});
     return cfm_launch_status();
+}
+
+}  // namespace
+
+extern "C" int cfm_ctc_beam_stream_commit(int B, int max_pending, int max_chunk_frames, int beam_width, int max_candidates, int lm,
+                                          int hw, const int64_t* lengths_or_null, void* state, size_t state_bytes, int* log, int L,
+                                          int64_t* total, int* committed_or_null, cfm_stream_t stream) {
+    return stream_commit(B, max_pending, max_chunk_frames, beam_width, max_candidates, lm, hw, lengths_or_null, state, state_bytes,
+                         log, L, total, committed_or_null, stream, nullptr);
 }
 
 extern "C" int cfm_ctc_beam_commit_reset_slots(int B, const int64_t* slots, int n_slots, int64_t* total, cfm_stream_t stream) {
@@ -1338,4 +1526,60 @@ extern "C" int cfm_ctc_beam_commit_reset_slots(int B, const int64_t* slots, int 
     hipLaunchKernelGGL(beam_commit_reset_slots_kernel, dim3((unsigned)((n_slots + 255) / 256)), dim3(256), 0,
                        static_cast<hipStream_t>(stream), total, B, slots, n_slots);
     return cfm_launch_status();
+}
+
+// ---- beam-search timestamps (include/conformer_hip_times.h) ----------------------------------------------------------------------
+
+extern "C" size_t cfm_ctc_beam_times_bytes(int B, int T, int W, int max_pending_or_0) {
+    if (!times_args_ok(B, T, W, max_pending_or_0)) return 0;
+    return times_carve(B, T, W, max_pending_or_0, nullptr, nullptr);
+}
+
+extern "C" int cfm_ctc_beam_times_reset(int B, const int64_t* slots_or_null, int n_slots, void* times, size_t times_bytes,
+                                        cfm_stream_t stream) {
+    CFM_REQUIRE(times, CFM_ERR_NULL);
+    CFM_REQUIRE(B > 0 && (slots_or_null ? n_slots >= 1 && n_slots <= B : n_slots == 0), CFM_ERR_BAD_SHAPE);
+    CFM_REQUIRE(times_bytes >= beam_align((size_t)B * sizeof(int64_t)), CFM_ERR_BAD_SHAPE);
+    const int n = slots_or_null ? n_slots : B;
+    hipLaunchKernelGGL(beam_times_reset_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       static_cast<int64_t*>(times), B, slots_or_null, n);
+    return cfm_launch_status();
+}
+
+extern "C" int cfm_ctc_beam_stream_step_times_f32(const float* logits, const int64_t* lengths_or_null, int B, int Tc, int V,
+                                                  int blank_id, int beam_width, int max_candidates, float token_min_logp,
+                                                  float beam_prune_logp, int n_best, const void* lm_tables_or_null, double alpha,
+                                                  double beta, double unk_score_offset, int score_boundary,
+                                                  const void* hw_tables_or_null, double hotword_weight, void* state,
+                                                  size_t state_bytes, int T_max, int t_used, int64_t* tokens, int64_t* counts,
+                                                  float* scores, float* am_scores_or_null, int64_t* num_hyps, void* times,
+                                                  size_t times_bytes, int64_t* token_frames, float* token_logp,
+                                                  cfm_stream_t stream) {
+    const Fusion fz{lm_tables_or_null, alpha, beta, unk_score_offset, score_boundary, hw_tables_or_null, hotword_weight};
+    const TimesArgs ta{times, times_bytes, token_frames, token_logp};
+    return stream_step(logits, lengths_or_null, B, Tc, V, blank_id, beam_width, max_candidates, token_min_logp, beam_prune_logp,
+                       n_best, fz, state, state_bytes, T_max, t_used, tokens, counts, scores, am_scores_or_null, num_hyps, stream,
+                       &ta);
+}
+
+extern "C" int cfm_ctc_beam_stream_finish_times_f32(int B, int beam_width, int max_candidates, int n_best,
+                                                    const void* lm_tables_or_null, double alpha, double beta,
+                                                    double unk_score_offset, int score_boundary, const void* hw_tables_or_null,
+                                                    double hotword_weight, void* state, size_t state_bytes, int T_max,
+                                                    int64_t* tokens, int64_t* counts, float* scores, float* am_scores_or_null,
+                                                    int64_t* num_hyps, void* times, size_t times_bytes, int64_t* token_frames,
+                                                    float* token_logp, cfm_stream_t stream) {
+    const Fusion fz{lm_tables_or_null, alpha, beta, unk_score_offset, score_boundary, hw_tables_or_null, hotword_weight};
+    const TimesArgs ta{times, times_bytes, token_frames, token_logp};
+    return stream_finish(B, beam_width, max_candidates, n_best, fz, state, state_bytes, T_max, tokens, counts, scores,
+                         am_scores_or_null, num_hyps, stream, &ta);
+}
+
+extern "C" int cfm_ctc_beam_stream_commit_times(int B, int max_pending, int max_chunk_frames, int beam_width, int max_candidates,
+                                                int lm, int hw, const int64_t* lengths_or_null, void* state, size_t state_bytes,
+                                                int* log, int L, int64_t* total, int* committed_or_null, void* times,
+                                                size_t times_bytes, int64_t* log_frames, float* log_logp, cfm_stream_t stream) {
+    const TimesArgs ta{times, times_bytes, log_frames, log_logp};
+    return stream_commit(B, max_pending, max_chunk_frames, beam_width, max_candidates, lm, hw, lengths_or_null, state, state_bytes,
+                         log, L, total, committed_or_null, stream, &ta);
 }

@@ -17,7 +17,10 @@ Hotword boosting, with or without the language model (`conformer_amd.hotwords`):
 The same search resumed chunk by chunk over a stream, in every mode: `beam_ctc_stream_init/step/finish` and
 `BeamCTCDecoder.stream`, semantics in INTEGRATION.md "Streaming (resumable) search".  With `max_pending` the stream has no end:
 after every step the prefix no live hypothesis can change is committed and the prefix tree re-rooted there, INTEGRATION.md
-"Committed-prefix streaming (max_pending)"."""
+"Committed-prefix streaming (max_pending)".
+
+Token and word timestamps from the search itself, in every mode above (`return_times=`, `times=True`, `BeamCTCDecoder.words`,
+`BeamCTCStream.pop_committed_words`): INTEGRATION.md "Beam-search timestamps"."""
 from __future__ import annotations
 
 import math
@@ -26,6 +29,7 @@ from typing import Callable, Iterable, List, Optional, Sequence, Tuple, Union
 import torch
 
 from . import _lib, ops
+from .align import Word, group_words
 from .hotwords import Hotwords, as_hotwords
 from .lm import NgramLanguageModel, as_language_model
 
@@ -85,12 +89,37 @@ def _beam_outputs(B: int, N: int, T: int, device, fused: bool):
     return tokens, counts, scores, am_scores, num_hyps
 
 
+def _flag(who: str, name: str, value) -> bool:
+    """A boolean option, checked on the host (a tensor or a count passed by position lands here)."""
+    if not isinstance(value, bool):
+        raise ValueError(f"{who}: {name} must be True or False, got {value!r}")
+    return value
+
+
+def _frame_seconds(who: str, value) -> float:
+    if isinstance(value, bool) or not isinstance(value, (int, float)) or not math.isfinite(value) or value <= 0:
+        raise ValueError(f"{who}: frame_seconds must be a positive finite number, got {value!r}")
+    return float(value)
+
+
+def token_words(decoder: "BeamCTCDecoder", ids: Sequence[int], frames: Sequence[int], logps: Sequence[float],
+                frame_seconds: float) -> List[Word]:
+    """Words of one hypothesis from the search's own timestamps (INTEGRATION.md "Beam-search timestamps"): token i spans
+    [frames[i], frames[i] + 1), a Word's score is the mean of its tokens' log-probabilities."""
+    v = decoder.vocab
+    delim = v.index(decoder.delim_token) if decoder.delim_token in v else None
+    return group_words(ids, frames, [f + 1 for f in frames], logps, v, delim, frame_seconds, decoder.skip_ids)
+
+
 def _beam_search(logits: torch.Tensor, blank_id: int, lengths: Optional[torch.Tensor], n_best: int, beam_width: int,
                  token_min_logp: float, beam_prune_logp: float, max_candidates: int, vocab: Optional[Sequence[str]] = None,
-                 fusion: Optional[Callable[[torch.device], _Fusion]] = None):
+                 fusion: Optional[Callable[[torch.device], _Fusion]] = None, return_times: bool = False):
     """The one-shot search behind beam_ctc_decode / beam_ctc_lm_decode / beam_ctc_hotword_decode and BeamCTCDecoder.
     `fusion(device)` builds the fusion group on the logits' device (None: the plain search); `vocab` must then have V tokens.
-    Returns (tokens, counts, scores, num_hyps), with am_scores before num_hyps when fused."""
+    Returns (tokens, counts, scores, num_hyps), with am_scores before num_hyps when fused.  return_times: the same search as
+    init / step / finish on a temporary stream state (bit for bit the one-shot result), with the trailing pair (token_frames
+    (B,N,T) int64 padded with -1, token_logp (B,N,T) fp32 padded with -inf)."""
+    _flag("beam search", "return_times", return_times)
     x = _logits(logits)
     if x.dim() != 3:
         raise ValueError(f"logits: expected (B,T,V), got {tuple(x.shape)}")
@@ -100,7 +129,15 @@ def _beam_search(logits: torch.Tensor, blank_id: int, lengths: Optional[torch.Te
     if lengths is not None:
         lengths = ops._req(lengths, "lengths", torch.int64)
     f = _PLAIN if fusion is None else fusion(x.device)
-    ws_bytes = _lib.load().cfm_ctc_beam_workspace_bytes(B, T, int(beam_width), int(max_candidates))
+    if return_times:
+        st = _stream_alloc("beam search", B, T, x.device, int(beam_width), int(max_candidates), f, None, 0, True)
+        beam_ctc_stream_step(st, x, blank_id, lengths, n_best=n_best, token_min_logp=token_min_logp,
+                             beam_prune_logp=beam_prune_logp)
+        tokens, counts, scores, am_scores, num_hyps, times = beam_ctc_stream_finish(st, n_best)
+        if f.fused:
+            return tokens, counts, scores, am_scores, num_hyps, times
+        return tokens, counts, scores, num_hyps, times
+    ws_bytes =_lib.load().cfm_ctc_beam_workspace_bytes(B, T, int(beam_width), int(max_candidates))
     workspace = torch.empty(max(int(ws_bytes), 1), dtype=torch.uint8, device=x.device)
     tokens, counts, scores, am_scores, num_hyps = _beam_outputs(B, int(n_best), T, x.device, f.fused)
     search = (x.data_ptr(), ops._p(lengths), B, T, V, int(blank_id), int(beam_width), int(max_candidates),
@@ -119,20 +156,23 @@ def _beam_search(logits: torch.Tensor, blank_id: int, lengths: Optional[torch.Te
 
 
 def beam_ctc_decode(logits: torch.Tensor, blank_id: int, lengths: Optional[torch.Tensor] = None, beam_width: int = 100,
-                    n_best: int = 1, token_min_logp: float = -5.0, beam_prune_logp: float = -10.0, max_candidates: int = 16
-                    ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+                    n_best: int = 1, token_min_logp: float = -5.0, beam_prune_logp: float = -10.0, max_candidates: int = 16,
+                    return_times: bool = False) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
     """CTC prefix beam search over logits (B,T,V) on the HIP device (fp32, or bf16 / fp16 cast to fp32).
     Returns (tokens (B,N,T) int64 padded with -1, counts (B,N) int64, scores (B,N) fp32, num_hyps (B) int64), N = n_best,
     hypotheses best first; unused rows hold count 0, tokens -1 and score -inf.  `lengths` (B) int64 on the device: frames
-    to consume per utterance (clamped to [0,T]; None = all).  Nothing synchronises with the host."""
-    return _beam_search(logits, blank_id, lengths, n_best, beam_width, token_min_logp, beam_prune_logp, max_candidates)
+    to consume per utterance (clamped to [0,T]; None = all).  Nothing synchronises with the host.
+    return_times: the result gains a trailing pair (token_frames (B,N,T) int64 padded with -1, token_logp (B,N,T) fp32 padded
+    with -inf), INTEGRATION.md "Beam-search timestamps"."""
+    return _beam_search(logits, blank_id, lengths, n_best, beam_width, token_min_logp, beam_prune_logp, max_candidates,
+                        return_times=return_times)
 
 
 def beam_ctc_lm_decode(logits: torch.Tensor, blank_id: int, lm: Union[NgramLanguageModel, str],
                        lengths: Optional[torch.Tensor] = None, *, vocab: Sequence[str], delim_token: str = "|",
                        skip_ids: Sequence[int] = (), alpha: float = 2.1, beta: float = 9.2, unk_score_offset: float = -10.0,
                        score_boundary: bool = True, beam_width: int = 100, n_best: int = 1, token_min_logp: float = -5.0,
-                       beam_prune_logp: float = -10.0, max_candidates: int = 16
+                       beam_prune_logp: float = -10.0, max_candidates: int = 16, return_times: bool = False
                        ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
     """CTC prefix beam search fused with the word n-gram model `lm` (an NgramLanguageModel or an ARPA path), on the HIP
     device.  `vocab` (V strings) spells the tokens: a token equal to `delim_token` (or " ") ends a word, tokens in
@@ -140,12 +180,12 @@ def beam_ctc_lm_decode(logits: torch.Tensor, blank_id: int, lm: Union[NgramLangu
     Returns (tokens (B,N,T) int64 padded with -1, counts (B,N) int64, scores (B,N) fp32 fused, am_scores (B,N) fp32
     acoustic, num_hyps (B) int64), best first by the final fused score; unused rows hold count 0, tokens -1 and scores
     -inf.  The device tables are packed and copied once per (lm, vocab, delim_token, skip_ids); after that nothing
-    synchronises with the host."""
+    synchronises with the host.  return_times: as beam_ctc_decode, a trailing (token_frames, token_logp)."""
     def fusion(device):
         return _Fusion(as_language_model(lm).device_tables(vocab, delim_token, skip_ids, device), None, alpha, beta,
                        unk_score_offset, score_boundary)
     return _beam_search(logits, blank_id, lengths, n_best, beam_width, token_min_logp, beam_prune_logp, max_candidates,
-                        vocab, fusion)
+                        vocab, fusion, return_times)
 
 
 def beam_ctc_hotword_decode(logits: torch.Tensor, blank_id: int, hotwords: Union[Hotwords, Iterable[str]],
@@ -154,7 +194,7 @@ def beam_ctc_hotword_decode(logits: torch.Tensor, blank_id: int, hotwords: Union
                             lm: Union[NgramLanguageModel, str, None] = None, alpha: float = 2.1, beta: float = 9.2,
                             unk_score_offset: float = -10.0, score_boundary: bool = True, beam_width: int = 100,
                             n_best: int = 1, token_min_logp: float = -5.0, beam_prune_logp: float = -10.0,
-                            max_candidates: int = 16
+                            max_candidates: int = 16, return_times: bool = False
                             ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
     """CTC prefix beam search with hotword boosting on the HIP device, fused with the word n-gram model `lm` when one is
     given (an NgramLanguageModel or an ARPA path; alpha, beta, unk_score_offset, score_boundary as in beam_ctc_lm_decode).
@@ -163,7 +203,7 @@ def beam_ctc_hotword_decode(logits: torch.Tensor, blank_id: int, hotwords: Union
     (B,N,T) int64 padded with -1, counts (B,N) int64, scores (B,N) fp32 final boosted score, am_scores (B,N) fp32 acoustic,
     num_hyps (B) int64), best first by the final score; unused rows hold count 0, tokens -1 and scores -inf.  The device
     tables are packed and copied once per (hotwords, vocab, delim_token, skip_ids); after that nothing synchronises with the
-    host."""
+    host.  return_times: as beam_ctc_decode, a trailing (token_frames, token_logp)."""
     if not math.isfinite(float(hotword_weight)):
         raise ValueError(f"hotword_weight must be finite, got {hotword_weight}")
 
@@ -173,7 +213,7 @@ def beam_ctc_hotword_decode(logits: torch.Tensor, blank_id: int, hotwords: Union
         lm_tables = None if lm is None else as_language_model(lm).device_tables(vocab, delim_token, skip_ids, device)
         return _Fusion(lm_tables, hw_tables, alpha, beta, unk_score_offset, score_boundary, hotword_weight)
     return _beam_search(logits, blank_id, lengths, n_best, beam_width, token_min_logp, beam_prune_logp, max_candidates,
-                        vocab, fusion)
+                        vocab, fusion, return_times)
 
 
 class BeamCTCDecoder:
@@ -211,12 +251,29 @@ class BeamCTCDecoder:
         self.hotword_weight = hotword_weight
 
     def stream(self, batch: int, max_frames: Optional[int], device=None, *, max_pending: Optional[int] = None,
-               max_chunk_frames: Optional[int] = None, commit_log: int = 4096) -> "BeamCTCStream":
+               max_chunk_frames: Optional[int] = None, commit_log: int = 4096, times: bool = False,
+               frame_seconds: float = 0.04) -> "BeamCTCStream":
         """A resumable search configured like this decoder (beam knobs, lm, hotwords) over `batch` utterances of at most
         `max_frames` frames in all: BeamCTCStream.  max_pending (tokens) with max_chunk_frames (logit frames per step) and
-        max_frames=None: a stream without an end in commit mode (beam_ctc_stream_init)."""
+        max_frames=None: a stream without an end in commit mode (beam_ctc_stream_init).  times: the search records token
+        timestamps and the stream hands out Words (pop_committed_words, partial_words, finish_words), frame_seconds per frame."""
         return BeamCTCStream(self, batch, max_frames, device, max_pending=max_pending, max_chunk_frames=max_chunk_frames,
-                             commit_log=commit_log)
+                             commit_log=commit_log, times=times, frame_seconds=frame_seconds)
+
+    def words(self, logits: torch.Tensor, lengths: Optional[torch.Tensor] = None, frame_seconds: float = 0.04
+              ) -> List[List[Word]]:
+        """The best hypothesis of every utterance of logits (B,T,V) as align.Words timed by the search itself (INTEGRATION.md
+        "Beam-search timestamps": a token's frame is its entry into the surviving lineage, not the Viterbi start CTCAligner
+        returns; Word.score is the mean token log-probability).  Synchronises."""
+        fs = _frame_seconds("BeamCTCDecoder.words", frame_seconds)
+        if lengths is not None and not (isinstance(lengths, torch.Tensor) and lengths.is_cuda):
+            lengths = torch.as_tensor(lengths, dtype=torch.int64).reshape(-1).to(logits.device)
+        fusion = None if self.lm is None and self.hotwords is None else self._fusion
+        out = _beam_search(logits, self.blank_id, lengths, 1, self.beam_width, self.token_min_logp, self.beam_prune_logp,
+                           self.max_candidates, self.vocab, fusion, True)
+        tk, ct = out[0][:, 0].cpu().tolist(), out[1][:, 0].cpu().tolist()
+        fr, lp = out[-1][0][:, 0].cpu().tolist(), out[-1][1][:, 0].cpu().tolist()
+        return [token_words(self, tk[b][:n], fr[b][:n], lp[b][:n], fs) for b, n in enumerate(ct)]
 
     def text(self, ids: Sequence[int]) -> str:
         joined = "".join(self.vocab[i] for i in ids if i not in self.skip_ids)
@@ -270,6 +327,16 @@ class _StreamState:
         self.log: Optional[torch.Tensor] = None          # (B, L) int32 ring of committed tokens
         self.total: Optional[torch.Tensor] = None        # (B) int64 tokens committed since the init / the slot's reset
         self.committed: Optional[torch.Tensor] = None    # (B) int32 tokens the latest step committed
+        # timestamps (beam_ctc_stream_init(times=True)): the times buffer beside `buf`, and in commit mode the rings beside `log`
+        self.times: Optional[torch.Tensor] = None
+        self.log_frames: Optional[torch.Tensor] = None   # (B, L) int64
+        self.log_logp: Optional[torch.Tensor] = None     # (B, L) fp32
+
+    def times_outputs(self, N: int):
+        """(times buffer, its size, token_frames, token_logp) as the *_times entries take them, and the pair they fill"""
+        tf = torch.empty(self.B, N, self.t_max, dtype=torch.int64, device=self.buf.device)
+        tl = torch.empty(self.B, N, self.t_max, dtype=torch.float32, device=self.buf.device)
+        return (self.times.data_ptr(), self.times.numel(), tf.data_ptr(), tl.data_ptr()), (tf, tl)
 
 
 def _commit_args(who: str, max_frames, max_pending, max_chunk_frames, commit_log=4096):
@@ -297,34 +364,48 @@ def beam_ctc_stream_init(batch: int, max_frames: Optional[int], device, *, beam_
                          lm_tables: Optional[torch.Tensor] = None, hw_tables: Optional[torch.Tensor] = None,
                          alpha: float = 2.1, beta: float = 9.2, unk_score_offset: float = -10.0, score_boundary: bool = True,
                          hotword_weight: float = 9.0, max_pending: Optional[int] = None,
-                         max_chunk_frames: Optional[int] = None, commit_log: int = 4096) -> _StreamState:
+                         max_chunk_frames: Optional[int] = None, commit_log: int = 4096, times: bool = False) -> _StreamState:
     """Allocate and initialise the state of a resumable CTC prefix beam search over `batch` utterances of at most
     `max_frames` frames, every utterance at the empty prefix.  `lm_tables` / `hw_tables`: the device blobs of
     NgramLanguageModel.device_tables / Hotwords.device_tables (None: not used).  Enqueues only.
     Commit mode: max_pending = M tokens with max_chunk_frames = k_cap logit frames per step and max_frames=None.  The state is
     then sized by (B, M, k_cap, W, K, lm, hw) alone and the stream has no end; the committed tokens go to a ring of
-    max(commit_log, M + k_cap) tokens per utterance (beam_ctc_stream_committed reads it)."""
+    max(commit_log, M + k_cap) tokens per utterance (beam_ctc_stream_committed reads it).
+    times: the search records token timestamps (INTEGRATION.md "Beam-search timestamps") in a buffer beside the state; step and
+    finish then return a trailing (token_frames, token_logp) and the commit log has frames and log-probabilities beside it."""
+    _flag("beam_ctc_stream_init", "times", times)
     commit = _commit_args("beam_ctc_stream_init", max_frames, max_pending, max_chunk_frames, commit_log)
-    B = int(batch)
-    W, K = int(beam_width), int(max_candidates)
+    fusion = _Fusion(lm_tables, hw_tables, alpha, beta, unk_score_offset, score_boundary, hotword_weight)
+    return _stream_alloc("beam_ctc_stream_init", int(batch), max_frames, device, int(beam_width), int(max_candidates), fusion,
+                         commit, commit_log, times)
+
+
+def _stream_alloc(who: str, B: int, max_frames: Optional[int], device, W: int, K: int, fusion: _Fusion, commit, commit_log: int,
+                  times: bool) -> _StreamState:
+    """The buffers of a resumable search (commit: None or (M, k_cap) of _commit_args), initialised."""
     lib = _lib.load()
-    lm, hw = int(lm_tables is not None), int(hw_tables is not None)
+    lm, hw = int(fusion.lm_tables is not None), int(fusion.hw_tables is not None)
     if commit is None:
         Tm = int(max_frames)
         nbytes = int(lib.cfm_ctc_beam_stream_state_bytes(B, Tm, W, K, lm, hw))
     else:
         Tm = commit[0] + commit[1]
         nbytes = int(lib.cfm_ctc_beam_commit_state_bytes(B, commit[0], commit[1], W, K, lm, hw))
-    if nbytes == 0:
-        raise ValueError(f"beam_ctc_stream_init: unsupported arguments (B={B}, max_frames={max_frames}, beam_width={W}, "
-                         f"max_candidates={K}, max_pending={max_pending}, max_chunk_frames={max_chunk_frames})")
+    tbytes = int(lib.cfm_ctc_beam_times_bytes(B, Tm, W, 0 if commit is None else commit[0])) if times and nbytes else 0
+    if nbytes == 0 or (times and tbytes == 0):
+        raise ValueError(f"{who}: unsupported arguments (B={B}, max_frames={max_frames}, beam_width={W}, max_candidates={K}, "
+                         f"(max_pending, max_chunk_frames)={commit})")
     buf = torch.empty(nbytes, dtype=torch.uint8, device=device)
-    st = _StreamState(buf, B, Tm, W, K,
-                      _Fusion(lm_tables, hw_tables, alpha, beta, unk_score_offset, score_boundary, hotword_weight))
+    st = _StreamState(buf, B, Tm, W, K, fusion)
     if commit is not None:
         st.max_pending, st.max_chunk_frames = commit
         st.log = torch.zeros(B, max(int(commit_log), Tm), dtype=torch.int32, device=device)
         st.total = torch.zeros(B, dtype=torch.int64, device=device)
+    if times:
+        st.times = torch.empty(tbytes, dtype=torch.uint8, device=device)
+        if commit is not None:
+            st.log_frames = torch.full(st.log.shape, -1, dtype=torch.int64, device=device)
+            st.log_logp = torch.full(st.log.shape, -math.inf, dtype=torch.float32, device=device)
     beam_ctc_stream_reset(st)
     return st
 
@@ -338,6 +419,8 @@ def beam_ctc_stream_reset(st: _StreamState) -> None:
     if st.max_pending is not None:
         st.total.zero_()
         st.committed = None
+    if st.times is not None:               # (every utterance's frames count from 0 again)
+        _lib.call("cfm_ctc_beam_times_reset", st.B, None, 0, st.times.data_ptr(), st.times.numel(), ops._stream())
 
 
 def beam_ctc_stream_reset_slots(st: _StreamState, slots: torch.Tensor) -> None:
@@ -352,6 +435,9 @@ def beam_ctc_stream_reset_slots(st: _StreamState, slots: torch.Tensor) -> None:
               ops._stream())
     if st.max_pending is not None:         # (the slots' committed prefixes are empty again; the other slots' logs stay)
         _lib.call("cfm_ctc_beam_commit_reset_slots", st.B, slots.data_ptr(), slots.numel(), st.total.data_ptr(), ops._stream())
+    if st.times is not None:               # (a slot's frames count from its own opening)
+        _lib.call("cfm_ctc_beam_times_reset", st.B, slots.data_ptr(), slots.numel(), st.times.data_ptr(), st.times.numel(),
+                  ops._stream())
 
 
 def beam_ctc_stream_step(st: _StreamState, logits: torch.Tensor, blank_id: int, lengths: Optional[torch.Tensor] = None, *,
@@ -366,7 +452,8 @@ def beam_ctc_stream_step(st: _StreamState, logits: torch.Tensor, blank_id: int, 
     Commit mode: Tc <= max_chunk_frames; the step is followed by the commit, the returned tokens are (B,N,max_pending +
     max_chunk_frames) and relative to the committed prefix as it was BEFORE this step (st.committed: the (B) int32 tokens this
     step then committed, so the pending best is tokens[b, r, st.committed[b]:counts[b, r]]); t_used is taken as a bound on
-    the frames stepped and capped at max_pending, which bounds what the tree holds after a commit."""
+    the frames stepped and capped at max_pending, which bounds what the tree holds after a commit.
+    A state made with times=True: the result gains a trailing pair (token_frames, token_logp), shaped and padded like tokens."""
     x = _logits(logits)
     if x.dim() != 3 or x.shape[0] != st.B:
         raise ValueError(f"logits: expected ({st.B},Tc,V), got {tuple(x.shape)}")
@@ -385,27 +472,40 @@ def beam_ctc_stream_step(st: _StreamState, logits: torch.Tensor, blank_id: int, 
     if lengths is not None:
         lengths = ops._req(lengths, "lengths", torch.int64)
     tokens, counts, scores, am_scores, num_hyps = _beam_outputs(st.B, int(n_best), st.t_max, x.device, st.fusion.fused)
-    _lib.call("cfm_ctc_beam_stream_step_f32", x.data_ptr(), ops._p(lengths), st.B, Tc, V, int(blank_id), st.beam_width,
-              st.max_candidates, float(token_min_logp), float(beam_prune_logp), int(n_best), *st.fusion.args, st.buf.data_ptr(),
-              st.buf.numel(), st.t_max, used, tokens.data_ptr(), counts.data_ptr(), scores.data_ptr(), ops._p(am_scores),
-              num_hyps.data_ptr(), ops._stream())
+    step = (x.data_ptr(), ops._p(lengths), st.B, Tc, V, int(blank_id), st.beam_width, st.max_candidates, float(token_min_logp),
+            float(beam_prune_logp), int(n_best), *st.fusion.args, st.buf.data_ptr(), st.buf.numel(), st.t_max, used,
+            tokens.data_ptr(), counts.data_ptr(), scores.data_ptr(), ops._p(am_scores), num_hyps.data_ptr())
+    pair = None
+    if st.times is None:
+        _lib.call("cfm_ctc_beam_stream_step_f32", *step, ops._stream())
+    else:
+        targs, pair = st.times_outputs(int(n_best))
+        _lib.call("cfm_ctc_beam_stream_step_times_f32", *step, *targs, ops._stream())
     if t_used is None:
         st.t_used += Tc
     if st.max_pending is not None:
         st.committed = torch.empty(st.B, dtype=torch.int32, device=x.device)
         f = st.fusion
-        _lib.call("cfm_ctc_beam_stream_commit", st.B, st.max_pending, st.max_chunk_frames, st.beam_width, st.max_candidates,
-                  int(f.lm_tables is not None), int(f.hw_tables is not None), ops._p(lengths), st.buf.data_ptr(), st.buf.numel(),
-                  st.log.data_ptr(), st.log.shape[1], st.total.data_ptr(), st.committed.data_ptr(), ops._stream())
+        commit = (st.B, st.max_pending, st.max_chunk_frames, st.beam_width, st.max_candidates, int(f.lm_tables is not None),
+                  int(f.hw_tables is not None), ops._p(lengths), st.buf.data_ptr(), st.buf.numel(), st.log.data_ptr(),
+                  st.log.shape[1], st.total.data_ptr(), st.committed.data_ptr())
+        if st.times is None:
+            _lib.call("cfm_ctc_beam_stream_commit", *commit, ops._stream())
+        else:
+            _lib.call("cfm_ctc_beam_stream_commit_times", *commit, st.times.data_ptr(), st.times.numel(),
+                      st.log_frames.data_ptr(), st.log_logp.data_ptr(), ops._stream())
+    if pair is not None:
+        return tokens, counts, scores, am_scores, num_hyps, pair
     return tokens, counts, scores, am_scores, num_hyps
 
 
-def beam_ctc_stream_committed(st: _StreamState, popped: Sequence[int], only: Optional[Sequence[int]] = None
-                              ) -> Tuple[List[List[int]], List[int]]:
+def beam_ctc_stream_committed(st: _StreamState, popped: Sequence[int], only: Optional[Sequence[int]] = None,
+                              times: bool = False):
     """Commit mode: per utterance the committed tokens from position popped[b] on, and the totals.  Synchronises.  `only`: the
     utterances to read (the others get an empty list and are not checked; only their rows of the log are copied).  RuntimeError
     naming the utterances, before anything is copied, where more than the ring holds were committed since popped[b] (the
-    oldest are overwritten)."""
+    oldest are overwritten).  times (a state made with times=True): (tokens, totals, frames, logps), the frames and
+    log-probabilities of the same rows and positions."""
     rows = list(range(st.B)) if only is None else [int(b) for b in only]
     total = st.total.cpu().tolist()
     L = st.log.shape[1]
@@ -414,23 +514,38 @@ def beam_ctc_stream_committed(st: _StreamState, popped: Sequence[int], only: Opt
         raise RuntimeError(f"utterance(s) {over}: {[total[b] - popped[b] for b in over]} tokens committed since the last pop, the "
                            f"commit log holds {L}: pop more often, give a larger commit_log, or discard them")
     out: List[List[int]] = [[] for _ in range(st.B)]
+    frames: List[List[int]] = [[] for _ in range(st.B)]
+    logps: List[List[float]] = [[] for _ in range(st.B)]
     if rows:
-        log = st.log.cpu() if only is None else st.log[torch.tensor(rows, device=st.log.device)].cpu()
+        def copy(ring):
+            return ring.cpu() if only is None else ring[torch.tensor(rows, device=ring.device)].cpu()
+        log = copy(st.log)
+        lf, ll = (copy(st.log_frames), copy(st.log_logp)) if times else (None, None)
         for i, b in enumerate(rows):
-            out[b] = log[i, torch.arange(popped[b], total[b]) % L].tolist()
+            at = torch.arange(popped[b], total[b]) % L
+            out[b] = log[i, at].tolist()
+            if times:
+                frames[b], logps[b] = lf[i, at].tolist(), ll[i, at].tolist()
+    if times:
+        return out, total, frames, logps
     return out, total
 
 
 def beam_ctc_stream_finish(st: _StreamState, n_best: int = 1):
     """The end-of-utterance step over the consumed frames: (tokens (B,N,max_frames), counts, scores, am_scores or None
     without LM and hotwords, num_hyps), equal bit for bit to one-shot decoding of the consumed frames (with T = max_frames).
-    Commit mode: the tokens are (B,N,max_pending + max_chunk_frames) and follow the committed prefix (st.log / st.total)."""
+    Commit mode: the tokens are (B,N,max_pending + max_chunk_frames) and follow the committed prefix (st.log / st.total).
+    A state made with times=True: the result gains a trailing pair (token_frames, token_logp)."""
     tokens, counts, scores, am_scores, num_hyps = _beam_outputs(st.B, int(n_best), st.t_max, st.buf.device,
                                                                 st.fusion.fused)
-    _lib.call("cfm_ctc_beam_stream_finish_f32", st.B, st.beam_width, st.max_candidates, int(n_best), *st.fusion.args,
-              st.buf.data_ptr(), st.buf.numel(), st.t_max, tokens.data_ptr(), counts.data_ptr(), scores.data_ptr(),
-              ops._p(am_scores), num_hyps.data_ptr(), ops._stream())
-    return tokens, counts, scores, am_scores, num_hyps
+    fin = (st.B, st.beam_width, st.max_candidates, int(n_best), *st.fusion.args, st.buf.data_ptr(), st.buf.numel(), st.t_max,
+           tokens.data_ptr(), counts.data_ptr(), scores.data_ptr(), ops._p(am_scores), num_hyps.data_ptr())
+    if st.times is None:
+        _lib.call("cfm_ctc_beam_stream_finish_f32", *fin, ops._stream())
+        return tokens, counts, scores, am_scores, num_hyps
+    targs, pair = st.times_outputs(int(n_best))
+    _lib.call("cfm_ctc_beam_stream_finish_times_f32", *fin, *targs, ops._stream())
+    return tokens, counts, scores, am_scores, num_hyps, pair
 
 
 class BeamCTCStream:
@@ -441,10 +556,18 @@ class BeamCTCStream:
     that have become final since the previous pop; `committed_text`, `partial_text` and `finish` speak of the text from the
     last pop on: (unpopped committed) [+ pending best | + final tokens], joined as token ids before `decoder.text`.
     Independent utterances (conformer_amd/slots.py): `step(t_used=)` takes the caller's bound, `reset_slots` starts some again
-    and `only=` reads (`finish`: ends) those utterances alone; the returned lists keep length B, "" or [] for the others."""
+    and `only=` reads (`finish`: ends) those utterances alone; the returned lists keep length B, "" or [] for the others.
+    times=True (INTEGRATION.md "Beam-search timestamps"): the search records when each token entered, and the stream hands out
+    align.Words: `partial_words`, `finish_words` and, in commit mode, `pop_committed_words`, which returns complete words only and
+    HOLDS the committed tokens after the last committed delimiter on the host until their delimiter is committed or the stream
+    finishes.  Held tokens count as popped: `pop_committed` never returns them, while the texts and words of `partial_*`,
+    `committed_text` and `finish*` still begin with them."""
 
     def __init__(self, decoder: "BeamCTCDecoder", batch: int, max_frames: Optional[int], device=None, *,
-                 max_pending: Optional[int] = None, max_chunk_frames: Optional[int] = None, commit_log: int = 4096) -> None:
+                 max_pending: Optional[int] = None, max_chunk_frames: Optional[int] = None, commit_log: int = 4096,
+                 times: bool = False, frame_seconds: float = 0.04) -> None:
+        self.times = _flag("BeamCTCStream", "times", times)
+        self.frame_seconds = _frame_seconds("BeamCTCStream", frame_seconds)
         self.commit = _commit_args("BeamCTCStream", max_frames, max_pending, max_chunk_frames, commit_log) is not None
         self.decoder = decoder
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
@@ -453,11 +576,15 @@ class BeamCTCStream:
                                           max_candidates=d.max_candidates, lm_tables=f.lm_tables, hw_tables=f.hw_tables,
                                           alpha=d.alpha, beta=d.beta, unk_score_offset=d.unk_score_offset,
                                           score_boundary=d.score_boundary, hotword_weight=d.hotword_weight,
-                                          max_pending=max_pending, max_chunk_frames=max_chunk_frames, commit_log=commit_log)
+                                          max_pending=max_pending, max_chunk_frames=max_chunk_frames, commit_log=commit_log,
+                                          times=self.times)
         self.finished = False
         self.last = None                   # interim outputs of the latest step
+        self.last_committed = None         # commit mode: the (B) tokens the latest step committed
         self.popped = [0] * int(batch)     # commit mode: committed tokens handed out by pop_committed, per utterance
         self.fresh = set(range(int(batch)))    # utterances reset since the latest step: `last` holds no row of theirs
+        # times: per utterance the (id, frame, logp) of the committed tokens pop_committed_words took but has not handed out
+        self.held: List[List[Tuple[int, int, float]]] = [[] for _ in range(int(batch))]
 
     def step(self, logits_chunk: torch.Tensor, lengths: Optional[torch.Tensor] = None, *, t_used: Optional[int] = None):
         """logits_chunk (B,Tc,V): the next frames of every utterance; `lengths` (B) int64: frames of the chunk to consume per
@@ -469,7 +596,8 @@ class BeamCTCStream:
             lengths = torch.as_tensor(lengths, dtype=torch.int64).reshape(-1).to(self.device)
         out = beam_ctc_stream_step(self.state, logits_chunk, d.blank_id, lengths, n_best=1, token_min_logp=d.token_min_logp,
                                    beam_prune_logp=d.beam_prune_logp, t_used=t_used)
-        self.last = out + (self.state.committed,) if self.commit else out
+        self.last = out
+        self.last_committed = self.state.committed if self.commit else None
         self.fresh.clear()
         return out[0], out[1], out[2]
 
@@ -483,6 +611,7 @@ class BeamCTCStream:
         beam_ctc_stream_reset_slots(self.state, idx)       # (commit mode: the utterances' committed totals too)
         for b in slots:
             self.popped[b] = 0
+            self.held[b] = []
         self.fresh.update(slots)
 
     def _need_commit(self, what: str) -> None:
@@ -497,6 +626,81 @@ class BeamCTCStream:
         if not self.commit:                # nothing is committed before the end
             return [[] for _ in self.popped], self.popped
         return beam_ctc_stream_committed(self.state, self.popped, only)
+
+    def _from_last_pop(self, only: Optional[Sequence[int]] = None) -> List[List[int]]:
+        """Per utterance the token ids the texts begin with: the held tokens (times), then the unpopped committed ones."""
+        ids = self._unpopped(only)[0]
+        return [[t[0] for t in h] + i for h, i in zip(self.held, ids)]
+
+    # ---- words (times=True)
+    def _need_times(self, what: str) -> None:
+        if not self.times:
+            raise RuntimeError(f"BeamCTCStream.{what}: the stream was made without times=True, the search recorded no timestamps")
+
+    def _unpopped_timed(self, only: Optional[Sequence[int]] = None):
+        """Per utterance the (id, frame, logp) of the held tokens and then of the unpopped committed ones; the totals."""
+        if not self.commit:
+            return [list(h) for h in self.held], self.popped
+        ids, total, frames, logps = beam_ctc_stream_committed(self.state, self.popped, only, times=True)
+        return [h + list(zip(i, f, p)) for h, i, f, p in zip(self.held, ids, frames, logps)], total
+
+    def _words(self, timed: Sequence[Tuple[int, int, float]]) -> List[Word]:
+        return token_words(self.decoder, [t[0] for t in timed], [t[1] for t in timed], [t[2] for t in timed],
+                           self.frame_seconds)
+
+    def pop_committed_words(self, only: Optional[Sequence[int]] = None) -> List[List[Word]]:
+        """Commit mode with times: per utterance the COMPLETE words committed since the previous pop: the committed tokens up
+        to the last committed delimiter.  The committed tokens after it are held on the host until their delimiter is committed
+        (or finish_words ends the stream); they count as popped, so pop_committed never returns them.  Synchronises; raises
+        like pop_committed, with nothing popped, when the commit log was lapped."""
+        self._need_times("pop_committed_words")
+        self._need_commit("pop_committed_words")
+        timed, total = self._unpopped_timed(only)
+        v = self.decoder.vocab
+        delim = v.index(self.decoder.delim_token) if self.decoder.delim_token in v else None
+        words: List[List[Word]] = [[] for _ in self.popped]
+        for b in self._rows(only):
+            seq = timed[b]
+            cut = max((i + 1 for i, t in enumerate(seq) if t[0] == delim), default=0)
+            words[b] = self._words(seq[:cut])
+            self.held[b] = seq[cut:]
+            self.popped[b] = total[b]
+        return words
+
+    def partial_words(self, only: Optional[Sequence[int]] = None) -> List[List[Word]]:
+        """With times: the words of partial_text: the held tokens, the committed tokens not yet popped and the pending best
+        of the latest step ([] before the first step and for an utterance reset since).  Changes nothing."""
+        self._need_times("partial_words")
+        words: List[List[Word]] = [[] for _ in self.popped]
+        rows = [b for b in self._rows(only) if b not in self.fresh]
+        if not rows:
+            return words
+        timed = self._unpopped_timed(only)[0]
+        tk, ct = self.last[0][:, 0].cpu().tolist(), self.last[1][:, 0].cpu().tolist()
+        fr, lp = self.last[5][0][:, 0].cpu().tolist(), self.last[5][1][:, 0].cpu().tolist()
+        nc = self.last_committed.cpu().tolist() if self.commit else [0] * len(ct)
+        for b in rows:
+            words[b] = self._words(timed[b] + list(zip(tk[b][nc[b]:ct[b]], fr[b][nc[b]:ct[b]], lp[b][nc[b]:ct[b]])))
+        return words
+
+    def finish_words(self, only: Optional[Sequence[int]] = None) -> List[List[Word]]:
+        """With times: the words of finish(): the held tokens, the unpopped committed tokens and the final tokens.  Ends the
+        stream as finish() does (only=[...]: those utterances alone)."""
+        self._need_times("finish_words")
+        if self.finished:
+            raise RuntimeError("BeamCTCStream.finish_words() after the finish: call reset() to start a new stream")
+        out = beam_ctc_stream_finish(self.state, n_best=1)
+        self.finished = only is None
+        timed = self._unpopped_timed(only)[0]
+        rows = self._rows(only)
+        idx = torch.tensor(rows, dtype=torch.int64, device=out[0].device)
+        tk, ct = out[0][idx, 0].cpu().tolist(), out[1][idx, 0].cpu().tolist()
+        fr, lp = out[5][0][idx, 0].cpu().tolist(), out[5][1][idx, 0].cpu().tolist()
+        words: List[List[Word]] = [[] for _ in self.popped]
+        for i, b in enumerate(rows):
+            n = ct[i]
+            words[b] = self._words(timed[b] + list(zip(tk[i][:n], fr[i][:n], lp[i][:n])))
+        return words
 
     def pop_committed(self, only: Optional[Sequence[int]] = None) -> List[List[int]]:
         """Commit mode: per utterance the token ids committed since the previous pop (they will never change), which are then
@@ -518,7 +722,7 @@ class BeamCTCStream:
     def committed_text(self, only: Optional[Sequence[int]] = None) -> List[str]:
         """Commit mode: the text of the committed tokens not yet popped."""
         self._need_commit("committed_text")
-        return [self.decoder.text(ids) for ids in self._unpopped(only)[0]]
+        return [self.decoder.text(ids) for ids in self._from_last_pop(only)]
 
     def partial_text(self, only: Optional[Sequence[int]] = None) -> List[str]:
         """The interim best transcript of every utterance after the latest step (empty strings before the first, and for an
@@ -527,9 +731,9 @@ class BeamCTCStream:
         rows = [b for b in self._rows(only) if b not in self.fresh]
         if not rows:
             return texts
-        ids = self._unpopped(only)[0]
+        ids = self._from_last_pop(only)
         tk, ct = self.last[0][:, 0].cpu().tolist(), self.last[1][:, 0].cpu().tolist()
-        nc = self.last[5].cpu().tolist() if self.commit else [0] * len(ct)     # the best is relative to the prefix before the step
+        nc = self.last_committed.cpu().tolist() if self.commit else [0] * len(ct)     # the best is relative to the prefix before the step
         for b in rows:
             texts[b] = self.decoder.text(ids[b] + tk[b][nc[b]:ct[b]])
         return texts
@@ -538,9 +742,9 @@ class BeamCTCStream:
         """only=[...]: those utterances' end alone (no search state is saved: the others go on); only their rows are copied."""
         if self.finished:
             raise RuntimeError("BeamCTCStream.finish() called twice: call reset() to start a new stream")
-        tokens, counts, _, _, _ = beam_ctc_stream_finish(self.state, n_best=1)
+        tokens, counts = beam_ctc_stream_finish(self.state, n_best=1)[:2]
         self.finished = only is None
-        ids = self._unpopped(only)[0]
+        ids = self._from_last_pop(only)
         if only is None:
             tk, ct = tokens[:, 0].cpu().tolist(), counts[:, 0].cpu().tolist()
         texts = [""] * len(self.popped)
@@ -554,4 +758,5 @@ class BeamCTCStream:
         beam_ctc_stream_reset(self.state)
         self.finished = False
         self.popped = [0] * len(self.popped)
+        self.held = [[] for _ in self.popped]
         self.fresh = set(range(len(self.popped)))

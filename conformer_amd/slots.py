@@ -35,10 +35,11 @@ import numpy as np
 import torch
 
 from . import ops
+from .align import Word
 from .decode import BeamCTCDecoder
 from .model.modules.encoder import Encoder
 from .streaming import ChunkedEncoder, _refuse_window_autocast, encoder_frames
-from .transcribe import decode_frames, lstm_state, search_plan, search_stream
+from .transcribe import decode_frames, lstm_state, search_plan, search_stream, times_plan
 
 _TAIL = 8                  # mel-tail buffer width: a slot carries 0..6 un-consumed frames
 
@@ -288,12 +289,16 @@ class SlotTranscriber:
     max_pending=M (tokens; needs left_context): every slot's search commits the prefix that can no longer change after each
     of its steps (INTEGRATION.md "Committed-prefix streaming (max_pending)"); the search buffers are sized by M and the largest
     step alone and max_mel_frames may be None.  pop_committed() hands out each open slot's final tokens as they come;
-    partial_text() and close(s) then speak of the slot's text from its last pop on."""
+    partial_text() and close(s) then speak of the slot's text from its last pop on.
+    times=True: every slot's search records token timestamps, counted from the slot's own open(s) (INTEGRATION.md "Beam-search
+    timestamps"): partial_words(), close_words(s) and, with max_pending, pop_committed_words() return align.Words at
+    frame_seconds per encoder frame.  A lapped commit log raises for the slot alone, as for the tokens."""
 
     def __init__(self, model, decoder: BeamCTCDecoder, slots: int, max_mel_frames: Optional[int],
                  dtype: Optional[torch.dtype] = None, *, left_context: Optional[int] = None,
                  max_chunk_mel_frames: Optional[int] = None, max_pending: Optional[int] = None,
-                 commit_log: int = 4096) -> None:
+                 commit_log: int = 4096, times: bool = False, frame_seconds: float = 0.04) -> None:
+        tplan = times_plan("SlotTranscriber", times, frame_seconds)
         self.dtype = _slot_dtype("SlotTranscriber", dtype)
         if self.dtype is not None and left_context is not None:
             raise NotImplementedError(f"SlotTranscriber: left_context with dtype={self.dtype} (no 16-bit window kernel yet)")
@@ -303,7 +308,7 @@ class SlotTranscriber:
         self.encoder = SlotStreamingEncoder(model.encoder, slots, max_mel_frames, dtype=self.dtype, left_context=left_context,
                                             max_chunk_mel_frames=max_chunk_mel_frames)
         self.S = self.encoder.S
-        self.beam = search_stream(decoder, self.commit, self.S, self.encoder.t_max, self.device, commit_log)
+        self.beam = search_stream(decoder, self.commit, self.S, self.encoder.t_max, self.device, commit_log, tplan)
 
     @property
     def is_open(self) -> List[bool]:
@@ -357,6 +362,28 @@ class SlotTranscriber:
         """With max_pending: per open slot the token ids that became final since its previous pop, which are then forgotten
         (synchronises).  RuntimeError, with nothing popped, if a slot committed more than commit_log tokens in between."""
         return self._open_slots(self.beam.pop_committed)
+
+    def pop_committed_words(self) -> Dict[int, List[Word]]:
+        """With max_pending and times: per open slot the complete words that became final since its previous pop
+        (BeamCTCStream.pop_committed_words: the tokens after the slot's last committed delimiter are held back)."""
+        return self._open_slots(self.beam.pop_committed_words)
+
+    def partial_words(self) -> Dict[int, List[Word]]:
+        """With times: the words of partial_text(), per open slot."""
+        return self._open_slots(self.beam.partial_words)
+
+    def finish_words(self) -> Dict[int, List[Word]]:
+        """With times: close_words(s) for every open slot."""
+        return {s: self.close_words(s) for s in range(self.S) if self.encoder.is_open[s]}
+
+    def close_words(self, s: int) -> List[Word]:
+        """With times: close(s) returning the final transcript as Words; the slot becomes free all the same."""
+        s = self.encoder._check_slot(s, want_open=True)
+        try:
+            return self.beam.finish_words(only=[s])[s]
+        finally:
+            self.beam.reset_slots([s])
+            self.encoder.close(s)
 
     def discard_committed(self, s: int) -> None:
         """With max_pending: forget slot s's committed tokens that were not popped (the way out when the slot committed more

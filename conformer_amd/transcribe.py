@@ -10,12 +10,13 @@ kernels; the model must be in eval mode on the HIP device.
 """
 from __future__ import annotations
 
-from typing import Callable, List, Optional
+from typing import Callable, List, Optional, Tuple
 
 import torch
 
 from . import ops
-from .decode import BeamCTCDecoder, BeamCTCStream
+from .align import Word
+from .decode import BeamCTCDecoder, BeamCTCStream, _flag, _frame_seconds
 from .streaming import StreamingEncoder, ring_plan
 
 
@@ -54,11 +55,19 @@ def search_plan(who: str, max_mel_frames, left_context, max_chunk_mel_frames, ma
     return int(max_pending), ring_plan(left_context, max_chunk_mel_frames)[2]
 
 
-def search_stream(decoder: BeamCTCDecoder, plan, batch: int, t_max: Optional[int], device, commit_log: int) -> BeamCTCStream:
-    """The transcribers' search for a search_plan: one that ends with the encoder's t_max frames, or a committing one."""
+def times_plan(who: str, times, frame_seconds) -> Tuple[bool, float]:
+    """The transcribers' timestamp options, checked on the host before anything else."""
+    return _flag(who, "times", times), _frame_seconds(who, frame_seconds)
+
+
+def search_stream(decoder: BeamCTCDecoder, plan, batch: int, t_max: Optional[int], device, commit_log: int,
+                  times: Tuple[bool, float] = (False, 0.04)) -> BeamCTCStream:
+    """The transcribers' search for a search_plan: one that ends with the encoder's t_max frames, or a committing one.
+    times: a times_plan; (False, ...) makes the stream exactly as before."""
+    kw = dict(times=True, frame_seconds=times[1]) if times[0] else {}
     if plan is None:
-        return decoder.stream(batch, t_max, device)
-    return decoder.stream(batch, None, device, max_pending=plan[0], max_chunk_frames=plan[1], commit_log=commit_log)
+        return decoder.stream(batch, t_max, device, **kw)
+    return decoder.stream(batch, None, device, max_pending=plan[0], max_chunk_frames=plan[1], commit_log=commit_log, **kw)
 
 
 def lstm_state(model, who: str, batch: int):
@@ -85,19 +94,22 @@ class StreamingTranscriber:
     buffers; with left_context the encoder no longer allocates by it).
     max_pending=M (tokens; needs left_context): the search commits the prefix that can no longer change after every step
     (INTEGRATION.md "Committed-prefix streaming (max_pending)"), its buffers are sized by M and the largest step alone, and
-    max_mel_frames may be None: a stream without an end.  pop_committed() hands out the final tokens as they come."""
+    max_mel_frames may be None: a stream without an end.  pop_committed() hands out the final tokens as they come.
+    times=True: the search records token timestamps (INTEGRATION.md "Beam-search timestamps"): partial_words(), finish_words()
+    and, with max_pending, pop_committed_words() return align.Words at frame_seconds per encoder frame."""
 
     def __init__(self, model, decoder: BeamCTCDecoder, batch: int, max_mel_frames: Optional[int], graphs: bool = False,
                  check_weights: bool = True, *, left_context: Optional[int] = None,
                  max_chunk_mel_frames: Optional[int] = None, max_pending: Optional[int] = None,
-                 commit_log: int = 4096) -> None:
+                 commit_log: int = 4096, times: bool = False, frame_seconds: float = 0.04) -> None:
+        tplan = times_plan("StreamingTranscriber", times, frame_seconds)
         plan = search_plan("StreamingTranscriber", max_mel_frames, left_context, max_chunk_mel_frames, max_pending)
         self.B = int(batch)
         device, self.state = lstm_state(model, "StreamingTranscriber", self.B)
         self.model = model
         self.encoder = StreamingEncoder(model.encoder, batch, max_mel_frames, graphs=graphs, check_weights=check_weights,
                                         left_context=left_context, max_chunk_mel_frames=max_chunk_mel_frames)
-        self.beam = search_stream(decoder, plan, self.B, self.encoder.t_max, device, commit_log)
+        self.beam = search_stream(decoder, plan, self.B, self.encoder.t_max, device, commit_log, tplan)
 
     def reset(self) -> None:
         self.encoder.reset()
@@ -134,3 +146,16 @@ class StreamingTranscriber:
 
     def finish(self, decode_func: Optional[Callable[[str], str]] = None) -> List[str]:
         return self.beam.finish(decode_func)
+
+    def pop_committed_words(self) -> List[List[Word]]:
+        """With max_pending and times: per utterance the complete words that became final since the previous pop
+        (BeamCTCStream.pop_committed_words: the tokens after the last committed delimiter are held back)."""
+        return self.beam.pop_committed_words()
+
+    def partial_words(self) -> List[List[Word]]:
+        """With times: the words of partial_text()."""
+        return self.beam.partial_words()
+
+    def finish_words(self) -> List[List[Word]]:
+        """With times: the words of finish(), which this call is in its place."""
+        return self.beam.finish_words()

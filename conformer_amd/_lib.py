@@ -88,6 +88,16 @@ _earlier = set(SIGNATURES) | set(EXT_SIGNATURES) | set(COMMIT_SIGNATURES)
 if set(TIMES_SIGNATURES) & _earlier:
     raise ConformerHipError(f"{TIMES_HEADER_PATH} declares again: {sorted(set(TIMES_SIGNATURES) & _earlier)}")
 PARAMS.update(_times_params)
+# the staging entry of the streaming audio front end, added the same way
+STREAM_FRONTEND_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "conformer_hip_stream_frontend.h")
+if not os.path.exists(STREAM_FRONTEND_HEADER_PATH):
+    raise ConformerHipError(f"{STREAM_FRONTEND_HEADER_PATH} is missing: the ctypes binding is derived from it")
+with open(STREAM_FRONTEND_HEADER_PATH) as _f:
+    STREAM_FRONTEND_SIGNATURES, _stream_frontend_params, _ = parse_header(_f.read())
+_earlier |= set(TIMES_SIGNATURES)
+if set(STREAM_FRONTEND_SIGNATURES) & _earlier:
+    raise ConformerHipError(f"{STREAM_FRONTEND_HEADER_PATH} declares again: {sorted(set(STREAM_FRONTEND_SIGNATURES) & _earlier)}")
+PARAMS.update(_stream_frontend_params)
 
 _lib = None
 
@@ -118,7 +128,7 @@ def load() -> ctypes.CDLL:
         fn.restype = res
         fn.argtypes = args
     for header, table in ((EXT_HEADER_PATH, EXT_SIGNATURES), (COMMIT_HEADER_PATH, COMMIT_SIGNATURES),
-                          (TIMES_HEADER_PATH, TIMES_SIGNATURES)):
+                          (TIMES_HEADER_PATH, TIMES_SIGNATURES), (STREAM_FRONTEND_HEADER_PATH, STREAM_FRONTEND_SIGNATURES)):
         for name, (res, args) in table.items():
             # same ABI revision, newer entry: a library built before the extension header existed passes the check above
             fn = getattr(lib, name, None)

@@ -34,6 +34,7 @@ def _newest_dep():
     deps.append(os.path.join(ROOT, "include", "conformer_hip_window.h"))
     deps.append(os.path.join(ROOT, "include", "conformer_hip_commit.h"))
     deps.append(os.path.join(ROOT, "include", "conformer_hip_times.h"))
+    deps.append(os.path.join(ROOT, "include", "conformer_hip_stream_frontend.h"))
     return max(os.path.getmtime(d) for d in deps)
 
 

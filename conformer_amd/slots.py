@@ -38,6 +38,7 @@ from . import ops
 from .align import Word
 from .decode import BeamCTCDecoder
 from .model.modules.encoder import Encoder
+from .stream_frontend import StreamingAudioFrontend
 from .streaming import ChunkedEncoder, _refuse_window_autocast, encoder_frames
 from .transcribe import decode_frames, lstm_state, search_plan, search_stream, times_plan
 
@@ -292,13 +293,21 @@ class SlotTranscriber:
     partial_text() and close(s) then speak of the slot's text from its last pop on.
     times=True: every slot's search records token timestamps, counted from the slot's own open(s) (INTEGRATION.md "Beam-search
     timestamps"): partial_words(), close_words(s) and, with max_pending, pop_committed_words() return align.Words at
-    frame_seconds per encoder frame.  A lapped commit log raises for the slot alone, as for the tokens."""
+    frame_seconds per encoder frame.  A lapped commit log raises for the slot alone, as for the tokens.
+    audio=StreamingAudioFrontend(frontend, slots, max_chunk_samples): step_audio(samples, counts, flush=()) takes the waveform
+    instead of mel frames (INTEGRATION.md "Streaming audio front end"); open, close and reset reach the front end too."""
+
+    audio: Optional[StreamingAudioFrontend] = None
 
     def __init__(self, model, decoder: BeamCTCDecoder, slots: int, max_mel_frames: Optional[int],
                  dtype: Optional[torch.dtype] = None, *, left_context: Optional[int] = None,
                  max_chunk_mel_frames: Optional[int] = None, max_pending: Optional[int] = None,
-                 commit_log: int = 4096, times: bool = False, frame_seconds: float = 0.04) -> None:
+                 commit_log: int = 4096, times: bool = False, frame_seconds: float = 0.04,
+                 audio: Optional[StreamingAudioFrontend] = None) -> None:
         tplan = times_plan("SlotTranscriber", times, frame_seconds)
+        if audio is not None and audio.S != int(slots):
+            raise ValueError(f"SlotTranscriber: the audio front end has {audio.S} slots, the transcriber {int(slots)}")
+        self.audio = audio
         self.dtype = _slot_dtype("SlotTranscriber", dtype)
         if self.dtype is not None and left_context is not None:
             raise NotImplementedError(f"SlotTranscriber: left_context with dtype={self.dtype} (no 16-bit window kernel yet)")
@@ -323,21 +332,46 @@ class SlotTranscriber:
     def open(self, s: int) -> None:
         """Start an utterance in free slot s (enqueues only)."""
         self.encoder.open(s)
+        if self.audio is not None:
+            self._drop_audio(s)
+            self.audio.open(s)
         for h, c in self.state:
             h[s].zero_()
             c[s].zero_()
         self.beam.reset_slots([s])
+
+    def _drop_audio(self, s: int) -> None:
+        """The front end's slot s free (a flush has freed it already; a close without a flush drops its tail)."""
+        if self.audio is not None and self.audio.is_open[s]:
+            self.audio.close(s)
+
+    def _refuse_step(self) -> None:
+        if self.model.training:
+            raise RuntimeError("SlotTranscriber: the model is in training mode; put it back in eval()")
+        if self.encoder.left is not None:
+            _refuse_window_autocast("SlotTranscriber")
+        _refuse_autocast("SlotTranscriber", self.dtype)
+
+    @torch.no_grad()
+    def step_audio(self, samples: torch.Tensor, counts: Sequence[int], flush=()) -> Tuple[torch.Tensor, List[int]]:
+        """step() from the waveform (needs audio=): samples (S, N) fp32, counts: S host sample counts <= N, flush: the slots
+        whose audio ends with this step (StreamingAudioFrontend.step).  Returns what step() returns for the mel frames the
+        samples complete.  A flushed slot stays open here: close(s) reads its text.  Every refusal, the front end's or the
+        encoder's, raises before anything is enqueued."""
+        if self.audio is None:
+            raise RuntimeError("SlotTranscriber: step_audio needs the audio= front end")
+        self._refuse_step()
+        p = self.audio.plan(samples, counts, flush)
+        self.encoder.plan(p.samples.new_empty(self.S, self.audio.fe.n_mels, p.f_max), p.frames)
+        mel, frames = self.audio.run(p)
+        return self.step(mel, frames)
 
     @torch.no_grad()
     def step(self, mel_chunk: torch.Tensor, frames: Sequence[int]) -> Tuple[torch.Tensor, List[int]]:
         """mel_chunk (S, n_mel, Tc), frames: S host counts <= Tc (0 = nothing for that slot; free slots take 0).  Returns the
         logits (S, k_max, V) of the new encoder frames (slot b's in rows 0 .. k[b]-1) and k; advances each slot's search over
         its own rows.  Nothing synchronises with the host."""
-        if self.model.training:
-            raise RuntimeError("SlotTranscriber: the model is in training mode; put it back in eval()")
-        if self.encoder.left is not None:
-            _refuse_window_autocast("SlotTranscriber")
-        _refuse_autocast("SlotTranscriber", self.dtype)
+        self._refuse_step()
         n0 = list(self.encoder.n0)
         enc, ks = self.encoder.step(mel_chunk, frames)
         k_max = max(ks)
@@ -384,6 +418,7 @@ class SlotTranscriber:
         finally:
             self.beam.reset_slots([s])
             self.encoder.close(s)
+            self._drop_audio(s)
 
     def discard_committed(self, s: int) -> None:
         """With max_pending: forget slot s's committed tokens that were not popped (the way out when the slot committed more
@@ -399,7 +434,10 @@ class SlotTranscriber:
         finally:
             self.beam.reset_slots([s])
             self.encoder.close(s)
+            self._drop_audio(s)
 
     def reset(self) -> None:
         """Every slot free (their states, the search's included, are reset when they are opened again)."""
         self.encoder.reset()
+        if self.audio is not None:
+            self.audio.reset()

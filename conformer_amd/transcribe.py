@@ -17,7 +17,8 @@ import torch
 from . import ops
 from .align import Word
 from .decode import BeamCTCDecoder, BeamCTCStream, _flag, _frame_seconds
-from .streaming import StreamingEncoder, ring_plan
+from .stream_frontend import StreamingAudioFrontend
+from .streaming import StreamingEncoder, encoder_frames, ring_plan
 
 
 @torch.no_grad()
@@ -96,15 +97,27 @@ class StreamingTranscriber:
     (INTEGRATION.md "Committed-prefix streaming (max_pending)"), its buffers are sized by M and the largest step alone, and
     max_mel_frames may be None: a stream without an end.  pop_committed() hands out the final tokens as they come.
     times=True: the search records token timestamps (INTEGRATION.md "Beam-search timestamps"): partial_words(), finish_words()
-    and, with max_pending, pop_committed_words() return align.Words at frame_seconds per encoder frame."""
+    and, with max_pending, pop_committed_words() return align.Words at frame_seconds per encoder frame.
+    audio=StreamingAudioFrontend(frontend, batch, max_chunk_samples): step_audio(samples, flush=False) takes the waveform
+    instead of mel frames (INTEGRATION.md "Streaming audio front end"); the transcriber opens every slot of it, reset() again."""
+
+    audio: Optional[StreamingAudioFrontend] = None
 
     def __init__(self, model, decoder: BeamCTCDecoder, batch: int, max_mel_frames: Optional[int], graphs: bool = False,
                  check_weights: bool = True, *, left_context: Optional[int] = None,
                  max_chunk_mel_frames: Optional[int] = None, max_pending: Optional[int] = None,
-                 commit_log: int = 4096, times: bool = False, frame_seconds: float = 0.04) -> None:
+                 commit_log: int = 4096, times: bool = False, frame_seconds: float = 0.04,
+                 audio: Optional[StreamingAudioFrontend] = None) -> None:
         tplan = times_plan("StreamingTranscriber", times, frame_seconds)
         plan = search_plan("StreamingTranscriber", max_mel_frames, left_context, max_chunk_mel_frames, max_pending)
         self.B = int(batch)
+        if audio is not None:
+            if audio.S != self.B:
+                raise ValueError(f"StreamingTranscriber: the audio front end has {audio.S} slots, the batch is {self.B}")
+            audio.reset()
+            for s in range(self.B):
+                audio.open(s)
+        self.audio = audio
         device, self.state = lstm_state(model, "StreamingTranscriber", self.B)
         self.model = model
         self.encoder = StreamingEncoder(model.encoder, batch, max_mel_frames, graphs=graphs, check_weights=check_weights,
@@ -117,6 +130,29 @@ class StreamingTranscriber:
             h.zero_()
             c.zero_()
         self.beam.reset()
+        if self.audio is not None:
+            self.audio.reset()
+            for s in range(self.B):
+                self.audio.open(s)
+
+    @torch.no_grad()
+    def step_audio(self, samples: torch.Tensor, flush: bool = False) -> torch.Tensor:
+        """step() from the waveform (needs audio=): samples (B, N) fp32, the next N samples of every utterance (lockstep: N >= 0
+        for all); flush=True with the last ones, which completes the frames that reflect the end of the audio.  Returns what
+        step() returns for the mel frames the samples complete.  After a flush the text is read with finish(); reset() starts
+        the next utterances.  Every refusal raises before anything is enqueued."""
+        if self.audio is None:
+            raise RuntimeError("StreamingTranscriber: step_audio needs the audio= front end")
+        n = samples.shape[1] if isinstance(samples, torch.Tensor) and samples.dim() == 2 else 0
+        p = self.audio.plan(samples, [n] * self.B, range(self.B) if flush else ())
+        enc = self.encoder
+        if enc.left is not None and p.f_max > enc.max_chunk:
+            raise ValueError(f"StreamingTranscriber: a step of {p.f_max} mel frames, the ring was sized for "
+                             f"max_chunk_mel_frames={enc.max_chunk}")
+        if enc.t_max is not None and enc.frames + max(0, encoder_frames(enc.tail_len + p.f_max)) > enc.t_max:
+            raise RuntimeError(f"StreamingTranscriber: stream longer than max_mel_frames (T'max = {enc.t_max})")
+        mel, _ = self.audio.run(p)
+        return self.step(mel)
 
     @torch.no_grad()
     def decode_frames(self, enc: torch.Tensor) -> torch.Tensor:

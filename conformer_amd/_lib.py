@@ -98,6 +98,16 @@ _earlier |= set(TIMES_SIGNATURES)
 if set(STREAM_FRONTEND_SIGNATURES) & _earlier:
     raise ConformerHipError(f"{STREAM_FRONTEND_HEADER_PATH} declares again: {sorted(set(STREAM_FRONTEND_SIGNATURES) & _earlier)}")
 PARAMS.update(_stream_frontend_params)
+# the resampler in front of the audio front end, added the same way
+RESAMPLE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "conformer_hip_resample.h")
+if not os.path.exists(RESAMPLE_HEADER_PATH):
+    raise ConformerHipError(f"{RESAMPLE_HEADER_PATH} is missing: the ctypes binding is derived from it")
+with open(RESAMPLE_HEADER_PATH) as _f:
+    RESAMPLE_SIGNATURES, _resample_params, _ = parse_header(_f.read())
+_earlier |= set(STREAM_FRONTEND_SIGNATURES)
+if set(RESAMPLE_SIGNATURES) & _earlier:
+    raise ConformerHipError(f"{RESAMPLE_HEADER_PATH} declares again: {sorted(set(RESAMPLE_SIGNATURES) & _earlier)}")
+PARAMS.update(_resample_params)
 
 _lib = None
 
@@ -128,7 +138,8 @@ def load() -> ctypes.CDLL:
         fn.restype = res
         fn.argtypes = args
     for header, table in ((EXT_HEADER_PATH, EXT_SIGNATURES), (COMMIT_HEADER_PATH, COMMIT_SIGNATURES),
-                          (TIMES_HEADER_PATH, TIMES_SIGNATURES), (STREAM_FRONTEND_HEADER_PATH, STREAM_FRONTEND_SIGNATURES)):
+                          (TIMES_HEADER_PATH, TIMES_SIGNATURES), (STREAM_FRONTEND_HEADER_PATH, STREAM_FRONTEND_SIGNATURES),
+                          (RESAMPLE_HEADER_PATH, RESAMPLE_SIGNATURES)):
         for name, (res, args) in table.items():
             # same ABI revision, newer entry: a library built before the extension header existed passes the check above
             fn = getattr(lib, name, None)

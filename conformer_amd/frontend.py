@@ -46,6 +46,7 @@ class ConformerAudioFrontend:
             raise NotImplementedError("the gfx950 log-mel kernel is built for n_fft = win_length = 400 (processor.py:19-20)")
         self.sample_rate, self.n_fft, self.hop_length, self.n_mels = sample_rate, n_fft, hop_length, n_mels
         self.device = torch.device(device)
+        self._resamplers = {}                                                        # input rate -> Resampler (sample_rates=)
         n = torch.arange(n_fft, dtype=torch.float64)
         win = 0.5 - 0.5 * torch.cos(2 * math.pi * n / win_length)                    # periodic Hann
         k = torch.arange(n_fft // 2 + 1, dtype=torch.float64)[:, None]
@@ -101,8 +102,35 @@ class ConformerAudioFrontend:
                   self.n_fft // 2 + 1, self.n_mels, 1e-5, ops._stream())
         return out
 
-    def __call__(self, audios: Sequence[torch.Tensor], augment: Optional["ConformerAugment"] = None) -> Tuple[torch.Tensor, torch.Tensor]:
-        """processor.py:373-394: zero-pad to the longest, log-mel, lengths = samples // hop + 1."""
+    def _to_own_rate(self, audios: Sequence[torch.Tensor], sample_rates: Sequence[int]) -> List[torch.Tensor]:
+        """processor.py:139-145: every audio whose rate is not self.sample_rate, resampled on the device (rows grouped by rate,
+        one Resampler launch per rate; (L,) or (L, C), float32 or int16: INTEGRATION.md "Input sample rates")."""
+        from .resample import Resampler
+        if len(sample_rates) != len(audios):
+            raise ValueError(f"sample_rates: expected {len(audios)} rates, got {len(sample_rates)}")
+        audios = list(audios)
+        groups = {}
+        for i, (a, r) in enumerate(zip(audios, sample_rates)):
+            if int(r) != self.sample_rate or a.dtype != torch.float32 or a.dim() != 1:
+                groups.setdefault((int(r), a.dtype, tuple(a.shape[1:])), []).append(i)
+        for (rate, dtype, rest), rows in groups.items():
+            lengths = [int(audios[i].shape[0]) for i in rows]
+            batch = torch.zeros(len(rows), max(lengths), *rest, device=self.device, dtype=dtype)
+            for k, i in enumerate(rows):
+                batch[k, :lengths[k]] = audios[i].to(self.device)
+            if rate not in self._resamplers:
+                self._resamplers[rate] = Resampler(rate, self.sample_rate, device=self.device)
+            y, out = self._resamplers[rate](batch, lengths)
+            for k, i in enumerate(rows):
+                audios[i] = y[k, :out[k]]
+        return audios
+
+    def __call__(self, audios: Sequence[torch.Tensor], augment: Optional["ConformerAugment"] = None,
+                 sample_rates: Optional[Sequence[int]] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """processor.py:373-394: zero-pad to the longest, log-mel, lengths = samples // hop + 1.  sample_rates: the rate of every
+        audio; those at another rate than self.sample_rate are resampled first (the default: all at self.sample_rate)."""
+        if sample_rates is not None:
+            audios = self._to_own_rate(audios, sample_rates)
         lengths = [int(a.numel()) for a in audios]
         batch = torch.zeros(len(audios), max(lengths), device=self.device, dtype=torch.float32)
         for i, a in enumerate(audios):

@@ -354,7 +354,8 @@ class SlotTranscriber:
 
     @torch.no_grad()
     def step_audio(self, samples: torch.Tensor, counts: Sequence[int], flush=()) -> Tuple[torch.Tensor, List[int]]:
-        """step() from the waveform (needs audio=): samples (S, N) fp32, counts: S host sample counts <= N, flush: the slots
+        """step() from the waveform (needs audio=): samples (S, N) fp32 (with a front end built with input=, whatever it takes:
+        INTEGRATION.md "Input sample rates"), counts: S host sample counts <= N, flush: the slots
         whose audio ends with this step (StreamingAudioFrontend.step).  Returns what step() returns for the mel frames the
         samples complete.  A flushed slot stays open here: close(s) reads its text.  Every refusal, the front end's or the
         encoder's, raises before anything is enqueued."""

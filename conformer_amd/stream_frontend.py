@@ -16,15 +16,20 @@ copy, and cfm_stream_stage_f32 gathers every slot's segment from [tail | new sam
 reflections applied, and writes the new tails (two buffers, swapped per step).  The DFT GEMM over overlapping rows and the
 power + mel + log kernel of the offline front end follow, unchanged.  The device sees tail-relative offsets only, so a stream has
 no length limit; nothing synchronises with the host.
+
+input=Resampler(device_rate, frontend.sample_rate): the streams arrive at another rate, as float32 or int16, mono or
+interleaved (INTEGRATION.md "Input sample rates").  A StreamingResampler runs in front of the staging kernel, per slot, and
+max_chunk_samples counts input-rate samples; everything above then holds for the resampled streams.
 """
 from __future__ import annotations
 
-from typing import Iterable, List, NamedTuple, Sequence, Tuple
+from typing import Iterable, List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
 from . import _lib, ops
 from .frontend import ConformerAudioFrontend
+from .resample import Resampler, ResampleStep, StreamingResampler
 
 TAIL_LD = 512              # floats per row of a tail buffer (include/conformer_hip_stream_frontend.h)
 TABLE_COLS = 8             # int32 per slot: tail_len, n_new, lead, n_frames, flush, off, keep, new_tail_len
@@ -81,6 +86,7 @@ class StepPlan(NamedTuple):
     slots: List[FramePlan]
     frames: List[int]
     f_max: int
+    resample: Optional[ResampleStep] = None    # with input=: the resampler's checked step; `samples` is then the buffer it fills
 
 
 class StreamingAudioFrontend:
@@ -89,9 +95,12 @@ class StreamingAudioFrontend:
 
         fe.open(s); mel, frames = fe.step(samples, counts, flush=()); fe.close(s)
 
-    Slot b's new frames are mel[b, :, :frames[b]]: what SlotStreamingEncoder.step(mel, frames) takes."""
+    Slot b's new frames are mel[b, :, :frames[b]]: what SlotStreamingEncoder.step(mel, frames) takes.
+    input: a Resampler to frontend.sample_rate; step() then takes samples at its orig_rate, (S, N) or (S, N, C), float32 or
+    int16, and max_chunk_samples counts those."""
 
-    def __init__(self, frontend: ConformerAudioFrontend, slots: int, max_chunk_samples: int) -> None:
+    def __init__(self, frontend: ConformerAudioFrontend, slots: int, max_chunk_samples: int,
+                 input: Optional[Resampler] = None) -> None:
         hop, n_fft = frontend.hop_length, frontend.n_fft
         if hop % 4 or hop > n_fft:
             raise NotImplementedError(f"StreamingAudioFrontend: hop_length {hop}: the overlapping-rows DFT GEMM needs hop % 4 == 0 "
@@ -99,16 +108,28 @@ class StreamingAudioFrontend:
         if int(slots) < 1 or int(max_chunk_samples) < 1:
             raise ValueError(f"StreamingAudioFrontend: slots ({slots}) and max_chunk_samples ({max_chunk_samples}) must be >= 1")
         self.fe, self.S, self.max_chunk = frontend, int(slots), int(max_chunk_samples)
+        self.input = None
+        if input is not None:
+            if input.new_rate != frontend.sample_rate or input.device != frontend.device:
+                raise ValueError(f"StreamingAudioFrontend: input resamples to {input.new_rate} Hz on {input.device}, the front end "
+                                 f"takes {frontend.sample_rate} Hz on {frontend.device}")
+            self.input = StreamingResampler(input, slots, max_chunk_samples)
+        # the most samples at the front end's rate one step can bring (with input=: the most outputs of a resampler step)
+        self.chunk = self.max_chunk if self.input is None else self.input.out_cap
         self.hop, self.n_fft, self.pad = hop, n_fft, n_fft // 2
         self.extra = (n_fft + hop - 1) // hop                              # rows per slot behind its frames: rpu = f_max + extra
         # the most frames one step can bring: E(n + c) - E(n) <= c // hop + 1, and a flush adds L // hop - (L - pad) // hop
-        self.f_cap = self.max_chunk // hop + 1 + self.pad // hop + 1
+        self.f_cap = self.chunk // hop + 1 + self.pad // hop + 1
         dev, S = frontend.device, self.S
         self.device = dev
         self.tails = [torch.zeros(S, TAIL_LD, device=dev, dtype=torch.float32) for _ in range(2)]
         self.xp = torch.zeros(S * (self.f_cap + self.extra) * hop + n_fft, device=dev, dtype=torch.float32)
         self.spec = torch.empty(S * (self.f_cap + self.extra), frontend.basis.shape[0], device=dev, dtype=torch.float32)
-        self.table = torch.zeros(S, TABLE_COLS, device=dev, dtype=torch.int32)
+        # with input=, the resampler's table sits behind this one: one copy per step sends both
+        self.tables = torch.zeros(1 if self.input is None else 2, S, TABLE_COLS, device=dev, dtype=torch.int32)
+        self.table = self.tables[0]
+        if self.input is not None:
+            self.input.table = self.tables[1]
         self.is_open = [False] * S
         self.received = [0] * S                                            # samples per slot since open
         self.emitted = [0] * S                                             # frames per slot since open
@@ -126,17 +147,29 @@ class StreamingAudioFrontend:
         s = self._check_slot(s, want_open=False)
         self.received[s] = self.emitted[s] = 0
         self.is_open[s] = True
+        if self.input is not None:
+            self.input.open(s)
 
     def close(self, s: int) -> None:
         """Drop slot s's stream without a flush."""
-        self.is_open[self._check_slot(s, want_open=True)] = False
+        s = self._check_slot(s, want_open=True)
+        self.is_open[s] = False
+        if self.input is not None:
+            self.input.close(s)
 
     def reset(self) -> None:
         """Every slot free."""
         self.is_open = [False] * self.S
+        if self.input is not None:
+            self.input.reset()
 
     def plan(self, samples: torch.Tensor, counts: Sequence[int], flush: Iterable[int] = ()) -> StepPlan:
-        """Check a step's arguments against the slots (raises before anything is enqueued, changes nothing)."""
+        """Check a step's arguments against the slots (raises before anything is enqueued, changes nothing).  With input= the
+        resampler's checks come first, then the front end's on the resampled counts, which the host knows without the samples."""
+        flush = list(flush)
+        if self.input is not None:
+            rp = self.input.plan(samples, counts, flush)
+            return self._plan(None, self.input.out_cap, rp.out_counts, flush, rp)
         if not isinstance(samples, torch.Tensor) or samples.dim() != 2 or samples.shape[0] != self.S:
             raise ValueError(f"samples: expected a ({self.S}, N) tensor, got {tuple(getattr(samples, 'shape', ()))}")
         N = samples.shape[1]
@@ -145,6 +178,11 @@ class StreamingAudioFrontend:
         counts = [int(c) for c in counts]
         if len(counts) != self.S:
             raise ValueError(f"counts: expected {self.S} counts, got {len(counts)}")
+        return self._plan(samples, N, counts, flush, None)
+
+    def _plan(self, samples: Optional[torch.Tensor], N: int, counts: List[int], flush: Iterable[int],
+              rp: Optional[ResampleStep]) -> StepPlan:
+        """The front end's own checks: counts[b] samples at its rate for slot b, of N per row."""
         ends = [False] * self.S
         for s in flush:
             s = int(s)
@@ -167,24 +205,33 @@ class StreamingAudioFrontend:
             except ValueError as e:
                 raise ValueError(f"slot {b}: {e}") from None
         frames = [p.frames for p in slots]
-        x = ops._req(samples, "samples")                                   # (fp32 on the HIP device: there is no CPU path)
-        return StepPlan(x, counts, ends, slots, frames, max(frames))
+        if rp is not None:
+            # the buffer run() has the resampler fill (an allocation enqueues nothing)
+            x = torch.empty(self.S, N, device=self.device, dtype=torch.float32)
+        else:
+            x = ops._req(samples, "samples")                               # (fp32 on the HIP device: there is no CPU path)
+        return StepPlan(x, counts, ends, slots, frames, max(frames), rp)
 
     @torch.no_grad()
     def step(self, samples: torch.Tensor, counts: Sequence[int], flush: Iterable[int] = ()) -> Tuple[torch.Tensor, List[int]]:
-        """samples (S, N) fp32 on the device: slot b's next counts[b] samples are samples[b, :counts[b]] (the rest is ignored;
-        free slots take 0).  flush: the slots whose stream ends with this step (a count of 0 is allowed); they are closed
-        afterwards.  Returns mel (S, n_mels, f_max) and frames (host list): slot b's new frames are mel[b, :, :frames[b]], the
-        columns behind them are finite and otherwise unspecified."""
+        """samples (S, N) fp32 on the device (with input=: (S, N) or (S, N, C), float32 or int16, at the input rate): slot b's
+        next counts[b] samples are samples[b, :counts[b]] (the rest is ignored; free slots take 0).  flush: the slots whose
+        stream ends with this step (a count of 0 is allowed); they are closed afterwards.  Returns mel (S, n_mels, f_max) and
+        frames (host list): slot b's new frames are mel[b, :, :frames[b]], the columns behind them are finite and otherwise
+        unspecified."""
         return self.run(self.plan(samples, counts, flush))
 
     @torch.no_grad()
     def run(self, p: StepPlan) -> Tuple[torch.Tensor, List[int]]:
         """Enqueue a step that plan() checked (no slot may have changed in between)."""
         S, hop, n_fft, fe = self.S, self.hop, self.n_fft, self.fe
-        host = torch.empty(S, TABLE_COLS, dtype=torch.int32, pin_memory=True)      # (a fresh one: the copy below may still be pending)
-        host.numpy()[:] = [q.row(c, e) for q, c, e in zip(p.slots, p.counts, p.flush)]
-        self.table.copy_(host, non_blocking=True)
+        host = torch.empty(self.tables.shape, dtype=torch.int32, pin_memory=True)  # (a fresh one: the copy below may still be pending)
+        host.numpy()[0] = [q.row(c, e) for q, c, e in zip(p.slots, p.counts, p.flush)]
+        if p.resample is not None:
+            host.numpy()[1] = self.input.rows(p.resample)
+        self.tables.copy_(host, non_blocking=True)
+        if p.resample is not None:
+            self.input.run(p.resample, out=p.samples, table_sent=True)
         x, f_max = p.samples, p.f_max
         stream = ops._stream()
         _lib.call("cfm_stream_stage_f32", x.data_ptr() if x.shape[1] else None, x.shape[1], x.shape[1],

@@ -138,12 +138,13 @@ class StreamingTranscriber:
     @torch.no_grad()
     def step_audio(self, samples: torch.Tensor, flush: bool = False) -> torch.Tensor:
         """step() from the waveform (needs audio=): samples (B, N) fp32, the next N samples of every utterance (lockstep: N >= 0
-        for all); flush=True with the last ones, which completes the frames that reflect the end of the audio.  Returns what
-        step() returns for the mel frames the samples complete.  After a flush the text is read with finish(); reset() starts
-        the next utterances.  Every refusal raises before anything is enqueued."""
+        for all; with a front end built with input=, whatever it takes: INTEGRATION.md "Input sample rates"); flush=True with
+        the last ones, which completes the frames that reflect the end of the audio.  Returns what step() returns for the mel
+        frames the samples complete.  After a flush the text is read with finish(); reset() starts the next utterances.  Every
+        refusal raises before anything is enqueued."""
         if self.audio is None:
             raise RuntimeError("StreamingTranscriber: step_audio needs the audio= front end")
-        n = samples.shape[1] if isinstance(samples, torch.Tensor) and samples.dim() == 2 else 0
+        n = samples.shape[1] if isinstance(samples, torch.Tensor) and samples.dim() in (2, 3) else 0
         p = self.audio.plan(samples, [n] * self.B, range(self.B) if flush else ())
         enc = self.encoder
         if enc.left is not None and p.f_max > enc.max_chunk:

@@ -153,3 +153,15 @@ template <> struct Lowp<_Float16> {
         return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
     }
 };
+
+// ---- diagnostics (host only): the block tile of the last launch of each GEMM family, so that a test can assert which kernel
+// it reached.  Written by the launchers, read and cleared by cfm_debug_gemm_last_tile (gemm_f32.hip).  One record per host
+// thread: it shows the launches of the calling thread.  ksplits: the K slices launched (gridDim.y).
+//   forward:  0 = gemm_f32.hip, 1 = gemm_mfma16.hip, 2 = gemm_split.hip.  form: the 16-bit kernel's operand form (src16: 0 fp32
+//             A and W, 1 16-bit W, 2 16-bit A and W) or the split kernel's plane count.
+//   backward: 3 = gemm_bwd_f32.hip launch_one, 4 = gemm_bwd_mfma16_impl.h launch_one, 5 = gemm_dw16_impl.h launch_dw16.
+//             form of 3 and 4: AROW | BROW << 1 | (EPI == BEPI_DSWISH) << 2 | aligned << 3 | B16 << 4 | GATHER << 5 (aligned: the
+//             16-bit kernel's ALIGNED instantiation; 0 in family 3); form of 5: A16 | B16 << 1 | gather << 2.
+constexpr int kGemmFamilies = 6;
+struct GemmTileRecord { int bm, bn, waves, ksplits, form, c16; };
+GemmTileRecord& gemm_last_tile(int family);

@@ -232,6 +232,7 @@ int launch_one(BwdArgs g, hipStream_t s) {
     const int64_t per = (g.Kc + splits - 1) / splits;
     g.k_per_split = (per + 15) / 16 * 16;
     const dim3 grid(tiles, (unsigned)splits, (unsigned)g.nbatch);
+    gemm_last_tile(3) = {BM, BN, 4, (int)grid.y, (int)AROW | (int)BROW << 1 | (EPI == BEPI_DSWISH) << 2 | GATHER << 5, 0};
     if constexpr (kCanSplit) {
         if (splits > 1) {
             hipLaunchKernelGGL((gemm_bwd_kernel<BM, BN, AROW, BROW, EPI, GATHER, true>), grid, dim3(256), 0, s, g);

@@ -460,6 +460,8 @@ int launch_one(BwdArgs g, hipStream_t s) {
     // backward's (T x T4) / (T x P4) tensors), so their partial 16-byte chunks may be loaded whole
     const bool aligned = ((AROW ? (g.Kc & 3) == 0 : (g.I & 3) == 0) || g.pad4) &&
                          ((BROW ? (g.Kc & 3) == 0 : (g.J & (B16 ? 7 : 3)) == 0) || (g.pad4 && !B16));
+    gemm_last_tile(4) = {BM, BN, 4, (int)grid.y,
+                         (int)AROW | (int)BROW << 1 | (EPI == BEPI_DSWISH) << 2 | (int)aligned << 3 | (int)B16 << 4 | GATHER << 5, g.c16 != 0};
     if constexpr (kCanSplit) {
         if (splits > 1) {
             if (aligned) hipLaunchKernelGGL((gemm_bwd_mfma16_kernel<T16, BM, BN, AROW, BROW, EPI, GATHER, true, B16, true>), grid, dim3(256), 0, s, g);

@@ -315,6 +315,7 @@ int launch_dw16(DwArgs g, int a16, int b16, hipStream_t s) {
     const int64_t span_a = (g.k_per_split + 64) * g.lda * (a16 ? 2 : 4), span_b = g.rowtab ? 0 : (g.k_per_split + 64) * g.ldb * (b16 ? 2 : 4);
     if (span_a >= (int64_t)1 << 31 || span_b >= (int64_t)1 << 31) return CFM_ERR_UNSUPPORTED;
     const dim3 grid(tiles, (unsigned)((g.Kc + g.k_per_split - 1) / g.k_per_split));
+    gemm_last_tile(5) ={128, 128, 4, (int)grid.y, (a16 != 0) | (b16 != 0) << 1 | (g.rowtab != nullptr) << 2, 0};
 #define DW(A_, B_) hipLaunchKernelGGL((gemm_dw16_kernel<T16, A_, B_>), grid, dim3(256), 0, s, g)
     if (g.rowtab) {
         if (!b16) return CFM_ERR_UNSUPPORTED;

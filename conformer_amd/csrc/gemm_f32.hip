@@ -740,15 +740,16 @@ extern "C" int cfm_debug_set_conv2_bk(int bk) {
 }
 
 GemmTileRecord& gemm_last_tile(int family) {
-    static thread_local GemmTileRecord rec[3];              // per host thread: launches on other threads neither race nor show
+    static thread_local GemmTileRecord rec[kGemmFamilies];  // per host thread: launches on other threads neither race nor show
     return rec[family];
 }
 
 // diagnostics (tests): out[0..5] = {BM, BN, waves, K slices, operand form, 16-bit C} of the last launch of GEMM family 0 (fp32),
-// 1 (16-bit) or 2 (split-plane) made by the calling thread since the previous call (all zero if none); the record is cleared.
+// 1 (16-bit), 2 (split-plane), 3 (backward fp32), 4 (backward 16-bit) or 5 (16-bit weight gradient) -- see GemmTileRecord in
+// cfm_common.h -- made by the calling thread since the previous call (all zero if none); the record is cleared.
 extern "C" int cfm_debug_gemm_last_tile(int family, int* out) {
     CFM_REQUIRE(out != nullptr, CFM_ERR_NULL);
-    CFM_REQUIRE(family >= 0 && family <= 2, CFM_ERR_BAD_SHAPE);
+    CFM_REQUIRE(family >= 0 && family < kGemmFamilies, CFM_ERR_BAD_SHAPE);
     GemmTileRecord& r = gemm_last_tile(family);
     out[0] = r.bm; out[1] = r.bn; out[2] = r.waves; out[3] = r.ksplits; out[4] = r.form; out[5] = r.c16;
     r = GemmTileRecord{};

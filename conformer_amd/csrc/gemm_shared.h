@@ -550,10 +550,3 @@ __device__ __forceinline__ void gemm_epilogue_rows(const GemmArgs& g, const f32x
 }
 
 }  // namespace
-
-// ---- diagnostics (host only): the block tile of the last launch of each forward GEMM family, so that a test can assert which
-// kernel it reached.  Family 0 = gemm_f32.hip, 1 = gemm_mfma16.hip, 2 = gemm_split.hip; written by their launchers, read and
-// cleared by cfm_debug_gemm_last_tile.  form: the 16-bit kernel's operand form (src16: 0 fp32 A and W, 1 16-bit W, 2 16-bit A
-// and W) or the split kernel's plane count.  One record per host thread: it shows the launches of the calling thread.
-struct GemmTileRecord { int bm, bn, waves, ksplits, form, c16; };
-GemmTileRecord& gemm_last_tile(int family);

@@ -452,9 +452,12 @@ int cfm_debug_dw16_trace(void* trace_or_null);            /* 2 x 64 stamps of cf
 int cfm_debug_lstm_trace(void* trace_or_null);            /* T x 2 x 8 stamps of cfm_lstm_fwd_f32's steps */
 int cfm_debug_gemm_mfma16_force_tile(int tile);           /* tuning: 0 auto, 1 4-wave tiles by shape, 2 256x128, 3 256x256 (16-bit W, else by shape), 4 128x64 (bias / residual), 5 64x64 */
 int cfm_debug_gemm_mfma16_trace(void* trace_or_null);     /* per-K-tile stamps of two workgroups of cfm_gemm_mfma16_f32 */
-/* diagnostics: out[0..5] = {BM, BN, waves, K slices, operand form, 16-bit C} of the last launch of forward GEMM family 0 (fp32),
- * 1 (16-bit; form = 0 fp32 A and W, 1 16-bit W, 2 16-bit A and W) or 2 (split-plane; form = planes) made by the calling host
- * thread; all zero if none since the previous call, which the call clears */
+/* diagnostics: out[0..5] = {BM, BN, waves, K slices launched, operand form, 16-bit C} of the last launch of GEMM family
+ *   0 forward fp32, 1 forward 16-bit (form = 0 fp32 A and W, 1 16-bit W, 2 16-bit A and W), 2 split-plane (form = planes),
+ *   3 cfm_gemm_bwd*_f32, 4 cfm_gemm_bwd_batched_mfma16_f32 (form = a index-major | b index-major << 1 | swish' << 2 |
+ *   aligned instantiation << 3 (16-bit only) | 16-bit B << 4 | stem gather << 5), 5 cfm_linear_bwd_weight_mfma16_f32 and the
+ *   stem's h16 weight gradient (form = 16-bit dy | 16-bit x << 1 | gather << 2)
+ * made by the calling host thread; all zero if none since the previous call, which the call clears */
 int cfm_debug_gemm_last_tile(int family, int* out);
 
 /* ---- tuning / diagnostics: the residual-epilogue GEMM with a forced block-tile shape

@@ -24,7 +24,8 @@ from tests.util import Calls as _Calls, rel_l2  # noqa: E402
 pytestmark = pytest.mark.gpu
 TOL = 2e-5                   # fp32 kernels
 TOL_ATOMIC = 5e-5            # fp32 kernels whose reductions are split over workgroups (atomics / split-K)
-TOL16 = {1: 1e-2, 2: 4e-3}   # PREC_BF16 / PREC_FP16 against a reference on operands rounded to the 16-bit type
+TOL16 = {1: 1e-2, 2: 4e-3}   # PREC_BF16 / PREC_FP16 where a kernel rounds INTERMEDIATES to the 16-bit type (LSTM, stem); the
+                             # linear_bwd products round their operands only: TOL / TOL_ATOMIC against the rounded operands
 DT16 = {1: torch.bfloat16, 2: torch.float16}
 SET = dict(deadline=None, derandomize=True, suppress_health_check=[HealthCheck.function_scoped_fixture, HealthCheck.too_slow])
 
@@ -147,7 +148,10 @@ def _run_linear_bwd(ops, prec, x, w, dy, z, f):
 
 
 def _linear_bwd_ref(ops, prec, x, w, dy, z, f):
+    """(dx, dw, db) in float64.  The products take their operands rounded to the 16-bit type; db sums dY AS STORED (fp32 unless the
+    caller stored it in the 16-bit type): neither cfm_colsum_f32 nor the fused weight-gradient kernel rounds what it sums."""
     xr, wr, dyr = r16(x, prec), r16(w, prec), r16(dy, prec)
+    dy_stored = dyr if f["dy16"] else dy.double()
     z = None if z is None else z[:, :x.shape[1]]
     a = f["alpha"]
     dx = None
@@ -157,25 +161,38 @@ def _linear_bwd_ref(ops, prec, x, w, dy, z, f):
             dx = dx * dswish(z.double())
             if f["drop_p"] > 0:
                 dx = dx * ops.dropout_apply(torch.ones(z.shape, device="cuda"), f["drop_p"], f["drop_seed"]).double().cpu()
-    return dx, a * dyr.t() @ xr, a * dyr.sum(0)
+    return dx, a * dyr.t() @ xr, a * dy_stored.sum(0)
+
+
+def _assert_linear_bwd(ops, prec, x, w, dy, z, f, got, want16):
+    """dx (fp32) to TOL, dw and db (atomics) to TOL_ATOMIC, under every precision mode; a 16-bit dx is, bit for bit, the fp32 dx
+    of the same call with dx16=False cast to the type ("identical results"), and that fp32 dx is held to TOL."""
+    dx, dw, db = got
+    rdx, rdw, rdb = _linear_bwd_ref(ops, prec, x, w, dy, z, f)
+    if f["need_dx"]:
+        assert dx.dtype == (DT16[prec] if want16 else torch.float32), (dx.dtype, f)
+        assert dx.shape == x.shape
+        if want16:
+            dx32 = _run_linear_bwd(ops, prec, x, w, dy, z, dict(f, dx16=False))[0]
+            assert dx32.dtype == torch.float32
+            assert torch.equal(dx, dx32.to(DT16[prec])), ("dx16 is not the fp32 dx rounded", f)
+            dx = dx32
+        e = rel_l2(dx, rdx)
+        assert e < TOL, ("dx", e, f)
+    else:
+        assert dx is None
+    assert dw.dtype == torch.float32 and db.dtype == torch.float32
+    ew, eb = rel_l2(dw, rdw), rel_l2(db, rdb)
+    assert ew < TOL_ATOMIC, ("dw", ew, f)
+    assert eb < TOL_ATOMIC, ("db", eb, f)
 
 
 def _check_linear_bwd(ops, M, N, K, prec, data):
     x, w, dy, z, f = _linear_bwd_case(ops, M, N, K, prec, data)
-    dx, dw, db = _run_linear_bwd(ops, prec, x, w, dy, z, f)
-    rdx, rdw, rdb = _linear_bwd_ref(ops, prec, x, w, dy, z, f)
-    tx, tw = (TOL, TOL_ATOMIC) if not prec else (TOL16[prec], TOL16[prec])
-    if f["need_dx"]:
-        # dx16 is honoured exactly where the 16-bit consumer can take it (the swish' routes with n, k % 8 == 0)
-        want16 = bool(prec and f["dx16"] and z is not None and N % 8 == 0 and K % 8 == 0)
-        assert dx.dtype == (DT16[prec] if want16 else torch.float32), (dx.dtype, f)
-        assert dx.shape == (M, K)
-        assert rel_l2(dx, rdx) < tx, ("dx", f)
-    else:
-        assert dx is None
-    assert dw.dtype == torch.float32 and db.dtype == torch.float32
-    assert rel_l2(dw, rdw) < tw, ("dw", f)
-    assert rel_l2(db, rdb) < tw, ("db", f)
+    got = _run_linear_bwd(ops, prec, x, w, dy, z, f)
+    # dx16 is honoured exactly where the 16-bit consumer can take it (the swish' routes with n, k % 8 == 0)
+    want16 = bool(prec and f["dx16"] and z is not None and N % 8 == 0 and K % 8 == 0)
+    _assert_linear_bwd(ops, prec, x, w, dy, z, f, got, want16)
 
 
 @settings(max_examples=30, **SET)
@@ -232,15 +249,9 @@ def test_linear_bwd_16bit_route_pinned(ops, route, prec, M, n8, k8, r, seed):
     x, w, dy = rnd(M, K, seed=seed), rnd(N, K, seed=seed + 1) / math.sqrt(K), rnd(M, N, seed=seed + 2)
     z = None if f["use_z"] is None else rnd(M, K + (4 if f["use_z"] == "strided" else 0), seed=seed + 3)
     with _Calls(_GEMM16, _GEMM16_BWD, _DW16) as seen:
-        dx, dw, db = _run_linear_bwd(ops, prec, x, w, dy, z, f)
+        got = _run_linear_bwd(ops, prec, x, w, dy, z, f)
     assert must <= seen and not (must_not & seen), (route, sorted(seen))
-    rdx, rdw, rdb = _linear_bwd_ref(ops, prec, x, w, dy, z, f)
-    if f["need_dx"]:
-        assert dx.dtype == (DT16[prec] if want16 else torch.float32)
-        assert rel_l2(dx, rdx) < TOL16[prec], route
-    else:
-        assert dx is None
-    assert rel_l2(dw, rdw) < TOL16[prec] and rel_l2(db, rdb) < TOL16[prec], route
+    _assert_linear_bwd(ops, prec, x, w, dy, z, f, got, bool(want16))
 
 
 @pytest.mark.parametrize("M,N,K,prec", [(1, 8, 4, 1), (37, 16, 12, 2), (300, 40, 36, 1)])
@@ -249,9 +260,7 @@ def test_linear_bwd_16bit_x_with_k_off_8(ops, M, N, K, prec):
     (found by the sweep above at M = 1, N = 8, K = 4: the kernel refused the 16-bit B operand)."""
     x, w, dy = rnd(M, K, seed=M), rnd(N, K, seed=N) / math.sqrt(K), rnd(M, N, seed=K)
     f = dict(alpha=1.0, need_dx=True, drop_p=0.0, x16=True, dy16=False, dx16=False, use_z=None, drop_seed=0)
-    dx, dw, db = _run_linear_bwd(ops, prec, x, w, dy, None, f)
-    rdx, rdw, rdb = _linear_bwd_ref(ops, prec, x, w, dy, None, f)
-    assert rel_l2(dx, rdx) < TOL16[prec] and rel_l2(dw, rdw) < TOL16[prec] and rel_l2(db, rdb) < TOL16[prec]
+    _assert_linear_bwd(ops, prec, x, w, dy, None, f, _run_linear_bwd(ops, prec, x, w, dy, None, f), False)
 
 
 def test_linear_bwd_refuses_mismatched_16bit_x(ops):

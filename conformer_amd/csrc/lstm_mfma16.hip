@@ -237,7 +237,12 @@ __global__ __launch_bounds__(512) void lstm_bwd_step16_kernel(const Lstm16BwdArg
     const float di = dct * gg * ig * (1.0f - ig), df = dct * cprev * fg * (1.0f - fg);
     const float dgg = dct * ig * (1.0f - gg * gg), dog = dh * th * og * (1.0f - og);
     dg[0] = di; dg[H] = df; dg[2 * H] = dgg; dg[3 * H] = dog;
-    dg_cur[gidx[0]] = (T16)di; dg_cur[gidx[1]] = (T16)df; dg_cur[gidx[2]] = (T16)dgg; dg_cur[gidx[3]] = (T16)dog;
+    // the 16-bit copies are rounded from the fp32 values just stored (kept opaque, as the forward keeps its h: fp16 would otherwise
+    // fold the last multiply of each into one fma_mix, a single rounding of the exact product, and step t-1 would contract a dG_t
+    // that is an fp16 ulp away from the rounding of the dG_t the caller gets -- rarely, and by up to 1e-5 of a gradient)
+    float e0 = di, e1 = df, e2 = dgg, e3 = dog;
+    asm volatile("" : "+v"(e0), "+v"(e1), "+v"(e2), "+v"(e3));
+    dg_cur[gidx[0]] = (T16)e0; dg_cur[gidx[1]] = (T16)e1; dg_cur[gidx[2]] = (T16)e2; dg_cur[gidx[3]] = (T16)e3;
     a.dc[(int64_t)b * H + unit] = dct * fg;
 }
 

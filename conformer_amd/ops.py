@@ -1458,32 +1458,41 @@ def swish_bn_eval(h, bn_mean, bn_var, bn_weight, bn_bias, eps: float = 1e-5):
     return out
 
 
-def lstm_backward(x, w_ih, w_hh, y, gates, cells, dy, lengths=None, need_dx: bool = True):
-    """Backward of lstm_forward(save=True): returns (dx or None, dw_ih, dw_hh, dbias) with dbias = d/d(b_ih) = d/d(b_hh).
-    The time recursion yields dG (B,T,4H); the weight / input gradients are dense GEMMs over all frames."""
-    B, T, D = x.shape
-    H = w_hh.shape[1]
+def lstm_bptt(w_hh, gates, cells, dy, lengths=None):
+    """The time recursion of lstm_backward: from the forward's saved gates (B,T,4H) and cells (B,T,H) and dy (B,T,H) to
+    (dG (B,T,4H), dc (B,H)): the gradient of the pre-activations of every frame and of the initial cell state."""
+    B, T, H = cells.shape
     dy = _req(dy, "dy")
-    dG = torch.empty(B, T, 4 * H, device=x.device, dtype=torch.float32)
-    dc = torch.empty(B, H, device=x.device, dtype=torch.float32)
+    dG = torch.empty(B, T, 4 * H, device=dy.device, dtype=torch.float32)
+    dc = torch.empty(B, H, device=dy.device, dtype=torch.float32)
     prec = mfma16_prec()
     wt16 = weight16(w_hh, prec, transposed=True) if prec and H % 16 == 0 else None
     if wt16 is not None:
         # W_hh^T (H,4H) in MFMA fragment order (H/16, 4H/16, 2, 16, 8); dG_t exchanged between steps in the same order
         wt16 = wt16.view(H // 16, 16, 4 * H // 16, 2, 8).permute(0, 2, 3, 1, 4).contiguous()
-        dg16 = torch.empty(2 * ((B + 15) // 16) * 16 * 4 * H, device=x.device, dtype=_DT16[prec])
+        dg16 = torch.empty(2 * ((B + 15) // 16) * 16 * 4 * H, device=dy.device, dtype=_DT16[prec])
         _lib.call("cfm_lstm_bwd_mfma16_f32", prec, dy.data_ptr(), gates.data_ptr(), cells.data_ptr(), wt16.data_ptr(), _p(lengths),
                   dG.data_ptr(), dc.data_ptr(), dg16.data_ptr(), B, T, H, _stream())
     elif H % 16 == 0:
         # fp32: W_hh^T (H,4H) -> (H/16, 4H/16, kq 4, unit 16, 4); dG_t exchanged between steps in the same order
         wtf = w_hh.t().reshape(H // 16, 16, 4 * H // 16, 4, 4).permute(0, 2, 3, 1, 4).contiguous()
-        dgf = torch.empty(2 * ((B + 15) // 16) * 16 * 4 * H, device=x.device, dtype=torch.float32)
+        dgf = torch.empty(2 * ((B + 15) // 16) * 16 * 4 * H, device=dy.device, dtype=torch.float32)
         _lib.call("cfm_lstm_bwd_frag_f32", dy.data_ptr(), gates.data_ptr(), cells.data_ptr(), wtf.data_ptr(), _p(lengths),
                   dG.data_ptr(), dc.data_ptr(), dgf.data_ptr(), B, T, H, _stream())
     else:
         whh_t = w_hh.t().contiguous()                                 # (H,4H): 6.5 MB of glue per step
         _lib.call("cfm_lstm_bwd_f32", dy.data_ptr(), gates.data_ptr(), cells.data_ptr(), whh_t.data_ptr(), _p(lengths),
                   dG.data_ptr(), dc.data_ptr(), B, T, H, _stream())
+    return dG, dc
+
+
+def lstm_backward(x, w_ih, w_hh, y, gates, cells, dy, lengths=None, need_dx: bool = True):
+    """Backward of lstm_forward(save=True): returns (dx or None, dw_ih, dw_hh, dbias) with dbias = d/d(b_ih) = d/d(b_hh).
+    The time recursion yields dG (B,T,4H); the weight / input gradients are dense GEMMs over all frames."""
+    B, T, D = x.shape
+    H = w_hh.shape[1]
+    prec = mfma16_prec()
+    dG, _ = lstm_bptt(w_hh, gates, cells, dy, lengths)
     dG2, x2 = dG.view(B * T, 4 * H), x.reshape(B * T, D)
     h_prev = torch.zeros(y.shape, device=y.device, dtype=torch.float32)                                      # h_{t-1}: y shifted by one frame per utterance
     h_prev[:, 1:] = y[:, :-1]

@@ -471,7 +471,9 @@ LSTM_BWD = {"row": "cfm_lstm_bwd_f32", "frag": "cfm_lstm_bwd_frag_f32", "bf16": 
 @example(B=48, T=20, d4=2, kind="fp16", hk=2, seed=5).via("16-bit BPTT under fp16, three 16-utterance tiles")
 def test_lstm_bptt_any_geometry(ops, B, T, d4, kind, hk, seed):
     """B across the 16- and 32-utterance tiles, ragged descending lengths with 1 and repeats; every gradient against
-    autograd through oracle.lstm_layer, y exactly zero beyond each length; the BPTT kernel that ran is asserted."""
+    autograd through oracle.lstm_layer, y exactly zero beyond each length; the BPTT kernel that ran is asserted.  The 1e-2
+    free-run bound of the 16-bit kinds is the end-to-end check; the kernels are held per element, one step at a time, in
+    test_lstm_step_gpu.py."""
     from conformer_amd.autograd import LstmFn
     H = 4 * (hk + (hk % 4 == 0)) if kind == "row" else 16 * ((hk - 1) % 6 + 1)        # row: H % 16 != 0
     prec = {"row": 0, "frag": 0, "bf16": 1, "fp16": 2}[kind]

@@ -108,6 +108,16 @@ _earlier |= set(STREAM_FRONTEND_SIGNATURES)
 if set(RESAMPLE_SIGNATURES) & _earlier:
     raise ConformerHipError(f"{RESAMPLE_HEADER_PATH} declares again: {sorted(set(RESAMPLE_SIGNATURES) & _earlier)}")
 PARAMS.update(_resample_params)
+# endpointing on the blank posterior, added the same way
+ENDPOINT_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "conformer_hip_endpoint.h")
+if not os.path.exists(ENDPOINT_HEADER_PATH):
+    raise ConformerHipError(f"{ENDPOINT_HEADER_PATH} is missing: the ctypes binding is derived from it")
+with open(ENDPOINT_HEADER_PATH) as _f:
+    ENDPOINT_SIGNATURES, _endpoint_params, _ = parse_header(_f.read())
+_earlier |= set(RESAMPLE_SIGNATURES)
+if set(ENDPOINT_SIGNATURES) & _earlier:
+    raise ConformerHipError(f"{ENDPOINT_HEADER_PATH} declares again: {sorted(set(ENDPOINT_SIGNATURES) & _earlier)}")
+PARAMS.update(_endpoint_params)
 
 _lib = None
 
@@ -139,7 +149,7 @@ def load() -> ctypes.CDLL:
         fn.argtypes = args
     for header, table in ((EXT_HEADER_PATH, EXT_SIGNATURES), (COMMIT_HEADER_PATH, COMMIT_SIGNATURES),
                           (TIMES_HEADER_PATH, TIMES_SIGNATURES), (STREAM_FRONTEND_HEADER_PATH, STREAM_FRONTEND_SIGNATURES),
-                          (RESAMPLE_HEADER_PATH, RESAMPLE_SIGNATURES)):
+                          (RESAMPLE_HEADER_PATH, RESAMPLE_SIGNATURES), (ENDPOINT_HEADER_PATH, ENDPOINT_SIGNATURES)):
         for name, (res, args) in table.items():
             # same ABI revision, newer entry: a library built before the extension header existed passes the check above
             fn = getattr(lib, name, None)

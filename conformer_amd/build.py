@@ -36,6 +36,7 @@ def _newest_dep():
     deps.append(os.path.join(ROOT, "include", "conformer_hip_times.h"))
     deps.append(os.path.join(ROOT, "include", "conformer_hip_stream_frontend.h"))
     deps.append(os.path.join(ROOT, "include", "conformer_hip_resample.h"))
+    deps.append(os.path.join(ROOT, "include", "conformer_hip_endpoint.h"))
     return max(os.path.getmtime(d) for d in deps)
 
 

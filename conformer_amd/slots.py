@@ -37,6 +37,7 @@ import torch
 from . import ops
 from .align import Word
 from .decode import BeamCTCDecoder
+from .endpoint import Endpoint, EndpointConfig, StreamingEndpointer
 from .model.modules.encoder import Encoder
 from .stream_frontend import StreamingAudioFrontend
 from .streaming import ChunkedEncoder, _refuse_window_autocast, encoder_frames
@@ -295,16 +296,28 @@ class SlotTranscriber:
     timestamps"): partial_words(), close_words(s) and, with max_pending, pop_committed_words() return align.Words at
     frame_seconds per encoder frame.  A lapped commit log raises for the slot alone, as for the tokens.
     audio=StreamingAudioFrontend(frontend, slots, max_chunk_samples): step_audio(samples, counts, flush=()) takes the waveform
-    instead of mel frames (INTEGRATION.md "Streaming audio front end"); open, close and reset reach the front end too."""
+    instead of mel frames (INTEGRATION.md "Streaming audio front end"); open, close and reset reach the front end too.
+    endpoint=EndpointConfig(...): every step also runs the endpoint rules on the logits it returns (INTEGRATION.md "Endpointing":
+    one more launch, nothing synchronises); open(s) arms slot s, endpoints() reads which open slots' utterances have ended.
+    Closing or segmenting an ended slot stays the caller's decision.  Without it nothing is launched or allocated.
+    segment(s) / segment_words(s): the text of slot s so far, as close(s) returns it, and the slot goes on OPEN with a new search
+    (and a re-armed endpointer) over the same stream: K/V caches, depthwise state, LSTM state and audio tail stay as they are.
+    Every time the object reports for s (words, endpoints) still counts from open(s)."""
 
     audio: Optional[StreamingAudioFrontend] = None
+    endpointer: Optional[StreamingEndpointer] = None
+    seg_start: Optional[List[int]] = None          # per slot the encoder frame at which its current segment began
 
     def __init__(self, model, decoder: BeamCTCDecoder, slots: int, max_mel_frames: Optional[int],
                  dtype: Optional[torch.dtype] = None, *, left_context: Optional[int] = None,
                  max_chunk_mel_frames: Optional[int] = None, max_pending: Optional[int] = None,
                  commit_log: int = 4096, times: bool = False, frame_seconds: float = 0.04,
-                 audio: Optional[StreamingAudioFrontend] = None) -> None:
+                 audio: Optional[StreamingAudioFrontend] = None, endpoint: Optional[EndpointConfig] = None) -> None:
         tplan = times_plan("SlotTranscriber", times, frame_seconds)
+        if endpoint is not None:
+            if not isinstance(endpoint, EndpointConfig):
+                raise ValueError(f"SlotTranscriber: endpoint must be an EndpointConfig, got {type(endpoint).__name__}")
+            endpoint.check(tplan[1])
         if audio is not None and audio.S != int(slots):
             raise ValueError(f"SlotTranscriber: the audio front end has {audio.S} slots, the transcriber {int(slots)}")
         self.audio = audio
@@ -318,6 +331,10 @@ class SlotTranscriber:
                                             max_chunk_mel_frames=max_chunk_mel_frames)
         self.S = self.encoder.S
         self.beam = search_stream(decoder, self.commit, self.S, self.encoder.t_max, self.device, commit_log, tplan)
+        self.frame_seconds = tplan[1]
+        self.seg_start = [0] * self.S
+        if endpoint is not None:
+            self.endpointer = StreamingEndpointer(self.S, decoder.blank_id, endpoint, tplan[1], self.device)
 
     @property
     def is_open(self) -> List[bool]:
@@ -339,6 +356,14 @@ class SlotTranscriber:
             h[s].zero_()
             c[s].zero_()
         self.beam.reset_slots([s])
+        self._new_segment(s, 0)
+
+    def _new_segment(self, s: int, first_frame: int) -> None:
+        """Slot s's segment begins at encoder frame first_frame of its stream: the endpointer armed again (enqueues only)."""
+        if self.seg_start is not None:
+            self.seg_start[s] = first_frame
+        if self.endpointer is not None:
+            self.endpointer.reset_slots([s])
 
     def _drop_audio(self, s: int) -> None:
         """The front end's slot s free (a flush has freed it already; a close without a flush drops its tail)."""
@@ -382,12 +407,58 @@ class SlotTranscriber:
         with _autocast(self.dtype):
             logits = decode_frames(self.model, self.state, enc, k_dev)
         # the search's bound: the furthest slot after this step, less the chunk (each slot's own frames_b + k_b <= T_max
-        # holds: the encoder refused more than max_mel_frames)
+        # holds: the encoder refused more than max_mel_frames).  After a segment() a slot's search is BEHIND its encoder
+        # position n0, so both forms below stay bounds on what the search consumed and the real limits only get looser.
         t_used = max(a + b for a, b in zip(n0, ks)) - k_max
         if self.commit:                    # after a commit a slot's tree holds at most min(max_pending, its frames) frames
             t_used = min(self.commit[0], max(n0))
         self.beam.step(logits, k_dev, t_used=t_used)
+        if self.endpointer is not None:
+            self.endpointer.step(logits, k_dev)
         return logits, ks
+
+    def endpoints(self) -> Dict[int, Endpoint]:
+        """With endpoint=: the open slots whose utterance (since open(s) or the last segment(s)) has ended, each with the rule
+        that fired and when; `frame` and `seconds` count from open(s).  Synchronises, as partial_text does."""
+        if self.endpointer is None:
+            raise RuntimeError("SlotTranscriber.endpoints: the object was made without endpoint=, no rule was evaluated")
+        out = {}
+        for s, e in self._open_slots(self.endpointer.read).items():
+            if e is not None:
+                f = e.frame + self.seg_start[s]
+                out[s] = Endpoint(e.rule, f, (f + 1) * self.frame_seconds, e.trailing_frames)
+        return out
+
+    def _shift(self, s: int, words: List[Word]) -> List[Word]:
+        """Words of slot s's current segment on the clock of open(s)."""
+        off = self.seg_start[s] if self.seg_start is not None else 0
+        if not off:
+            return words
+        sec = off * self.frame_seconds
+        return [Word(w.text, w.start_frame + off, w.end_frame + off, w.start + sec, w.end + sec, w.score) for w in words]
+
+    def _shift_all(self, words: Dict[int, List[Word]]) -> Dict[int, List[Word]]:
+        return {s: self._shift(s, w) for s, w in words.items()}
+
+    def segment(self, s: int, decode_func: Optional[Callable[[str], str]] = None) -> str:
+        """End slot s's utterance but not its stream: returns what close(s) would, then the slot goes on, open, with a new
+        search and a re-armed endpointer; encoder caches, LSTM state and audio front end stay as they are.  With max_pending the
+        text is from the last pop on, and a lapped commit log raises for s alone (the new segment begun all the same)."""
+        s = self.encoder._check_slot(s, want_open=True)
+        try:
+            return self.beam.finish(decode_func, only=[s])[s]
+        finally:
+            self.beam.reset_slots([s])
+            self._new_segment(s, self.encoder.n0[s])
+
+    def segment_words(self, s: int) -> List[Word]:
+        """With times: segment(s) returning the segment's transcript as Words (times counted from open(s))."""
+        s = self.encoder._check_slot(s, want_open=True)
+        try:
+            return self._shift(s, self.beam.finish_words(only=[s])[s])
+        finally:
+            self.beam.reset_slots([s])
+            self._new_segment(s, self.encoder.n0[s])
 
     def partial_text(self) -> Dict[int, str]:
         """The interim best transcript of every open slot (the one step-side call that synchronises)."""
@@ -401,11 +472,11 @@ class SlotTranscriber:
     def pop_committed_words(self) -> Dict[int, List[Word]]:
         """With max_pending and times: per open slot the complete words that became final since its previous pop
         (BeamCTCStream.pop_committed_words: the tokens after the slot's last committed delimiter are held back)."""
-        return self._open_slots(self.beam.pop_committed_words)
+        return self._shift_all(self._open_slots(self.beam.pop_committed_words))
 
     def partial_words(self) -> Dict[int, List[Word]]:
         """With times: the words of partial_text(), per open slot."""
-        return self._open_slots(self.beam.partial_words)
+        return self._shift_all(self._open_slots(self.beam.partial_words))
 
     def finish_words(self) -> Dict[int, List[Word]]:
         """With times: close_words(s) for every open slot."""
@@ -415,7 +486,7 @@ class SlotTranscriber:
         """With times: close(s) returning the final transcript as Words; the slot becomes free all the same."""
         s = self.encoder._check_slot(s, want_open=True)
         try:
-            return self.beam.finish_words(only=[s])[s]
+            return self._shift(s, self.beam.finish_words(only=[s])[s])
         finally:
             self.beam.reset_slots([s])
             self.encoder.close(s)

@@ -118,6 +118,16 @@ _earlier |= set(RESAMPLE_SIGNATURES)
 if set(ENDPOINT_SIGNATURES) & _earlier:
     raise ConformerHipError(f"{ENDPOINT_HEADER_PATH} declares again: {sorted(set(ENDPOINT_SIGNATURES) & _earlier)}")
 PARAMS.update(_endpoint_params)
+# error counts (WER / CER / token error rate) on the device, added the same way
+ERROR_RATE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "conformer_hip_error_rate.h")
+if not os.path.exists(ERROR_RATE_HEADER_PATH):
+    raise ConformerHipError(f"{ERROR_RATE_HEADER_PATH} is missing: the ctypes binding is derived from it")
+with open(ERROR_RATE_HEADER_PATH) as _f:
+    ERROR_RATE_SIGNATURES, _error_rate_params, _ = parse_header(_f.read())
+_earlier |= set(ENDPOINT_SIGNATURES)
+if set(ERROR_RATE_SIGNATURES) & _earlier:
+    raise ConformerHipError(f"{ERROR_RATE_HEADER_PATH} declares again: {sorted(set(ERROR_RATE_SIGNATURES) & _earlier)}")
+PARAMS.update(_error_rate_params)
 
 _lib = None
 
@@ -149,7 +159,8 @@ def load() -> ctypes.CDLL:
         fn.argtypes = args
     for header, table in ((EXT_HEADER_PATH, EXT_SIGNATURES), (COMMIT_HEADER_PATH, COMMIT_SIGNATURES),
                           (TIMES_HEADER_PATH, TIMES_SIGNATURES), (STREAM_FRONTEND_HEADER_PATH, STREAM_FRONTEND_SIGNATURES),
-                          (RESAMPLE_HEADER_PATH, RESAMPLE_SIGNATURES), (ENDPOINT_HEADER_PATH, ENDPOINT_SIGNATURES)):
+                          (RESAMPLE_HEADER_PATH, RESAMPLE_SIGNATURES), (ENDPOINT_HEADER_PATH, ENDPOINT_SIGNATURES),
+                          (ERROR_RATE_HEADER_PATH, ERROR_RATE_SIGNATURES)):
         for name, (res, args) in table.items():
             # same ABI revision, newer entry: a library built before the extension header existed passes the check above
             fn = getattr(lib, name, None)

@@ -1,6 +1,7 @@
 """Surface of the reference's evaluation.py: ConformerCriterion (CTC loss, evaluation.py:8-16) on the gfx950 lattice
 kernels, ConformerMetric (WER / CER, evaluation.py:18-27) as a plain host-side edit distance (the reference delegates to
-torchmetrics' WordErrorRate / CharErrorRate: total edit distance / total reference length over the batch)."""
+torchmetrics' WordErrorRate / CharErrorRate: total edit distance / total reference length over the batch).  wer_tokens /
+cer_tokens take token ids on the device instead of strings and score them there (conformer_amd.error_rate)."""
 from __future__ import annotations
 
 from typing import List, Sequence, Union
@@ -51,3 +52,16 @@ class ConformerMetric:
 
     def cer_score(self, prediction: Union[str, List[str]], target: Union[str, List[str]]) -> torch.Tensor:
         return _error_rate(prediction, target, list)
+
+    def wer_tokens(self, hyp_tokens: torch.Tensor, hyp_counts: torch.Tensor, ref_tokens: torch.Tensor,
+                   ref_counts: torch.Tensor, tables) -> torch.Tensor:
+        """wer_score of the texts these token rows spell, computed on the device from the ids (error_rate.error_counts takes the
+        same arguments; `tables` is an error_rate.ErrorRateTables).  A 0-dim float64 device tensor; nothing synchronises."""
+        from .error_rate import rate_tokens
+        return rate_tokens(hyp_tokens, hyp_counts, ref_tokens, ref_counts, tables, "word")
+
+    def cer_tokens(self, hyp_tokens: torch.Tensor, hyp_counts: torch.Tensor, ref_tokens: torch.Tensor,
+                   ref_counts: torch.Tensor, tables) -> torch.Tensor:
+        """cer_score of the texts these token rows spell, computed on the device from the ids, as wer_tokens."""
+        from .error_rate import rate_tokens
+        return rate_tokens(hyp_tokens, hyp_counts, ref_tokens, ref_counts, tables, "char")

@@ -128,6 +128,16 @@ _earlier |= set(ENDPOINT_SIGNATURES)
 if set(ERROR_RATE_SIGNATURES) & _earlier:
     raise ConformerHipError(f"{ERROR_RATE_HEADER_PATH} declares again: {sorted(set(ERROR_RATE_SIGNATURES) & _earlier)}")
 PARAMS.update(_error_rate_params)
+# token and word confidence from the frame posteriors, added the same way (its defines name the methods and aggregations)
+CONFIDENCE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "conformer_hip_confidence.h")
+if not os.path.exists(CONFIDENCE_HEADER_PATH):
+    raise ConformerHipError(f"{CONFIDENCE_HEADER_PATH} is missing: the ctypes binding is derived from it")
+with open(CONFIDENCE_HEADER_PATH) as _f:
+    CONFIDENCE_SIGNATURES, _confidence_params, CONFIDENCE_CONSTANTS = parse_header(_f.read())
+_earlier |= set(ERROR_RATE_SIGNATURES)
+if set(CONFIDENCE_SIGNATURES) & _earlier:
+    raise ConformerHipError(f"{CONFIDENCE_HEADER_PATH} declares again: {sorted(set(CONFIDENCE_SIGNATURES) & _earlier)}")
+PARAMS.update(_confidence_params)
 
 _lib = None
 
@@ -160,7 +170,7 @@ def load() -> ctypes.CDLL:
     for header, table in ((EXT_HEADER_PATH, EXT_SIGNATURES), (COMMIT_HEADER_PATH, COMMIT_SIGNATURES),
                           (TIMES_HEADER_PATH, TIMES_SIGNATURES), (STREAM_FRONTEND_HEADER_PATH, STREAM_FRONTEND_SIGNATURES),
                           (RESAMPLE_HEADER_PATH, RESAMPLE_SIGNATURES), (ENDPOINT_HEADER_PATH, ENDPOINT_SIGNATURES),
-                          (ERROR_RATE_HEADER_PATH, ERROR_RATE_SIGNATURES)):
+                          (ERROR_RATE_HEADER_PATH, ERROR_RATE_SIGNATURES), (CONFIDENCE_HEADER_PATH, CONFIDENCE_SIGNATURES)):
         for name, (res, args) in table.items():
             # same ABI revision, newer entry: a library built before the extension header existed passes the check above
             fn = getattr(lib, name, None)

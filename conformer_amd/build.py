@@ -38,6 +38,7 @@ def _newest_dep():
     deps.append(os.path.join(ROOT, "include", "conformer_hip_resample.h"))
     deps.append(os.path.join(ROOT, "include", "conformer_hip_endpoint.h"))
     deps.append(os.path.join(ROOT, "include", "conformer_hip_error_rate.h"))
+    deps.append(os.path.join(ROOT, "include", "conformer_hip_confidence.h"))
     return max(os.path.getmtime(d) for d in deps)
 
 

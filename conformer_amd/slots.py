@@ -36,6 +36,7 @@ import torch
 
 from . import ops
 from .align import Word
+from .confidence import ConfidenceConfig, StreamingConfidence, transcriber_confidence
 from .decode import BeamCTCDecoder
 from .endpoint import Endpoint, EndpointConfig, StreamingEndpointer
 from .model.modules.encoder import Encoder
@@ -302,18 +303,25 @@ class SlotTranscriber:
     Closing or segmenting an ended slot stays the caller's decision.  Without it nothing is launched or allocated.
     segment(s) / segment_words(s): the text of slot s so far, as close(s) returns it, and the slot goes on OPEN with a new search
     (and a re-armed endpointer) over the same stream: K/V caches, depthwise state, LSTM state and audio tail stay as they are.
-    Every time the object reports for s (words, endpoints) still counts from open(s)."""
+    Every time the object reports for s (words, endpoints) still counts from open(s).
+    confidence=ConfidenceConfig(...) (needs times=True): every step also keeps the frame confidence of the logits it returns,
+    for each slot's last confidence_history frames counted from open(s) (INTEGRATION.md "Confidence": two more launches, nothing
+    synchronises); word_confidence(words) gives the Words this object returned their confidence.  Without it nothing is
+    launched or allocated."""
 
     audio: Optional[StreamingAudioFrontend] = None
     endpointer: Optional[StreamingEndpointer] = None
+    confidence: Optional[StreamingConfidence] = None
     seg_start: Optional[List[int]] = None          # per slot the encoder frame at which its current segment began
 
     def __init__(self, model, decoder: BeamCTCDecoder, slots: int, max_mel_frames: Optional[int],
                  dtype: Optional[torch.dtype] = None, *, left_context: Optional[int] = None,
                  max_chunk_mel_frames: Optional[int] = None, max_pending: Optional[int] = None,
                  commit_log: int = 4096, times: bool = False, frame_seconds: float = 0.04,
-                 audio: Optional[StreamingAudioFrontend] = None, endpoint: Optional[EndpointConfig] = None) -> None:
+                 audio: Optional[StreamingAudioFrontend] = None, endpoint: Optional[EndpointConfig] = None,
+                 confidence: Optional[ConfidenceConfig] = None, confidence_history: int = 4096) -> None:
         tplan = times_plan("SlotTranscriber", times, frame_seconds)
+        cplan = transcriber_confidence("SlotTranscriber", confidence, confidence_history, tplan[0])
         if endpoint is not None:
             if not isinstance(endpoint, EndpointConfig):
                 raise ValueError(f"SlotTranscriber: endpoint must be an EndpointConfig, got {type(endpoint).__name__}")
@@ -335,6 +343,8 @@ class SlotTranscriber:
         self.seg_start = [0] * self.S
         if endpoint is not None:
             self.endpointer = StreamingEndpointer(self.S, decoder.blank_id, endpoint, tplan[1], self.device)
+        if cplan is not None:
+            self.confidence = StreamingConfidence(self.S, decoder.blank_id, cplan[0], cplan[1], self.device)
 
     @property
     def is_open(self) -> List[bool]:
@@ -357,6 +367,8 @@ class SlotTranscriber:
             c[s].zero_()
         self.beam.reset_slots([s])
         self._new_segment(s, 0)
+        if self.confidence is not None:                                    # (a segment does not: its words count from open(s))
+            self.confidence.reset_slots([s])
 
     def _new_segment(self, s: int, first_frame: int) -> None:
         """Slot s's segment begins at encoder frame first_frame of its stream: the endpointer armed again (enqueues only)."""
@@ -415,7 +427,22 @@ class SlotTranscriber:
         self.beam.step(logits, k_dev, t_used=t_used)
         if self.endpointer is not None:
             self.endpointer.step(logits, k_dev)
+        if self.confidence is not None:
+            self.confidence.step(logits, k_dev)
         return logits, ks
+
+    def word_confidence(self, words: Dict[int, List[Word]]) -> Dict[int, List[float]]:
+        """With confidence=: the confidence of Words this object returned ({slot: its words}, as partial_words, finish_words
+        and pop_committed_words give them, or {s: close_words(s)}), each over its frames [start_frame, end_frame) counted from
+        open(s); nan for a word whose start has left the slot's confidence_history.  A closed slot's history stays until it
+        is opened again.  Synchronises."""
+        if self.confidence is None:
+            raise RuntimeError("SlotTranscriber.word_confidence: the object was made without confidence=, no frame was scored")
+        bad = [s for s in words if not 0 <= int(s) < self.S]
+        if bad:
+            raise ValueError(f"slots {bad} outside [0, {self.S})")
+        out = self.confidence.words([list(words.get(s, ())) for s in range(self.S)])
+        return {s: out[s] for s in words}
 
     def endpoints(self) -> Dict[int, Endpoint]:
         """With endpoint=: the open slots whose utterance (since open(s) or the last segment(s)) has ended, each with the rule
@@ -513,3 +540,5 @@ class SlotTranscriber:
         self.encoder.reset()
         if self.audio is not None:
             self.audio.reset()
+        if self.confidence is not None:
+            self.confidence.reset()

@@ -16,6 +16,7 @@ import torch
 
 from . import ops
 from .align import Word
+from .confidence import ConfidenceConfig, StreamingConfidence, transcriber_confidence
 from .decode import BeamCTCDecoder, BeamCTCStream, _flag, _frame_seconds
 from .stream_frontend import StreamingAudioFrontend
 from .streaming import StreamingEncoder, encoder_frames, ring_plan
@@ -99,16 +100,22 @@ class StreamingTranscriber:
     times=True: the search records token timestamps (INTEGRATION.md "Beam-search timestamps"): partial_words(), finish_words()
     and, with max_pending, pop_committed_words() return align.Words at frame_seconds per encoder frame.
     audio=StreamingAudioFrontend(frontend, batch, max_chunk_samples): step_audio(samples, flush=False) takes the waveform
-    instead of mel frames (INTEGRATION.md "Streaming audio front end"); the transcriber opens every slot of it, reset() again."""
+    instead of mel frames (INTEGRATION.md "Streaming audio front end"); the transcriber opens every slot of it, reset() again.
+    confidence=ConfidenceConfig(...) (needs times=True): every step also keeps the frame confidence of the logits it returns, for
+    the last confidence_history frames (INTEGRATION.md "Confidence"); word_confidence(words) gives the Words this object
+    returned their confidence.  Without it nothing is launched or allocated."""
 
     audio: Optional[StreamingAudioFrontend] = None
+    confidence: Optional[StreamingConfidence] = None
 
     def __init__(self, model, decoder: BeamCTCDecoder, batch: int, max_mel_frames: Optional[int], graphs: bool = False,
                  check_weights: bool = True, *, left_context: Optional[int] = None,
                  max_chunk_mel_frames: Optional[int] = None, max_pending: Optional[int] = None,
                  commit_log: int = 4096, times: bool = False, frame_seconds: float = 0.04,
-                 audio: Optional[StreamingAudioFrontend] = None) -> None:
+                 audio: Optional[StreamingAudioFrontend] = None, confidence: Optional[ConfidenceConfig] = None,
+                 confidence_history: int = 4096) -> None:
         tplan = times_plan("StreamingTranscriber", times, frame_seconds)
+        cplan = transcriber_confidence("StreamingTranscriber", confidence, confidence_history, tplan[0])
         plan = search_plan("StreamingTranscriber", max_mel_frames, left_context, max_chunk_mel_frames, max_pending)
         self.B = int(batch)
         if audio is not None:
@@ -123,9 +130,13 @@ class StreamingTranscriber:
         self.encoder = StreamingEncoder(model.encoder, batch, max_mel_frames, graphs=graphs, check_weights=check_weights,
                                         left_context=left_context, max_chunk_mel_frames=max_chunk_mel_frames)
         self.beam = search_stream(decoder, plan, self.B, self.encoder.t_max, device, commit_log, tplan)
+        if cplan is not None:
+            self.confidence = StreamingConfidence(self.B, decoder.blank_id, cplan[0], cplan[1], device)
 
     def reset(self) -> None:
         self.encoder.reset()
+        if self.confidence is not None:
+            self.confidence.reset()
         for h, c in self.state:
             h.zero_()
             c.zero_()
@@ -169,7 +180,18 @@ class StreamingTranscriber:
             return enc.new_empty(self.B, 0, self.model.decoder.linear.out_features)
         logits = self.decode_frames(enc)
         self.beam.step(logits)
+        if self.confidence is not None:
+            self.confidence.step(logits)
         return logits
+
+    def word_confidence(self, words: List[List[Word]]) -> List[List[float]]:
+        """With confidence=: per utterance the confidence of Words this object returned (partial_words, finish_words,
+        pop_committed_words), each over its frames [start_frame, end_frame); nan for a word whose start has left
+        confidence_history.  Synchronises."""
+        if self.confidence is None:
+            raise RuntimeError("StreamingTranscriber.word_confidence: the object was made without confidence=, no frame was "
+                               "scored")
+        return self.confidence.words(words)
 
     def partial_text(self) -> List[str]:
         return self.beam.partial_text()

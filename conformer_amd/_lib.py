@@ -1,23 +1,36 @@
-"""ctypes binding of libconformer_hip.so, derived from the one statement of its C ABI: include/conformer_hip.h.
+"""ctypes binding of libconformer_hip.so, derived from the one statement of its C ABI: include/conformer_hip.h and the extension
+headers listed in EXTENSION_HEADERS.
 
-The header is parsed once at import (no torch needed): SIGNATURES and PARAMS from its declarations, CONSTANTS from its `#define
-CFM_*` lines and `enum cfm_status`.  A type the parser does not know, or a `cfm_*(` it cannot read, is an error, never a guess.
-There is NO fallback: a missing header or library, or a non-zero status, raises.  Nothing here imports the CPU oracle.
+Every header is parsed once at import (no torch needed) into HEADERS; ENTRIES and PARAMS span all of them, SIGNATURES and
+CONSTANTS are the main header's declarations and its `#define CFM_*` lines and `enum cfm_status`.  A type the parser does not
+know, or a `cfm_*(` it cannot read, is an error, never a guess.  There is NO fallback: a missing header or library, or a
+non-zero status, raises.  Nothing here imports the CPU oracle.
 """
 from __future__ import annotations
 
 import ctypes
 import os
 import re
+from typing import NamedTuple
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # (CONFORMER_AMD_LIB: A/B a differently built library from tools/*, development only)
 LIB_PATH = os.environ.get("CONFORMER_AMD_LIB") or os.path.join(_HERE, "lib", "libconformer_hip.so")
-HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "conformer_hip.h")
-# entries added to the library without touching the main header (no existing signature moves, so the ABI revision stays)
-EXT_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "conformer_hip_window.h")
-# the committed-prefix streaming search, added the same way (its own table: EXT_SIGNATURES stays the window header's)
-COMMIT_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "conformer_hip_commit.h")
+_INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
+MAIN_HEADER = "conformer_hip.h"             # ABI_VERSION and enum cfm_status come from this one
+HEADER_PATH = os.path.join(_INCLUDE, MAIN_HEADER)
+# entry families added to the library without touching the main header (no existing signature moves, so the ABI revision
+# stays), in the order they were added.  A new family is its header under include/, its .hip file and one line here.
+EXTENSION_HEADERS = (
+    "conformer_hip_window.h",               # bounded-history attention over ring K/V caches
+    "conformer_hip_commit.h",               # the committed-prefix streaming search
+    "conformer_hip_times.h",                # token timestamps from the resumable beam search
+    "conformer_hip_stream_frontend.h",      # the staging entry of the streaming audio front end
+    "conformer_hip_resample.h",             # the resampler in front of the audio front end
+    "conformer_hip_endpoint.h",             # endpointing on the blank posterior
+    "conformer_hip_error_rate.h",           # error counts (WER / CER / token error rate)
+    "conformer_hip_confidence.h",           # token and word confidence (its defines name the methods and aggregations)
+)
 _CTYPES = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "float": ctypes.c_float, "double": ctypes.c_double,
            "uint64_t": ctypes.c_uint64, "size_t": ctypes.c_size_t, "cfm_stream_t": ctypes.c_void_p}
 _DECL = re.compile(r"^[ \t]*((?:const\s+)?\w+[\s*]+?)(cfm_\w+)\s*\(([^()]*)\)\s*;", re.M)
@@ -58,86 +71,41 @@ def parse_header(text: str):
     return signatures, params, {k: int(v) for k, v in constants}
 
 
-if not os.path.exists(HEADER_PATH):
-    raise ConformerHipError(f"{HEADER_PATH} is missing: the ctypes binding is derived from it")
-with open(HEADER_PATH) as _f:
-    SIGNATURES, PARAMS, CONSTANTS = parse_header(_f.read())
+class Header(NamedTuple):
+    """one header of include/: its path and what `parse_header` read from it"""
+    path: str
+    signatures: dict
+    params: dict
+    constants: dict
+
+
+def read_header(path: str, earlier=()) -> Header:
+    """Parse the header at `path`; a name it shares with `earlier` (the entries of the headers read before it) is an error."""
+    if not os.path.exists(path):
+        raise ConformerHipError(f"{path} is missing: the ctypes binding is derived from it")
+    with open(path) as f:
+        header = Header(path, *parse_header(f.read()))
+    if set(header.signatures) & set(earlier):
+        raise ConformerHipError(f"{path} declares again: {sorted(set(header.signatures) & set(earlier))}")
+    return header
+
+
+HEADERS: dict = {}        # basename -> Header, the main header first; an extension header's own defines stay with its record
+ENTRIES: dict = {}        # name -> (restype, [argtypes]) over all headers: what `load` binds
+PARAMS: dict = {}         # name -> [parameter names] over all headers (`call` names a parameter of any of them)
+for _name in (MAIN_HEADER, *EXTENSION_HEADERS):
+    HEADERS[_name] = read_header(os.path.join(_INCLUDE, _name), ENTRIES)
+    ENTRIES.update(HEADERS[_name].signatures)
+    PARAMS.update(HEADERS[_name].params)
+SIGNATURES = HEADERS[MAIN_HEADER].signatures      # the main header's entries
+CONSTANTS = HEADERS[MAIN_HEADER].constants        # ... and its defines and status codes
 ABI_VERSION = CONSTANTS["CFM_ABI_VERSION"]        # checked in load()
-if not os.path.exists(EXT_HEADER_PATH):
-    raise ConformerHipError(f"{EXT_HEADER_PATH} is missing: the ctypes binding is derived from it")
-with open(EXT_HEADER_PATH) as _f:
-    EXT_SIGNATURES, _ext_params, _ = parse_header(_f.read())
-if set(EXT_SIGNATURES) & set(SIGNATURES):
-    raise ConformerHipError(f"{EXT_HEADER_PATH} declares again: {sorted(set(EXT_SIGNATURES) & set(SIGNATURES))}")
-PARAMS.update(_ext_params)                        # (`call` names a parameter of either header)
-if not os.path.exists(COMMIT_HEADER_PATH):
-    raise ConformerHipError(f"{COMMIT_HEADER_PATH} is missing: the ctypes binding is derived from it")
-with open(COMMIT_HEADER_PATH) as _f:
-    COMMIT_SIGNATURES, _commit_params, _ = parse_header(_f.read())
-if set(COMMIT_SIGNATURES) & (set(SIGNATURES) | set(EXT_SIGNATURES)):
-    raise ConformerHipError(f"{COMMIT_HEADER_PATH} declares again: "
-                            f"{sorted(set(COMMIT_SIGNATURES) & (set(SIGNATURES) | set(EXT_SIGNATURES)))}")
-PARAMS.update(_commit_params)
-# token timestamps from the resumable beam search, added the same way
-TIMES_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "conformer_hip_times.h")
-if not os.path.exists(TIMES_HEADER_PATH):
-    raise ConformerHipError(f"{TIMES_HEADER_PATH} is missing: the ctypes binding is derived from it")
-with open(TIMES_HEADER_PATH) as _f:
-    TIMES_SIGNATURES, _times_params, _ = parse_header(_f.read())
-_earlier = set(SIGNATURES) | set(EXT_SIGNATURES) | set(COMMIT_SIGNATURES)
-if set(TIMES_SIGNATURES) & _earlier:
-    raise ConformerHipError(f"{TIMES_HEADER_PATH} declares again: {sorted(set(TIMES_SIGNATURES) & _earlier)}")
-PARAMS.update(_times_params)
-# the staging entry of the streaming audio front end, added the same way
-STREAM_FRONTEND_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "conformer_hip_stream_frontend.h")
-if not os.path.exists(STREAM_FRONTEND_HEADER_PATH):
-    raise ConformerHipError(f"{STREAM_FRONTEND_HEADER_PATH} is missing: the ctypes binding is derived from it")
-with open(STREAM_FRONTEND_HEADER_PATH) as _f:
-    STREAM_FRONTEND_SIGNATURES, _stream_frontend_params, _ = parse_header(_f.read())
-_earlier |= set(TIMES_SIGNATURES)
-if set(STREAM_FRONTEND_SIGNATURES) & _earlier:
-    raise ConformerHipError(f"{STREAM_FRONTEND_HEADER_PATH} declares again: {sorted(set(STREAM_FRONTEND_SIGNATURES) & _earlier)}")
-PARAMS.update(_stream_frontend_params)
-# the resampler in front of the audio front end, added the same way
-RESAMPLE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "conformer_hip_resample.h")
-if not os.path.exists(RESAMPLE_HEADER_PATH):
-    raise ConformerHipError(f"{RESAMPLE_HEADER_PATH} is missing: the ctypes binding is derived from it")
-with open(RESAMPLE_HEADER_PATH) as _f:
-    RESAMPLE_SIGNATURES, _resample_params, _ = parse_header(_f.read())
-_earlier |= set(STREAM_FRONTEND_SIGNATURES)
-if set(RESAMPLE_SIGNATURES) & _earlier:
-    raise ConformerHipError(f"{RESAMPLE_HEADER_PATH} declares again: {sorted(set(RESAMPLE_SIGNATURES) & _earlier)}")
-PARAMS.update(_resample_params)
-# endpointing on the blank posterior, added the same way
-ENDPOINT_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "conformer_hip_endpoint.h")
-if not os.path.exists(ENDPOINT_HEADER_PATH):
-    raise ConformerHipError(f"{ENDPOINT_HEADER_PATH} is missing: the ctypes binding is derived from it")
-with open(ENDPOINT_HEADER_PATH) as _f:
-    ENDPOINT_SIGNATURES, _endpoint_params, _ = parse_header(_f.read())
-_earlier |= set(RESAMPLE_SIGNATURES)
-if set(ENDPOINT_SIGNATURES) & _earlier:
-    raise ConformerHipError(f"{ENDPOINT_HEADER_PATH} declares again: {sorted(set(ENDPOINT_SIGNATURES) & _earlier)}")
-PARAMS.update(_endpoint_params)
-# error counts (WER / CER / token error rate) on the device, added the same way
-ERROR_RATE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "conformer_hip_error_rate.h")
-if not os.path.exists(ERROR_RATE_HEADER_PATH):
-    raise ConformerHipError(f"{ERROR_RATE_HEADER_PATH} is missing: the ctypes binding is derived from it")
-with open(ERROR_RATE_HEADER_PATH) as _f:
-    ERROR_RATE_SIGNATURES, _error_rate_params, _ = parse_header(_f.read())
-_earlier |= set(ENDPOINT_SIGNATURES)
-if set(ERROR_RATE_SIGNATURES) & _earlier:
-    raise ConformerHipError(f"{ERROR_RATE_HEADER_PATH} declares again: {sorted(set(ERROR_RATE_SIGNATURES) & _earlier)}")
-PARAMS.update(_error_rate_params)
-# token and word confidence from the frame posteriors, added the same way (its defines name the methods and aggregations)
-CONFIDENCE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "conformer_hip_confidence.h")
-if not os.path.exists(CONFIDENCE_HEADER_PATH):
-    raise ConformerHipError(f"{CONFIDENCE_HEADER_PATH} is missing: the ctypes binding is derived from it")
-with open(CONFIDENCE_HEADER_PATH) as _f:
-    CONFIDENCE_SIGNATURES, _confidence_params, CONFIDENCE_CONSTANTS = parse_header(_f.read())
-_earlier |= set(ERROR_RATE_SIGNATURES)
-if set(CONFIDENCE_SIGNATURES) & _earlier:
-    raise ConformerHipError(f"{CONFIDENCE_HEADER_PATH} declares again: {sorted(set(CONFIDENCE_SIGNATURES) & _earlier)}")
-PARAMS.update(_confidence_params)
+
+
+def header_of(name: str) -> str:
+    """basename of the header that declares the entry `name`"""
+    return next(basename for basename, header in HEADERS.items() if name in header.signatures)
+
 
 _lib = None
 
@@ -163,19 +131,12 @@ def load() -> ctypes.CDLL:
     if got != ABI_VERSION:
         raise ConformerHipError(f"{LIB_PATH} implements C-ABI revision {got}, this binding needs {ABI_VERSION}: rebuild it with "
                                 "`python -m conformer_amd.build`")
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    for header, table in ((EXT_HEADER_PATH, EXT_SIGNATURES), (COMMIT_HEADER_PATH, COMMIT_SIGNATURES),
-                          (TIMES_HEADER_PATH, TIMES_SIGNATURES), (STREAM_FRONTEND_HEADER_PATH, STREAM_FRONTEND_SIGNATURES),
-                          (RESAMPLE_HEADER_PATH, RESAMPLE_SIGNATURES), (ENDPOINT_HEADER_PATH, ENDPOINT_SIGNATURES),
-                          (ERROR_RATE_HEADER_PATH, ERROR_RATE_SIGNATURES), (CONFIDENCE_HEADER_PATH, CONFIDENCE_SIGNATURES)):
-        for name, (res, args) in table.items():
-            # same ABI revision, newer entry: a library built before the extension header existed passes the check above
+    for basename, header in HEADERS.items():
+        for name, (res, args) in header.signatures.items():
+            # same ABI revision, newer entry: a library built before an extension header existed passes the check above
             fn = getattr(lib, name, None)
             if fn is None:
-                raise ConformerHipError(f"{LIB_PATH} lacks {name} (include/{os.path.basename(header)}): rebuild it with "
+                raise ConformerHipError(f"{LIB_PATH} lacks {name} (include/{basename}): rebuild it with "
                                         "`python -m conformer_amd.build`")
             fn.restype = res
             fn.argtypes = args

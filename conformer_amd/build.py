@@ -17,6 +17,7 @@ from concurrent.futures import ThreadPoolExecutor
 PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
+INCLUDE = os.path.join(ROOT, "include")
 OBJ = os.path.join(ROOT, "build", "obj")
 LIB = os.path.join(PKG, "lib", "libconformer_hip.so")
 ARCH = "gfx950"
@@ -28,23 +29,23 @@ def sources():
     return sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hip"))
 
 
+def dependencies():
+    """every header a source file may include: a change to any of them recompiles everything"""
+    return sorted(os.path.join(d, f) for d in (CSRC, INCLUDE) for f in os.listdir(d) if f.endswith(".h"))
+
+
 def _newest_dep():
-    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
-    deps.append(os.path.join(ROOT, "include", "conformer_hip.h"))
-    deps.append(os.path.join(ROOT, "include", "conformer_hip_window.h"))
-    deps.append(os.path.join(ROOT, "include", "conformer_hip_commit.h"))
-    deps.append(os.path.join(ROOT, "include", "conformer_hip_times.h"))
-    deps.append(os.path.join(ROOT, "include", "conformer_hip_stream_frontend.h"))
-    deps.append(os.path.join(ROOT, "include", "conformer_hip_resample.h"))
-    deps.append(os.path.join(ROOT, "include", "conformer_hip_endpoint.h"))
-    deps.append(os.path.join(ROOT, "include", "conformer_hip_error_rate.h"))
-    deps.append(os.path.join(ROOT, "include", "conformer_hip_confidence.h"))
-    return max(os.path.getmtime(d) for d in deps)
+    return max(os.path.getmtime(d) for d in dependencies())
 
 
-def _compile(src: str, force: bool) -> str:
+def _jobs(n_sources: int) -> int:
+    """compile processes at a time: MAX_JOBS where it is set (os.cpu_count() reports the whole machine, not this job's share)"""
+    return max(1, min(int(os.environ.get("MAX_JOBS") or min(os.cpu_count() or 4, 16)), n_sources))
+
+
+def _compile(src: str, force: bool, newest_dep: float) -> str:
     obj = os.path.join(OBJ, os.path.basename(src)[:-4] + ".o")
-    if not force and os.path.exists(obj) and os.path.getmtime(obj) > max(os.path.getmtime(src), _newest_dep()):
+    if not force and os.path.exists(obj) and os.path.getmtime(obj) > max(os.path.getmtime(src), newest_dep):
         return obj
     cmd = [HIPCC, *CFLAGS, "-c", src, "-o", obj]
     r = subprocess.run(cmd, capture_output=True, text=True)
@@ -59,12 +60,11 @@ def build_library(force: bool = False, verbose: bool = True) -> str:
     os.makedirs(OBJ, exist_ok=True)
     os.makedirs(os.path.dirname(LIB), exist_ok=True)
     srcs = sources()
-    with ThreadPoolExecutor(max_workers=min(os.cpu_count() or 4, len(srcs))) as ex:
-        objs = list(ex.map(lambda s: _compile(s, force), srcs))
+    newest_dep = _newest_dep()
+    with ThreadPoolExecutor(max_workers=_jobs(len(srcs))) as ex:
+        objs = list(ex.map(lambda s: _compile(s, force, newest_dep), srcs))
     if force or not os.path.exists(LIB) or any(os.path.getmtime(o) > os.path.getmtime(LIB) for o in objs):
-        cmd = [HIPCC, "-shared", "-fPIC", f"--offload-arch={ARCH}", "-fno-gpu-rdc", "--no-hip-rt" if False else "",
-               "-o", LIB, *objs]
-        cmd = [c for c in cmd if c]
+        cmd = [HIPCC, "-shared", "-fPIC", f"--offload-arch={ARCH}", "-fno-gpu-rdc", "-o", LIB, *objs]
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError(f"link failed:\n{r.stderr}")

@@ -22,7 +22,7 @@ import torch
 from . import _lib, ops
 from .align import Alignment, Word
 
-_C = _lib.CONFIDENCE_CONSTANTS
+_C = _lib.HEADERS["conformer_hip_confidence.h"].constants
 METHODS = {"max_prob": _C["CFM_CONFIDENCE_MAX_PROB"], "entropy": _C["CFM_CONFIDENCE_ENTROPY"],
            "tsallis": _C["CFM_CONFIDENCE_TSALLIS"], "renyi": _C["CFM_CONFIDENCE_RENYI"]}
 AGGREGATIONS = {"mean": _C["CFM_CONFIDENCE_MEAN"], "min": _C["CFM_CONFIDENCE_MIN"], "max": _C["CFM_CONFIDENCE_MAX"],

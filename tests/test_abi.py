@@ -1,5 +1,5 @@
 """CPU-side checks of the drop-in boundary: the shared library builds/loads and exports exactly the symbols
-include/conformer_hip.h declares (no compute calls: there is no GPU here), the ctypes table matches the
+the headers under include/ declare (no compute calls: there is no GPU here), the ctypes table matches the
 header, and the product refuses to run without its HIP path."""
 import ctypes
 import os
@@ -12,8 +12,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "conformer_hip.h")
 
 
-def header_functions():
-    src = open(HEADER).read()
+def header_functions(path=HEADER):
+    src = open(path).read()
     src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
     decls = re.findall(r"\b(?:int|int64_t|size_t|const char\*)\s+(cfm_\w+)\s*\(([^;]*?)\)\s*;", src, flags=re.S)
     out = {}
@@ -41,11 +41,15 @@ def test_header_declares_the_path():
 
 def test_library_exports_every_declared_symbol(lib):
     from conformer_amd import _lib
-    fns = header_functions()
-    assert set(fns) == set(_lib.SIGNATURES), set(fns) ^ set(_lib.SIGNATURES)
+    assert set(header_functions()) == set(_lib.SIGNATURES), set(header_functions()) ^ set(_lib.SIGNATURES)
+    fns = {}
+    for basename in sorted(os.listdir(os.path.dirname(HEADER))):                 # every header, the extension headers included
+        fns.update(header_functions(os.path.join(os.path.dirname(HEADER), basename)))
+    assert set(fns) == set(_lib.ENTRIES), set(fns) ^ set(_lib.ENTRIES)
+    assert len(fns) == 162
     for name, nargs in fns.items():
         assert hasattr(lib, name), f"{name} missing from libconformer_hip.so"
-        assert len(_lib.SIGNATURES[name][1]) == nargs, f"ctypes arity of {name} differs from the header"
+        assert len(_lib.ENTRIES[name][1]) == nargs, f"ctypes arity of {name} differs from the header"
 
 
 def test_host_side_entry_points(lib):

@@ -197,25 +197,21 @@ def test_the_transcribers_refuse_confidence_without_times_before_the_model_is_us
 
 # ---- the binding ----------------------------------------------------------------------------------------------------------------------
 def test_the_header_parses_into_its_own_table():
+    """what every header shares (record, names, binding, rebuild message, build) is asserted in test_abi_binding_cpu"""
     names = ["cfm_confidence_frames_f32", "cfm_confidence_spans_f32", "cfm_confidence_greedy_spans_i64"]
-    assert list(_lib.CONFIDENCE_SIGNATURES) == names
-    others = (set(_lib.SIGNATURES) | set(_lib.EXT_SIGNATURES) | set(_lib.COMMIT_SIGNATURES) | set(_lib.TIMES_SIGNATURES)
-              | set(_lib.STREAM_FRONTEND_SIGNATURES) | set(_lib.RESAMPLE_SIGNATURES) | set(_lib.ENDPOINT_SIGNATURES)
-              | set(_lib.ERROR_RATE_SIGNATURES))
-    assert not set(names) & others
+    header = _lib.HEADERS["conformer_hip_confidence.h"]
+    assert list(header.signatures) == names
     p, i, i64, f = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float
-    assert _lib.CONFIDENCE_SIGNATURES[names[0]] == (i, [p, i64, i64, p, i, i, i, f, p, p, p, i, i, p])
-    assert _lib.CONFIDENCE_SIGNATURES[names[1]] == (i, [p, p, p, i, p, p, p, i, i, p, i, p, i, p])
-    assert _lib.CONFIDENCE_SIGNATURES[names[2]] == (i, [p, p, p, p, i, i, i, i, p])
+    assert header.signatures[names[0]] == (i, [p, i64, i64, p, i, i, i, f, p, p, p, i, i, p])
+    assert header.signatures[names[1]] == (i, [p, p, p, i, p, p, p, i, i, p, i, p, i, p])
+    assert header.signatures[names[2]] == (i, [p, p, p, p, i, i, i, i, p])
     assert _lib.PARAMS[names[0]] == ["logits", "ld_slot", "ld_row", "k", "k_max", "V", "method", "alpha", "conf", "ids", "total",
                                      "R", "S", "stream"]
     assert _lib.PARAMS[names[1]] == ["conf", "ids", "total", "R", "starts", "ends", "n_spans", "L", "aggregation", "exclude_ids",
                                      "n_exclude", "out", "S", "stream"]
     assert _lib.PARAMS[names[2]] == ["frame_ids", "lengths_or_null", "token_start", "token_end", "B", "T", "pad_id", "unk_id",
                                      "stream"]
-    with open(_lib.CONFIDENCE_HEADER_PATH) as fh:
-        sigs, _, consts = _lib.parse_header(fh.read())
-    assert sigs == _lib.CONFIDENCE_SIGNATURES and consts == _lib.CONFIDENCE_CONSTANTS
+    consts = header.constants
     assert sorted(consts) == sorted(f"CFM_CONFIDENCE_{n.upper()}" for n in R.METHODS + R.AGGREGATIONS)
     assert not set(consts) & set(_lib.CONSTANTS)
     with open(_lib.HEADER_PATH) as fh:

@@ -2,7 +2,6 @@
 extension header and its binding, the size of the commit state, argument validation of the new C entries (it happens before
 any HIP call, so it runs without a GPU) and the Python refusals."""
 import ctypes
-import inspect
 import os
 
 import numpy as np
@@ -79,36 +78,13 @@ def test_forced_commits_depend_on_the_chunking():
 
 # ---- header and binding ------------------------------------------------------------------------------------------------------
 def test_commit_header_is_bound_from_its_own_table(lib):
-    with open(_lib.COMMIT_HEADER_PATH) as f:
-        text = f.read()
-    sigs, params, consts = _lib.parse_header(text)
-    assert sigs == _lib.COMMIT_SIGNATURES and set(sigs) == NAMES and "#define CFM_" not in text and not consts
-    assert not NAMES & set(_lib.SIGNATURES) and not NAMES & set(_lib.EXT_SIGNATURES)
-    assert len(_lib.SIGNATURES) == 144 and set(_lib.EXT_SIGNATURES) == {"cfm_relpos_attention_window_f32"}
-    assert os.path.basename(_lib.EXT_HEADER_PATH) == "conformer_hip_window.h"
+    """what every header shares (record, names, binding, rebuild message, build) is asserted in test_abi_binding_cpu"""
+    sigs = _lib.HEADERS["conformer_hip_commit.h"].signatures
+    assert set(sigs) == NAMES and not NAMES & set(_lib.SIGNATURES) and len(_lib.SIGNATURES) == 144
     assert sigs["cfm_ctc_beam_commit_state_bytes"] == (ctypes.c_size_t, [ctypes.c_int] * 7)
-    for name, (r, a) in sigs.items():                                      # the built library exports and binds them
-        fn = getattr(lib, name)
-        assert fn.restype is r and list(fn.argtypes) == a
-        assert _lib.PARAMS[name] == params[name] and len(params[name]) == len(a)
     assert _lib.ABI_VERSION == 4 and lib.cfm_abi_version() == 4            # nothing existing moved
     with pytest.raises(_lib.ConformerHipError, match="argument 2 .`max_pending`."):
         _lib.call("cfm_ctc_beam_stream_commit", 1, "x", 1, 1, 1, 0, 0, None, None, 0, None, 0, None, None, None)
-
-
-def test_a_library_without_the_commit_entries_asks_for_a_rebuild(lib, monkeypatch):
-    monkeypatch.setattr(_lib, "_lib", None)
-    monkeypatch.setattr(_lib, "COMMIT_SIGNATURES", {"cfm_not_built_yet": (ctypes.c_int, [])})
-    with pytest.raises(_lib.ConformerHipError, match="conformer_hip_commit.h.*rebuild"):
-        _lib.load()
-    assert _lib._lib is None
-
-
-def test_build_and_hook_track_the_commit_header():
-    assert build._newest_dep() >= os.path.getmtime(_lib.COMMIT_HEADER_PATH)
-    assert "conformer_hip_commit.h" in inspect.getsource(build._newest_dep)
-    import __graft_entry__ as entry
-    assert "COMMIT_SIGNATURES" in inspect.getsource(entry.build)
 
 
 # ---- the state size ----------------------------------------------------------------------------------------------------------

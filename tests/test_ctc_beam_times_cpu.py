@@ -2,7 +2,6 @@
 assembly of BeamCTCStream over a fake search state, the fourth header and its binding, argument validation of the new C entries
 (it happens before any HIP call, so it runs without a GPU) and the Python refusals."""
 import ctypes
-import inspect
 import math
 import os
 import types
@@ -220,18 +219,11 @@ def buf():
 
 
 def test_times_header_is_bound_from_its_own_table(lib):
-    with open(_lib.TIMES_HEADER_PATH) as f:
-        text = f.read()
-    sigs, params, consts = _lib.parse_header(text)
-    assert sigs == _lib.TIMES_SIGNATURES and set(sigs) == NAMES and "#define CFM_" not in text and not consts
-    for table in (_lib.SIGNATURES, _lib.EXT_SIGNATURES, _lib.COMMIT_SIGNATURES):
-        assert not NAMES & set(table)
-    assert os.path.basename(_lib.TIMES_HEADER_PATH) == "conformer_hip_times.h"
+    """what every header shares (record, names, binding, rebuild message, build) is asserted in test_abi_binding_cpu"""
+    header = _lib.HEADERS["conformer_hip_times.h"]
+    sigs, params = header.signatures, header.params
+    assert set(sigs) == NAMES and not NAMES & set(_lib.SIGNATURES)
     assert sigs["cfm_ctc_beam_times_bytes"] == (ctypes.c_size_t, [ctypes.c_int] * 4)
-    for name, (r, a) in sigs.items():
-        fn = getattr(lib, name)
-        assert fn.restype is r and list(fn.argtypes) == a
-        assert _lib.PARAMS[name] == params[name] and len(params[name]) == len(a)
     # the *_times entries take the plain entries' lists, then the four times arguments, then the stream
     for plain, timed in (("cfm_ctc_beam_stream_step_f32", "cfm_ctc_beam_stream_step_times_f32"),
                          ("cfm_ctc_beam_stream_finish_f32", "cfm_ctc_beam_stream_finish_times_f32")):
@@ -239,21 +231,6 @@ def test_times_header_is_bound_from_its_own_table(lib):
     assert params["cfm_ctc_beam_stream_commit_times"] == (_lib.PARAMS["cfm_ctc_beam_stream_commit"][:-1]
                                                           + ["times", "times_bytes", "log_frames", "log_logp", "stream"])
     assert lib.cfm_abi_version() == _lib.ABI_VERSION
-
-
-def test_a_library_without_the_times_entries_asks_for_a_rebuild(lib, monkeypatch):
-    monkeypatch.setattr(_lib, "_lib", None)
-    monkeypatch.setattr(_lib, "TIMES_SIGNATURES", {"cfm_not_built_yet": (ctypes.c_int, [])})
-    with pytest.raises(_lib.ConformerHipError, match="conformer_hip_times.h.*rebuild"):
-        _lib.load()
-    assert _lib._lib is None
-
-
-def test_build_and_hook_track_the_times_header():
-    assert build._newest_dep() >= os.path.getmtime(_lib.TIMES_HEADER_PATH)
-    assert "conformer_hip_times.h" in inspect.getsource(build._newest_dep)
-    import __graft_entry__ as entry
-    assert "TIMES_SIGNATURES" in inspect.getsource(entry.build)
 
 
 def test_times_bytes(lib):

@@ -159,20 +159,15 @@ def test_slot_transcriber_refuses_a_bad_endpoint_before_the_model_is_used():
 
 # ---- the binding ----------------------------------------------------------------------------------------------------------------
 def test_the_header_parses_into_its_own_table():
-    assert list(_lib.ENDPOINT_SIGNATURES) == ["cfm_endpoint_step_f32"]
-    others = (set(_lib.SIGNATURES) | set(_lib.EXT_SIGNATURES) | set(_lib.COMMIT_SIGNATURES) | set(_lib.TIMES_SIGNATURES)
-              | set(_lib.STREAM_FRONTEND_SIGNATURES) | set(_lib.RESAMPLE_SIGNATURES))
-    assert not set(_lib.ENDPOINT_SIGNATURES) & others
+    """what every header shares (record, names, binding, rebuild message, build) is asserted in test_abi_binding_cpu"""
+    signatures = _lib.HEADERS["conformer_hip_endpoint.h"].signatures
+    assert list(signatures) == ["cfm_endpoint_step_f32"]
     p, i, i64, f = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float
-    res, args = _lib.ENDPOINT_SIGNATURES["cfm_endpoint_step_f32"]
+    res, args = signatures["cfm_endpoint_step_f32"]
     assert res is i and len(args) == 14
     assert args == [p, i64, i64, p, i, i, p, i, f, p, i, p, i, p]
     assert _lib.PARAMS["cfm_endpoint_step_f32"] == ["logits", "ld_slot", "ld_row", "k", "k_max", "V", "silence_ids", "n_silence",
                                                      "log_threshold", "rules", "n_rules", "state", "S", "stream"]
-    with open(_lib.ENDPOINT_HEADER_PATH) as fh:
-        text = fh.read()
-    sigs, _, consts = _lib.parse_header(text)
-    assert sigs == _lib.ENDPOINT_SIGNATURES and consts == {}                     # no CFM_* define of its own
     with open(_lib.HEADER_PATH) as fh:
         main = fh.read()
     assert "conformer_hip_endpoint.h" not in main and "cfm_endpoint" not in main # the main header stays as it was

@@ -1,7 +1,6 @@
 """Error rates without a GPU: the plain-Python restatement against ConformerMetric on BeamCTCDecoder.text strings (the public
 definition the device numbers are tied to), the binding of include/conformer_hip_error_rate.h, and the host refusals."""
 import ctypes
-import inspect
 import math
 import os
 import random
@@ -179,64 +178,30 @@ def test_a_zero_denominator_gives_nan_with_errors_counted():
 
 # ---- the binding ----------------------------------------------------------------------------------------------------------------
 def test_the_header_parses_into_its_own_table():
-    assert list(_lib.ERROR_RATE_SIGNATURES) == ["cfm_error_rate_units", "cfm_error_rate_distance"]
-    others = (set(_lib.SIGNATURES) | set(_lib.EXT_SIGNATURES) | set(_lib.COMMIT_SIGNATURES) | set(_lib.TIMES_SIGNATURES)
-              | set(_lib.STREAM_FRONTEND_SIGNATURES) | set(_lib.RESAMPLE_SIGNATURES) | set(_lib.ENDPOINT_SIGNATURES))
-    assert not set(_lib.ERROR_RATE_SIGNATURES) & others
+    """what every header shares (record, names, binding, rebuild message, build) is asserted in test_abi_binding_cpu"""
+    header = _lib.HEADERS["conformer_hip_error_rate.h"]
+    signatures = header.signatures
+    assert list(signatures) == ["cfm_error_rate_units", "cfm_error_rate_distance"]
     p, i, i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64
-    res, args = _lib.ERROR_RATE_SIGNATURES["cfm_error_rate_units"]
+    res, args = signatures["cfm_error_rate_units"]
     assert res is i and args == [p, i64, p, i, i, p, p, p, i, i, p, i64, p, i64, p, i64, p, p]
     assert _lib.PARAMS["cfm_error_rate_units"] == ["ids", "ld_ids", "counts", "R", "L", "tok_kind", "tok_off", "tok_cp", "V",
                                                     "max_token_cps", "cps", "ld_cps", "words", "ld_words", "toks", "ld_toks",
                                                     "lens", "stream"]
-    res, args = _lib.ERROR_RATE_SIGNATURES["cfm_error_rate_distance"]
+    res, args = signatures["cfm_error_rate_distance"]
     assert res is i and args == [p, i64, p, i64, p, i64, p, p, i64, p, i64, p, i64, p, i, i, i, p, p, p, p]
     assert _lib.PARAMS["cfm_error_rate_distance"][-7:] == ["B", "N", "unit", "errors", "hyp_units", "ref_units", "stream"]
-    with open(_lib.ERROR_RATE_HEADER_PATH) as fh:
-        text = fh.read()
-    sigs, _, consts = _lib.parse_header(text)
-    assert sigs == _lib.ERROR_RATE_SIGNATURES and consts == {}               # no CFM_* define of its own
-    assert str(MAX_UNITS) in text                                             # the cap is stated in the header
+    with open(header.path) as fh:
+        assert str(MAX_UNITS) in fh.read()                                    # the cap is stated in the header
     with open(_lib.HEADER_PATH) as fh:
         main = fh.read()
     assert "conformer_hip_error_rate.h" not in main and "cfm_error_rate" not in main   # the main header stays as it was
     assert os.path.exists(_lib.LIB_PATH), "build the library first (python -m conformer_amd.build)"
     with open(_lib.LIB_PATH, "rb") as fh:
         blob = fh.read()
-    for name in _lib.ERROR_RATE_SIGNATURES:
+    for name in signatures:
         assert re.search(name.encode() + b"\0", blob), f"{name} is not in the library's symbol strings"
-
-
-def test_the_header_is_registered_with_the_build_and_the_entry():
-    assert "conformer_hip_error_rate.h" in inspect.getsource(build._newest_dep)
-    assert build._newest_dep() >= os.path.getmtime(_lib.ERROR_RATE_HEADER_PATH)
     assert any(s.endswith("error_rate.hip") for s in build.sources())
-    import __graft_entry__
-    assert "ERROR_RATE_SIGNATURES" in inspect.getsource(__graft_entry__.build)
-    assert "ERROR_RATE_SIGNATURES" in inspect.getsource(_lib.load)
-
-
-def test_a_library_without_the_entries_asks_for_a_rebuild(monkeypatch):
-    """load() on a stand-in library that has every entry but these names the header and the remedy"""
-    class Fn:
-        restype = argtypes = None
-
-        def __call__(self, *a):
-            return _lib.ABI_VERSION
-
-    class Lib:
-        def __getattr__(self, name):
-            if name.startswith("cfm_error_rate"):
-                raise AttributeError(name)
-            fn = Fn()
-            object.__setattr__(self, name, fn)
-            return fn
-
-    monkeypatch.setattr(_lib, "_lib", None)
-    monkeypatch.setattr(ctypes, "CDLL", lambda *a, **kw: Lib())
-    with pytest.raises(_lib.ConformerHipError, match=r"lacks cfm_error_rate_units \(include/conformer_hip_error_rate.h\): rebuild"):
-        _lib.load()
-    assert _lib._lib is None
 
 
 def test_a_meter_with_a_device_has_its_totals_from_the_start():

@@ -155,16 +155,12 @@ def test_conversion_and_downmix_restated():
 
 
 def test_header_and_binding():
-    """The new header parses, declares only the new entries, shares none with the other tables, and the library exports them."""
+    """The two entries take the same list and the library exports them; what every header shares (its record, its names, the
+    binding, the rebuild message, the build) is in test_abi_binding_cpu."""
     from conformer_amd import _lib
-    assert sorted(_lib.RESAMPLE_SIGNATURES) == ["cfm_resample_f32", "cfm_resample_i16"]
-    others = (set(_lib.SIGNATURES) | set(_lib.EXT_SIGNATURES) | set(_lib.COMMIT_SIGNATURES) | set(_lib.TIMES_SIGNATURES)
-              | set(_lib.STREAM_FRONTEND_SIGNATURES))
-    assert not set(_lib.RESAMPLE_SIGNATURES) & others
-    with open(_lib.RESAMPLE_HEADER_PATH) as f:
-        text = f.read()
-    sigs, params, consts = _lib.parse_header(text)
-    assert sigs == _lib.RESAMPLE_SIGNATURES and consts == {}
+    header = _lib.HEADERS["conformer_hip_resample.h"]
+    sigs, params = header.signatures, header.params
+    assert sorted(sigs) == ["cfm_resample_f32", "cfm_resample_i16"]
     assert params["cfm_resample_f32"] == params["cfm_resample_i16"] == [
         "samples", "ld_samples", "n_max", "C", "tail_in", "tail_out", "table", "bank_t", "o", "n", "width", "y", "ld_y", "S",
         "stream"]
@@ -174,5 +170,5 @@ def test_header_and_binding():
     assert os.path.exists(_lib.LIB_PATH), "build the library first (python -m conformer_amd.build)"
     with open(_lib.LIB_PATH, "rb") as f:
         blob = f.read()
-    for name in _lib.RESAMPLE_SIGNATURES:
+    for name in sigs:
         assert re.search(name.encode() + b"\0", blob), f"{name} is not in the library's symbol strings"

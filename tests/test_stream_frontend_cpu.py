@@ -162,10 +162,10 @@ def test_host_refusals_raise_before_the_device_and_change_nothing():
 
 
 def test_the_entry_is_bound_from_its_own_header():
+    """what every header shares (record, names, binding, rebuild message, build) is asserted in test_abi_binding_cpu"""
     from conformer_amd import _lib
-    with open(_lib.STREAM_FRONTEND_HEADER_PATH) as f:
-        sigs, params, consts = _lib.parse_header(f.read())
-    assert set(sigs) == set(_lib.STREAM_FRONTEND_SIGNATURES) == {"cfm_stream_stage_f32"} and not consts
-    assert params["cfm_stream_stage_f32"] == ["samples", "ld_samples", "n_max", "tail_in", "tail_out", "table", "xp", "S", "f_max",
-                                              "hop", "n_fft", "stream"]
+    header = _lib.HEADERS["conformer_hip_stream_frontend.h"]
+    assert set(header.signatures) == {"cfm_stream_stage_f32"}
+    assert _lib.PARAMS["cfm_stream_stage_f32"] == header.params["cfm_stream_stage_f32"] == [
+        "samples", "ld_samples", "n_max", "tail_in", "tail_out", "table", "xp", "S", "f_max", "hop", "n_fft", "stream"]
     assert "cfm_stream_stage_f32" not in _lib.SIGNATURES

@@ -100,42 +100,21 @@ def test_window_entry_validates_without_gpu(lib, ptr):
 
 
 def test_extension_header_is_bound_separately(lib):
+    """what every header shares (record, names, binding, rebuild message, build) is asserted in test_abi_binding_cpu"""
     from conformer_amd import _lib
-    assert set(_lib.EXT_SIGNATURES) == {"cfm_relpos_attention_window_f32"}
-    assert not set(_lib.EXT_SIGNATURES) & set(_lib.SIGNATURES)
-    with open(_lib.EXT_HEADER_PATH) as f:
-        text = f.read()
-    sigs, params, consts = _lib.parse_header(text)
-    assert sigs == _lib.EXT_SIGNATURES and "#define CFM_" not in text and not consts
-    res, args = sigs["cfm_relpos_attention_window_f32"]
+    header = _lib.HEADERS["conformer_hip_window.h"]
+    assert "cfm_relpos_attention_window_f32" not in _lib.SIGNATURES and len(_lib.SIGNATURES) == 144
+    res, args = header.signatures["cfm_relpos_attention_window_f32"]
     vp, i64, i32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int
     assert res is i32 and args == [vp, vp, vp, i64, vp, i64, i32, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, i32, vp]
-    assert _lib.PARAMS["cfm_relpos_attention_window_f32"] == params["cfm_relpos_attention_window_f32"] == [
+    assert _lib.ENTRIES["cfm_relpos_attention_window_f32"] == (res, args)
+    assert _lib.PARAMS["cfm_relpos_attention_window_f32"] == header.params["cfm_relpos_attention_window_f32"] == [
         "q", "k", "v", "ld", "pos", "ldp", "P", "u", "vbias", "q_begin", "q_count", "ctx", "ldo", "B", "R", "H", "dh", "q_max",
         "left", "stream"]
-    for name, (r, a) in _lib.EXT_SIGNATURES.items():                             # the built library exports and binds them
-        fn = getattr(lib, name)
-        assert fn.restype is r and list(fn.argtypes) == a
     assert _lib.ABI_VERSION == 4 and lib.cfm_abi_version() == 4                  # nothing existing moved
     with pytest.raises(_lib.ConformerHipError, match="argument 7 .`P`."):        # `call` names the parameters of this header too
         _lib.call("cfm_relpos_attention_window_f32", None, None, None, 0, None, 0, "x", None, None, None, None, None, 0, 1, 32, 1,
                   4, 1, 0, None)
-
-
-def test_a_library_without_the_entry_asks_for_a_rebuild(lib, monkeypatch):
-    from conformer_amd import _lib
-    monkeypatch.setattr(_lib, "_lib", None)
-    monkeypatch.setattr(_lib, "EXT_SIGNATURES", {"cfm_not_built_yet": (ctypes.c_int, [])})
-    with pytest.raises(_lib.ConformerHipError, match="rebuild"):
-        _lib.load()
-    assert _lib._lib is None
-
-
-def test_build_tracks_the_extension_header():
-    from conformer_amd import _lib, build
-    assert build._newest_dep() >= os.path.getmtime(_lib.EXT_HEADER_PATH)
-    import inspect
-    assert "conformer_hip_window.h" in inspect.getsource(build._newest_dep)
 
 
 # ---- host arithmetic -----------------------------------------------------------------------------------------------------------

@@ -1,0 +1,308 @@
+"""Offline transcription of recordings of any length: overlapped windows through the full-context encoder (INTEGRATION.md
+"Offline and long-form transcription").
+
+Encoder.forward attends over its whole input, so a one-hour recording would be one attention over ~90 000 frames.  Here a
+recording is cut into fixed windows of W mel frames that overlap by O; the windows of all recordings run through the encoder as
+ordinary (B, n_mel, W) batches -- the shape it is fastest at -- and every encoder frame of the recording is taken from the window
+in which it has the most context on both sides.  The decoder head, the beam search and the confidences then run once over the
+stitched frames of the whole recording, so word times are global by construction.
+
+Three layers: window_plan (host arithmetic), BufferedEncoder (mel frames in, stitched encoder frames out) and Transcriber
+(waveforms or mel frames in, Transcripts out).  There is no kernel of its own in here: the hot path is Encoder.forward, the
+decoder head and the search, which are gfx950 kernels already; the plan, the batching and the stitching are slices and copies.
+"""
+from __future__ import annotations
+
+import math
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
+
+import torch
+
+from .align import Word
+from .confidence import ConfidenceConfig, frame_confidence, transcriber_confidence, word_confidence
+from .decode import BeamCTCDecoder
+from .frontend import ConformerAudioFrontend
+from .graph import GraphedEncoder
+from .streaming import encoder_frames
+from .transcribe import lstm_state, times_plan
+
+MIN_MEL_FRAMES = 7                      # the fewest mel frames the stem makes an encoder frame of
+
+
+class Window(NamedTuple):
+    """One window of a plan.  It reads the mel frames [start, start + mel) and makes the encoder frames [first, first +
+    encoder_frames(mel)) of the recording's own grid (first = start / 4); the rows [keep_from, keep_to) of that grid are taken
+    from it, which are its local rows [keep_from - first, keep_to - first)."""
+    start: int
+    mel: int
+    first: int
+    keep_from: int
+    keep_to: int
+
+
+def check_window(window: int, overlap: int) -> Tuple[int, int]:
+    """Refuse a window / overlap pair (mel frames) that window_plan cannot tile with; returns (W, H), H = W - O the hop."""
+    for name, v in (("window", window), ("overlap", overlap)):
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise ValueError(f"window_plan: {name} must be a number of mel frames, got {v!r}")
+    W, H = window, window - overlap
+    if W < 12:
+        raise ValueError(f"window_plan: window = {W} mel frames, the least is 12 (a right-aligned last window may be 3 shorter and "
+                         f"still has to make an encoder frame)")
+    if H < 4:
+        raise ValueError(f"window_plan: window - overlap = {H} mel frames, the least is 4 (one encoder frame)")
+    if H % 4:
+        raise ValueError(f"window_plan: window - overlap = {H} mel frames is no multiple of 4 (window starts have to fall on the "
+                         "encoder's frame grid)")
+    if encoder_frames(W) < H // 4:
+        raise ValueError(f"window_plan: a window of {W} mel frames makes {encoder_frames(W)} encoder frames, consecutive windows "
+                         f"start {H // 4} apart: they would leave a gap (raise overlap)")
+    return W, H
+
+
+def window_plan(n_mel: int, window: int, overlap: int) -> List[Window]:
+    """The windows of a recording of n_mel mel frames, `window` = W and `overlap` = O in mel frames, H = W - O.
+
+    One window (0, n_mel) if n_mel <= W.  Otherwise ceil((n_mel - W) / H) + 1 windows: window i starts at i * H and is W long,
+    except the last, which is right-aligned: it starts at 4 * ceil((n_mel - W) / 4) and runs to the end (W - 3 .. W frames).
+    Every start is a multiple of 4, so the local encoder frame j of a window that starts at s is the frame s / 4 + j of the
+    recording's own grid (frame j covers the mel frames s + 4j .. s + 4j + 6) and the last window ends at encoder_frames(n_mel).
+    Consecutive windows are cut in the middle of the frames they share: window i keeps [c_(i-1), c_i) with
+    c_i = first_(i+1) + (end_i - first_(i+1)) // 2; the first keeps from 0, the last up to encoder_frames(n_mel).  The kept
+    ranges tile [0, encoder_frames(n_mel)) exactly once.
+
+    ValueError for W < 12, H < 4, H % 4 != 0, encoder_frames(W) < H / 4 (a gap between windows) and n_mel < 7 (no encoder
+    frame at all)."""
+    W, H = check_window(window, overlap)
+    if isinstance(n_mel, bool) or not isinstance(n_mel, int) or n_mel < MIN_MEL_FRAMES:
+        raise ValueError(f"window_plan: a recording of {n_mel!r} mel frames makes no encoder frame (the least is {MIN_MEL_FRAMES})")
+    if n_mel <= W:
+        spans = [(0, n_mel)]
+    else:
+        n = -(-(n_mel - W) // H) + 1
+        last = 4 * (-(-(n_mel - W) // 4))
+        spans = [(i * H, W) for i in range(n - 1)] + [(last, n_mel - last)]
+    first = [s // 4 for s, _ in spans]
+    end = [a + encoder_frames(m) for a, (_, m) in zip(first, spans)]
+    cuts = [0] + [first[i + 1] + (end[i] - first[i + 1]) // 2 for i in range(len(spans) - 1)] + [encoder_frames(n_mel)]
+    return [Window(s, m, first[i], cuts[i], cuts[i + 1]) for i, (s, m) in enumerate(spans)]
+
+
+def window_frames(window_seconds: float, overlap_seconds: float, mel_seconds: float) -> Tuple[int, int]:
+    """(window, overlap) in mel frames of mel_seconds each for window_plan: the window is the most whole frames inside
+    window_seconds, the hop W - O is rounded DOWN to a multiple of 4 frames, so that the overlap used is at least
+    overlap_seconds.  Refuses (ValueError) what is no positive finite time, an overlap that is not shorter than the window and
+    whatever window_plan refuses."""
+    for name, v in (("window_seconds", window_seconds), ("overlap_seconds", overlap_seconds), ("mel_seconds", mel_seconds)):
+        least = 0.0 if name == "overlap_seconds" else math.ulp(0.0)          # the overlap may be 0, the other two not
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v < least:
+            raise ValueError(f"window_frames: {name} must be a positive finite number of seconds, got {v!r}")
+    if overlap_seconds >= window_seconds:
+        raise ValueError(f"window_frames: overlap_seconds = {overlap_seconds} is not shorter than window_seconds = {window_seconds}")
+    W = int(math.floor(window_seconds / mel_seconds + 1e-6))
+    least = int(math.ceil(overlap_seconds / mel_seconds - 1e-6))
+    H = (W - least) // 4 * 4
+    check_window(W, W - H)
+    return W, W - H
+
+
+def _ambient_autocast(who: str) -> Optional[torch.dtype]:
+    if not torch.is_autocast_enabled("cuda"):
+        return None
+    dt = torch.get_autocast_dtype("cuda")
+    if dt not in (torch.bfloat16, torch.float16):
+        raise RuntimeError(f"{who}: torch.autocast of {dt} has no gfx950 path (none, bfloat16 or float16)")
+    return dt
+
+
+class BufferedEncoder:
+    """The encoder over recordings of any length, window by window (the module docstring).
+
+        be = BufferedEncoder(model.encoder, window=3000, overlap=800); hs = be.encode([mel_a, mel_b])
+
+    encoder: an Encoder in eval() mode on the HIP device.  window, overlap: mel frames, as window_plan takes them.  The windows
+    of ALL recordings of a call are pooled, sorted by length (longest first, stable) and cut into batches of at most
+    batch_windows.  A batch whose windows all have one length runs as encoder(x, None); a ragged one is zero-padded to its
+    longest window and runs as encoder(x, lengths): an offline batch as it always was, so a list of recordings that each fit
+    one window IS the reference's sorted, padded batch.  Each window's kept rows are then copied to their place in the
+    recording's output.
+    graphs=True: the full batches of full windows (batch_windows, n_mel, window) replay one captured graph (GraphedEncoder, one
+    per ambient autocast type); everything else runs eagerly.  Changed weights are seen by the existing derived-weight rule
+    (GraphedEncoder's fingerprint, the pack caches), there is nothing to call here.
+    Under torch.autocast (bfloat16 / float16) the encoder runs its 16-bit path; the output keeps the encoder's dtype.
+
+    Memory: beyond the inputs and the outputs (encoder_frames(n_i) x d floats per recording) a call holds ONE batch of windows:
+    its input (batch_windows x n_mel x window floats), the activations of one Encoder.forward on it and its output
+    (batch_windows x encoder_frames(window) x d floats), whatever the recordings' lengths; with graphs=True the captured graph
+    keeps such a batch for the object's lifetime."""
+
+    def __init__(self, encoder, window: int, overlap: int, batch_windows: int = 32, graphs: bool = False) -> None:
+        self.window, self.hop = check_window(window, overlap)
+        self.overlap = self.window - self.hop
+        if isinstance(batch_windows, bool) or not isinstance(batch_windows, int) or batch_windows < 1:
+            raise ValueError(f"BufferedEncoder: batch_windows must be a number of windows >= 1, got {batch_windows!r}")
+        if not isinstance(graphs, bool):
+            raise ValueError(f"BufferedEncoder: graphs must be True or False, got {graphs!r}")
+        self.batch_windows, self.graphs = batch_windows, graphs
+        self.encoder = encoder
+        self._refuse()
+        self._graphed: Dict[Optional[torch.dtype], GraphedEncoder] = {}
+
+    def _refuse(self) -> torch.device:
+        enc = self.encoder
+        if enc.training:
+            raise RuntimeError("BufferedEncoder: put the encoder in eval() mode (running BatchNorm statistics, no dropout)")
+        p = next(enc.parameters())
+        if not p.is_cuda or p.dtype != torch.float32:
+            raise RuntimeError("BufferedEncoder: the encoder must live on the HIP device in fp32 (no CPU fallback)")
+        return p.device
+
+    def plan(self, mel_frames: Sequence[int]) -> List[List[Window]]:
+        """window_plan of every recording."""
+        return [window_plan(int(n), self.window, self.overlap) for n in mel_frames]
+
+    def batches(self, plans: Sequence[Sequence[Window]]) -> List[List[Tuple[int, int]]]:
+        """The pool of (recording, window index) pairs, sorted by mel length (longest first, stable), in batches."""
+        pool = [(r, i) for r, ws in enumerate(plans) for i in range(len(ws))]
+        pool.sort(key=lambda ri: -plans[ri[0]][ri[1]].mel)
+        return [pool[k:k + self.batch_windows] for k in range(0, len(pool), self.batch_windows)]
+
+    def _forward(self, x: torch.Tensor, lengths: Optional[torch.Tensor], amp: Optional[torch.dtype]) -> torch.Tensor:
+        if self.graphs and lengths is None and x.shape[0] == self.batch_windows and x.shape[2] == self.window:
+            if amp not in self._graphed:
+                self._graphed[amp] = GraphedEncoder(self.encoder, x, None, autocast_dtype=amp)
+            return self._graphed[amp](x, None)[0]
+        return self.encoder(x, lengths)[0]
+
+    @torch.no_grad()
+    def encode(self, mels: Sequence[torch.Tensor]) -> List[torch.Tensor]:
+        """mels: per recording its log-mel frames (n_mel, n_i), n_i >= 7 (on the device, or on the host: windows are copied
+        over batch by batch).  Returns per recording its encoder frames (encoder_frames(n_i), d) on the device."""
+        device = self._refuse()
+        amp = _ambient_autocast("BufferedEncoder")
+        mels = list(mels)
+        for r, m in enumerate(mels):
+            if not isinstance(m, torch.Tensor) or m.dim() != 2 or m.dtype != torch.float32:
+                raise ValueError(f"BufferedEncoder: recording {r}: expected fp32 log-mel frames (n_mel, n), got "
+                                 f"{tuple(m.shape) if isinstance(m, torch.Tensor) else type(m).__name__}")
+            if m.shape[0] != mels[0].shape[0]:
+                raise ValueError(f"BufferedEncoder: recording {r} has {m.shape[0]} mel channels, recording 0 has {mels[0].shape[0]}")
+        plans = self.plan([m.shape[1] for m in mels])
+        outs: List[Optional[torch.Tensor]] = [None] * len(mels)
+        for batch in self.batches(plans):
+            ws = [plans[r][i] for r, i in batch]
+            longest = ws[0].mel
+            ragged = ws[-1].mel != longest
+            x = (torch.zeros if ragged else torch.empty)(len(ws), mels[0].shape[0], longest, device=device, dtype=torch.float32)
+            for k, ((r, _), w) in enumerate(zip(batch, ws)):
+                x[k, :, :w.mel].copy_(mels[r][:, w.start:w.start + w.mel], non_blocking=True)
+            lengths = torch.tensor([w.mel for w in ws], dtype=torch.int64).to(device, non_blocking=True) if ragged else None
+            y = self._forward(x, lengths, amp)
+            for k, ((r, _), w) in enumerate(zip(batch, ws)):
+                if outs[r] is None:
+                    outs[r] = torch.empty(plans[r][-1].keep_to, y.shape[2], device=device, dtype=y.dtype)
+                outs[r][w.keep_from:w.keep_to].copy_(y[k, w.keep_from - w.first:w.keep_to - w.first])
+        return outs
+
+
+class Transcript(NamedTuple):
+    """text: the best hypothesis; words: its align.Words with global times (None without times=True); word_confidence: one
+    float per Word (None without confidence=); frames: encoder frames of the recording; seconds: its duration (mel frames x the
+    front end's hop)."""
+    text: str
+    words: Optional[List[Word]]
+    word_confidence: Optional[List[float]]
+    frames: int
+    seconds: float
+
+
+class Transcriber:
+    """Offline transcription: a list of recordings in, a list of Transcripts out, in the caller's order.
+
+        tr = Transcriber(model, decoder, frontend, window_seconds=30.0, overlap_seconds=8.0, times=True)
+        for t in tr.transcribe(waves, sample_rates=rates): print(t.text)
+
+    model: a Conformer in eval() mode on the HIP device; decoder: a BeamCTCDecoder (its lm and hotwords apply); frontend: a
+    ConformerAudioFrontend, then `audios` are waveforms (with sample_rates= whatever the front end takes); None: `audios` are
+    log-mel tensors (n_mel, n_i).  Pipeline: front end -> BufferedEncoder.encode -> model.decoder on the stitched frames
+    (recordings sorted by length, batches of at most batch_windows) -> the decoder's offline search (text; with times=True
+    decoder.words at frame_seconds per encoder frame) -> with confidence=ConfidenceConfig(...) (needs times=True)
+    frame_confidence and word_confidence.
+    window_seconds, overlap_seconds have NO default: no trained checkpoint was at hand, so no word error rate was measured for
+    any choice; 30 s / 8 s is the usual starting point.  They are converted once to mel frames (window_frames: the front end's
+    hop, or frame_seconds / 4 per mel frame without one); overlap_seconds is the lower bound of the overlap used.
+    batch_windows, graphs: as BufferedEncoder.
+    Memory: only the encoder is bounded by one batch of windows.  transcribe holds the stitched frames of every recording and,
+    per group, a second, padded copy of them (B, T', d) for the decoder head, so twice the stitched output of a group; the head's
+    own intermediates, the logits and the search's buffers all grow with the recording's length."""
+
+    def __init__(self, model, decoder: BeamCTCDecoder, frontend: Optional[ConformerAudioFrontend] = None, *,
+                 window_seconds: float, overlap_seconds: float, batch_windows: int = 32, graphs: bool = False,
+                 times: bool = False, frame_seconds: float = 0.04, confidence: Optional[ConfidenceConfig] = None) -> None:
+        self.times, self.frame_seconds = times_plan("Transcriber", times, frame_seconds)
+        cplan = transcriber_confidence("Transcriber", confidence, 1, self.times)
+        self.confidence = None if cplan is None else cplan[0]
+        if not isinstance(decoder, BeamCTCDecoder):
+            raise ValueError(f"Transcriber: decoder must be a BeamCTCDecoder, got {type(decoder).__name__}")
+        if frontend is not None and not isinstance(frontend, ConformerAudioFrontend):
+            raise ValueError(f"Transcriber: frontend must be a ConformerAudioFrontend or None, got {type(frontend).__name__}")
+        self.mel_seconds = self.frame_seconds / 4 if frontend is None else frontend.hop_length / frontend.sample_rate
+        self.window, self.overlap = window_frames(window_seconds, overlap_seconds, self.mel_seconds)
+        if isinstance(batch_windows, bool) or not isinstance(batch_windows, int) or batch_windows < 1:
+            raise ValueError(f"Transcriber: batch_windows must be a number of windows >= 1, got {batch_windows!r}")
+        if not isinstance(graphs, bool):
+            raise ValueError(f"Transcriber: graphs must be True or False, got {graphs!r}")
+        self.device, _ = lstm_state(model, "Transcriber", 1)
+        self.model, self.decoder, self.frontend = model, decoder, frontend
+        self.batch_windows = batch_windows
+        self.encoder = BufferedEncoder(model.encoder, self.window, self.overlap, batch_windows, graphs)
+
+    @torch.no_grad()
+    def features(self, audios: Sequence[torch.Tensor], sample_rates: Optional[Sequence[int]] = None) -> List[torch.Tensor]:
+        """Per recording its log-mel frames (n_mel, n_i): the front end's batch cut back to every recording's own length, or
+        `audios` themselves without a front end."""
+        if self.frontend is None:
+            if sample_rates is not None:
+                raise ValueError("Transcriber: sample_rates needs the frontend= (without one the inputs are log-mel frames)")
+            return list(audios)
+        mels, lengths = self.frontend(audios, sample_rates=sample_rates)
+        return [mels[i, :, :n] for i, n in enumerate(lengths.cpu().tolist())]
+
+    @torch.no_grad()
+    def decoder_head(self, h: torch.Tensor, lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """model.decoder on stitched encoder frames h (B, T', d), `lengths` (B) int64 frames per recording: logits (B, T', V)."""
+        return self.model.decoder(h, lengths)
+
+    def groups(self, frames: Sequence[int]) -> List[List[int]]:
+        """The recordings sorted by encoder frames (longest first, stable), in batches of at most batch_windows."""
+        order = sorted(range(len(frames)), key=lambda i: -frames[i])
+        return [order[k:k + self.batch_windows] for k in range(0, len(order), self.batch_windows)]
+
+    @torch.no_grad()
+    def transcribe(self, audios: Sequence[torch.Tensor], sample_rates: Optional[Sequence[int]] = None) -> List[Transcript]:
+        """audios: waveforms as the front end takes them (sample_rates: their rates, None: all at the front end's own), or log-mel
+        tensors (n_mel, n_i) without a front end; every recording needs at least 7 mel frames.  One Transcript per recording, in
+        the caller's order.  Synchronises (the texts are read back)."""
+        lstm_state(self.model, "Transcriber", 1)
+        _ambient_autocast("Transcriber")
+        if len(audios) == 0:
+            return []
+        mels = self.features(audios, sample_rates)
+        hs = self.encoder.encode(mels)
+        out: List[Optional[Transcript]] = [None] * len(hs)
+        for group in self.groups([h.shape[0] for h in hs]):
+            n = [hs[i].shape[0] for i in group]
+            h = hs[group[0]].new_zeros(len(group), n[0], hs[group[0]].shape[1])
+            for k, i in enumerate(group):
+                h[k, :n[k]] = hs[i]
+            lengths = torch.tensor(n, dtype=torch.int64).to(self.device, non_blocking=True)
+            logits = self.decoder_head(h, lengths)
+            texts = self.decoder(logits, lengths)
+            words = self.decoder.words(logits, lengths, self.frame_seconds) if self.times else [None] * len(group)
+            scores = [None] * len(group)
+            if self.confidence is not None:
+                conf, ids = frame_confidence(logits, lengths, self.confidence)
+                scores = word_confidence(words, conf, ids, self.decoder.blank_id, lengths, self.confidence)
+            for k, i in enumerate(group):
+                out[i] = Transcript(texts[k], words[k], scores[k], n[k], mels[i].shape[1] * self.mel_seconds)
+        return out

@@ -5,6 +5,10 @@ Every header is parsed once at import (no torch needed) into HEADERS; ENTRIES an
 CONSTANTS are the main header's declarations and its `#define CFM_*` lines and `enum cfm_status`.  A type the parser does not
 know, or a `cfm_*(` it cannot read, is an error, never a guess.  There is NO fallback: a missing header or library, or a
 non-zero status, raises.  Nothing here imports the CPU oracle.
+
+That table is the first generation and is closed.  Families added after it are the second generation (EXTRA_HEADERS: symbols
+cfm2_*, defines CFM2_*, one header per family in conformer_amd/csrc/), parsed by the same parser into EXTRA_ENTRIES, EXTRA_PARAMS
+and EXTRA_CONSTANTS and bound by `load` after the first, with the same refusal of a library that lacks one.
 """
 from __future__ import annotations
 
@@ -33,16 +37,24 @@ EXTENSION_HEADERS = (
 )
 _CTYPES = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "float": ctypes.c_float, "double": ctypes.c_double,
            "uint64_t": ctypes.c_uint64, "size_t": ctypes.c_size_t, "cfm_stream_t": ctypes.c_void_p}
-_DECL = re.compile(r"^[ \t]*((?:const\s+)?\w+[\s*]+?)(cfm_\w+)\s*\(([^()]*)\)\s*;", re.M)
+# second generation: families added after the first-generation table (the nine headers under include/, their cfm_* entries
+# and CFM_* defines) was closed.  Symbols cfm2_*, defines CFM2_*, one header per family beside the kernels in csrc/.
+EXTRA_HEADERS = (
+    os.path.join(_HERE, "csrc", "conformer_hip2_align_long.h"),     # CTC forced alignment without a length limit
+)
+EXTRA_PREFIX = "cfm2_"
 
 
 class ConformerHipError(RuntimeError):
     pass
 
 
-def parse_header(text: str):
+def parse_header(text: str, prefix: str = "cfm_"):
     """(SIGNATURES, PARAMS, CONSTANTS) of the header `text`: name -> (restype, [argtypes]), name -> [parameter names]
-    (`arg<i>` where the header names none), and every `#define CFM_X <integer>` / `CFM_X = <integer>` enum member -> int."""
+    (`arg<i>` where the header names none), and every `#define CFM_X <integer>` / `CFM_X = <integer>` enum member -> int.
+    `prefix`: what the entries' names start with; the defines read start with its upper case ("cfm2_": cfm2_* and CFM2_*)."""
+    fn, define = re.escape(prefix), re.escape(prefix.upper())
+
     def ctype(words, where):            # words: the type without `const`, every `*` glued to the word before it
         if words[-1].endswith("*"):
             return ctypes.c_void_p
@@ -52,7 +64,7 @@ def parse_header(text: str):
 
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     signatures, params = {}, {}
-    for ret, name, plist in _DECL.findall(text):
+    for ret, name, plist in re.findall(rf"^[ \t]*((?:const\s+)?\w+[\s*]+?)({fn}\w+)\s*\(([^()]*)\)\s*;", text, flags=re.M):
         ret = re.sub(r"\s*\*\s*", "* ", ret).split()
         restype = ctypes.c_char_p if ret == ["const", "char*"] else ctype(ret, name)
         argtypes, names = [], []
@@ -62,12 +74,13 @@ def parse_header(text: str):
             argtypes.append(ctype(words[:-1] if named else words, f"{name}, parameter {i + 1} `{p.strip()}`"))
             names.append(words[-1] if named else f"arg{i}")
         signatures[name], params[name] = (restype, argtypes), names
-    tokens = re.findall(r"cfm_\w+\s*\(", text)
+    tokens = re.findall(rf"{fn}\w+\s*\(", text)
     if len(tokens) != len(signatures):           # a declaration the pattern above did not read (or read twice)
         missed = sorted({t.rstrip("( \t\n") for t in tokens} - set(signatures)) or "a duplicate"
-        raise ConformerHipError(f"{HEADER_PATH}: {len(tokens)} `cfm_*(` tokens but {len(signatures)} declarations read: {missed}")
-    constants = re.findall(r"^[ \t]*#[ \t]*define[ \t]+(CFM_\w+)[ \t]+(-?\d+)[ \t]*$", text, flags=re.M)
-    constants += re.findall(r"^[ \t]*(CFM_\w+)[ \t]*=[ \t]*(-?\d+)[ \t]*,?[ \t]*$", text, flags=re.M)
+        raise ConformerHipError(f"{HEADER_PATH}: {len(tokens)} `{prefix}*(` tokens but {len(signatures)} declarations read: "
+                                f"{missed}")
+    constants = re.findall(rf"^[ \t]*#[ \t]*define[ \t]+({define}\w+)[ \t]+(-?\d+)[ \t]*$", text, flags=re.M)
+    constants += re.findall(rf"^[ \t]*({define}\w+)[ \t]*=[ \t]*(-?\d+)[ \t]*,?[ \t]*$", text, flags=re.M)
     return signatures, params, {k: int(v) for k, v in constants}
 
 
@@ -79,12 +92,12 @@ class Header(NamedTuple):
     constants: dict
 
 
-def read_header(path: str, earlier=()) -> Header:
+def read_header(path: str, earlier=(), prefix: str = "cfm_") -> Header:
     """Parse the header at `path`; a name it shares with `earlier` (the entries of the headers read before it) is an error."""
     if not os.path.exists(path):
         raise ConformerHipError(f"{path} is missing: the ctypes binding is derived from it")
     with open(path) as f:
-        header = Header(path, *parse_header(f.read()))
+        header = Header(path, *parse_header(f.read(), prefix))
     if set(header.signatures) & set(earlier):
         raise ConformerHipError(f"{path} declares again: {sorted(set(header.signatures) & set(earlier))}")
     return header
@@ -100,6 +113,16 @@ for _name in (MAIN_HEADER, *EXTENSION_HEADERS):
 SIGNATURES = HEADERS[MAIN_HEADER].signatures      # the main header's entries
 CONSTANTS = HEADERS[MAIN_HEADER].constants        # ... and its defines and status codes
 ABI_VERSION = CONSTANTS["CFM_ABI_VERSION"]        # checked in load()
+
+EXTRA: dict = {}          # path -> Header of the second-generation headers, in the order of EXTRA_HEADERS
+EXTRA_ENTRIES: dict = {}  # name -> (restype, [argtypes]): bound by `load` after ENTRIES
+EXTRA_PARAMS: dict = {}   # name -> [parameter names]
+EXTRA_CONSTANTS: dict = {}  # basename -> the header's own CFM2_* defines
+for _path in EXTRA_HEADERS:
+    EXTRA[_path] = read_header(_path, EXTRA_ENTRIES, EXTRA_PREFIX)
+    EXTRA_ENTRIES.update(EXTRA[_path].signatures)
+    EXTRA_PARAMS.update(EXTRA[_path].params)
+    EXTRA_CONSTANTS[os.path.basename(_path)] = EXTRA[_path].constants
 
 
 def header_of(name: str) -> str:
@@ -140,6 +163,14 @@ def load() -> ctypes.CDLL:
                                         "`python -m conformer_amd.build`")
             fn.restype = res
             fn.argtypes = args
+    for path, header in EXTRA.items():                # the second generation, after the first
+        for name, (res, args) in header.signatures.items():
+            fn = getattr(lib, name, None)
+            if fn is None:
+                raise ConformerHipError(f"{LIB_PATH} lacks {name} (csrc/{os.path.basename(path)}): rebuild it with "
+                                        "`python -m conformer_amd.build`")
+            fn.restype = res
+            fn.argtypes = args
     _lib = lib
     return lib
 
@@ -170,6 +201,7 @@ def call(name: str, *args) -> None:
         status = getattr(lib, name)(*args)
     except ctypes.ArgumentError as e:
         i = int(re.search(r"argument (\d+)", str(e)).group(1))
-        raise ConformerHipError(f"{name}: argument {i} (`{PARAMS[name][i - 1]}`) has the wrong Python type: {e}") from None
+        names = PARAMS.get(name) or EXTRA_PARAMS[name]
+        raise ConformerHipError(f"{name}: argument {i} (`{names[i - 1]}`) has the wrong Python type: {e}") from None
     if status:
         raise ConformerHipError(f"{name} failed: {lib.cfm_strerror(status).decode()} (status {status})")

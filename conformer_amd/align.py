@@ -1,7 +1,8 @@
 """CTC forced alignment on the device: token and word timestamps (INTEGRATION.md "Forced alignment").
 
-`ctc_forced_align` aligns known targets to logits: the best path of the CTC lattice (the one the loss sums over), its
-frames, the span and mean log-probability of every target token and the path's log-probability.  `CTCAligner` puts words
+`ctc_forced_align` (T <= 16384 frames, Lmax <= 4096; `ctc_forced_align_long` beyond that) aligns known targets to logits:
+the best path of the CTC lattice (the one the loss sums over), its frames, the span and mean log-probability of every
+target token and the path's log-probability.  `CTCAligner` puts words
 on top: texts or token ids in, `Word(text, start_frame, end_frame, start, end, score)` out; `CTCAligner.hypotheses` does
 the same for what a `BeamCTCDecoder` search returned.  Timestamps of a finished stream (`StreamingTranscriber`,
 `SlotTranscriber`) come from aligning the final text against the collected logits.
@@ -17,6 +18,8 @@ from . import _lib, ops
 
 MAX_FRAMES = _lib.CONSTANTS["CFM_CTC_ALIGN_MAX_FRAMES"]
 MAX_TARGET = _lib.CONSTANTS["CFM_CTC_ALIGN_MAX_TARGET"]
+LONG_MAX_FRAMES = _lib.EXTRA_CONSTANTS["conformer_hip2_align_long.h"]["CFM2_CTC_ALIGN_LONG_MAX_FRAMES"]
+LONG_MAX_TARGET = _lib.EXTRA_CONSTANTS["conformer_hip2_align_long.h"]["CFM2_CTC_ALIGN_LONG_MAX_TARGET"]
 
 
 class Alignment(NamedTuple):
@@ -39,18 +42,9 @@ class Word(NamedTuple):
     score: float                   # frame-weighted mean of the tokens' scores
 
 
-def ctc_forced_align(logits: torch.Tensor, targets: torch.Tensor, blank_id: int, lengths: Optional[torch.Tensor] = None,
-                     target_lengths: Optional[torch.Tensor] = None) -> Alignment:
-    """Align targets (B,Lmax) int64 (padded, as the CTC loss takes them) to logits (B,T,V) on the HIP device (fp32, or
-    bf16 / fp16 cast to fp32).  `lengths` / `target_lengths` (B) int64 on the device: frames / labels per utterance
-    (clamped to [0,T] / [0,Lmax]; None = all).  The path is the maximum of the sum of raw logits over the lattice's paths,
-    ties resolved to the latest alignment.  An utterance with no frames, or fewer frames than labels plus adjacent
-    repeats, is not an error: ok False, score -inf, padding elsewhere.
-
-    Target ids are clamped to [0,V) on the device, as the loss does (checking them would synchronise with the host); a
-    target equal to `blank_id` is not detected here and is aligned as a label that emits the blank symbol.  CTCAligner,
-    which builds the targets on the host, refuses both.  Logits are expected to be finite.  Nothing synchronises with
-    the host."""
+def _checked(who: str, logits, targets, blank_id, lengths, target_lengths, max_frames: int, max_target: int):
+    """The argument checks both aligners share: (x, y, lengths, target_lengths, B, T, V, L), with one unused target slot
+    where there is none at all (every target length 0 then)."""
     if isinstance(logits, torch.Tensor) and logits.dtype in (torch.bfloat16, torch.float16):
         logits = logits.float()
     x = ops._req(logits, "logits")
@@ -65,32 +59,92 @@ def ctc_forced_align(logits: torch.Tensor, targets: torch.Tensor, blank_id: int,
         raise ValueError(f"blank_id {blank_id} outside [0,{V})")
     if B < 1 or T < 1 or V < 2:
         raise ValueError(f"logits: empty or degenerate shape {tuple(x.shape)}")
-    if T > MAX_FRAMES or L > MAX_TARGET:
-        raise ValueError(f"ctc_forced_align supports T <= {MAX_FRAMES} and Lmax <= {MAX_TARGET}, got T={T}, Lmax={L}")
+    if T > max_frames or L > max_target:
+        raise ValueError(f"{who} supports T <= {max_frames} and Lmax <= {max_target}, got T={T}, Lmax={L}")
     for name, t in (("lengths", lengths), ("target_lengths", target_lengths)):
         if t is not None and tuple(ops._req(t, name, torch.int64).shape) != (B,):
             raise ValueError(f"{name}: expected ({B},), got {tuple(t.shape)}")
     lengths = None if lengths is None else ops._req(lengths, "lengths", torch.int64)
     target_lengths = None if target_lengths is None else ops._req(target_lengths, "target_lengths", torch.int64)
-    dev = x.device
     if L == 0:                                    # no target slot at all: one unused slot, every target length 0
-        y = torch.zeros(B, 1, dtype=torch.int64, device=dev)
-        target_lengths = torch.zeros(B, dtype=torch.int64, device=dev)
+        y = torch.zeros(B, 1, dtype=torch.int64, device=x.device)
+        target_lengths = torch.zeros(B, dtype=torch.int64, device=x.device)
+    return x, y, lengths, target_lengths, B, T, V, L
+
+
+def _outputs(B: int, T: int, lmax: int, dev):
+    return (torch.empty(B, T, dtype=torch.int64, device=dev), torch.empty(B, T, dtype=torch.int64, device=dev),
+            torch.empty(B, lmax, dtype=torch.int64, device=dev), torch.empty(B, lmax, dtype=torch.int64, device=dev),
+            torch.empty(B, lmax, dtype=torch.float32, device=dev), torch.empty(B, dtype=torch.float64, device=dev),
+            torch.empty(B, dtype=torch.bool, device=dev))
+
+
+def ctc_forced_align(logits: torch.Tensor, targets: torch.Tensor, blank_id: int, lengths: Optional[torch.Tensor] = None,
+                     target_lengths: Optional[torch.Tensor] = None) -> Alignment:
+    """Align targets (B,Lmax) int64 (padded, as the CTC loss takes them) to logits (B,T,V) on the HIP device (fp32, or
+    bf16 / fp16 cast to fp32).  `lengths` / `target_lengths` (B) int64 on the device: frames / labels per utterance
+    (clamped to [0,T] / [0,Lmax]; None = all).  The path is the maximum of the sum of raw logits over the lattice's paths,
+    ties resolved to the latest alignment.  An utterance with no frames, or fewer frames than labels plus adjacent
+    repeats, is not an error: ok False, score -inf, padding elsewhere.
+
+    Target ids are clamped to [0,V) on the device, as the loss does (checking them would synchronise with the host); a
+    target equal to `blank_id` is not detected here and is aligned as a label that emits the blank symbol.  CTCAligner,
+    which builds the targets on the host, refuses both.  Logits are expected to be finite.  Nothing synchronises with
+    the host."""
+    x, y, lengths, target_lengths, B, T, V, L = _checked("ctc_forced_align", logits, targets, blank_id, lengths,
+                                                         target_lengths, MAX_FRAMES, MAX_TARGET)
     lmax = max(L, 1)
     lib = _lib.load()
     ws_bytes = int(lib.cfm_ctc_align_workspace_bytes(B, T, lmax))
     if ws_bytes == 0:
         raise ValueError(f"ctc_forced_align: unsupported shape (B={B}, T={T}, Lmax={L})")
-    workspace = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    frame_tokens = torch.empty(B, T, dtype=torch.int64, device=dev)
-    frame_index = torch.empty(B, T, dtype=torch.int64, device=dev)
-    token_start = torch.empty(B, lmax, dtype=torch.int64, device=dev)
-    token_end = torch.empty(B, lmax, dtype=torch.int64, device=dev)
-    token_score = torch.empty(B, lmax, dtype=torch.float32, device=dev)
-    score = torch.empty(B, dtype=torch.float64, device=dev)
-    ok = torch.empty(B, dtype=torch.bool, device=dev)
+    workspace = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
+    frame_tokens, frame_index, token_start, token_end, token_score, score, ok = _outputs(B, T, lmax, x.device)
     _lib.call("cfm_ctc_align_f32", x.data_ptr(), y.data_ptr(), ops._p(lengths), ops._p(target_lengths), B, T, V, lmax,
               int(blank_id), workspace.data_ptr(), ws_bytes, frame_tokens.data_ptr(), frame_index.data_ptr(),
+              token_start.data_ptr(), token_end.data_ptr(), token_score.data_ptr(), score.data_ptr(), ok.data_ptr(), ops._stream())
+    return Alignment(frame_tokens, frame_index, token_start[:, :L], token_end[:, :L], token_score[:, :L], score, ok)
+
+
+def long_workspace_bytes(B: int, T: int, Lmax: int, tile_pairs: Optional[int] = None, chunk_frames: Optional[int] = None,
+                         max_workspace_bytes: int = 16 << 30) -> int:
+    """Bytes of device workspace ctc_forced_align_long takes for a shape (host arithmetic of the library, no device needed).
+    ValueError for a tiling or shape it does not support and for one that needs more than `max_workspace_bytes`."""
+    tp, cf = (0 if v is None else int(v) for v in (tile_pairs, chunk_frames))
+    if (tile_pairs is not None and not (512 <= tp <= 8192 and tp % 512 == 0)) or \
+            (chunk_frames is not None and not (16 <= cf <= 65536 and cf % 16 == 0)):
+        raise ValueError(f"ctc_forced_align_long: tile_pairs must be a multiple of 512 in [512,8192] and chunk_frames a "
+                         f"multiple of 16 in [16,65536] (or None), got {tile_pairs!r}, {chunk_frames!r}")
+    ws_bytes = int(_lib.load().cfm2_ctc_align_long_workspace_bytes(int(B), int(T), int(Lmax), tp, cf))
+    if ws_bytes == 0:
+        raise ValueError(f"ctc_forced_align_long: unsupported shape (B={B}, T={T}, Lmax={Lmax})")
+    if ws_bytes > int(max_workspace_bytes):
+        raise ValueError(f"ctc_forced_align_long: (B={B}, T={T}, Lmax={Lmax}) needs a workspace of {ws_bytes} bytes, "
+                         f"max_workspace_bytes is {int(max_workspace_bytes)}")
+    return ws_bytes
+
+
+def ctc_forced_align_long(logits: torch.Tensor, targets: torch.Tensor, blank_id: int, lengths: Optional[torch.Tensor] = None,
+                          target_lengths: Optional[torch.Tensor] = None, *, tile_pairs: Optional[int] = None,
+                          chunk_frames: Optional[int] = None, max_workspace_bytes: int = 16 << 30) -> Alignment:
+    """ctc_forced_align without its limits (INTEGRATION.md "Long form"): T <= LONG_MAX_FRAMES, Lmax <= LONG_MAX_TARGET, the
+    same arguments, the same Alignment (dtypes, padding, infeasible rows).  The lattice is cut into cells of `tile_pairs`
+    target positions (a multiple of 512 in [512,8192]) x `chunk_frames` frames (a multiple of 16 in [16,65536]); None: the
+    measured defaults.  The tiling changes the time, never the result.  The recursion runs in float64 without re-centring,
+    so for any finite logits the path is that of the float64 recursion on the raw logits, ties included.
+
+    The workspace is dominated by the moves: B * T * ceil((Lmax+1)/tile_pairs) * tile_pairs / 2 bytes (1.4 GB for an hour
+    of audio with 30 000 tokens).  A shape that needs more than `max_workspace_bytes` raises ValueError with the number of
+    bytes it needs.  Nothing synchronises with the host."""
+    x, y, lengths, target_lengths, B, T, V, L = _checked("ctc_forced_align_long", logits, targets, blank_id, lengths,
+                                                         target_lengths, LONG_MAX_FRAMES, LONG_MAX_TARGET)
+    lmax = max(L, 1)
+    ws_bytes = long_workspace_bytes(B, T, lmax, tile_pairs, chunk_frames, max_workspace_bytes)
+    tp, cf = int(tile_pairs or 0), int(chunk_frames or 0)
+    workspace = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
+    frame_tokens, frame_index, token_start, token_end, token_score, score, ok = _outputs(B, T, lmax, x.device)
+    _lib.call("cfm2_ctc_align_long_f32", x.data_ptr(), y.data_ptr(), ops._p(lengths), ops._p(target_lengths), B, T, V, lmax,
+              int(blank_id), tp, cf, workspace.data_ptr(), ws_bytes, frame_tokens.data_ptr(), frame_index.data_ptr(),
               token_start.data_ptr(), token_end.data_ptr(), token_score.data_ptr(), score.data_ptr(), ok.data_ptr(), ops._stream())
     return Alignment(frame_tokens, frame_index, token_start[:, :L], token_end[:, :L], token_score[:, :L], score, ok)
 
@@ -181,8 +235,9 @@ class CTCAligner:
                 raise ValueError(f"target id {i} is outside [0,{len(self.vocab)}) or is the blank id {self.blank_id}")
         return ids
 
-    def align(self, logits: torch.Tensor, targets: Sequence, lengths: Optional[torch.Tensor] = None):
-        """The targets as id lists and the Alignment of ctc_forced_align for them."""
+    def align(self, logits: torch.Tensor, targets: Sequence, lengths: Optional[torch.Tensor] = None, long: bool = False):
+        """The targets as id lists and the Alignment of ctc_forced_align for them (long=True: of ctc_forced_align_long,
+        for recordings beyond MAX_FRAMES / MAX_TARGET)."""
         ids = [self._ids(t) for t in targets]
         if logits.dim() != 3 or logits.shape[0] != len(ids):
             raise ValueError(f"logits: expected ({len(ids)},T,V), got {tuple(logits.shape)}")
@@ -193,7 +248,8 @@ class CTCAligner:
         tlen = torch.tensor([len(i) for i in ids], dtype=torch.int64)
         if lengths is not None and not (isinstance(lengths, torch.Tensor) and lengths.is_cuda):
             lengths = torch.as_tensor(lengths, dtype=torch.int64).reshape(-1).to(logits.device)
-        return ids, ctc_forced_align(logits, padded.to(logits.device), self.blank_id, lengths, tlen.to(logits.device))
+        fn = ctc_forced_align_long if long else ctc_forced_align
+        return ids, fn(logits, padded.to(logits.device), self.blank_id, lengths, tlen.to(logits.device))
 
     def words(self, ids: Sequence[Sequence[int]], al: Alignment) -> List[List[Word]]:
         """Words of every utterance from its Alignment (one device-to-host copy; an infeasible utterance gives [])."""
@@ -207,11 +263,11 @@ class CTCAligner:
         return out
 
     def __call__(self, logits: torch.Tensor, targets: Union[Sequence[str], Sequence[Sequence[int]]],
-                 lengths: Optional[torch.Tensor] = None) -> List[List[Word]]:
+                 lengths: Optional[torch.Tensor] = None, long: bool = False) -> List[List[Word]]:
         single = logits.dim() == 2
         if single:
             logits, targets = logits.unsqueeze(0), [targets]
-        ids, al = self.align(logits, targets, lengths)
+        ids, al = self.align(logits, targets, lengths, long)
         out = self.words(ids, al)
         return out[0] if single else out
 

@@ -17,7 +17,12 @@
 //            run, so every element has one writer: no atomics), a wave per token for the mean, a fixed-order float64
 //            reduction for the utterance score.
 // Latency-bound on the T sequential steps, like the loss; nothing synchronises with the host and nothing is allocated.
+//
+//   long   : the chain for recordings beyond one workgroup's registers (conformer_hip2_align_long.h), further down: the
+//            lattice in cells of tile_pairs x chunk_frames, one workgroup per cell, an anti-diagonal of cells per launch,
+//            float64 state.  It writes the same moves rows, so trace, frames and spans above serve it unchanged.
 #include "cfm_common.h"
+#include "conformer_hip2_align_long.h"
 
 namespace {
 
@@ -376,6 +381,285 @@ size_t align_layout(int B, int T, int Lmax, AlignArgs* a) {
     return lp_bytes + end_bytes + frames * row_bytes;
 }
 
+// ---- long form (conformer_hip2_align_long.h): the chain stage cut into cells, no limit on T or L but memory ----------------
+//
+// The pairs i = 0..L are cut into tiles of tile_pairs, the frames into chunks of chunk_frames; cell (k, c) is ONE workgroup
+// running tile k over chunk c in the workgroup form above (a thread owns 8 pairs, one cross-lane value per step, an LDS word
+// and one barrier per frame between waves).  It needs the tile's state after chunk c - 1 (the carry, rewritten in place:
+// a tile has one cell per launch) and, for every frame t - 1 it steps from, the last label state of tile k - 1 (the edge
+// column, one value per tile and frame).  Launch d runs the cells with k + c = d; (k, c - 1), (k - 1, c) and (k - 1, c - 1)
+// lie on the diagonals d - 1 and d - 2, so the order of the stream provides both: no workgroup ever waits for another.
+//
+// The state is float64 and is never re-centred: a value is e + max(...) over doubles converted once from the fp32 logits,
+// the very additions and comparisons of the float64 restatement, so the moves are the restatement's for any finite input.
+//
+// Dead cells are skipped by the whole workgroup; they store -inf in their carry and edge slice and no moves.
+//   front-dead: the cell's first pair lies beyond its last frame.  Pair i cannot be entered before frame i (one pair per
+//               step at the most), so every true value in the cell IS -inf: nothing changes.
+//   back-dead : the cell's last pair at its first frame is more than the remaining frames away from pair L - 1, so no
+//               state of the cell lies on a path that reaches the end.
+// Why the second is safe: call a (frame, state) live when it lies on some path from the start to the end.  Every
+// predecessor of a live state on such a path is live too, and a state that can reach the end makes every state that can
+// move into it able to reach the end: the states that cannot reach the end are closed under "successor of", so lowering
+// them to -inf changes only values of states that cannot reach the end either.  The trace starts at a live state and only
+// ever steps to the predecessor a live state chose among values that are all unchanged or lowered dead ones (which lose
+// to the live maximum exactly as before, or tie at -inf where no predecessor is live, which a live state never has).
+// So the traced path and every value on it are those of the full lattice.
+
+struct LongArgs {
+    AlignArgs a;
+    double* carry;                   // (B, n_tiles, 2, tile_pairs): blank states, then label states, after the tile's last chunk
+    double* edge;                    // (B, n_tiles, T): the tile's last label state after every frame
+    int* flags;                      // (B) 1: the target fits the frames
+    int tile_pairs, chunk_frames, n_tiles, n_chunks;
+};
+
+constexpr double NEG_INF64 = -__builtin_inf();
+constexpr int LONG_P = 8;
+
+__global__ __launch_bounds__(256) void align_long_feasible_kernel(const LongArgs g) {
+    __shared__ int part[4];
+    const AlignArgs& a = g.a;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    int Tb, Lb; int64_t off;
+    align_geometry(a, b, Tb, Lb, off);
+    int repeats = 0;
+    for (int i = 1 + tid; i < Lb; i += 256) repeats += align_label(a, off, i) == align_label(a, off, i - 1) ? 1 : 0;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) repeats += __shfl_xor(repeats, o, 64);
+    if ((tid & 63) == 0) part[tid >> 6] = repeats;
+    __syncthreads();
+    if (tid == 0) {
+        repeats = part[0] + part[1] + part[2] + part[3];
+        const bool fits = !(Tb == 0 || Tb < Lb + repeats);
+        g.flags[b] = fits ? 1 : 0;
+        a.end_state[b] = -1;                                             // a feasible row: align_long_end_kernel
+    }
+}
+
+// WAVES: the most waves of a workgroup (tile_pairs / 512 <= WAVES); it sets the register budget and with it the prefetch depth
+template <int WAVES>
+__global__ __launch_bounds__(64 * WAVES) void align_long_cell_kernel(const LongArgs g, const int diag, const int k_lo) {
+    constexpr int P = LONG_P, U = WAVES == 1 ? 8 : (WAVES <= 8 ? 4 : 2);
+    constexpr bool WG = WAVES > 1;
+    __shared__ double edge_lds[2][WAVES];                                // last label state of each wave, double-buffered
+    const AlignArgs& a = g.a;
+    const int b = blockIdx.y, k = k_lo + (int)blockIdx.x, c = diag - k;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, threads = (int)blockDim.x;
+    if (!g.flags[b]) return;
+    int Tb, Lb; int64_t off;
+    align_geometry(a, b, Tb, Lb, off);
+    const int tp = g.tile_pairs;
+    const int t_first = c * g.chunk_frames, i_first = k * tp;
+    if (t_first >= Tb || i_first > Lb) return;                           // beyond the utterance, as every cell that reads this one
+    const int t_end = min(t_first + g.chunk_frames, Tb);                 // exclusive
+    double* carry = g.carry + ((int64_t)b * g.n_tiles + k) * 2 * tp;
+    double* edge_out = g.edge + ((int64_t)b * g.n_tiles + k) * a.T;
+    const double* edge_in = k > 0 ? edge_out - a.T : edge_out;           // tile k - 1 (read for k > 0 only)
+    // dead cells (the argument stands above LongArgs); uniform over the workgroup
+    const bool front_dead = i_first > t_end - 1;
+    const bool back_dead = Lb - 1 - (i_first + tp - 1) > Tb - 1 - t_first;
+    if (front_dead || back_dead) {
+        for (int j = tid; j < 2 * tp; j += threads) carry[j] = NEG_INF64;
+        for (int t = t_first + tid; t < t_end; t += threads) edge_out[t] = NEG_INF64;
+        return;
+    }
+    const int i0 = i_first + tid * P;
+    int col[P];                   // column of the label's logit, in range for threads past the target too
+    bool hop[P];                  // state 2i+1 may be entered from 2i-1
+    {
+        int prv = (i0 >= 1 && i0 - 1 < Lb) ? align_label(a, off, i0 - 1) : -i0;
+#pragma unroll
+        for (int p = 0; p < P; ++p) {
+            const int i = i0 + p;
+            const int lab = i < Lb ? align_label(a, off, i) : -1 - i;   // distinct negatives: never equal to a neighbour
+            hop[p] = (i >= 1) && (i < Lb) && lab != prv;
+            col[p] = lab >= 0 ? lab : a.blank;
+            prv = lab;
+        }
+    }
+    double sb[P], sl[P];          // current value of the thread's blank / label states
+#pragma unroll
+    for (int p = 0; p < P; ++p) {
+        sb[p] = c > 0 ? carry[tid * P + p] : NEG_INF64;
+        sl[p] = c > 0 ? carry[tp + tid * P + p] : NEG_INF64;
+    }
+    const float* x = a.logits + (int64_t)b * a.T * a.V;
+    unsigned char* moves = a.moves + (int64_t)b * a.T * a.row_bytes + (int64_t)k * (tp / 2);
+    float cb[U], cl[U][P], nb[U], nl[U][P];
+    double ce[U], ne[U];          // thread 0: the last label state of tile k - 1 at the frame stepped from
+    auto load_block = [&](int t_from, float (&vb)[U], float (&vl)[U][P], double (&ve)[U]) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int t = min(t_from + u, t_end - 1);                    // clamped to the chunk: its edge values are all written
+            const float* row = x + (int64_t)t * a.V;
+            vb[u] = row[a.blank];
+#pragma unroll
+            for (int p = 0; p < P; ++p) vl[u][p] = row[col[p]];
+            ve[u] = (tid == 0 && k > 0 && t >= 1) ? edge_in[t - 1] : NEG_INF64;
+        }
+    };
+    load_block(t_first, cb, cl, ce);
+    int par = 0;
+    if (WG) {
+        if (lane == 63) edge_lds[0][wave] = sl[P - 1];
+        __syncthreads();
+    }
+    for (int t0 = t_first; t0 < t_end; t0 += U) {
+        load_block(t0 + U, nb, nl, ne);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            if (t0 + u >= t_end) break;                                  // uniform
+            const int t = t0 + u;
+            unsigned bits = 0;
+            if (t == 0) {
+#pragma unroll
+                for (int p = 0; p < P; ++p) {
+                    const int i = i0 + p;
+                    sb[p] = i == 0 ? (double)cb[u] : NEG_INF64;                       // state 0
+                    sl[p] = (i == 0 && Lb > 0) ? (double)cl[u][p] : NEG_INF64;        // state 1
+                }
+            } else {
+                double left = __shfl_up(sl[P - 1], 1, 64);
+                if (lane == 0) left = (WG && wave > 0) ? edge_lds[par][wave - 1] : ce[u];
+                const double eb = (double)cb[u];
+#pragma unroll
+                for (int p = 0; p < P; ++p) {
+                    const int i = i0 + p;
+                    const double ob = sb[p], ol = sl[p];
+                    // ties take the smaller move: a larger move wins only when strictly greater
+                    const unsigned mb = left > ob ? 1u : 0u;
+                    const double vb = (mb ? left : ob) + eb;
+                    unsigned ml = ob > ol ? 1u : 0u;
+                    double best = ml ? ob : ol;
+                    if (hop[p] && left > best) { ml = 2u; best = left; }
+                    const double vl = best + (double)cl[u][p];
+                    sb[p] = i <= Lb ? vb : NEG_INF64;
+                    sl[p] = i < Lb ? vl : NEG_INF64;
+                    bits |= (mb | (ml << 2)) << (4 * p);
+                    left = ol;
+                }
+            }
+            if (WG) {
+                par ^= 1;
+                if (lane == 63) edge_lds[par][wave] = sl[P - 1];
+                __syncthreads();
+            }
+            if (tid == threads - 1) edge_out[t] = sl[P - 1];
+            MoveStore<P>::put(moves + (int64_t)t * a.row_bytes, tid, bits);
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            cb[u] = nb[u];
+            ce[u] = ne[u];
+#pragma unroll
+            for (int p = 0; p < P; ++p) cl[u][p] = nl[u][p];
+        }
+    }
+#pragma unroll
+    for (int p = 0; p < P; ++p) {
+        carry[tid * P + p] = sb[p];
+        carry[tp + tid * P + p] = sl[p];
+    }
+}
+
+// the path ends in state 2L or 2L-1, a tie in 2L: the two values lie in the carries, possibly of two tiles
+__global__ __launch_bounds__(64) void align_long_end_kernel(const LongArgs g) {
+    const AlignArgs& a = g.a;
+    const int b = (int)(blockIdx.x * 64 + threadIdx.x);
+    if (b >= a.B || !g.flags[b]) return;
+    int Tb, Lb; int64_t off;
+    align_geometry(a, b, Tb, Lb, off);
+    const int tp = g.tile_pairs;
+    const double* cr = g.carry + (int64_t)b * g.n_tiles * 2 * tp;
+    const double fb = cr[(int64_t)(Lb / tp) * 2 * tp + Lb % tp];
+    const double fl = Lb > 0 ? cr[(int64_t)((Lb - 1) / tp) * 2 * tp + tp + (Lb - 1) % tp] : NEG_INF64;
+    a.end_state[b] = (Lb > 0 && fl > fb) ? 2 * Lb - 1 : 2 * Lb;
+}
+
+constexpr int LONG_DEFAULT_TILE_PAIRS = 512;           // the fastest pair of profiles/ctc_align_long_bench.json at (90000, 30000):
+constexpr int LONG_DEFAULT_CHUNK_FRAMES = 128;         // one wave per cell (no barrier in the step), 762 launches
+
+struct LongPlan {
+    int tile_pairs, chunk_frames, n_tiles, n_chunks;
+    size_t lp_bytes, end_bytes, carry_bytes, edge_bytes, row_bytes, moves_bytes;
+    size_t total() const { return lp_bytes + end_bytes + carry_bytes + edge_bytes + moves_bytes; }
+};
+
+// the tiling of a shape and the size of every part of its workspace; false: unsupported
+bool align_long_plan(int B, int T, int Lmax, int tile_pairs, int chunk_frames, LongPlan* p) {
+    if (B < 1 || B > 65535 || T < 1 || T > CFM2_CTC_ALIGN_LONG_MAX_FRAMES || Lmax < 1 || Lmax > CFM2_CTC_ALIGN_LONG_MAX_TARGET)
+        return false;
+    if ((int64_t)B * T > ((int64_t)1 << 31)) return false;              // the per-frame kernel: a wave per frame, 4 per workgroup
+    const int l_up = (Lmax + 1 + 511) / 512 * 512, t_up = (T + 15) / 16 * 16;
+    if (tile_pairs == 0) tile_pairs = LONG_DEFAULT_TILE_PAIRS < l_up ? LONG_DEFAULT_TILE_PAIRS : l_up;
+    if (chunk_frames == 0) chunk_frames = LONG_DEFAULT_CHUNK_FRAMES < t_up ? LONG_DEFAULT_CHUNK_FRAMES : t_up;
+    if (tile_pairs < 512 || tile_pairs > 8192 || tile_pairs % 512) return false;
+    if (chunk_frames < 16 || chunk_frames > 65536 || chunk_frames % 16) return false;
+    auto pad = [](size_t n) { return (n + 15) / 16 * 16; };
+    p->tile_pairs = tile_pairs;
+    p->chunk_frames = chunk_frames;
+    p->n_tiles = (Lmax + 1 + tile_pairs - 1) / tile_pairs;
+    p->n_chunks = (T + chunk_frames - 1) / chunk_frames;
+    const size_t frames = (size_t)B * T, tiles = (size_t)B * p->n_tiles;
+    p->lp_bytes = pad(frames * sizeof(double));
+    p->end_bytes = pad((size_t)B * 2 * sizeof(int));
+    p->carry_bytes = tiles * 2 * tile_pairs * sizeof(double);
+    p->edge_bytes = pad(tiles * T * sizeof(double));
+    p->row_bytes = (size_t)p->n_tiles * tile_pairs / 2;
+    p->moves_bytes = frames * p->row_bytes;
+    return true;
+}
+
+int align_long_run(const float* logits, const int64_t* targets, const int64_t* lengths_or_null,
+                   const int64_t* target_lengths_or_null, int B, int T, int V, int Lmax, int blank_id, int tile_pairs,
+                   int chunk_frames, void* workspace, size_t workspace_bytes, int64_t* frame_tokens, int64_t* frame_index,
+                   int64_t* token_start, int64_t* token_end, float* token_score, double* score, unsigned char* ok,
+                   bool chain_only, cfm_stream_t stream) {
+    CFM_REQUIRE(logits && targets && workspace, CFM_ERR_NULL);
+    CFM_REQUIRE(chain_only || (frame_tokens && frame_index && token_start && token_end && token_score && score && ok),
+                CFM_ERR_NULL);
+    CFM_REQUIRE(B > 0 && T > 0 && V >= 2 && Lmax >= 1 && blank_id >= 0 && blank_id < V, CFM_ERR_BAD_SHAPE);
+    LongPlan plan;
+    CFM_REQUIRE(align_long_plan(B, T, Lmax, tile_pairs, chunk_frames, &plan), CFM_ERR_UNSUPPORTED);
+    CFM_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, CFM_ERR_ALIGN);
+    CFM_REQUIRE(workspace_bytes >= plan.total(), CFM_ERR_BAD_SHAPE);
+    LongArgs g{};
+    AlignArgs& a = g.a;
+    a.logits = logits; a.targets = targets; a.in_len = lengths_or_null; a.tgt_len = target_lengths_or_null;
+    char* base = reinterpret_cast<char*>(workspace);
+    a.frame_lp = reinterpret_cast<double*>(base);
+    a.end_state = reinterpret_cast<int*>(base + plan.lp_bytes);
+    g.flags = a.end_state + B;
+    g.carry = reinterpret_cast<double*>(base + plan.lp_bytes + plan.end_bytes);
+    g.edge = reinterpret_cast<double*>(base + plan.lp_bytes + plan.end_bytes + plan.carry_bytes);
+    a.moves = reinterpret_cast<unsigned char*>(base + plan.lp_bytes + plan.end_bytes + plan.carry_bytes + plan.edge_bytes);
+    a.frame_tokens = frame_tokens; a.frame_index = frame_index; a.token_start = token_start; a.token_end = token_end;
+    a.token_score = token_score; a.score = score; a.ok = ok;
+    a.tgt_numel = (int64_t)B * Lmax;
+    a.B = B; a.T = T; a.V = V; a.Lmax = Lmax; a.blank = blank_id;
+    a.P = LONG_P; a.threads = plan.tile_pairs / LONG_P; a.row_bytes = (int)plan.row_bytes;
+    g.tile_pairs = plan.tile_pairs; g.chunk_frames = plan.chunk_frames; g.n_tiles = plan.n_tiles; g.n_chunks = plan.n_chunks;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const dim3 per_row((unsigned)B), block((unsigned)a.threads);
+    hipLaunchKernelGGL(align_long_feasible_kernel, per_row, dim3(256), 0, s, g);
+    for (int d = 0; d < plan.n_tiles + plan.n_chunks - 1; ++d) {         // one launch per anti-diagonal k + c = d
+        const int k_lo = d > plan.n_chunks - 1 ? d - (plan.n_chunks - 1) : 0, k_hi = d < plan.n_tiles - 1 ? d : plan.n_tiles - 1;
+        const dim3 grid((unsigned)(k_hi - k_lo + 1), (unsigned)B);
+        if (a.threads == 64) hipLaunchKernelGGL((align_long_cell_kernel<1>), grid, block, 0, s, g, d, k_lo);
+        else if (a.threads <= 512) hipLaunchKernelGGL((align_long_cell_kernel<8>), grid, block, 0, s, g, d, k_lo);
+        else hipLaunchKernelGGL((align_long_cell_kernel<16>), grid, block, 0, s, g, d, k_lo);
+    }
+    hipLaunchKernelGGL(align_long_end_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, g);
+    if (chain_only) return cfm_launch_status();
+    hipLaunchKernelGGL(align_trace_kernel, per_row, dim3(64), 0, s, a);
+    const int64_t frames = (int64_t)B * T;
+    hipLaunchKernelGGL(align_frame_kernel, dim3((unsigned)((frames + 3) / 4)), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(align_span_kernel, per_row, dim3(256), 0, s, a);
+    return cfm_launch_status();
+}
+
 }  // namespace
 
 extern "C" size_t cfm_ctc_align_workspace_bytes(int B, int T, int Lmax) {
@@ -418,4 +702,33 @@ extern "C" int cfm_ctc_align_f32(const float* logits, const int64_t* targets, co
     hipLaunchKernelGGL(align_frame_kernel, dim3((unsigned)((frames + 3) / 4)), dim3(256), 0, s, a);
     hipLaunchKernelGGL(align_span_kernel, grid, dim3(256), 0, s, a);
     return cfm_launch_status();
+}
+
+extern "C" size_t cfm2_ctc_align_long_workspace_bytes(int B, int T, int Lmax, int tile_pairs, int chunk_frames) {
+    LongPlan plan;
+    return align_long_plan(B, T, Lmax, tile_pairs, chunk_frames, &plan) ? plan.total() : 0;
+}
+
+extern "C" int cfm2_ctc_align_long_launches(int T, int Lmax, int tile_pairs, int chunk_frames) {
+    LongPlan plan;
+    return align_long_plan(1, T, Lmax, tile_pairs, chunk_frames, &plan) ? plan.n_tiles + plan.n_chunks - 1 : 0;
+}
+
+extern "C" int cfm2_ctc_align_long_f32(const float* logits, const int64_t* targets, const int64_t* lengths_or_null,
+                                       const int64_t* target_lengths_or_null, int B, int T, int V, int Lmax, int blank_id,
+                                       int tile_pairs, int chunk_frames, void* workspace, size_t workspace_bytes,
+                                       int64_t* frame_tokens, int64_t* frame_index, int64_t* token_start, int64_t* token_end,
+                                       float* token_score, double* score, unsigned char* ok, cfm_stream_t stream) {
+    return align_long_run(logits, targets, lengths_or_null, target_lengths_or_null, B, T, V, Lmax, blank_id, tile_pairs,
+                          chunk_frames, workspace, workspace_bytes, frame_tokens, frame_index, token_start, token_end,
+                          token_score, score, ok, false, stream);
+}
+
+extern "C" int cfm2_ctc_align_long_chain_f32(const float* logits, const int64_t* targets, const int64_t* lengths_or_null,
+                                             const int64_t* target_lengths_or_null, int B, int T, int V, int Lmax,
+                                             int blank_id, int tile_pairs, int chunk_frames, void* workspace,
+                                             size_t workspace_bytes, cfm_stream_t stream) {
+    return align_long_run(logits, targets, lengths_or_null, target_lengths_or_null, B, T, V, Lmax, blank_id, tile_pairs,
+                          chunk_frames, workspace, workspace_bytes, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                          nullptr, true, stream);
 }

@@ -8,8 +8,10 @@ in which it has the most context on both sides.  The decoder head, the beam sear
 stitched frames of the whole recording, so word times are global by construction.
 
 Three layers: window_plan (host arithmetic), BufferedEncoder (mel frames in, stitched encoder frames out) and Transcriber
-(waveforms or mel frames in, Transcripts out).  There is no kernel of its own in here: the hot path is Encoder.forward, the
-decoder head and the search, which are gfx950 kernels already; the plan, the batching and the stitching are slices and copies.
+(waveforms or mel frames in, Transcripts out).  Transcriber.align puts a KNOWN transcript on the time axis of a whole recording
+(align.ctc_forced_align_long on the stitched frames) and cut_utterances cuts the aligned words into training utterances.
+There is no kernel of its own in here: the hot path is Encoder.forward, the decoder head, the search and the aligner, which
+are gfx950 kernels already; the plan, the batching and the stitching are slices and copies.
 """
 from __future__ import annotations
 
@@ -18,7 +20,7 @@ from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
-from .align import Word
+from .align import CTCAligner, Word
 from .confidence import ConfidenceConfig, frame_confidence, transcriber_confidence, word_confidence
 from .decode import BeamCTCDecoder
 from .frontend import ConformerAudioFrontend
@@ -216,6 +218,58 @@ class Transcript(NamedTuple):
     seconds: float
 
 
+class Aligned(NamedTuple):
+    """words: the transcript's align.Words with global times ([] when the text does not fit the frames); score: the sum over the
+    frames of the log-probability of the aligned symbol (-inf when it does not fit); ok: it fits; frames, seconds: as Transcript."""
+    words: List[Word]
+    score: float
+    ok: bool
+    frames: int
+    seconds: float
+
+
+class Utterance(NamedTuple):
+    """A run of aligned words cut out for training: start / end in seconds, the words [first_word, last_word] of the list it was
+    cut from joined by a space, and the mean of their scores weighted by their frames."""
+    start: float
+    end: float
+    text: str
+    score: float
+    first_word: int
+    last_word: int                       # inclusive
+
+
+def cut_utterances(words: Sequence[Word], max_seconds: float, min_gap_seconds: float) -> List[Utterance]:
+    """Cut the aligned words of a recording into utterances (host arithmetic, for corpus building).
+    1. Split wherever next.start - prev.end >= min_gap_seconds.
+    2. Split any piece longer than max_seconds (last end - first start) at its largest internal gap, the earliest of equal
+       ones; repeat until every piece fits or is a single word (a single word longer than max_seconds stands as it is).
+    The pieces are returned in order; together they hold every word once."""
+    for name, v in (("max_seconds", max_seconds), ("min_gap_seconds", min_gap_seconds)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v <= 0:
+            raise ValueError(f"cut_utterances: {name} must be a positive finite number of seconds, got {v!r}")
+    words = list(words)
+    pieces, first = [], 0
+    for i in range(1, len(words) + 1):
+        if i == len(words) or words[i].start - words[i - 1].end >= min_gap_seconds:
+            pieces.append((first, i - 1))
+            first = i
+    out: List[Utterance] = []
+    stack = pieces[::-1] if words else []
+    while stack:
+        lo, hi = stack.pop()
+        if hi > lo and words[hi].end - words[lo].start > max_seconds:
+            gaps = [words[i + 1].start - words[i].end for i in range(lo, hi)]
+            cut = lo + gaps.index(max(gaps))                     # index() takes the earliest of equal gaps
+            stack += [(cut + 1, hi), (lo, cut)]
+            continue
+        frames = [w.end_frame - w.start_frame for w in words[lo:hi + 1]]
+        total = sum(frames)
+        score = sum(w.score * f for w, f in zip(words[lo:hi + 1], frames)) / total if total > 0 else -math.inf
+        out.append(Utterance(words[lo].start, words[hi].end, " ".join(w.text for w in words[lo:hi + 1]), score, lo, hi))
+    return out
+
+
 class Transcriber:
     """Offline transcription: a list of recordings in, a list of Transcripts out, in the caller's order.
 
@@ -305,4 +359,37 @@ class Transcriber:
                 scores = word_confidence(words, conf, ids, self.decoder.blank_id, lengths, self.confidence)
             for k, i in enumerate(group):
                 out[i] = Transcript(texts[k], words[k], scores[k], n[k], mels[i].shape[1] * self.mel_seconds)
+        return out
+
+    @torch.no_grad()
+    def align(self, audios: Sequence[torch.Tensor], texts: Sequence, sample_rates: Optional[Sequence[int]] = None) -> List[Aligned]:
+        """Forced alignment of whole recordings: `texts` holds one transcript per recording, strings or token-id sequences as
+        CTCAligner takes them.  Same pipeline as transcribe up to the logits (front end, BufferedEncoder.encode, decoder_head on
+        the stitched frames in the same groups), then CTCAligner.from_decoder(decoder, frame_seconds) with long=True: no limit
+        on the recording's length but the workspace (align.ctc_forced_align_long).  One Aligned per recording, in the caller's
+        order.  Synchronises (the words are read back)."""
+        lstm_state(self.model, "Transcriber", 1)
+        _ambient_autocast("Transcriber")
+        if isinstance(texts, str) or len(texts) != len(audios):
+            raise ValueError(f"Transcriber.align: one text per recording, got {len(audios)} recordings and "
+                             f"{'a single string' if isinstance(texts, str) else f'{len(texts)} texts'}")
+        if len(audios) == 0:
+            return []
+        aligner = CTCAligner.from_decoder(self.decoder, self.frame_seconds)
+        targets = [aligner._ids(t) for t in texts]                   # refuses a bad text before anything runs
+        mels = self.features(audios, sample_rates)
+        hs = self.encoder.encode(mels)
+        out: List[Optional[Aligned]] = [None] * len(hs)
+        for group in self.groups([h.shape[0] for h in hs]):
+            n = [hs[i].shape[0] for i in group]
+            h = hs[group[0]].new_zeros(len(group), n[0], hs[group[0]].shape[1])
+            for k, i in enumerate(group):
+                h[k, :n[k]] = hs[i]
+            lengths = torch.tensor(n, dtype=torch.int64).to(self.device, non_blocking=True)
+            logits = self.decoder_head(h, lengths)
+            ids, al = aligner.align(logits, [targets[i] for i in group], lengths, long=True)
+            words = aligner.words(ids, al)
+            ok, score = al.ok.cpu().tolist(), al.score.cpu().tolist()
+            for k, i in enumerate(group):
+                out[i] = Aligned(words[k], score[k], bool(ok[k]), n[k], mels[i].shape[1] * self.mel_seconds)
         return out

@@ -8,7 +8,13 @@ non-zero status, raises.  Nothing here imports the CPU oracle.
 
 That table is the first generation and is closed.  Families added after it are the second generation (EXTRA_HEADERS: symbols
 cfm2_*, defines CFM2_*, one header per family in conformer_amd/csrc/), parsed by the same parser into EXTRA_ENTRIES, EXTRA_PARAMS
-and EXTRA_CONSTANTS and bound by `load` after the first, with the same refusal of a library that lacks one.
+and EXTRA_CONSTANTS and bound by `load` after the first, with the same refusal of a library that lacks one.  That table is
+closed too (one family, CTC forced alignment without a length limit).
+
+The third generation is OPEN: every conformer_amd/csrc/conformer_hip3_<family>.h (symbols cfm3_*, defines CFM3_*) is discovered
+from the directory, in sorted order, parsed into OPEN_ENTRIES, OPEN_PARAMS and OPEN_CONSTANTS and bound by `load` after the
+second generation.  A new family is its header in csrc/ and its `extern "C"` definitions in a .hip file there: no list here or
+anywhere else names it.
 """
 from __future__ import annotations
 
@@ -43,6 +49,10 @@ EXTRA_HEADERS = (
     os.path.join(_HERE, "csrc", "conformer_hip2_align_long.h"),     # CTC forced alignment without a length limit
 )
 EXTRA_PREFIX = "cfm2_"
+# third generation, open: whatever conformer_hip3_*.h lies beside the kernels
+OPEN_PREFIX = "cfm3_"
+OPEN_HEADERS = tuple(sorted(os.path.join(_HERE, "csrc", f) for f in os.listdir(os.path.join(_HERE, "csrc"))
+                            if f.startswith("conformer_hip3_") and f.endswith(".h")))
 
 
 class ConformerHipError(RuntimeError):
@@ -124,6 +134,16 @@ for _path in EXTRA_HEADERS:
     EXTRA_PARAMS.update(EXTRA[_path].params)
     EXTRA_CONSTANTS[os.path.basename(_path)] = EXTRA[_path].constants
 
+OPEN: dict = {}           # path -> Header of the third-generation headers, in the order of OPEN_HEADERS
+OPEN_ENTRIES: dict = {}   # name -> (restype, [argtypes]): bound by `load` after EXTRA_ENTRIES
+OPEN_PARAMS: dict = {}    # name -> [parameter names]
+OPEN_CONSTANTS: dict = {}  # basename -> the header's own CFM3_* defines
+for _path in OPEN_HEADERS:
+    OPEN[_path] = read_header(_path, OPEN_ENTRIES, OPEN_PREFIX)
+    OPEN_ENTRIES.update(OPEN[_path].signatures)
+    OPEN_PARAMS.update(OPEN[_path].params)
+    OPEN_CONSTANTS[os.path.basename(_path)] = OPEN[_path].constants
+
 
 def header_of(name: str) -> str:
     """basename of the header that declares the entry `name`"""
@@ -163,7 +183,7 @@ def load() -> ctypes.CDLL:
                                         "`python -m conformer_amd.build`")
             fn.restype = res
             fn.argtypes = args
-    for path, header in EXTRA.items():                # the second generation, after the first
+    for path, header in (*EXTRA.items(), *OPEN.items()):      # the second generation after the first, then the third
         for name, (res, args) in header.signatures.items():
             fn = getattr(lib, name, None)
             if fn is None:
@@ -201,7 +221,7 @@ def call(name: str, *args) -> None:
         status = getattr(lib, name)(*args)
     except ctypes.ArgumentError as e:
         i = int(re.search(r"argument (\d+)", str(e)).group(1))
-        names = PARAMS.get(name) or EXTRA_PARAMS[name]
+        names = PARAMS.get(name) or EXTRA_PARAMS.get(name) or OPEN_PARAMS[name]
         raise ConformerHipError(f"{name}: argument {i} (`{names[i - 1]}`) has the wrong Python type: {e}") from None
     if status:
         raise ConformerHipError(f"{name} failed: {lib.cfm_strerror(status).decode()} (status {status})")

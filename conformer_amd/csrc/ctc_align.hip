@@ -21,13 +21,19 @@
 //   long   : the chain for recordings beyond one workgroup's registers (conformer_hip2_align_long.h), further down: the
 //            lattice in cells of tile_pairs x chunk_frames, one workgroup per cell, an anti-diagonal of cells per launch,
 //            float64 state.  It writes the same moves rows, so trace, frames and spans above serve it unchanged.
+//
+//   wild   : wildcard target positions (conformer_hip3_align_wild.h): the WILD instantiations of the kernels here.  A frame
+//            pass writes w[t] = row maximum - penalty; a wildcard is the label V of the logits with that column appended,
+//            which are never built: the chains select between the gathered logit and w[t].  WILD = false is the plain code.
 #include "cfm_common.h"
 #include "conformer_hip2_align_long.h"
+#include "conformer_hip3_align_wild.h"
 
 namespace {
 
 struct AlignArgs {
     const float* logits; const int64_t* targets; const int64_t* in_len; const int64_t* tgt_len;
+    const float* wild;               // (B, T) what a wildcard emits: row maximum - penalty (the WILD forms only)
     unsigned char* moves;            // (B, T, row_bytes)
     double* frame_lp;                // (B, T) log-probability of the emitted symbol
     int* end_state;                  // (B) last state of the path, -1: infeasible
@@ -35,6 +41,7 @@ struct AlignArgs {
     float* token_score; double* score; unsigned char* ok;
     int64_t tgt_numel;
     int B, T, V, Lmax, blank, P, threads, row_bytes;
+    float penalty;                   // wildcard_penalty (the WILD forms only)
 };
 
 constexpr float NEG_INF = -__builtin_inff();
@@ -54,6 +61,12 @@ __device__ __forceinline__ void align_geometry(const AlignArgs& a, int b, int& T
 __device__ __forceinline__ int align_label(const AlignArgs& a, int64_t off, int i) {
     const int64_t v = a.targets[off + i];
     return (int)(v < 0 ? 0 : (v >= a.V ? a.V - 1 : v));
+}
+// WILD (conformer_hip3_align_wild.h): a wildcard is the label V, the column the definition appends; one more label value
+// to `hop`, the repeats and the feasibility test
+template <bool WILD> __device__ __forceinline__ int align_label_w(const AlignArgs& a, int64_t off, int i) {
+    if (WILD && a.targets[off + i] == CFM3_CTC_ALIGN_WILDCARD) return a.V;
+    return align_label(a, off, i);
 }
 
 template <int P> struct MoveStore;       // the 4P move bits of a thread -> its P/2 bytes of the row
@@ -87,7 +100,9 @@ constexpr int RECENTRE_EVERY = 64;       // workgroup form: steps between two re
 
 // Thread tid owns the pairs i = tid*P .. tid*P+P-1: blank state 2i (exists for i <= L) and label state 2i+1 (i < L).
 // WG: several waves per utterance (blockDim.x = a.threads), else one.
-template <int P, bool WG>
+// WILD: wildcard positions (a P-bit mask per thread) emit a.wild[t], prefetched with the block and uniform over the workgroup
+// like the blank column; the emission is a select (made once per prefetched value, off the chain), the moves are the same three.
+template <int P, bool WG, bool WILD = false>
 __global__ __launch_bounds__(WG ? 64 * ALIGN_MAX_WAVES : 64) void align_chain_kernel(const AlignArgs a) {
     constexpr int U = 32 / P > 16 ? 16 : 32 / P;                          // time steps per prefetch block
     __shared__ float edge[2][ALIGN_MAX_WAVES];                            // last label state of each wave, double-buffered
@@ -103,7 +118,7 @@ __global__ __launch_bounds__(WG ? 64 * ALIGN_MAX_WAVES : 64) void align_chain_ke
 #pragma unroll
     for (int p = 0; p < P; ++p) {
         const int i = tid * P + p;
-        lab[p] = i < Lb ? align_label(a, off, i) : -1 - i;               // distinct negatives: never equal to a neighbour
+        lab[p] = i < Lb ? align_label_w<WILD>(a, off, i) : -1 - i;       // distinct negatives: never equal to a neighbour
     }
     int prev_lab = __shfl_up(lab[P - 1], 1, 64);
     if (WG) {
@@ -134,22 +149,43 @@ __global__ __launch_bounds__(WG ? 64 * ALIGN_MAX_WAVES : 64) void align_chain_ke
     }
     int col[P];                   // column of the label's logit, in range for threads past the target too
 #pragma unroll
-    for (int p = 0; p < P; ++p) col[p] = lab[p] >= 0 ? lab[p] : a.blank;
+    for (int p = 0; p < P; ++p) col[p] = (lab[p] >= 0 && !(WILD && lab[p] == a.V)) ? lab[p] : a.blank;
+    unsigned wmask = 0;           // WILD: bit p: pair p is a wildcard
+    if (WILD) {
+#pragma unroll
+        for (int p = 0; p < P; ++p) wmask |= lab[p] == a.V ? 1u << p : 0u;
+    }
 
     const float* x = a.logits + (int64_t)b * a.T * a.V;
+    const float* wrow = WILD ? a.wild + (int64_t)b * a.T : nullptr;
     unsigned char* moves = a.moves + (int64_t)b * a.T * a.row_bytes;
     float sb[P], sl[P];           // current value of the thread's blank / label states
     float cb[U], cl[U][P], nb[U], nl[U][P];
+    float nw[WILD ? U : 1];       // WILD: a.wild[t] of the block in flight
     auto load_block = [&](int t_first, float (&vb)[U], float (&vl)[U][P]) {      // clamped: always in range
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            const float* row = x + (int64_t)min(t_first + u, Tb - 1) * a.V;
+            const int t = min(t_first + u, Tb - 1);
+            const float* row = x + (int64_t)t * a.V;
             vb[u] = row[a.blank];
+            if (WILD) nw[u] = wrow[t];
 #pragma unroll
             for (int p = 0; p < P; ++p) vl[u][p] = row[col[p]];
         }
     };
+    // WILD, the label emission: a select on the thread's mask between the gathered logit and w[t].  It is made where a loaded
+    // block becomes the current one (in place of that copy), so the T dependent steps below are those of the plain chain.
+    auto emission = [&](float gathered, int u, int p) -> float {
+        if (!WILD) return gathered;
+        return ((wmask >> p) & 1u) ? nw[u] : gathered;
+    };
     load_block(0, cb, cl);
+    if (WILD) {
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+#pragma unroll
+            for (int p = 0; p < P; ++p) cl[u][p] = emission(cl[u][p], u, p);
+    }
     int par = 0;
     for (int t0 = 0; t0 < Tb; t0 += U) {
         load_block(t0 + U, nb, nl);
@@ -216,7 +252,7 @@ __global__ __launch_bounds__(WG ? 64 * ALIGN_MAX_WAVES : 64) void align_chain_ke
         for (int u = 0; u < U; ++u) {
             cb[u] = nb[u];
 #pragma unroll
-            for (int p = 0; p < P; ++p) cl[u][p] = nl[u][p];
+            for (int p = 0; p < P; ++p) cl[u][p] = emission(nl[u][p], u, p);
         }
     }
     // the path ends in state 2L or 2L-1, a tie in 2L
@@ -240,6 +276,7 @@ __global__ __launch_bounds__(WG ? 64 * ALIGN_MAX_WAVES : 64) void align_chain_ke
 constexpr int TRACE_WIN = 64;            // frames per window = lanes
 constexpr int TRACE_DW = 10;             // dwords of a row a window can touch: 127 states at any alignment span <= 9
 
+template <bool WILD = false>
 __global__ __launch_bounds__(64) void align_trace_kernel(const AlignArgs a) {
     __shared__ unsigned patch[TRACE_WIN][TRACE_DW + 1];
     const int b = blockIdx.x, lane = threadIdx.x;
@@ -273,12 +310,16 @@ __global__ __launch_bounds__(64) void align_trace_kernel(const AlignArgs a) {
             const int t = t_hi - lane;
             const bool is_label = (mine & 1) != 0;
             const int i = min(mine >> 1, max(Lb - 1, 0));
-            ftok[t] = is_label ? align_label(a, off, i) : a.blank;
+            int tok = is_label ? align_label_w<WILD>(a, off, i) : a.blank;
+            if (WILD && tok == a.V) tok = CFM3_CTC_ALIGN_WILDCARD;
+            ftok[t] = tok;
             fidx[t] = is_label ? i : -1;
         }
     }
 }
 
+// WILD: a wildcard frame (frame_tokens -2) emitted the row maximum: its log-probability is max - lse
+template <bool WILD = false>
 __global__ __launch_bounds__(256) void align_frame_kernel(const AlignArgs a) {
     const int lane = threadIdx.x & 63;
     const int64_t frame = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -299,8 +340,25 @@ __global__ __launch_bounds__(256) void align_frame_kernel(const AlignArgs a) {
     if (lane == 0) {
         const int64_t tok = a.frame_tokens[frame];
         const int c = (int)(tok < 0 ? 0 : (tok >= a.V ? a.V - 1 : tok));
-        a.frame_lp[frame] = (double)r[c] - lse;
+        a.frame_lp[frame] = ((WILD && tok == CFM3_CTC_ALIGN_WILDCARD) ? (double)m : (double)r[c]) - lse;
     }
+}
+
+// The frame pass in front of a WILD chain, one wave per frame: w[b,t] = fl32(row maximum - penalty), the blank column included.
+// Frames beyond the utterance's length are left unwritten: the chain clamps its reads to the frames before them.
+__global__ __launch_bounds__(256) void align_wild_kernel(const AlignArgs a, float* wild) {
+    const int lane = threadIdx.x & 63;
+    const int64_t frame = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (frame >= (int64_t)a.B * a.T) return;
+    const int b = (int)(frame / a.T), t = (int)(frame - (int64_t)b * a.T);
+    int Tb, Lb; int64_t off;
+    align_geometry(a, b, Tb, Lb, off);
+    if (t >= Tb) return;
+    const float* r = a.logits + frame * a.V;
+    float m = NEG_INF;
+    for (int c = lane; c < a.V; c += 64) m = fmaxf(m, r[c]);
+    m = wave_max(m);
+    if (lane == 0) wild[frame] = m - a.penalty;
 }
 
 __global__ __launch_bounds__(256) void align_span_kernel(const AlignArgs a) {
@@ -417,6 +475,7 @@ struct LongArgs {
 constexpr double NEG_INF64 = -__builtin_inf();
 constexpr int LONG_P = 8;
 
+template <bool WILD = false>
 __global__ __launch_bounds__(256) void align_long_feasible_kernel(const LongArgs g) {
     __shared__ int part[4];
     const AlignArgs& a = g.a;
@@ -424,7 +483,8 @@ __global__ __launch_bounds__(256) void align_long_feasible_kernel(const LongArgs
     int Tb, Lb; int64_t off;
     align_geometry(a, b, Tb, Lb, off);
     int repeats = 0;
-    for (int i = 1 + tid; i < Lb; i += 256) repeats += align_label(a, off, i) == align_label(a, off, i - 1) ? 1 : 0;
+    for (int i = 1 + tid; i < Lb; i += 256)
+        repeats += align_label_w<WILD>(a, off, i) == align_label_w<WILD>(a, off, i - 1) ? 1 : 0;
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) repeats += __shfl_xor(repeats, o, 64);
     if ((tid & 63) == 0) part[tid >> 6] = repeats;
@@ -438,7 +498,8 @@ __global__ __launch_bounds__(256) void align_long_feasible_kernel(const LongArgs
 }
 
 // WAVES: the most waves of a workgroup (tile_pairs / 512 <= WAVES); it sets the register budget and with it the prefetch depth
-template <int WAVES>
+// WILD: as in align_chain_kernel: a P-bit mask of the thread's wildcard pairs, a.wild[t] prefetched with the block, a select
+template <int WAVES, bool WILD = false>
 __global__ __launch_bounds__(64 * WAVES) void align_long_cell_kernel(const LongArgs g, const int diag, const int k_lo) {
     constexpr int P = LONG_P, U = WAVES == 1 ? 8 : (WAVES <= 8 ? 4 : 2);
     constexpr bool WG = WAVES > 1;
@@ -467,14 +528,16 @@ __global__ __launch_bounds__(64 * WAVES) void align_long_cell_kernel(const LongA
     const int i0 = i_first + tid * P;
     int col[P];                   // column of the label's logit, in range for threads past the target too
     bool hop[P];                  // state 2i+1 may be entered from 2i-1
+    unsigned wmask = 0;           // WILD: bit p: pair p is a wildcard
     {
-        int prv = (i0 >= 1 && i0 - 1 < Lb) ? align_label(a, off, i0 - 1) : -i0;
+        int prv = (i0 >= 1 && i0 - 1 < Lb) ? align_label_w<WILD>(a, off, i0 - 1) : -i0;
 #pragma unroll
         for (int p = 0; p < P; ++p) {
             const int i = i0 + p;
-            const int lab = i < Lb ? align_label(a, off, i) : -1 - i;   // distinct negatives: never equal to a neighbour
+            const int lab = i < Lb ? align_label_w<WILD>(a, off, i) : -1 - i;   // distinct negatives: never equal to a neighbour
             hop[p] = (i >= 1) && (i < Lb) && lab != prv;
-            col[p] = lab >= 0 ? lab : a.blank;
+            col[p] = (lab >= 0 && !(WILD && lab == a.V)) ? lab : a.blank;
+            if (WILD) wmask |= lab == a.V ? 1u << p : 0u;
             prv = lab;
         }
     }
@@ -486,7 +549,9 @@ __global__ __launch_bounds__(64 * WAVES) void align_long_cell_kernel(const LongA
     }
     const float* x = a.logits + (int64_t)b * a.T * a.V;
     unsigned char* moves = a.moves + (int64_t)b * a.T * a.row_bytes + (int64_t)k * (tp / 2);
+    const float* wrow = WILD ? a.wild + (int64_t)b * a.T : nullptr;
     float cb[U], cl[U][P], nb[U], nl[U][P];
+    float nw[WILD ? U : 1];       // WILD: a.wild[t] of the block in flight
     double ce[U], ne[U];          // thread 0: the last label state of tile k - 1 at the frame stepped from
     auto load_block = [&](int t_from, float (&vb)[U], float (&vl)[U][P], double (&ve)[U]) {
 #pragma unroll
@@ -494,12 +559,24 @@ __global__ __launch_bounds__(64 * WAVES) void align_long_cell_kernel(const LongA
             const int t = min(t_from + u, t_end - 1);                    // clamped to the chunk: its edge values are all written
             const float* row = x + (int64_t)t * a.V;
             vb[u] = row[a.blank];
+            if (WILD) nw[u] = wrow[t];
 #pragma unroll
             for (int p = 0; p < P; ++p) vl[u][p] = row[col[p]];
             ve[u] = (tid == 0 && k > 0 && t >= 1) ? edge_in[t - 1] : NEG_INF64;
         }
     };
+    // WILD, the label emission: as in align_chain_kernel, selected where a loaded block becomes the current one
+    auto emission = [&](float gathered, int u, int p) -> float {
+        if (!WILD) return gathered;
+        return ((wmask >> p) & 1u) ? nw[u] : gathered;
+    };
     load_block(t_first, cb, cl, ce);
+    if (WILD) {
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+#pragma unroll
+            for (int p = 0; p < P; ++p) cl[u][p] = emission(cl[u][p], u, p);
+    }
     int par = 0;
     if (WG) {
         if (lane == 63) edge_lds[0][wave] = sl[P - 1];
@@ -554,7 +631,7 @@ __global__ __launch_bounds__(64 * WAVES) void align_long_cell_kernel(const LongA
             cb[u] = nb[u];
             ce[u] = ne[u];
 #pragma unroll
-            for (int p = 0; p < P; ++p) cl[u][p] = nl[u][p];
+            for (int p = 0; p < P; ++p) cl[u][p] = emission(nl[u][p], u, p);
         }
     }
 #pragma unroll
@@ -612,19 +689,25 @@ bool align_long_plan(int B, int T, int Lmax, int tile_pairs, int chunk_frames, L
     return true;
 }
 
+size_t wild_bytes(int B, int T) { return ((size_t)B * T * sizeof(float) + 15) / 16 * 16; }     // the w part of a WILD workspace
+bool penalty_ok(float p) { return p >= 0.0f && p <= 3.402823466e38f; }                        // finite, not NaN, not negative
+
+// WILD: the entries of conformer_hip3_align_wild.h (w behind the workspace of the plain form); else `penalty` is not read
+template <bool WILD>
 int align_long_run(const float* logits, const int64_t* targets, const int64_t* lengths_or_null,
-                   const int64_t* target_lengths_or_null, int B, int T, int V, int Lmax, int blank_id, int tile_pairs,
-                   int chunk_frames, void* workspace, size_t workspace_bytes, int64_t* frame_tokens, int64_t* frame_index,
-                   int64_t* token_start, int64_t* token_end, float* token_score, double* score, unsigned char* ok,
-                   bool chain_only, cfm_stream_t stream) {
+                   const int64_t* target_lengths_or_null, int B, int T, int V, int Lmax, int blank_id, float penalty,
+                   int tile_pairs, int chunk_frames, void* workspace, size_t workspace_bytes, int64_t* frame_tokens,
+                   int64_t* frame_index, int64_t* token_start, int64_t* token_end, float* token_score, double* score,
+                   unsigned char* ok, bool chain_only, cfm_stream_t stream) {
     CFM_REQUIRE(logits && targets && workspace, CFM_ERR_NULL);
     CFM_REQUIRE(chain_only || (frame_tokens && frame_index && token_start && token_end && token_score && score && ok),
                 CFM_ERR_NULL);
     CFM_REQUIRE(B > 0 && T > 0 && V >= 2 && Lmax >= 1 && blank_id >= 0 && blank_id < V, CFM_ERR_BAD_SHAPE);
+    CFM_REQUIRE(!WILD || penalty_ok(penalty), CFM_ERR_BAD_SHAPE);
     LongPlan plan;
     CFM_REQUIRE(align_long_plan(B, T, Lmax, tile_pairs, chunk_frames, &plan), CFM_ERR_UNSUPPORTED);
     CFM_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, CFM_ERR_ALIGN);
-    CFM_REQUIRE(workspace_bytes >= plan.total(), CFM_ERR_BAD_SHAPE);
+    CFM_REQUIRE(workspace_bytes >= plan.total() + (WILD ? wild_bytes(B, T) : 0), CFM_ERR_BAD_SHAPE);
     LongArgs g{};
     AlignArgs& a = g.a;
     a.logits = logits; a.targets = targets; a.in_len = lengths_or_null; a.tgt_len = target_lengths_or_null;
@@ -643,20 +726,73 @@ int align_long_run(const float* logits, const int64_t* targets, const int64_t* l
     g.tile_pairs = plan.tile_pairs; g.chunk_frames = plan.chunk_frames; g.n_tiles = plan.n_tiles; g.n_chunks = plan.n_chunks;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const dim3 per_row((unsigned)B), block((unsigned)a.threads);
-    hipLaunchKernelGGL(align_long_feasible_kernel, per_row, dim3(256), 0, s, g);
+    const int64_t frames = (int64_t)B * T;
+    if (WILD) {
+        float* wild = reinterpret_cast<float*>(base + plan.total());
+        a.wild = wild; a.penalty = penalty;
+        hipLaunchKernelGGL(align_wild_kernel, dim3((unsigned)((frames + 3) / 4)), dim3(256), 0, s, a, wild);
+    }
+    hipLaunchKernelGGL(align_long_feasible_kernel<WILD>, per_row, dim3(256), 0, s, g);
     for (int d = 0; d < plan.n_tiles + plan.n_chunks - 1; ++d) {         // one launch per anti-diagonal k + c = d
         const int k_lo = d > plan.n_chunks - 1 ? d - (plan.n_chunks - 1) : 0, k_hi = d < plan.n_tiles - 1 ? d : plan.n_tiles - 1;
         const dim3 grid((unsigned)(k_hi - k_lo + 1), (unsigned)B);
-        if (a.threads == 64) hipLaunchKernelGGL((align_long_cell_kernel<1>), grid, block, 0, s, g, d, k_lo);
-        else if (a.threads <= 512) hipLaunchKernelGGL((align_long_cell_kernel<8>), grid, block, 0, s, g, d, k_lo);
-        else hipLaunchKernelGGL((align_long_cell_kernel<16>), grid, block, 0, s, g, d, k_lo);
+        if (a.threads == 64) hipLaunchKernelGGL((align_long_cell_kernel<1, WILD>), grid, block, 0, s, g, d, k_lo);
+        else if (a.threads <= 512) hipLaunchKernelGGL((align_long_cell_kernel<8, WILD>), grid, block, 0, s, g, d, k_lo);
+        else hipLaunchKernelGGL((align_long_cell_kernel<16, WILD>), grid, block, 0, s, g, d, k_lo);
     }
     hipLaunchKernelGGL(align_long_end_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, g);
     if (chain_only) return cfm_launch_status();
-    hipLaunchKernelGGL(align_trace_kernel, per_row, dim3(64), 0, s, a);
-    const int64_t frames = (int64_t)B * T;
-    hipLaunchKernelGGL(align_frame_kernel, dim3((unsigned)((frames + 3) / 4)), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(align_trace_kernel<WILD>, per_row, dim3(64), 0, s, a);
+    hipLaunchKernelGGL(align_frame_kernel<WILD>, dim3((unsigned)((frames + 3) / 4)), dim3(256), 0, s, a);
     hipLaunchKernelGGL(align_span_kernel, per_row, dim3(256), 0, s, a);
+    return cfm_launch_status();
+}
+
+size_t align_wild_offset(int B, int T, int Lmax) { return (align_layout(B, T, Lmax, nullptr) + 15) / 16 * 16; }
+
+template <bool WILD>
+int align_run(const float* logits, const int64_t* targets, const int64_t* lengths_or_null,
+              const int64_t* target_lengths_or_null, int B, int T, int V, int Lmax, int blank_id, float penalty,
+              void* workspace, size_t workspace_bytes, int64_t* frame_tokens, int64_t* frame_index,
+              int64_t* token_start, int64_t* token_end, float* token_score, double* score,
+              unsigned char* ok, cfm_stream_t stream) {
+    CFM_REQUIRE(logits && targets && workspace && frame_tokens && frame_index && token_start && token_end && token_score &&
+                score && ok, CFM_ERR_NULL);
+    CFM_REQUIRE(B > 0 && T > 0 && V >= 2 && Lmax >= 1 && blank_id >= 0 && blank_id < V, CFM_ERR_BAD_SHAPE);
+    CFM_REQUIRE(!WILD || penalty_ok(penalty), CFM_ERR_BAD_SHAPE);
+    CFM_REQUIRE(align_in_range(B, T, Lmax), CFM_ERR_UNSUPPORTED);
+    CFM_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, CFM_ERR_ALIGN);
+    AlignArgs a{};
+    a.logits = logits; a.targets = targets; a.in_len = lengths_or_null; a.tgt_len = target_lengths_or_null;
+    a.frame_lp = reinterpret_cast<double*>(workspace);
+    const size_t plain_bytes = align_layout(B, T, Lmax, &a);
+    CFM_REQUIRE(workspace_bytes >= (WILD ? align_wild_offset(B, T, Lmax) + wild_bytes(B, T) : plain_bytes), CFM_ERR_BAD_SHAPE);
+    a.frame_tokens = frame_tokens; a.frame_index = frame_index; a.token_start = token_start; a.token_end = token_end;
+    a.token_score = token_score; a.score = score; a.ok = ok;
+    a.tgt_numel = (int64_t)B * Lmax;
+    a.B = B; a.T = T; a.V = V; a.Lmax = Lmax; a.blank = blank_id;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const dim3 grid((unsigned)B);
+    const int64_t frames = (int64_t)B * T;
+    if (WILD) {
+        float* wild = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + align_wild_offset(B, T, Lmax));
+        a.wild = wild; a.penalty = penalty;
+        hipLaunchKernelGGL(align_wild_kernel, dim3((unsigned)((frames + 3) / 4)), dim3(256), 0, s, a, wild);
+    }
+    if (a.threads > 64) {
+        hipLaunchKernelGGL((align_chain_kernel<8, true, WILD>), grid, dim3((unsigned)a.threads), 0, s, a);
+    } else {
+        switch (a.P) {
+            case 1: hipLaunchKernelGGL((align_chain_kernel<1, false, WILD>), grid, dim3(64), 0, s, a); break;
+            case 2: hipLaunchKernelGGL((align_chain_kernel<2, false, WILD>), grid, dim3(64), 0, s, a); break;
+            case 4: hipLaunchKernelGGL((align_chain_kernel<4, false, WILD>), grid, dim3(64), 0, s, a); break;
+            case 8: hipLaunchKernelGGL((align_chain_kernel<8, false, WILD>), grid, dim3(64), 0, s, a); break;
+            default: hipLaunchKernelGGL((align_chain_kernel<16, false, WILD>), grid, dim3(64), 0, s, a); break;
+        }
+    }
+    hipLaunchKernelGGL(align_trace_kernel<WILD>, grid, dim3(64), 0, s, a);
+    hipLaunchKernelGGL(align_frame_kernel<WILD>, dim3((unsigned)((frames + 3) / 4)), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(align_span_kernel, grid, dim3(256), 0, s, a);
     return cfm_launch_status();
 }
 
@@ -671,37 +807,22 @@ extern "C" int cfm_ctc_align_f32(const float* logits, const int64_t* targets, co
                                  void* workspace, size_t workspace_bytes, int64_t* frame_tokens, int64_t* frame_index,
                                  int64_t* token_start, int64_t* token_end, float* token_score, double* score,
                                  unsigned char* ok, cfm_stream_t stream) {
-    CFM_REQUIRE(logits && targets && workspace && frame_tokens && frame_index && token_start && token_end && token_score &&
-                score && ok, CFM_ERR_NULL);
-    CFM_REQUIRE(B > 0 && T > 0 && V >= 2 && Lmax >= 1 && blank_id >= 0 && blank_id < V, CFM_ERR_BAD_SHAPE);
-    CFM_REQUIRE(align_in_range(B, T, Lmax), CFM_ERR_UNSUPPORTED);
-    CFM_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, CFM_ERR_ALIGN);
-    AlignArgs a{};
-    a.logits = logits; a.targets = targets; a.in_len = lengths_or_null; a.tgt_len = target_lengths_or_null;
-    a.frame_lp = reinterpret_cast<double*>(workspace);
-    CFM_REQUIRE(workspace_bytes >= align_layout(B, T, Lmax, &a), CFM_ERR_BAD_SHAPE);
-    a.frame_tokens = frame_tokens; a.frame_index = frame_index; a.token_start = token_start; a.token_end = token_end;
-    a.token_score = token_score; a.score = score; a.ok = ok;
-    a.tgt_numel = (int64_t)B * Lmax;
-    a.B = B; a.T = T; a.V = V; a.Lmax = Lmax; a.blank = blank_id;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const dim3 grid((unsigned)B);
-    if (a.threads > 64) {
-        hipLaunchKernelGGL((align_chain_kernel<8, true>), grid, dim3((unsigned)a.threads), 0, s, a);
-    } else {
-        switch (a.P) {
-            case 1: hipLaunchKernelGGL((align_chain_kernel<1, false>), grid, dim3(64), 0, s, a); break;
-            case 2: hipLaunchKernelGGL((align_chain_kernel<2, false>), grid, dim3(64), 0, s, a); break;
-            case 4: hipLaunchKernelGGL((align_chain_kernel<4, false>), grid, dim3(64), 0, s, a); break;
-            case 8: hipLaunchKernelGGL((align_chain_kernel<8, false>), grid, dim3(64), 0, s, a); break;
-            default: hipLaunchKernelGGL((align_chain_kernel<16, false>), grid, dim3(64), 0, s, a); break;
-        }
-    }
-    hipLaunchKernelGGL(align_trace_kernel, grid, dim3(64), 0, s, a);
-    const int64_t frames = (int64_t)B * T;
-    hipLaunchKernelGGL(align_frame_kernel, dim3((unsigned)((frames + 3) / 4)), dim3(256), 0, s, a);
-    hipLaunchKernelGGL(align_span_kernel, grid, dim3(256), 0, s, a);
-    return cfm_launch_status();
+    return align_run<false>(logits, targets, lengths_or_null, target_lengths_or_null, B, T, V, Lmax, blank_id, 0.0f, workspace,
+                            workspace_bytes, frame_tokens, frame_index, token_start, token_end, token_score, score, ok, stream);
+}
+
+extern "C" size_t cfm3_ctc_align_wild_workspace_bytes(int B, int T, int Lmax) {
+    return align_in_range(B, T, Lmax) ? align_wild_offset(B, T, Lmax) + wild_bytes(B, T) : 0;
+}
+
+extern "C" int cfm3_ctc_align_wild_f32(const float* logits, const int64_t* targets, const int64_t* lengths_or_null,
+                                       const int64_t* target_lengths_or_null, int B, int T, int V, int Lmax, int blank_id,
+                                       float wildcard_penalty, void* workspace, size_t workspace_bytes, int64_t* frame_tokens,
+                                       int64_t* frame_index, int64_t* token_start, int64_t* token_end, float* token_score,
+                                       double* score, unsigned char* ok, cfm_stream_t stream) {
+    return align_run<true>(logits, targets, lengths_or_null, target_lengths_or_null, B, T, V, Lmax, blank_id, wildcard_penalty,
+                           workspace, workspace_bytes, frame_tokens, frame_index, token_start, token_end, token_score, score, ok,
+                           stream);
 }
 
 extern "C" size_t cfm2_ctc_align_long_workspace_bytes(int B, int T, int Lmax, int tile_pairs, int chunk_frames) {
@@ -719,16 +840,32 @@ extern "C" int cfm2_ctc_align_long_f32(const float* logits, const int64_t* targe
                                        int tile_pairs, int chunk_frames, void* workspace, size_t workspace_bytes,
                                        int64_t* frame_tokens, int64_t* frame_index, int64_t* token_start, int64_t* token_end,
                                        float* token_score, double* score, unsigned char* ok, cfm_stream_t stream) {
-    return align_long_run(logits, targets, lengths_or_null, target_lengths_or_null, B, T, V, Lmax, blank_id, tile_pairs,
-                          chunk_frames, workspace, workspace_bytes, frame_tokens, frame_index, token_start, token_end,
-                          token_score, score, ok, false, stream);
+    return align_long_run<false>(logits, targets, lengths_or_null, target_lengths_or_null, B, T, V, Lmax, blank_id, 0.0f,
+                                 tile_pairs, chunk_frames, workspace, workspace_bytes, frame_tokens, frame_index, token_start,
+                                 token_end, token_score, score, ok, false, stream);
+}
+
+extern "C" size_t cfm3_ctc_align_long_wild_workspace_bytes(int B, int T, int Lmax, int tile_pairs, int chunk_frames) {
+    LongPlan plan;
+    return align_long_plan(B, T, Lmax, tile_pairs, chunk_frames, &plan) ? plan.total() + wild_bytes(B, T) : 0;
+}
+
+extern "C" int cfm3_ctc_align_long_wild_f32(const float* logits, const int64_t* targets, const int64_t* lengths_or_null,
+                                            const int64_t* target_lengths_or_null, int B, int T, int V, int Lmax,
+                                            int blank_id, float wildcard_penalty, int tile_pairs, int chunk_frames,
+                                            void* workspace, size_t workspace_bytes, int64_t* frame_tokens, int64_t* frame_index,
+                                            int64_t* token_start, int64_t* token_end, float* token_score, double* score,
+                                            unsigned char* ok, cfm_stream_t stream) {
+    return align_long_run<true>(logits, targets, lengths_or_null, target_lengths_or_null, B, T, V, Lmax, blank_id,
+                                wildcard_penalty, tile_pairs, chunk_frames, workspace, workspace_bytes, frame_tokens,
+                                frame_index, token_start, token_end, token_score, score, ok, false, stream);
 }
 
 extern "C" int cfm2_ctc_align_long_chain_f32(const float* logits, const int64_t* targets, const int64_t* lengths_or_null,
                                              const int64_t* target_lengths_or_null, int B, int T, int V, int Lmax,
                                              int blank_id, int tile_pairs, int chunk_frames, void* workspace,
                                              size_t workspace_bytes, cfm_stream_t stream) {
-    return align_long_run(logits, targets, lengths_or_null, target_lengths_or_null, B, T, V, Lmax, blank_id, tile_pairs,
-                          chunk_frames, workspace, workspace_bytes, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                          nullptr, true, stream);
+    return align_long_run<false>(logits, targets, lengths_or_null, target_lengths_or_null, B, T, V, Lmax, blank_id, 0.0f,
+                                 tile_pairs, chunk_frames, workspace, workspace_bytes, nullptr, nullptr, nullptr, nullptr,
+                                 nullptr, nullptr, nullptr, true, stream);
 }

@@ -9,7 +9,8 @@ stitched frames of the whole recording, so word times are global by construction
 
 Three layers: window_plan (host arithmetic), BufferedEncoder (mel frames in, stitched encoder frames out) and Transcriber
 (waveforms or mel frames in, Transcripts out).  Transcriber.align puts a KNOWN transcript on the time axis of a whole recording
-(align.ctc_forced_align_long on the stitched frames) and cut_utterances cuts the aligned words into training utterances.
+(align.ctc_forced_align_long on the stitched frames) and cut_utterances cuts the aligned words into training utterances;
+Transcriber.segments locates given utterances in a recording that holds other audio too (wildcards between them).
 There is no kernel of its own in here: the hot path is Encoder.forward, the decoder head, the search and the aligner, which
 are gfx950 kernels already; the plan, the batching and the stitching are slices and copies.
 """
@@ -20,7 +21,7 @@ from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
-from .align import CTCAligner, Word
+from .align import CTCAligner, Segment, Word
 from .confidence import ConfidenceConfig, frame_confidence, transcriber_confidence, word_confidence
 from .decode import BeamCTCDecoder
 from .frontend import ConformerAudioFrontend
@@ -228,6 +229,16 @@ class Aligned(NamedTuple):
     seconds: float
 
 
+class Segmented(NamedTuple):
+    """segments: one align.Segment per utterance, in the order given ([] when they do not fit the frames); score, ok, frames,
+    seconds: as Aligned (the score counts the wildcard frames at the log-probability of their most likely symbol)."""
+    segments: List[Segment]
+    score: float
+    ok: bool
+    frames: int
+    seconds: float
+
+
 class Utterance(NamedTuple):
     """A run of aligned words cut out for training: start / end in seconds, the words [first_word, last_word] of the list it was
     cut from joined by a space, and the mean of their scores weighted by their frames."""
@@ -361,13 +372,27 @@ class Transcriber:
                 out[i] = Transcript(texts[k], words[k], scores[k], n[k], mels[i].shape[1] * self.mel_seconds)
         return out
 
+    def _group_logits(self, audios: Sequence[torch.Tensor], sample_rates: Optional[Sequence[int]]):
+        """transcribe's pipeline up to the logits: per group of recordings (group, frames of each, their seconds, logits, lengths)"""
+        mels = self.features(audios, sample_rates)
+        hs = self.encoder.encode(mels)
+        for group in self.groups([h.shape[0] for h in hs]):
+            n = [hs[i].shape[0] for i in group]
+            h = hs[group[0]].new_zeros(len(group), n[0], hs[group[0]].shape[1])
+            for k, i in enumerate(group):
+                h[k, :n[k]] = hs[i]
+            lengths = torch.tensor(n, dtype=torch.int64).to(self.device, non_blocking=True)
+            yield group, n, [mels[i].shape[1] * self.mel_seconds for i in group], self.decoder_head(h, lengths), lengths
+
     @torch.no_grad()
-    def align(self, audios: Sequence[torch.Tensor], texts: Sequence, sample_rates: Optional[Sequence[int]] = None) -> List[Aligned]:
+    def align(self, audios: Sequence[torch.Tensor], texts: Sequence, sample_rates: Optional[Sequence[int]] = None,
+              wildcard_token: Optional[str] = None, wildcard_penalty: Optional[float] = None) -> List[Aligned]:
         """Forced alignment of whole recordings: `texts` holds one transcript per recording, strings or token-id sequences as
         CTCAligner takes them.  Same pipeline as transcribe up to the logits (front end, BufferedEncoder.encode, decoder_head on
         the stitched frames in the same groups), then CTCAligner.from_decoder(decoder, frame_seconds) with long=True: no limit
         on the recording's length but the workspace (align.ctc_forced_align_long).  One Aligned per recording, in the caller's
-        order.  Synchronises (the words are read back)."""
+        order.  Synchronises (the words are read back).
+        wildcard_token, wildcard_penalty: CTCAligner's, for a transcript that skips audio (a wildcard where it does)."""
         lstm_state(self.model, "Transcriber", 1)
         _ambient_autocast("Transcriber")
         if isinstance(texts, str) or len(texts) != len(audios):
@@ -375,21 +400,42 @@ class Transcriber:
                              f"{'a single string' if isinstance(texts, str) else f'{len(texts)} texts'}")
         if len(audios) == 0:
             return []
-        aligner = CTCAligner.from_decoder(self.decoder, self.frame_seconds)
+        aligner = CTCAligner.from_decoder(self.decoder, self.frame_seconds, wildcard_token, wildcard_penalty)
         targets = [aligner._ids(t) for t in texts]                   # refuses a bad text before anything runs
-        mels = self.features(audios, sample_rates)
-        hs = self.encoder.encode(mels)
-        out: List[Optional[Aligned]] = [None] * len(hs)
-        for group in self.groups([h.shape[0] for h in hs]):
-            n = [hs[i].shape[0] for i in group]
-            h = hs[group[0]].new_zeros(len(group), n[0], hs[group[0]].shape[1])
-            for k, i in enumerate(group):
-                h[k, :n[k]] = hs[i]
-            lengths = torch.tensor(n, dtype=torch.int64).to(self.device, non_blocking=True)
-            logits = self.decoder_head(h, lengths)
+        out: List[Optional[Aligned]] = [None] * len(audios)
+        for group, n, seconds, logits, lengths in self._group_logits(audios, sample_rates):
             ids, al = aligner.align(logits, [targets[i] for i in group], lengths, long=True)
             words = aligner.words(ids, al)
             ok, score = al.ok.cpu().tolist(), al.score.cpu().tolist()
             for k, i in enumerate(group):
-                out[i] = Aligned(words[k], score[k], bool(ok[k]), n[k], mels[i].shape[1] * self.mel_seconds)
+                out[i] = Aligned(words[k], score[k], bool(ok[k]), n[k], seconds[k])
+        return out
+
+    @torch.no_grad()
+    def segments(self, audios: Sequence[torch.Tensor], utterance_lists: Sequence[Sequence], wildcard_penalty: float,
+                 sample_rates: Optional[Sequence[int]] = None, ends: bool = True) -> List[Segmented]:
+        """Locate utterances in whole recordings: `utterance_lists` holds per recording the texts or token-id sequences it
+        contains somewhere, in spoken order; the audio in front of, between and behind them is absorbed by wildcards at
+        `wildcard_penalty` logit units per frame (CTCAligner.segments; ends=False: the recording starts and ends with the
+        utterances).  The pipeline and the groups of `align`, the long form.  One Segmented per recording, in the caller's
+        order.  Synchronises."""
+        lstm_state(self.model, "Transcriber", 1)
+        _ambient_autocast("Transcriber")
+        if isinstance(utterance_lists, str) or len(utterance_lists) != len(audios) or \
+                any(isinstance(u, str) for u in utterance_lists):
+            raise ValueError(f"Transcriber.segments: one LIST of utterances per recording, got {len(audios)} recordings and "
+                             f"{utterance_lists!r}"[:300])
+        aligner = CTCAligner.from_decoder(self.decoder, self.frame_seconds, None, wildcard_penalty)
+        if aligner.wildcard_penalty is None:
+            raise ValueError("Transcriber.segments: wildcard_penalty has no default (it depends on the model's posteriors)")
+        if len(audios) == 0:
+            return []
+        built = [aligner.segment_targets(u, ends) for u in utterance_lists]      # refuses a bad utterance before anything runs
+        out: List[Optional[Segmented]] = [None] * len(audios)
+        for group, n, seconds, logits, lengths in self._group_logits(audios, sample_rates):
+            ids, al = aligner.align(logits, [built[i][0] for i in group], lengths, long=True)
+            segs = aligner.segments_of([utterance_lists[i] for i in group], ids, [built[i][1] for i in group], al)
+            ok, score = al.ok.cpu().tolist(), al.score.cpu().tolist()
+            for k, i in enumerate(group):
+                out[i] = Segmented(segs[k], score[k], bool(ok[k]), n[k], seconds[k])
         return out

@@ -11,6 +11,8 @@ Three layers: window_plan (host arithmetic), BufferedEncoder (mel frames in, sti
 (waveforms or mel frames in, Transcripts out).  Transcriber.align puts a KNOWN transcript on the time axis of a whole recording
 (align.ctc_forced_align_long on the stitched frames) and cut_utterances cuts the aligned words into training utterances;
 Transcriber.segments locates given utterances in a recording that holds other audio too (wildcards between them).
+Transcriber(vad=VadConfig(...)) puts the voice activity detector (conformer_amd.vad) in front of the plan: only the speech
+islands of a recording are encoded, and the words keep the recording's own times.
 There is no kernel of its own in here: the hot path is Encoder.forward, the decoder head, the search and the aligner, which
 are gfx950 kernels already; the plan, the batching and the stitching are slices and copies.
 """
@@ -210,8 +212,8 @@ class BufferedEncoder:
 
 class Transcript(NamedTuple):
     """text: the best hypothesis; words: its align.Words with global times (None without times=True); word_confidence: one
-    float per Word (None without confidence=); frames: encoder frames of the recording; seconds: its duration (mel frames x the
-    front end's hop)."""
+    float per Word (None without confidence=); frames: encoder frames of the recording (with Transcriber(vad=...): the frames
+    decoded, those of its speech islands); seconds: its duration (mel frames x the front end's hop)."""
     text: str
     words: Optional[List[Word]]
     word_confidence: Optional[List[float]]
@@ -297,13 +299,20 @@ class Transcriber:
     any choice; 30 s / 8 s is the usual starting point.  They are converted once to mel frames (window_frames: the front end's
     hop, or frame_seconds / 4 per mel frame without one); overlap_seconds is the lower bound of the overlap used.
     batch_windows, graphs: as BufferedEncoder.
+    vad=VadConfig(...) (None: off): the voice activity detector runs on the features first (vad.speech_segments, then
+    vad.speech_islands) and only the speech islands are encoded: the islands of all recordings go through one
+    BufferedEncoder.encode as if they were recordings, each recording's island frames are concatenated for the head and the
+    search, and every Word is mapped back to the recording's own time axis.  Transcript.frames is then the number of frames
+    decoded, and a recording without speech gives Transcript("", [] or None, [] or None, 0, seconds).  `speech` returns the
+    islands.  `align` and `segments` do not use vad: they place a known text on the whole recording.
     Memory: only the encoder is bounded by one batch of windows.  transcribe holds the stitched frames of every recording and,
     per group, a second, padded copy of them (B, T', d) for the decoder head, so twice the stitched output of a group; the head's
     own intermediates, the logits and the search's buffers all grow with the recording's length."""
 
     def __init__(self, model, decoder: BeamCTCDecoder, frontend: Optional[ConformerAudioFrontend] = None, *,
                  window_seconds: float, overlap_seconds: float, batch_windows: int = 32, graphs: bool = False,
-                 times: bool = False, frame_seconds: float = 0.04, confidence: Optional[ConfidenceConfig] = None) -> None:
+                 times: bool = False, frame_seconds: float = 0.04, confidence: Optional[ConfidenceConfig] = None,
+                 vad=None) -> None:
         self.times, self.frame_seconds = times_plan("Transcriber", times, frame_seconds)
         cplan = transcriber_confidence("Transcriber", confidence, 1, self.times)
         self.confidence = None if cplan is None else cplan[0]
@@ -321,6 +330,12 @@ class Transcriber:
         self.model, self.decoder, self.frontend = model, decoder, frontend
         self.batch_windows = batch_windows
         self.encoder = BufferedEncoder(model.encoder, self.window, self.overlap, batch_windows, graphs)
+        self.vad = vad
+        if vad is not None:                                      # (the vad module is imported by the objects that use it)
+            from .vad import VadConfig
+            if not isinstance(vad, VadConfig):
+                raise ValueError(f"Transcriber: vad must be a VadConfig or None, got {type(vad).__name__}")
+            vad.check(self.mel_seconds, frontend.n_mels if frontend is not None else (vad.band or (0, 1))[1])
 
     @torch.no_grad()
     def features(self, audios: Sequence[torch.Tensor], sample_rates: Optional[Sequence[int]] = None) -> List[torch.Tensor]:
@@ -353,7 +368,13 @@ class Transcriber:
         if len(audios) == 0:
             return []
         mels = self.features(audios, sample_rates)
-        hs = self.encoder.encode(mels)
+        if self.vad is not None:
+            return self._transcribe_islands(mels)
+        return self._decode(self.encoder.encode(mels), [m.shape[1] * self.mel_seconds for m in mels])
+
+    def _decode(self, hs: Sequence[torch.Tensor], seconds: Sequence[float]) -> List[Transcript]:
+        """The decoder head, the search and the confidences over encoder frames hs (one (T', d) tensor per recording), in
+        groups; one Transcript per recording, in the order given."""
         out: List[Optional[Transcript]] = [None] * len(hs)
         for group in self.groups([h.shape[0] for h in hs]):
             n = [hs[i].shape[0] for i in group]
@@ -369,7 +390,52 @@ class Transcriber:
                 conf, ids = frame_confidence(logits, lengths, self.confidence)
                 scores = word_confidence(words, conf, ids, self.decoder.blank_id, lengths, self.confidence)
             for k, i in enumerate(group):
-                out[i] = Transcript(texts[k], words[k], scores[k], n[k], mels[i].shape[1] * self.mel_seconds)
+                out[i] = Transcript(texts[k], words[k], scores[k], n[k], seconds[i])
+        return out
+
+    def _islands(self, mels: Sequence[torch.Tensor]) -> List[List[Tuple[int, int]]]:
+        """Per recording its speech islands in mel frames: vad.speech_segments, then vad.speech_islands."""
+        from . import vad as _vad
+        p = self.vad.check(self.mel_seconds, int(mels[0].shape[0]))
+        for r, m in enumerate(mels):
+            if m.shape[1] < MIN_MEL_FRAMES:
+                raise ValueError(f"Transcriber: recording {r} has {m.shape[1]} mel frames, the least is {MIN_MEL_FRAMES}")
+        segments = _vad.speech_segments(mels, config=self.vad, mel_seconds=self.mel_seconds)
+        return [_vad.speech_islands(s, int(m.shape[1]), p.pad_before, p.pad_after, p.min_gap) for s, m in zip(segments, mels)]
+
+    @torch.no_grad()
+    def speech(self, audios: Sequence[torch.Tensor], sample_rates: Optional[Sequence[int]] = None) -> List[List[Tuple[float, float]]]:
+        """Per recording the speech islands transcribe would encode, as (start, end) in seconds.  Needs vad=.  Synchronises."""
+        if self.vad is None:
+            raise ValueError("Transcriber.speech: this Transcriber was made without vad=")
+        if len(audios) == 0:
+            return []
+        mels = [m if m.is_cuda else m.to(self.device) for m in self.features(audios, sample_rates)]
+        return [[(a * self.mel_seconds, b * self.mel_seconds) for a, b in isl] for isl in self._islands(mels)]
+
+    def _transcribe_islands(self, mels: Sequence[torch.Tensor]) -> List[Transcript]:
+        """transcribe with vad=: the islands of all recordings through ONE BufferedEncoder.encode as if they were recordings,
+        per recording their encoder frames concatenated, _decode over the concatenations, and every Word mapped back to the
+        recording's own time axis: frame c of the concatenation that lies j frames into the island (a, b) is the recording's
+        frame a / 4 + j; a word's end is the mapped last frame + 1."""
+        mels = [m if m.is_cuda else m.to(self.device) for m in mels]
+        seconds = [m.shape[1] * self.mel_seconds for m in mels]
+        islands = self._islands(mels)
+        pieces = [(r, a, b) for r, isl in enumerate(islands) for a, b in isl]
+        encoded = self.encoder.encode([mels[r][:, a:b] for r, a, b in pieces]) if pieces else []
+        spoken = [r for r, isl in enumerate(islands) if isl]
+        mine = {r: [h for h, (r2, _, _) in zip(encoded, pieces) if r2 == r] for r in spoken}
+        decoded = self._decode([torch.cat(mine[r]) for r in spoken], [seconds[r] for r in spoken])
+        out = [Transcript("", [] if self.times else None, [] if self.confidence is not None else None, 0, s) for s in seconds]
+        fs = self.frame_seconds
+        for r, t in zip(spoken, decoded):
+            if t.words is not None:
+                to_global: List[int] = []                        # frame of the concatenation -> frame of the recording
+                for (a, _), h in zip(islands[r], mine[r]):
+                    to_global += range(a // 4, a // 4 + h.shape[0])
+                spans = [(to_global[w.start_frame], to_global[w.end_frame - 1] + 1) for w in t.words]
+                t = t._replace(words=[Word(w.text, a, b, a * fs, b * fs, w.score) for w, (a, b) in zip(t.words, spans)])
+            out[r] = t
         return out
 
     def _group_logits(self, audios: Sequence[torch.Tensor], sample_rates: Optional[Sequence[int]]):

@@ -478,6 +478,28 @@ class Transcriber:
         return out
 
     @torch.no_grad()
+    def spot(self, audios: Sequence[torch.Tensor], keywords, sample_rates: Optional[Sequence[int]] = None) -> List[list]:
+        """Keyword spotting over whole recordings (INTEGRATION.md "Keyword spotting"): `keywords` is a kws.Keywords.  Same
+        pipeline as transcribe up to the logits, as `align`; then kws.spot_keywords on every group's logits.  Per recording,
+        in the caller's order, its kws.Detections sorted by (end_frame, keyword), times in seconds of the recording at
+        frame_seconds per encoder frame.  Does not use vad.  Synchronises."""
+        from . import kws as _kws                                # (imported by the objects that use it)
+        lstm_state(self.model, "Transcriber", 1)
+        _ambient_autocast("Transcriber")
+        if not isinstance(keywords, _kws.Keywords):
+            raise ValueError(f"Transcriber.spot: keywords must be a kws.Keywords, got {type(keywords).__name__}")
+        if keywords.blank_id != self.decoder.blank_id:
+            raise ValueError(f"Transcriber.spot: the keywords' blank is {keywords.blank_id}, the decoder's {self.decoder.blank_id}")
+        out: List[Optional[list]] = [None] * len(audios)
+        if len(audios) == 0:
+            return out
+        for group, _, _, logits, lengths in self._group_logits(audios, sample_rates):
+            found = _kws.spot_keywords(logits, keywords, lengths, self.frame_seconds)
+            for k, i in enumerate(group):
+                out[i] = found[k]
+        return out
+
+    @torch.no_grad()
     def segments(self, audios: Sequence[torch.Tensor], utterance_lists: Sequence[Sequence], wildcard_penalty: float,
                  sample_rates: Optional[Sequence[int]] = None, ends: bool = True) -> List[Segmented]:
         """Locate utterances in whole recordings: `utterance_lists` holds per recording the texts or token-id sequences it

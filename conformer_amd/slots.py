@@ -307,11 +307,17 @@ class SlotTranscriber:
     confidence=ConfidenceConfig(...) (needs times=True): every step also keeps the frame confidence of the logits it returns,
     for each slot's last confidence_history frames counted from open(s) (INTEGRATION.md "Confidence": two more launches, nothing
     synchronises); word_confidence(words) gives the Words this object returned their confidence.  Without it nothing is
-    launched or allocated."""
+    launched or allocated.
+    keywords=kws.Keywords(...): every step also runs the keyword spotter on the logits it returns, with the step's own device k
+    (INTEGRATION.md "Keyword spotting": two more launches, nothing synchronises; max_detections rows per slot and group of
+    keywords between two reads).  open(s) arms slot s; segment(s) does NOT arm it again, so every time counts from open(s).
+    keywords() pops the open slots' new detections, close_keywords(s) ends slot s's stream of detections (close(s) itself is
+    unchanged).  Without it the module is not imported and nothing is launched or allocated."""
 
     audio: Optional[StreamingAudioFrontend] = None
     endpointer: Optional[StreamingEndpointer] = None
     confidence: Optional[StreamingConfidence] = None
+    spotter = None                                 # a kws.StreamingKeywordSpotter with keywords=
     seg_start: Optional[List[int]] = None          # per slot the encoder frame at which its current segment began
 
     def __init__(self, model, decoder: BeamCTCDecoder, slots: int, max_mel_frames: Optional[int],
@@ -319,7 +325,8 @@ class SlotTranscriber:
                  max_chunk_mel_frames: Optional[int] = None, max_pending: Optional[int] = None,
                  commit_log: int = 4096, times: bool = False, frame_seconds: float = 0.04,
                  audio: Optional[StreamingAudioFrontend] = None, endpoint: Optional[EndpointConfig] = None,
-                 confidence: Optional[ConfidenceConfig] = None, confidence_history: int = 4096) -> None:
+                 confidence: Optional[ConfidenceConfig] = None, confidence_history: int = 4096, keywords=None,
+                 max_detections: int = 64) -> None:
         tplan = times_plan("SlotTranscriber", times, frame_seconds)
         cplan = transcriber_confidence("SlotTranscriber", confidence, confidence_history, tplan[0])
         if endpoint is not None:
@@ -345,6 +352,13 @@ class SlotTranscriber:
             self.endpointer = StreamingEndpointer(self.S, decoder.blank_id, endpoint, tplan[1], self.device)
         if cplan is not None:
             self.confidence = StreamingConfidence(self.S, decoder.blank_id, cplan[0], cplan[1], self.device)
+        if keywords is not None:                                           # (the module is imported by the objects that use it)
+            from .kws import Keywords, StreamingKeywordSpotter
+            if not isinstance(keywords, Keywords):
+                raise ValueError(f"SlotTranscriber: keywords must be a kws.Keywords or None, got {type(keywords).__name__}")
+            if keywords.blank_id != decoder.blank_id:
+                raise ValueError(f"SlotTranscriber: the keywords' blank is {keywords.blank_id}, the decoder's {decoder.blank_id}")
+            self.spotter = StreamingKeywordSpotter(self.S, keywords, tplan[1], max_detections, None, self.device)
 
     @property
     def is_open(self) -> List[bool]:
@@ -369,6 +383,8 @@ class SlotTranscriber:
         self._new_segment(s, 0)
         if self.confidence is not None:                                    # (a segment does not: its words count from open(s))
             self.confidence.reset_slots([s])
+        if self.spotter is not None:                                       # (nor here: detections count from open(s))
+            self.spotter.reset_slots([s])
 
     def _new_segment(self, s: int, first_frame: int) -> None:
         """Slot s's segment begins at encoder frame first_frame of its stream: the endpointer armed again (enqueues only)."""
@@ -429,7 +445,27 @@ class SlotTranscriber:
             self.endpointer.step(logits, k_dev)
         if self.confidence is not None:
             self.confidence.step(logits, k_dev)
+        if self.spotter is not None:
+            self.spotter.step(logits, k_dev)
         return logits, ks
+
+    def keywords(self) -> Dict[int, list]:
+        """With keywords=: per open slot the kws.Detections emitted since the last call, sorted by (end_frame, keyword); times
+        count from open(s).  A detection is emitted once a later frame has closed it, so the last one of a stream comes with
+        close_keywords(s).  Synchronises, as partial_text does."""
+        if self.spotter is None:
+            raise RuntimeError("SlotTranscriber.keywords: the object was made without keywords=, nothing was spotted")
+        return self._open_slots(self.spotter.pop)
+
+    def close_keywords(self, s: int) -> list:
+        """With keywords=: end slot s's stream of detections: what keywords() has not handed out yet together with what the
+        slot still holds (StreamingKeywordSpotter.flush).  The slot itself stays as it is, open or closed: call it beside
+        close(s), before the slot is opened again.  Synchronises."""
+        if self.spotter is None:
+            raise RuntimeError("SlotTranscriber.close_keywords: the object was made without keywords=, nothing was spotted")
+        if isinstance(s, bool) or not isinstance(s, int) or not 0 <= s < self.S:
+            raise ValueError(f"slot {s!r} outside [0, {self.S})")
+        return self.spotter.flush(s)
 
     def word_confidence(self, words: Dict[int, List[Word]]) -> Dict[int, List[float]]:
         """With confidence=: the confidence of Words this object returned ({slot: its words}, as partial_words, finish_words
@@ -542,3 +578,5 @@ class SlotTranscriber:
             self.audio.reset()
         if self.confidence is not None:
             self.confidence.reset()
+        if self.spotter is not None:
+            self.spotter.reset()

@@ -35,6 +35,10 @@
 // matches, its window of undecided words and its count (the window rule of hotword.h); the node each extension reaches is
 // kept in LDS (x_hn), and the window step a delimiter takes is done once per thread (x_hc, x_hd, x_hwl, x_hw).
 //
+// Per-request hotwords (conformer_hip3_hotword_rows.h, INTEGRATION.md "Per-request hotwords"): LmParams<LM, true> may carry a
+// table pointer and a weight per utterance; each workgroup resolves its own pair once before the frame loop (block-uniform, so
+// the view stays in scalar registers) and everything above runs on it.  Null arrays: the launch-wide pair, as before.
+//
 // Timestamps (beam_search_kernel<LM, HW, true, true>, beam_commit_kernel<true>, INTEGRATION.md "Beam-search timestamps"): the
 // resumable search also records, per created tree node, the absolute frame and the log-probability of its extension
 // (TimesParams), the tracebacks return them beside the tokens and the commit carries them along (CommitTimes).
@@ -43,6 +47,7 @@
 #include "cfm_common.h"
 #include "../../include/conformer_hip_commit.h"
 #include "../../include/conformer_hip_times.h"
+#include "conformer_hip3_hotword_rows.h"
 #include "hotword.h"
 #include "ngram_lm.h"
 
@@ -70,6 +75,10 @@ template <bool LM> struct LmParams<LM, true> {
     float* am_scores;
     const void* hw_tables;               // cfm_hotword_pack blob on the device
     double hw_weight;
+    // per-request hotwords (conformer_hip3_hotword_rows.h): (B) device arrays, the table and the weight of each utterance;
+    // null: every utterance takes the pair above
+    const void* const* hw_rows;
+    const double* hw_row_weights;
 };
 
 // Resumable search (beam_search_kernel<LM, HW, true>, INTEGRATION.md "Streaming (resumable) search"): the state the one-shot
@@ -317,8 +326,17 @@ __global__ __launch_bounds__(BEAM_MAX_W) void beam_search_kernel(
     if constexpr (LM) lmv = lm_view(lp.tables);
     [[maybe_unused]] HwView hwv;
     [[maybe_unused]] const int32_t* tok_cp = nullptr;      // code points of the tokens (LM blob, else hotword blob)
+    [[maybe_unused]] double hww = 0.0;                     // this utterance's hotword weight
     if constexpr (HW) {
-        hwv = hw_view(lp.hw_tables);
+        // the table and the weight of this utterance: b is blockIdx.x, so both loads and the view are workgroup-uniform
+        const void* hwt = lp.hw_tables;
+        hww = lp.hw_weight;
+        // (a pointer loaded from memory is a generic one to the compiler and every table read would become a flat load; the
+        // tables are device memory, so it goes through the global address space like the launch-wide kernel argument)
+        typedef __attribute__((address_space(1))) const char* global_table;
+        if (lp.hw_rows) hwt = (const void*)(global_table)(uintptr_t)lp.hw_rows[b];
+        if (lp.hw_row_weights) hww = lp.hw_row_weights[b];
+        hwv = hw_view(hwt);
         if constexpr (LM) tok_cp = lmv.tok_cp;
         else tok_cp = hwv.tok_cp;
     }
@@ -418,10 +436,10 @@ __global__ __launch_bounds__(BEAM_MAX_W) void beam_search_kernel(
             }
             if constexpr (HW) {
                 hn = h_hn[cur][tid]; hc = h_hc[cur][tid];
-                hwc = lp.hw_weight * (double)hc;
+                hwc = hww * (double)hc;
                 double r;
-                if constexpr (LM) r = hn >= 0 ? hw_bonus(hwv, hn, lp.hw_weight) : lm_pen(tn, pl, lp.unk_offset);
-                else r = hw_bonus(hwv, hn, lp.hw_weight);
+                if constexpr (LM) r = hn >= 0 ? hw_bonus(hwv, hn, hww) : lm_pen(tn, pl, lp.unk_offset);
+                else r = hw_bonus(hwv, hn, hww);
                 lmp = (lm + hwc) + r;
             }
             st_pb = s + ((double)lrow[blank] - lse);
@@ -514,7 +532,7 @@ __global__ __launch_bounds__(BEAM_MAX_W) void beam_search_kernel(
                     x_hc[tid] = c; x_hd[tid] = dec; x_hwl[tid] = wl;
 #pragma unroll
                     for (int u = 0; u < HW_WIN; ++u) x_hw[u][tid] = (short)ids[u];
-                    xhwc = lp.hw_weight * (double)c;
+                    xhwc = hww * (double)c;
                 }
                 // hotword-trie walks of the character candidates, LM_WALK at a time
                 auto cp_at = [&](int k, int q) { return q < LM_TOK_CP ? c_cp[k][q] : tok_cp[c_off[k] + q]; };
@@ -567,8 +585,8 @@ __global__ __launch_bounds__(BEAM_MAX_W) void beam_search_kernel(
                 if (kind == LM_TOK_CHARS) {
                     const int xn = x_hn[k][tid];
                     double r;
-                    if constexpr (LM) r = xn >= 0 ? hw_bonus(hwv, xn, lp.hw_weight) : lm_pen(x_node[k][tid], pl + c_len[k], lp.unk_offset);
-                    else r = hw_bonus(hwv, xn, lp.hw_weight);
+                    if constexpr (LM) r = xn >= 0 ? hw_bonus(hwv, xn, hww) : lm_pen(x_node[k][tid], pl + c_len[k], lp.unk_offset);
+                    else r = hw_bonus(hwv, xn, hww);
                     return (lm + hwc) + r;
                 }
                 if (kind == LM_TOK_DELIM && hn != 0) return ((lm + term) + xhwc) + 0.0;
@@ -787,9 +805,9 @@ __global__ __launch_bounds__(BEAM_MAX_W) void beam_search_kernel(
                     sp.hn[o] = hn; sp.hd[o] = h_hd[cur][tid]; sp.hwl[o] = h_hwl[cur][tid]; sp.hc[o] = hc;
                     for (int u = 0; u < HW_WIN; ++u) sp.hw[((int64_t)b * HW_WIN + u) * W + tid] = h_hw[cur][u][tid];
                     double r;
-                    if constexpr (LM) r = hn >= 0 ? hw_bonus(hwv, hn, lp.hw_weight) : lm_pen(h_tn[cur][tid], h_pl[cur][tid], lp.unk_offset);
-                    else r = hw_bonus(hwv, hn, lp.hw_weight);
-                    lmp = (lm + lp.hw_weight * (double)hc) + r;
+                    if constexpr (LM) r = hn >= 0 ? hw_bonus(hwv, hn, hww) : lm_pen(h_tn[cur][tid], h_pl[cur][tid], lp.unk_offset);
+                    else r = hw_bonus(hwv, hn, hww);
+                    lmp = (lm + hww * (double)hc) + r;
                 }
                 f = h_s[cur][tid];
                 if constexpr (LM || HW) f = f + lmp;
@@ -854,7 +872,7 @@ __global__ __launch_bounds__(BEAM_MAX_W) void beam_search_kernel(
                     int wl = h_hwl[cur][tid], dec = h_hd[cur][tid];
                     fc = hw_push(hwv, ids, wl, dec, fhn > 0 ? hwv.cnode[fhn].x : -1);
                 }
-                lmf = lmf + lp.hw_weight * (double)fc;
+                lmf = lmf + hww * (double)fc;
             }
             m_val[tid] = h_s[cur][tid] + lmf;
         }
@@ -1209,6 +1227,8 @@ struct Fusion {
     int score_boundary;
     const void* hw_tables;
     double hw_weight;
+    const void* const* hw_rows = nullptr;            // per-request hotwords: hw_tables is then the mode flag only
+    const double* hw_row_weights = nullptr;
     bool on() const { return lm_tables || hw_tables; }
     bool finite() const {
         return __builtin_isfinite(alpha) && __builtin_isfinite(beta) && __builtin_isfinite(unk) && __builtin_isfinite(hw_weight);
@@ -1232,7 +1252,10 @@ template <bool LM, bool HW> LmParams<LM, HW> lm_params(const Fusion& fz, float* 
         lp.score_boundary = fz.score_boundary ? 1 : 0;
         lp.am_scores = am_scores;
     }
-    if constexpr (HW) { lp.hw_tables = fz.hw_tables; lp.hw_weight = fz.hw_weight; }
+    if constexpr (HW) {
+        lp.hw_tables = fz.hw_tables; lp.hw_weight = fz.hw_weight;
+        lp.hw_rows = fz.hw_rows; lp.hw_row_weights = fz.hw_row_weights;
+    }
     return lp;
 }
 
@@ -1582,4 +1605,73 @@ extern "C" int cfm_ctc_beam_stream_commit_times(int B, int max_pending, int max_
     const TimesArgs ta{times, times_bytes, log_frames, log_logp};
     return stream_commit(B, max_pending, max_chunk_frames, beam_width, max_candidates, lm, hw, lengths_or_null, state, state_bytes,
                          log, L, total, committed_or_null, stream, &ta);
+}
+
+// ---- per-request hotwords (conformer_hip3_hotword_rows.h) ------------------------------------------------------------------------
+
+namespace {
+
+// the fusion group of the per-row entries: the mode is <LM?, HW>, the launch-wide pair is never read (hw_tables is the flag)
+Fusion rows_fusion(const void* lm_tables_or_null, double alpha, double beta, double unk_score_offset, int score_boundary,
+                   const void* const* hw_row_tables, const double* hw_row_weights) {
+    Fusion fz{lm_tables_or_null, alpha, beta, unk_score_offset, score_boundary, hw_row_tables, 0.0};
+    fz.hw_rows = hw_row_tables;
+    fz.hw_row_weights = hw_row_weights;
+    return fz;
+}
+
+// the nullable times group of the per-row stream entries: whole (1), absent (0) or neither (-1)
+int times_group(const void* times, size_t times_bytes, const int64_t* token_frames, const float* token_logp) {
+    if (times && token_frames && token_logp) return 1;
+    return !times && !times_bytes && !token_frames && !token_logp ? 0 : -1;
+}
+
+}  // namespace
+
+extern "C" int cfm3_ctc_beam_hw_rows_decode_f32(const float* logits, const int64_t* lengths_or_null, int B, int T, int V,
+                                                int blank_id, int beam_width, int max_candidates, float token_min_logp,
+                                                float beam_prune_logp, int n_best, const void* lm_tables_or_null, double alpha,
+                                                double beta, double unk_score_offset, int score_boundary,
+                                                const void* const* hw_row_tables, const double* hw_row_weights, void* workspace,
+                                                size_t workspace_bytes, int64_t* tokens, int64_t* counts, float* scores,
+                                                float* am_scores, int64_t* num_hyps, cfm_stream_t stream) {
+    CFM_REQUIRE(logits && hw_row_tables && hw_row_weights && workspace && tokens && counts && scores && am_scores && num_hyps,
+                CFM_ERR_NULL);
+    const Fusion fz = rows_fusion(lm_tables_or_null, alpha, beta, unk_score_offset, score_boundary, hw_row_tables, hw_row_weights);
+    return beam_decode(logits, lengths_or_null, B, T, V, blank_id, beam_width, max_candidates, token_min_logp, beam_prune_logp,
+                       n_best, fz, workspace, workspace_bytes, tokens, counts, scores, am_scores, num_hyps, stream);
+}
+
+extern "C" int cfm3_ctc_beam_hw_rows_stream_step_f32(const float* logits, const int64_t* lengths_or_null, int B, int Tc, int V,
+                                                     int blank_id, int beam_width, int max_candidates, float token_min_logp,
+                                                     float beam_prune_logp, int n_best, const void* lm_tables_or_null,
+                                                     double alpha, double beta, double unk_score_offset, int score_boundary,
+                                                     const void* const* hw_row_tables, const double* hw_row_weights, void* state,
+                                                     size_t state_bytes, int T_max, int t_used, int64_t* tokens, int64_t* counts,
+                                                     float* scores, float* am_scores_or_null, int64_t* num_hyps,
+                                                     void* times_or_null, size_t times_bytes, int64_t* token_frames_or_null,
+                                                     float* token_logp_or_null, cfm_stream_t stream) {
+    const int tg = times_group(times_or_null, times_bytes, token_frames_or_null, token_logp_or_null);
+    CFM_REQUIRE(hw_row_tables && hw_row_weights && tg >= 0, CFM_ERR_NULL);
+    const Fusion fz = rows_fusion(lm_tables_or_null, alpha, beta, unk_score_offset, score_boundary, hw_row_tables, hw_row_weights);
+    const TimesArgs ta{times_or_null, times_bytes, token_frames_or_null, token_logp_or_null};
+    return stream_step(logits, lengths_or_null, B, Tc, V, blank_id, beam_width, max_candidates, token_min_logp, beam_prune_logp,
+                       n_best, fz, state, state_bytes, T_max, t_used, tokens, counts, scores, am_scores_or_null, num_hyps, stream,
+                       tg ? &ta : nullptr);
+}
+
+extern "C" int cfm3_ctc_beam_hw_rows_stream_finish_f32(int B, int beam_width, int max_candidates, int n_best,
+                                                       const void* lm_tables_or_null, double alpha, double beta,
+                                                       double unk_score_offset, int score_boundary,
+                                                       const void* const* hw_row_tables, const double* hw_row_weights,
+                                                       void* state, size_t state_bytes, int T_max, int64_t* tokens,
+                                                       int64_t* counts, float* scores, float* am_scores, int64_t* num_hyps,
+                                                       void* times_or_null, size_t times_bytes, int64_t* token_frames_or_null,
+                                                       float* token_logp_or_null, cfm_stream_t stream) {
+    const int tg = times_group(times_or_null, times_bytes, token_frames_or_null, token_logp_or_null);
+    CFM_REQUIRE(hw_row_tables && hw_row_weights && tg >= 0, CFM_ERR_NULL);
+    const Fusion fz = rows_fusion(lm_tables_or_null, alpha, beta, unk_score_offset, score_boundary, hw_row_tables, hw_row_weights);
+    const TimesArgs ta{times_or_null, times_bytes, token_frames_or_null, token_logp_or_null};
+    return stream_finish(B, beam_width, max_candidates, n_best, fz, state, state_bytes, T_max, tokens, counts, scores, am_scores,
+                         num_hyps, stream, tg ? &ta : nullptr);
 }

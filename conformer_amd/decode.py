@@ -12,7 +12,8 @@ The same search fused with a word n-gram model (`conformer_amd.lm`, an ARPA file
 `BeamCTCDecoder(lm=...)`, semantics in INTEGRATION.md "Language-model fusion".
 
 Hotword boosting, with or without the language model (`conformer_amd.hotwords`): `beam_ctc_hotword_decode` and
-`BeamCTCDecoder(hotwords=...)`, semantics in INTEGRATION.md "Hotword boosting".
+`BeamCTCDecoder(hotwords=...)`, semantics in INTEGRATION.md "Hotword boosting".  A list and a weight per utterance
+(`hotwords=[...]` per call, `BeamCTCStream.set_hotwords`): INTEGRATION.md "Per-request hotwords".
 
 The same search resumed chunk by chunk over a stream, in every mode: `beam_ctc_stream_init/step/finish` and
 `BeamCTCDecoder.stream`, semantics in INTEGRATION.md "Streaming (resumable) search".  With `max_pending` the stream has no end:
@@ -30,7 +31,8 @@ import torch
 
 from . import _lib, ops
 from .align import Word, group_words
-from .hotwords import Hotwords, as_hotwords
+from . import hotwords as _hw
+from .hotwords import HotwordRows, Hotwords, as_hotwords
 from .lm import NgramLanguageModel, as_language_model
 
 
@@ -59,18 +61,28 @@ def tokens_to_text(tokens: torch.Tensor, counts: torch.Tensor, vocab: Sequence[s
 class _Fusion:
     """The fusion group of a search: the device tables of the language model and of the hotwords (None: not used) and the
     knobs.  `args` is the group as the C entries take it (lm_tables, alpha, beta, unk_score_offset, score_boundary, hw_tables,
-    hotword_weight); `fused`: the search has LM or hotword terms (and returns am_scores)."""
+    hotword_weight); `fused`: the search has LM or hotword terms (and returns am_scores).
+    `rows`: per-request hotwords, (buffer, pointers (B) int64, weights (B) float64) on the device (HotwordRows.to_device, or a
+    stream's reserved regions).  The search is then the hotword search through the entries of conformer_hip3_hotword_rows.h,
+    which take the same group with the two arrays in the place of (hw_tables, hotword_weight); `hw_tables` is the buffer, which
+    the init, reset and commit entries read as the mode flag only."""
 
     def __init__(self, lm_tables: Optional[torch.Tensor], hw_tables: Optional[torch.Tensor], alpha: float, beta: float,
-                 unk_score_offset: float, score_boundary: bool, hotword_weight: float = 0.0) -> None:
+                 unk_score_offset: float, score_boundary: bool, hotword_weight: float = 0.0, rows=None) -> None:
+        self.rows = rows
+        if rows is not None:
+            hw_tables = rows[0]
         self.lm_tables, self.hw_tables = lm_tables, hw_tables
         self.score_boundary = 1 if score_boundary else 0
         self.fused = lm_tables is not None or hw_tables is not None
         self.args = (ops._p(lm_tables), float(alpha), float(beta), float(unk_score_offset), self.score_boundary,
                      ops._p(hw_tables), float(hotword_weight))
+        if rows is not None:
+            self.args = self.args[:5] + (rows[1].data_ptr(), rows[2].data_ptr())
 
 
 _PLAIN = _Fusion(None, None, 0.0, 0.0, 0.0, False)
+_NO_TIMES = (None, 0, None, None)          # the absent times group of the per-row stream entries
 
 
 def _logits(logits: torch.Tensor) -> torch.Tensor:
@@ -94,6 +106,15 @@ def _flag(who: str, name: str, value) -> bool:
     if not isinstance(value, bool):
         raise ValueError(f"{who}: {name} must be True or False, got {value!r}")
     return value
+
+
+def _is_rows(hotwords) -> bool:
+    """`hotwords` is one entry per utterance (not one list of phrases): a list or tuple with an element that is no str."""
+    return isinstance(hotwords, (list, tuple)) and any(not isinstance(e, str) for e in hotwords)
+
+
+def _per_row(hotwords, hotword_weight) -> bool:
+    return _is_rows(hotwords) or isinstance(hotword_weight, (list, tuple))
 
 
 def _frame_seconds(who: str, value) -> float:
@@ -143,7 +164,11 @@ def _beam_search(logits: torch.Tensor, blank_id: int, lengths: Optional[torch.Te
     search = (x.data_ptr(), ops._p(lengths), B, T, V, int(blank_id), int(beam_width), int(max_candidates),
               float(token_min_logp), float(beam_prune_logp), int(n_best))
     out = (workspace.data_ptr(), int(ws_bytes), tokens.data_ptr(), counts.data_ptr(), scores.data_ptr())
-    if f.hw_tables is not None:
+    if f.rows is not None:
+        if f.rows[1].numel() != B:
+            raise ValueError(f"hotwords: {f.rows[1].numel()} per-utterance tables, the logits have {B} utterances")
+        name, args = "cfm3_ctc_beam_hw_rows_decode_f32", search + f.args + out + (am_scores.data_ptr(),)
+    elif f.hw_tables is not None:
         name, args = "cfm_ctc_beam_hw_decode_f32", search + f.args + out + (am_scores.data_ptr(),)
     elif f.lm_tables is not None:      # the LM entry takes the group without the hotword pair
         name, args = "cfm_ctc_beam_lm_decode_f32", search + f.args[:5] + out + (am_scores.data_ptr(),)
@@ -203,7 +228,22 @@ def beam_ctc_hotword_decode(logits: torch.Tensor, blank_id: int, hotwords: Union
     (B,N,T) int64 padded with -1, counts (B,N) int64, scores (B,N) fp32 final boosted score, am_scores (B,N) fp32 acoustic,
     num_hyps (B) int64), best first by the final score; unused rows hold count 0, tokens -1 and scores -inf.  The device
     tables are packed and copied once per (hotwords, vocab, delim_token, skip_ids); after that nothing synchronises with the
-    host.  return_times: as beam_ctc_decode, a trailing (token_frames, token_logp)."""
+    host.  return_times: as beam_ctc_decode, a trailing (token_frames, token_logp).
+    Per-request hotwords (INTEGRATION.md "Per-request hotwords"): `hotwords` may be a list or tuple of B entries, one per
+    utterance -- None, () or []: no hotwords for that utterance; a Hotwords; or a sequence of phrases -- and `hotword_weight` a
+    list or tuple of B floats.  Row b of every output then equals this call on utterance b alone with its list and weight."""
+    if _per_row(hotwords, hotword_weight):
+        # per-request hotwords: `hotwords` is one entry per utterance (None or (): no hotwords, a Hotwords, or phrases) and / or
+        # `hotword_weight` one float per utterance; row b is the single-list call on utterance b alone
+        B = logits.shape[0] if isinstance(logits, torch.Tensor) and logits.dim() == 3 else 0
+        entries = hotwords if _is_rows(hotwords) else [hotwords] * B
+        rows = HotwordRows(entries, hotword_weight, vocab, delim_token, skip_ids, batch=B)
+
+        def fusion_rows(device):
+            lm_tables = None if lm is None else as_language_model(lm).device_tables(vocab, delim_token, skip_ids, device)
+            return _Fusion(lm_tables, None, alpha, beta, unk_score_offset, score_boundary, rows=rows.to_device(device))
+        return _beam_search(logits, blank_id, lengths, n_best, beam_width, token_min_logp, beam_prune_logp, max_candidates,
+                            vocab, fusion_rows, return_times)
     if not math.isfinite(float(hotword_weight)):
         raise ValueError(f"hotword_weight must be finite, got {hotword_weight}")
 
@@ -252,23 +292,25 @@ class BeamCTCDecoder:
 
     def stream(self, batch: int, max_frames: Optional[int], device=None, *, max_pending: Optional[int] = None,
                max_chunk_frames: Optional[int] = None, commit_log: int = 4096, times: bool = False,
-               frame_seconds: float = 0.04) -> "BeamCTCStream":
+               frame_seconds: float = 0.04, hotword_rows: Optional[Tuple[int, int]] = None) -> "BeamCTCStream":
         """A resumable search configured like this decoder (beam knobs, lm, hotwords) over `batch` utterances of at most
         `max_frames` frames in all: BeamCTCStream.  max_pending (tokens) with max_chunk_frames (logit frames per step) and
         max_frames=None: a stream without an end in commit mode (beam_ctc_stream_init).  times: the search records token
-        timestamps and the stream hands out Words (pop_committed_words, partial_words, finish_words), frame_seconds per frame."""
+        timestamps and the stream hands out Words (pop_committed_words, partial_words, finish_words), frame_seconds per frame.
+        hotword_rows=(max_phrases, max_code_points): every utterance may take its own hotword list within those bounds
+        (BeamCTCStream.set_hotwords); None: the stream exactly as before."""
         return BeamCTCStream(self, batch, max_frames, device, max_pending=max_pending, max_chunk_frames=max_chunk_frames,
-                             commit_log=commit_log, times=times, frame_seconds=frame_seconds)
+                             commit_log=commit_log, times=times, frame_seconds=frame_seconds, hotword_rows=hotword_rows)
 
-    def words(self, logits: torch.Tensor, lengths: Optional[torch.Tensor] = None, frame_seconds: float = 0.04
-              ) -> List[List[Word]]:
+    def words(self, logits: torch.Tensor, lengths: Optional[torch.Tensor] = None, frame_seconds: float = 0.04, *,
+              hotwords=None, hotword_weight=None) -> List[List[Word]]:
         """The best hypothesis of every utterance of logits (B,T,V) as align.Words timed by the search itself (INTEGRATION.md
         "Beam-search timestamps": a token's frame is its entry into the surviving lineage, not the Viterbi start CTCAligner
-        returns; Word.score is the mean token log-probability).  Synchronises."""
+        returns; Word.score is the mean token log-probability).  Synchronises.  hotwords, hotword_weight: as __call__."""
         fs = _frame_seconds("BeamCTCDecoder.words", frame_seconds)
         if lengths is not None and not (isinstance(lengths, torch.Tensor) and lengths.is_cuda):
             lengths = torch.as_tensor(lengths, dtype=torch.int64).reshape(-1).to(logits.device)
-        fusion = None if self.lm is None and self.hotwords is None else self._fusion
+        fusion = self._call_fusion(logits.shape[0], hotwords, hotword_weight)
         out = _beam_search(logits, self.blank_id, lengths, 1, self.beam_width, self.token_min_logp, self.beam_prune_logp,
                            self.max_candidates, self.vocab, fusion, True)
         tk, ct = out[0][:, 0].cpu().tolist(), out[1][:, 0].cpu().tolist()
@@ -297,14 +339,34 @@ class BeamCTCDecoder:
             preds.append(decode_func(text) if decode_func is not None else text)
         return preds
 
+    def _call_fusion(self, B: int, hotwords, hotword_weight):
+        """The `fusion` argument of _beam_search for one call: the decoder's own group, or, with per-request hotwords, the
+        group with a table and a weight per utterance (packed and uploaded for this call; no cache of the decoder grows)."""
+        if hotwords is None and hotword_weight is None:
+            return None if self.lm is None and self.hotwords is None else self._fusion
+        rows = HotwordRows([None] * B if hotwords is None else hotwords, hotword_weight, self.vocab, self.delim_token,
+                           self.skip_ids, batch=B, default=self.hotwords, default_weight=self.hotword_weight)
+
+        def fusion(device):
+            skip = tuple(sorted(self.skip_ids))
+            lm_tables = None if self.lm is None else self.lm.device_tables(self.vocab, self.delim_token, skip, device)
+            return _Fusion(lm_tables, None, self.alpha, self.beta, self.unk_score_offset, self.score_boundary,
+                           rows=rows.to_device(device))
+        return fusion
+
     def __call__(self, logits: torch.Tensor, lengths: Optional[torch.Tensor] = None,
-                 decode_func: Optional[Callable[[str], str]] = None) -> Union[str, List[str]]:
+                 decode_func: Optional[Callable[[str], str]] = None, *, hotwords=None, hotword_weight=None
+                 ) -> Union[str, List[str]]:
+        """hotwords: one entry per utterance (B of them; for (T,V) logits a list of one) -- None: the decoder's own list, () or
+        []: no hotwords, a Hotwords, or a sequence of phrases, which REPLACES the decoder's list for that utterance;
+        hotword_weight: one float or B of them (None: the decoder's).  Utterance b's text is what a decoder constructed with
+        its list and weight returns for it alone (INTEGRATION.md "Per-request hotwords").  Neither given: the call as before."""
         single = logits.dim() == 2
         if single:
             logits = logits.unsqueeze(0)
         if lengths is not None and not (isinstance(lengths, torch.Tensor) and lengths.is_cuda):
             lengths = torch.as_tensor(lengths, dtype=torch.int64).reshape(-1).to(logits.device)   # numpy lengths, as lm.py takes
-        fusion = None if self.lm is None and self.hotwords is None else self._fusion
+        fusion = self._call_fusion(logits.shape[0], hotwords, hotword_weight)
         out = _beam_search(logits, self.blank_id, lengths, 1, self.beam_width, self.token_min_logp, self.beam_prune_logp,
                            self.max_candidates, self.vocab, fusion)
         preds = self._texts(out[0], out[1], decode_func)
@@ -331,12 +393,73 @@ class _StreamState:
         self.times: Optional[torch.Tensor] = None
         self.log_frames: Optional[torch.Tensor] = None   # (B, L) int64
         self.log_logp: Optional[torch.Tensor] = None     # (B, L) fp32
+        # per-request hotwords (beam_ctc_stream_init(hotword_rows=...)): the reserved regions (fusion.rows holds the arrays)
+        self.regions: Optional["_HotwordRegions"] = None
 
     def times_outputs(self, N: int):
         """(times buffer, its size, token_frames, token_logp) as the *_times entries take them, and the pair they fill"""
         tf = torch.empty(self.B, N, self.t_max, dtype=torch.int64, device=self.buf.device)
         tl = torch.empty(self.B, N, self.t_max, dtype=torch.float32, device=self.buf.device)
         return (self.times.data_ptr(), self.times.numel(), tf.data_ptr(), tl.data_ptr()), (tf, tl)
+
+
+class _HotwordRegions:
+    """The reservation of a stream with per-request hotwords: one uint8 tensor of B regions of `stride` bytes (each large enough
+    for any list within `bounds`, each starting as the table of the empty list), the (B) int64 pointers the search reads -- to
+    an utterance's own region, or to `shared`, the decoder's own table -- and the (B) float64 weights.  Nothing is allocated
+    on the device after construction."""
+
+    def __init__(self, B: int, bounds, vocab: Sequence[str], delim_token: str, skip_ids, device, shared: Optional[torch.Tensor],
+                 weight: float) -> None:
+        self.bounds = _hw.check_bounds(bounds)
+        self.vocab, self.delim_token, self.skip = list(vocab), delim_token, frozenset(int(i) for i in skip_ids)
+        self.empty = torch.from_numpy(_hw._EMPTY.pack(self.vocab, delim_token, self.skip))
+        self.stride = _hw._align(_hw.reserved_bytes(*self.bounds, self.vocab, delim_token, self.skip))
+        self.shared, self.default_weight = shared, _hw.row_weight(weight, 0.0)
+        self.buf = torch.empty(B * self.stride, dtype=torch.uint8, device=device)
+        self.buf.view(B, self.stride)[:, :self.empty.numel()] = self.empty.to(device)
+        base = self.buf.data_ptr()
+        self.own = [base + b * self.stride for b in range(B)]
+        ptrs = self.own if shared is None else [shared.data_ptr()] * B
+        self.ptrs = torch.tensor(ptrs, dtype=torch.int64).to(device)
+        self.weights = torch.full((B,), self.default_weight, dtype=torch.float64).to(device)
+
+    def pack(self, hotwords, who: str) -> torch.Tensor:
+        """The table of a list (a Hotwords or phrases) as a host tensor, refused with ValueError over the reserved bounds."""
+        hw = hotwords if isinstance(hotwords, Hotwords) else Hotwords(hotwords)
+        _hw.fits(hw, self.bounds, who)
+        if not len(hw):
+            return self.empty
+        blob = hw.pack(self.vocab, self.delim_token, self.skip) if hotwords is hw else hw._pack(self.vocab, self.delim_token, self.skip)
+        if blob.nbytes > self.stride:            # (reserved_bytes is an upper bound: not reached)
+            raise ValueError(f"{who}: a table of {blob.nbytes} bytes, the region holds {self.stride}")
+        return torch.from_numpy(blob)
+
+
+def beam_ctc_stream_set_hotwords(st: "_StreamState", b: int, table: Optional[torch.Tensor], weight: float) -> None:
+    """Utterance b of a state made with hotword_rows= takes `table` (a packed host table, _HotwordRegions.pack; None: the shared
+    table the state was made with, or no hotwords without one) and `weight`.  The caller guarantees that b's search is at the
+    empty prefix.  The table, the pointer and the weight go through ONE fresh pinned tensor per call (so no copy in flight ever
+    reads memory that is written again) and the copies are only enqueued on the current stream."""
+    r = st.regions
+    if r is None:
+        raise ValueError("beam_ctc_stream_set_hotwords: the state was made without hotword_rows")
+    b = int(b)
+    if not 0 <= b < st.B:
+        raise ValueError(f"beam_ctc_stream_set_hotwords: utterance {b} outside [0, {st.B})")
+    if table is None and r.shared is None:
+        table = r.empty
+    n = 0 if table is None else table.numel()
+    n8 = (n + 7) // 8 * 8
+    host = torch.empty(n8 + 16, dtype=torch.uint8, pin_memory=r.buf.is_cuda)
+    if n:
+        host[:n] = table
+    host[n8:n8 + 8].view(torch.int64)[0] = r.shared.data_ptr() if table is None else r.own[b]
+    host[n8 + 8:].view(torch.float64)[0] = _hw.row_weight(weight, r.default_weight)
+    if n:
+        r.buf[b * r.stride:b * r.stride + n].copy_(host[:n], non_blocking=True)
+    r.ptrs[b:b + 1].copy_(host[n8:n8 + 8].view(torch.int64), non_blocking=True)
+    r.weights[b:b + 1].copy_(host[n8 + 8:].view(torch.float64), non_blocking=True)
 
 
 def _commit_args(who: str, max_frames, max_pending, max_chunk_frames, commit_log=4096):
@@ -364,7 +487,9 @@ def beam_ctc_stream_init(batch: int, max_frames: Optional[int], device, *, beam_
                          lm_tables: Optional[torch.Tensor] = None, hw_tables: Optional[torch.Tensor] = None,
                          alpha: float = 2.1, beta: float = 9.2, unk_score_offset: float = -10.0, score_boundary: bool = True,
                          hotword_weight: float = 9.0, max_pending: Optional[int] = None,
-                         max_chunk_frames: Optional[int] = None, commit_log: int = 4096, times: bool = False) -> _StreamState:
+                         max_chunk_frames: Optional[int] = None, commit_log: int = 4096, times: bool = False,
+                         hotword_rows: Optional[Tuple[int, int]] = None, vocab: Optional[Sequence[str]] = None,
+                         delim_token: str = "|", skip_ids: Sequence[int] = ()) -> _StreamState:
     """Allocate and initialise the state of a resumable CTC prefix beam search over `batch` utterances of at most
     `max_frames` frames, every utterance at the empty prefix.  `lm_tables` / `hw_tables`: the device blobs of
     NgramLanguageModel.device_tables / Hotwords.device_tables (None: not used).  Enqueues only.
@@ -372,12 +497,26 @@ def beam_ctc_stream_init(batch: int, max_frames: Optional[int], device, *, beam_
     then sized by (B, M, k_cap, W, K, lm, hw) alone and the stream has no end; the committed tokens go to a ring of
     max(commit_log, M + k_cap) tokens per utterance (beam_ctc_stream_committed reads it).
     times: the search records token timestamps (INTEGRATION.md "Beam-search timestamps") in a buffer beside the state; step and
-    finish then return a trailing (token_frames, token_logp) and the commit log has frames and log-probabilities beside it."""
+    finish then return a trailing (token_frames, token_logp) and the commit log has frames and log-probabilities beside it.
+    hotword_rows=(max_phrases, max_code_points) with vocab (and delim_token, skip_ids): per-request hotwords (INTEGRATION.md
+    "Per-request hotwords").  The state reserves, per utterance, a table region for any list within those bounds (each starts
+    as the table of the empty list), a table pointer and a weight; every utterance starts with `hw_tables` (None: no hotwords)
+    and `hotword_weight`, and beam_ctc_stream_set_hotwords gives one its own.  Nothing is allocated after this call."""
     _flag("beam_ctc_stream_init", "times", times)
     commit = _commit_args("beam_ctc_stream_init", max_frames, max_pending, max_chunk_frames, commit_log)
-    fusion = _Fusion(lm_tables, hw_tables, alpha, beta, unk_score_offset, score_boundary, hotword_weight)
-    return _stream_alloc("beam_ctc_stream_init", int(batch), max_frames, device, int(beam_width), int(max_candidates), fusion,
-                         commit, commit_log, times)
+    regions = None
+    if hotword_rows is not None:
+        if vocab is None:
+            raise ValueError("beam_ctc_stream_init: hotword_rows needs vocab (the tables spell the tokens)")
+        regions = _HotwordRegions(int(batch), hotword_rows, vocab, delim_token, skip_ids, device, hw_tables, hotword_weight)
+        fusion = _Fusion(lm_tables, None, alpha, beta, unk_score_offset, score_boundary,
+                         rows=(regions.buf, regions.ptrs, regions.weights))
+    else:
+        fusion = _Fusion(lm_tables, hw_tables, alpha, beta, unk_score_offset, score_boundary, hotword_weight)
+    st = _stream_alloc("beam_ctc_stream_init", int(batch), max_frames, device, int(beam_width), int(max_candidates), fusion,
+                       commit, commit_log, times)
+    st.regions = regions
+    return st
 
 
 def _stream_alloc(who: str, B: int, max_frames: Optional[int], device, W: int, K: int, fusion: _Fusion, commit, commit_log: int,
@@ -476,10 +615,13 @@ def beam_ctc_stream_step(st: _StreamState, logits: torch.Tensor, blank_id: int, 
             float(beam_prune_logp), int(n_best), *st.fusion.args, st.buf.data_ptr(), st.buf.numel(), st.t_max, used,
             tokens.data_ptr(), counts.data_ptr(), scores.data_ptr(), ops._p(am_scores), num_hyps.data_ptr())
     pair = None
-    if st.times is None:
+    if st.times is not None:
+        targs, pair = st.times_outputs(int(n_best))
+    if st.fusion.rows is not None:         # per-request hotwords: one entry, the times group nullable
+        _lib.call("cfm3_ctc_beam_hw_rows_stream_step_f32", *step, *(targs if pair is not None else _NO_TIMES), ops._stream())
+    elif st.times is None:
         _lib.call("cfm_ctc_beam_stream_step_f32", *step, ops._stream())
     else:
-        targs, pair = st.times_outputs(int(n_best))
         _lib.call("cfm_ctc_beam_stream_step_times_f32", *step, *targs, ops._stream())
     if t_used is None:
         st.t_used += Tc
@@ -540,11 +682,16 @@ def beam_ctc_stream_finish(st: _StreamState, n_best: int = 1):
                                                                 st.fusion.fused)
     fin = (st.B, st.beam_width, st.max_candidates, int(n_best), *st.fusion.args, st.buf.data_ptr(), st.buf.numel(), st.t_max,
            tokens.data_ptr(), counts.data_ptr(), scores.data_ptr(), ops._p(am_scores), num_hyps.data_ptr())
+    rows = st.fusion.rows is not None
     if st.times is None:
-        _lib.call("cfm_ctc_beam_stream_finish_f32", *fin, ops._stream())
+        if rows:
+            _lib.call("cfm3_ctc_beam_hw_rows_stream_finish_f32", *fin, *_NO_TIMES, ops._stream())
+        else:
+            _lib.call("cfm_ctc_beam_stream_finish_f32", *fin, ops._stream())
         return tokens, counts, scores, am_scores, num_hyps
     targs, pair = st.times_outputs(int(n_best))
-    _lib.call("cfm_ctc_beam_stream_finish_times_f32", *fin, *targs, ops._stream())
+    _lib.call("cfm3_ctc_beam_hw_rows_stream_finish_f32" if rows else "cfm_ctc_beam_stream_finish_times_f32", *fin, *targs,
+              ops._stream())
     return tokens, counts, scores, am_scores, num_hyps, pair
 
 
@@ -561,11 +708,14 @@ class BeamCTCStream:
     align.Words: `partial_words`, `finish_words` and, in commit mode, `pop_committed_words`, which returns complete words only and
     HOLDS the committed tokens after the last committed delimiter on the host until their delimiter is committed or the stream
     finishes.  Held tokens count as popped: `pop_committed` never returns them, while the texts and words of `partial_*`,
-    `committed_text` and `finish*` still begin with them."""
+    `committed_text` and `finish*` still begin with them.
+    hotword_rows=(max_phrases, max_code_points) (INTEGRATION.md "Per-request hotwords"): every utterance starts with the
+    decoder's own list and weight, and `set_hotwords(b, ...)` gives utterance b its own while its search is at the empty prefix:
+    after construction, `reset` or `reset_slots`, before the next `step`.  `reset` and `reset_slots` do not change the lists."""
 
     def __init__(self, decoder: "BeamCTCDecoder", batch: int, max_frames: Optional[int], device=None, *,
                  max_pending: Optional[int] = None, max_chunk_frames: Optional[int] = None, commit_log: int = 4096,
-                 times: bool = False, frame_seconds: float = 0.04) -> None:
+                 times: bool = False, frame_seconds: float = 0.04, hotword_rows: Optional[Tuple[int, int]] = None) -> None:
         self.times = _flag("BeamCTCStream", "times", times)
         self.frame_seconds = _frame_seconds("BeamCTCStream", frame_seconds)
         self.commit = _commit_args("BeamCTCStream", max_frames, max_pending, max_chunk_frames, commit_log) is not None
@@ -577,7 +727,10 @@ class BeamCTCStream:
                                           alpha=d.alpha, beta=d.beta, unk_score_offset=d.unk_score_offset,
                                           score_boundary=d.score_boundary, hotword_weight=d.hotword_weight,
                                           max_pending=max_pending, max_chunk_frames=max_chunk_frames, commit_log=commit_log,
-                                          times=self.times)
+                                          times=self.times,
+                                          **({} if hotword_rows is None else dict(
+                                              hotword_rows=hotword_rows, vocab=d.vocab, delim_token=d.delim_token,
+                                              skip_ids=tuple(sorted(d.skip_ids)))))
         self.finished = False
         self.last = None                   # interim outputs of the latest step
         self.last_committed = None         # commit mode: the (B) tokens the latest step committed
@@ -600,6 +753,35 @@ class BeamCTCStream:
         self.last_committed = self.state.committed if self.commit else None
         self.fresh.clear()
         return out[0], out[1], out[2]
+
+    def plan_hotwords(self, hotwords, hotword_weight=None):
+        """The host half of set_hotwords: (table or None, weight), packed and checked; ValueError (naming the limit) for a list
+        over the reserved bounds, a malformed list or a non-finite weight.  Nothing is enqueued."""
+        r = self.state.regions
+        if r is None:
+            raise ValueError("BeamCTCStream.set_hotwords: the stream was made without hotword_rows=(max_phrases, "
+                             "max_code_points), no table region is reserved")
+        weight = _hw.row_weight(hotword_weight, r.default_weight)
+        return (None if hotwords is None else r.pack(hotwords, "BeamCTCStream.set_hotwords")), weight
+
+    def apply_hotwords(self, b: int, plan) -> None:
+        """The device half of set_hotwords for a plan_hotwords result: RuntimeError unless utterance b is at the empty prefix."""
+        b = int(b)
+        if not 0 <= b < len(self.popped):
+            raise ValueError(f"BeamCTCStream.set_hotwords: utterance {b} outside [0, {len(self.popped)})")
+        if b not in self.fresh or self.finished:
+            raise RuntimeError(f"BeamCTCStream.set_hotwords: utterance {b} has been stepped since its last reset; a hotword list "
+                               "can only change at the empty prefix (the saved trie nodes index the old tables): reset() or "
+                               "reset_slots([b]) first")
+        beam_ctc_stream_set_hotwords(self.state, b, plan[0], plan[1])
+
+    def set_hotwords(self, b: int, hotwords, hotword_weight: Optional[float] = None) -> None:
+        """Utterance b's hotword list and weight (a stream made with hotword_rows=).  hotwords: None (the decoder's own list),
+        () or [] (no hotwords), a Hotwords, or phrases, which replace the decoder's list; hotword_weight: None is the
+        decoder's.  Packs on the host, then only enqueues the copies into b's reserved region on the current stream.
+        ValueError, before anything is enqueued, for a list over the reserved bounds; RuntimeError once b has been stepped
+        since its last reset (a step with lengths[b] == 0 counts: the host does not read the lengths)."""
+        self.apply_hotwords(b, self.plan_hotwords(hotwords, hotword_weight))
 
     def reset_slots(self, slots: Sequence[int]) -> None:
         """The utterances `slots` (host ints) back at the empty prefix with nothing committed and nothing popped, the others

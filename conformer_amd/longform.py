@@ -111,6 +111,19 @@ def window_frames(window_seconds: float, overlap_seconds: float, mel_seconds: fl
     return W, W - H
 
 
+def _recording_hotwords(n: int, hotwords, hotword_weight):
+    """transcribe's per-recording hotwords as (entries, weights), n of each, or None when neither was given."""
+    if hotwords is None and hotword_weight is None:
+        return None
+    entries = [None] * n if hotwords is None else list(hotwords)
+    if isinstance(hotwords, str) or len(entries) != n:
+        raise ValueError(f"Transcriber: hotwords must have one entry per recording ({n}), got {len(entries)}")
+    weights = list(hotword_weight) if isinstance(hotword_weight, (list, tuple)) else [hotword_weight] * n
+    if len(weights) != n:
+        raise ValueError(f"Transcriber: hotword_weight must be one float or one per recording ({n}), got {len(weights)}")
+    return entries, weights
+
+
 def _ambient_autocast(who: str) -> Optional[torch.dtype]:
     if not torch.is_autocast_enabled("cuda"):
         return None
@@ -359,22 +372,28 @@ class Transcriber:
         return [order[k:k + self.batch_windows] for k in range(0, len(order), self.batch_windows)]
 
     @torch.no_grad()
-    def transcribe(self, audios: Sequence[torch.Tensor], sample_rates: Optional[Sequence[int]] = None) -> List[Transcript]:
+    def transcribe(self, audios: Sequence[torch.Tensor], sample_rates: Optional[Sequence[int]] = None, hotwords=None,
+                   hotword_weight=None) -> List[Transcript]:
         """audios: waveforms as the front end takes them (sample_rates: their rates, None: all at the front end's own), or log-mel
         tensors (n_mel, n_i) without a front end; every recording needs at least 7 mel frames.  One Transcript per recording, in
-        the caller's order.  Synchronises (the texts are read back)."""
+        the caller's order.  Synchronises (the texts are read back).
+        hotwords: one entry per recording (None: the decoder's own list, () or []: none, a Hotwords or phrases), hotword_weight:
+        one float or one per recording (None: the decoder's) -- BeamCTCDecoder.__call__, INTEGRATION.md "Per-request hotwords";
+        text, words and confidence of a recording all come from the search with its list."""
         lstm_state(self.model, "Transcriber", 1)
         _ambient_autocast("Transcriber")
         if len(audios) == 0:
             return []
+        rows = _recording_hotwords(len(audios), hotwords, hotword_weight)
         mels = self.features(audios, sample_rates)
         if self.vad is not None:
-            return self._transcribe_islands(mels)
-        return self._decode(self.encoder.encode(mels), [m.shape[1] * self.mel_seconds for m in mels])
+            return self._transcribe_islands(mels, rows)
+        return self._decode(self.encoder.encode(mels), [m.shape[1] * self.mel_seconds for m in mels], rows)
 
-    def _decode(self, hs: Sequence[torch.Tensor], seconds: Sequence[float]) -> List[Transcript]:
+    def _decode(self, hs: Sequence[torch.Tensor], seconds: Sequence[float], rows=None) -> List[Transcript]:
         """The decoder head, the search and the confidences over encoder frames hs (one (T', d) tensor per recording), in
-        groups; one Transcript per recording, in the order given."""
+        groups; one Transcript per recording, in the order given.  rows: None or (hotwords, weights), one entry per recording
+        (the same order as hs), which follow their recordings into the groups."""
         out: List[Optional[Transcript]] = [None] * len(hs)
         for group in self.groups([h.shape[0] for h in hs]):
             n = [hs[i].shape[0] for i in group]
@@ -383,8 +402,9 @@ class Transcriber:
                 h[k, :n[k]] = hs[i]
             lengths = torch.tensor(n, dtype=torch.int64).to(self.device, non_blocking=True)
             logits = self.decoder_head(h, lengths)
-            texts = self.decoder(logits, lengths)
-            words = self.decoder.words(logits, lengths, self.frame_seconds) if self.times else [None] * len(group)
+            kw = {} if rows is None else dict(hotwords=[rows[0][i] for i in group], hotword_weight=[rows[1][i] for i in group])
+            texts = self.decoder(logits, lengths, **kw)
+            words = self.decoder.words(logits, lengths, self.frame_seconds, **kw) if self.times else [None] * len(group)
             scores = [None] * len(group)
             if self.confidence is not None:
                 conf, ids = frame_confidence(logits, lengths, self.confidence)
@@ -413,7 +433,7 @@ class Transcriber:
         mels = [m if m.is_cuda else m.to(self.device) for m in self.features(audios, sample_rates)]
         return [[(a * self.mel_seconds, b * self.mel_seconds) for a, b in isl] for isl in self._islands(mels)]
 
-    def _transcribe_islands(self, mels: Sequence[torch.Tensor]) -> List[Transcript]:
+    def _transcribe_islands(self, mels: Sequence[torch.Tensor], rows=None) -> List[Transcript]:
         """transcribe with vad=: the islands of all recordings through ONE BufferedEncoder.encode as if they were recordings,
         per recording their encoder frames concatenated, _decode over the concatenations, and every Word mapped back to the
         recording's own time axis: frame c of the concatenation that lies j frames into the island (a, b) is the recording's
@@ -425,7 +445,8 @@ class Transcriber:
         encoded = self.encoder.encode([mels[r][:, a:b] for r, a, b in pieces]) if pieces else []
         spoken = [r for r, isl in enumerate(islands) if isl]
         mine = {r: [h for h, (r2, _, _) in zip(encoded, pieces) if r2 == r] for r in spoken}
-        decoded = self._decode([torch.cat(mine[r]) for r in spoken], [seconds[r] for r in spoken])
+        decoded = self._decode([torch.cat(mine[r]) for r in spoken], [seconds[r] for r in spoken],
+                               None if rows is None else ([rows[0][r] for r in spoken], [rows[1][r] for r in spoken]))
         out = [Transcript("", [] if self.times else None, [] if self.confidence is not None else None, 0, s) for s in seconds]
         fs = self.frame_seconds
         for r, t in zip(spoken, decoded):

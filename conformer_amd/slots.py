@@ -312,7 +312,10 @@ class SlotTranscriber:
     (INTEGRATION.md "Keyword spotting": two more launches, nothing synchronises; max_detections rows per slot and group of
     keywords between two reads).  open(s) arms slot s; segment(s) does NOT arm it again, so every time counts from open(s).
     keywords() pops the open slots' new detections, close_keywords(s) ends slot s's stream of detections (close(s) itself is
-    unchanged).  Without it the module is not imported and nothing is launched or allocated."""
+    unchanged).  Without it the module is not imported and nothing is launched or allocated.
+    slot_hotwords=(max_phrases, max_code_points): every slot may carry its own hotword list within those bounds (INTEGRATION.md
+    "Per-request hotwords"): open(s, hotwords=..., hotword_weight=...) sets slot s's list (None: the decoder's own list and
+    weight; () or []: none), segment(s) keeps it.  Without it open() refuses a list and the object is exactly as before."""
 
     audio: Optional[StreamingAudioFrontend] = None
     endpointer: Optional[StreamingEndpointer] = None
@@ -326,7 +329,7 @@ class SlotTranscriber:
                  commit_log: int = 4096, times: bool = False, frame_seconds: float = 0.04,
                  audio: Optional[StreamingAudioFrontend] = None, endpoint: Optional[EndpointConfig] = None,
                  confidence: Optional[ConfidenceConfig] = None, confidence_history: int = 4096, keywords=None,
-                 max_detections: int = 64) -> None:
+                 max_detections: int = 64, slot_hotwords: Optional[Tuple[int, int]] = None) -> None:
         tplan = times_plan("SlotTranscriber", times, frame_seconds)
         cplan = transcriber_confidence("SlotTranscriber", confidence, confidence_history, tplan[0])
         if endpoint is not None:
@@ -345,7 +348,8 @@ class SlotTranscriber:
         self.encoder = SlotStreamingEncoder(model.encoder, slots, max_mel_frames, dtype=self.dtype, left_context=left_context,
                                             max_chunk_mel_frames=max_chunk_mel_frames)
         self.S = self.encoder.S
-        self.beam = search_stream(decoder, self.commit, self.S, self.encoder.t_max, self.device, commit_log, tplan)
+        self.slot_hotwords = slot_hotwords
+        self.beam = search_stream(decoder, self.commit, self.S, self.encoder.t_max, self.device, commit_log, tplan, slot_hotwords)
         self.frame_seconds = tplan[1]
         self.seg_start = [0] * self.S
         if endpoint is not None:
@@ -370,8 +374,17 @@ class SlotTranscriber:
         out = read(only=open_slots)
         return {s: out[s] for s in open_slots}
 
-    def open(self, s: int) -> None:
-        """Start an utterance in free slot s (enqueues only)."""
+    def open(self, s: int, hotwords=None, hotword_weight: Optional[float] = None) -> None:
+        """Start an utterance in free slot s (enqueues only).  With slot_hotwords=: the slot's hotword list (None: the decoder's
+        own; () or []: none; a Hotwords or phrases replace the decoder's) and weight (None: the decoder's), packed on the host
+        and refused with ValueError, before anything is enqueued, over the reserved bounds.  Without slot_hotwords= a list or a
+        weight raises ValueError."""
+        plan = None
+        if self.slot_hotwords is not None:
+            plan = self.beam.plan_hotwords(hotwords, hotword_weight)
+        elif hotwords is not None or hotword_weight is not None:
+            raise ValueError("SlotTranscriber.open: a hotword list per slot needs slot_hotwords=(max_phrases, max_code_points) at "
+                             "construction")
         self.encoder.open(s)
         if self.audio is not None:
             self._drop_audio(s)
@@ -380,6 +393,8 @@ class SlotTranscriber:
             h[s].zero_()
             c[s].zero_()
         self.beam.reset_slots([s])
+        if plan is not None:                                               # (the slot's search is at the empty prefix)
+            self.beam.apply_hotwords(s, plan)
         self._new_segment(s, 0)
         if self.confidence is not None:                                    # (a segment does not: its words count from open(s))
             self.confidence.reset_slots([s])

@@ -63,10 +63,13 @@ def times_plan(who: str, times, frame_seconds) -> Tuple[bool, float]:
 
 
 def search_stream(decoder: BeamCTCDecoder, plan, batch: int, t_max: Optional[int], device, commit_log: int,
-                  times: Tuple[bool, float] = (False, 0.04)) -> BeamCTCStream:
+                  times: Tuple[bool, float] = (False, 0.04), hotword_rows: Optional[Tuple[int, int]] = None) -> BeamCTCStream:
     """The transcribers' search for a search_plan: one that ends with the encoder's t_max frames, or a committing one.
-    times: a times_plan; (False, ...) makes the stream exactly as before."""
+    times: a times_plan; (False, ...) makes the stream exactly as before.  hotword_rows: (max_phrases, max_code_points) reserved
+    per utterance for per-request hotwords; None makes the stream exactly as before."""
     kw = dict(times=True, frame_seconds=times[1]) if times[0] else {}
+    if hotword_rows is not None:
+        kw["hotword_rows"] = hotword_rows
     if plan is None:
         return decoder.stream(batch, t_max, device, **kw)
     return decoder.stream(batch, None, device, max_pending=plan[0], max_chunk_frames=plan[1], commit_log=commit_log, **kw)
@@ -103,7 +106,10 @@ class StreamingTranscriber:
     instead of mel frames (INTEGRATION.md "Streaming audio front end"); the transcriber opens every slot of it, reset() again.
     confidence=ConfidenceConfig(...) (needs times=True): every step also keeps the frame confidence of the logits it returns, for
     the last confidence_history frames (INTEGRATION.md "Confidence"); word_confidence(words) gives the Words this object
-    returned their confidence.  Without it nothing is launched or allocated."""
+    returned their confidence.  Without it nothing is launched or allocated.
+    hotword_rows=(max_phrases, max_code_points): every utterance may take its own hotword list within those bounds (INTEGRATION.md
+    "Per-request hotwords"): set_hotwords(b, ...) after construction or reset(), before the next step.  Without it the object is
+    exactly as before."""
 
     audio: Optional[StreamingAudioFrontend] = None
     confidence: Optional[StreamingConfidence] = None
@@ -113,7 +119,7 @@ class StreamingTranscriber:
                  max_chunk_mel_frames: Optional[int] = None, max_pending: Optional[int] = None,
                  commit_log: int = 4096, times: bool = False, frame_seconds: float = 0.04,
                  audio: Optional[StreamingAudioFrontend] = None, confidence: Optional[ConfidenceConfig] = None,
-                 confidence_history: int = 4096) -> None:
+                 confidence_history: int = 4096, hotword_rows: Optional[Tuple[int, int]] = None) -> None:
         tplan = times_plan("StreamingTranscriber", times, frame_seconds)
         cplan = transcriber_confidence("StreamingTranscriber", confidence, confidence_history, tplan[0])
         plan = search_plan("StreamingTranscriber", max_mel_frames, left_context, max_chunk_mel_frames, max_pending)
@@ -129,9 +135,14 @@ class StreamingTranscriber:
         self.model = model
         self.encoder = StreamingEncoder(model.encoder, batch, max_mel_frames, graphs=graphs, check_weights=check_weights,
                                         left_context=left_context, max_chunk_mel_frames=max_chunk_mel_frames)
-        self.beam = search_stream(decoder, plan, self.B, self.encoder.t_max, device, commit_log, tplan)
+        self.beam = search_stream(decoder, plan, self.B, self.encoder.t_max, device, commit_log, tplan, hotword_rows)
         if cplan is not None:
             self.confidence = StreamingConfidence(self.B, decoder.blank_id, cplan[0], cplan[1], device)
+
+    def set_hotwords(self, b: int, hotwords, hotword_weight: Optional[float] = None) -> None:
+        """With hotword_rows=: utterance b's hotword list and weight (BeamCTCStream.set_hotwords), after construction or reset()
+        and before the next step.  The lists stay over reset()."""
+        self.beam.set_hotwords(b, hotwords, hotword_weight)
 
     def reset(self) -> None:
         self.encoder.reset()

@@ -20,6 +20,7 @@ from typing import List, NamedTuple, Optional, Sequence, Tuple
 import torch
 
 from . import _lib, ops
+from ._slot_state import SlotFollower, frame_chunks
 from .align import Alignment, Word
 
 _C = _lib.HEADERS["conformer_hip_confidence.h"].constants
@@ -248,49 +249,33 @@ def word_confidence(words: Sequence[Sequence[Word]], conf: torch.Tensor, frame_i
     return [row[:len(ws)] for row, ws in zip(out, words)]
 
 
-class StreamingConfidence:
+class StreamingConfidence(SlotFollower):
     """Frame confidence for `slots` independent streams (or the utterances of a lockstep batch), kept for the last `history`
     frames of each.
 
         sc = StreamingConfidence(S, blank_id); sc.step(logits, k); ...; sc.words(words_per_slot); sc.reset_slots([s])
 
     `conf` (S, history) fp32 and `ids` (S, history) int64 are rings: frame t of slot b, counted from its last reset, is at
-    column t mod history; `total` (S) int64 is the number of frames the slot has taken.  step and the resets enqueue only."""
+    column t mod history; `total` (S) int64 is the number of frames the slot has taken.  step and the resets enqueue only;
+    after reset_slots the slots' histories start again at frame 0 (conf NaN, ids -1, total 0)."""
+
+    _what = "confidence only exists as gfx950 kernels"
 
     def __init__(self, slots: int, blank_id: int, config: ConfidenceConfig = ConfidenceConfig(), history: int = 4096,
                  device=None) -> None:
         self.method, self.alpha, self.aggregation = _config("StreamingConfidence", config)
         self.exclude = _blank("StreamingConfidence", blank_id, config)
         self.config, self.blank_id = config, blank_id
-        self.S = int(slots)
-        if self.S < 1:
-            raise ValueError(f"StreamingConfidence: slots must be >= 1, got {slots}")
+        self._init_slots("StreamingConfidence", slots, strict=False)
         if isinstance(history, bool) or not isinstance(history, int) or history < 1:
             raise ValueError(f"StreamingConfidence: history must be a number of frames >= 1, got {history!r}")
         self.R = history
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        if self.device.type != "cuda":
-            raise _lib.ConformerHipError(f"StreamingConfidence: device {self.device}; confidence only exists as gfx950 kernels "
-                                         "(no CPU fallback)")
+        self._init_device("StreamingConfidence", device)
         self.conf = torch.full((self.S, self.R), math.nan, dtype=torch.float32, device=self.device)
         self.ids = torch.full((self.S, self.R), -1, dtype=torch.int64, device=self.device)
         self.total = torch.zeros(self.S, dtype=torch.int64, device=self.device)
         self.exclude_dev = _exclude_ids(self.exclude, self.device)
-        self._all: dict = {}               # k=None: the (S) int64 tensor of a k_max, made once per k_max
-
-    def _k(self, k, k_max: int) -> torch.Tensor:
-        if k is None:
-            if k_max not in self._all:
-                self._all[k_max] = torch.full((self.S,), k_max, dtype=torch.int64, device=self.device)
-            return self._all[k_max]
-        if isinstance(k, torch.Tensor) and k.is_cuda:
-            k = ops._req(k, "k", torch.int64)
-        else:
-            host = torch.as_tensor(k, dtype=torch.int64).reshape(-1)
-            k = host.pin_memory().to(self.device, non_blocking=True)
-        if k.dim() != 1 or k.numel() != self.S:
-            raise ValueError(f"k: expected {self.S} frame counts, got shape {tuple(k.shape)}")
-        return k
+        self._armed_state = [(self.conf, math.nan), (self.ids, -1), (self.total, 0)]
 
     @torch.no_grad()
     def step(self, logits: torch.Tensor, k=None) -> None:
@@ -304,28 +289,9 @@ class StreamingConfidence:
             raise ValueError(f"logits: V = {V} outside [2, {V_MAX}]")
         if k_max == 0:
             return
-        k = self._k(k, k_max)
-        for t0 in range(0, k_max, self.R):                                 # (a launch takes at most one lap of the ring)
-            n = min(self.R, k_max - t0)
-            kk = k if k_max <= self.R else (k - t0).clamp_(0, n)
+        k = self._frame_counts(k, k_max)
+        for t0, n, kk in frame_chunks(k, k_max, self.R):                   # (a launch takes at most one lap of the ring)
             _frames(x[:, t0:t0 + n], kk, self.method, self.alpha, self.conf, self.ids, self.total)
-
-    def reset_slots(self, slots: Sequence[int]) -> None:
-        """The slots' histories start again at frame 0 (conf NaN, ids -1, total 0).  Enqueues only."""
-        slots = [int(s) for s in slots]
-        if any(not 0 <= s < self.S for s in slots):
-            raise ValueError(f"slots {slots} outside [0, {self.S})")
-        if not slots:
-            return
-        idx = torch.tensor(slots, dtype=torch.int64).pin_memory().to(self.device, non_blocking=True)
-        self.conf.index_fill_(0, idx, math.nan)
-        self.ids.index_fill_(0, idx, -1)
-        self.total.index_fill_(0, idx, 0)
-
-    def reset(self) -> None:
-        self.conf.fill_(math.nan)
-        self.ids.fill_(-1)
-        self.total.zero_()
 
     @torch.no_grad()
     def spans(self, starts: torch.Tensor, ends: torch.Tensor, n_spans: torch.Tensor) -> torch.Tensor:

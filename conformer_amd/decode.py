@@ -30,6 +30,7 @@ from typing import Callable, Iterable, List, Optional, Sequence, Tuple, Union
 import torch
 
 from . import _lib, ops
+from ._slot_state import positive_seconds
 from .align import Word, group_words
 from . import hotwords as _hw
 from .hotwords import HotwordRows, Hotwords, as_hotwords
@@ -115,12 +116,6 @@ def _is_rows(hotwords) -> bool:
 
 def _per_row(hotwords, hotword_weight) -> bool:
     return _is_rows(hotwords) or isinstance(hotword_weight, (list, tuple))
-
-
-def _frame_seconds(who: str, value) -> float:
-    if isinstance(value, bool) or not isinstance(value, (int, float)) or not math.isfinite(value) or value <= 0:
-        raise ValueError(f"{who}: frame_seconds must be a positive finite number, got {value!r}")
-    return float(value)
 
 
 def token_words(decoder: "BeamCTCDecoder", ids: Sequence[int], frames: Sequence[int], logps: Sequence[float],
@@ -307,7 +302,7 @@ class BeamCTCDecoder:
         """The best hypothesis of every utterance of logits (B,T,V) as align.Words timed by the search itself (INTEGRATION.md
         "Beam-search timestamps": a token's frame is its entry into the surviving lineage, not the Viterbi start CTCAligner
         returns; Word.score is the mean token log-probability).  Synchronises.  hotwords, hotword_weight: as __call__."""
-        fs = _frame_seconds("BeamCTCDecoder.words", frame_seconds)
+        fs = positive_seconds("BeamCTCDecoder.words", "frame_seconds", frame_seconds)
         if lengths is not None and not (isinstance(lengths, torch.Tensor) and lengths.is_cuda):
             lengths = torch.as_tensor(lengths, dtype=torch.int64).reshape(-1).to(logits.device)
         fusion = self._call_fusion(logits.shape[0], hotwords, hotword_weight)
@@ -717,7 +712,7 @@ class BeamCTCStream:
                  max_pending: Optional[int] = None, max_chunk_frames: Optional[int] = None, commit_log: int = 4096,
                  times: bool = False, frame_seconds: float = 0.04, hotword_rows: Optional[Tuple[int, int]] = None) -> None:
         self.times = _flag("BeamCTCStream", "times", times)
-        self.frame_seconds = _frame_seconds("BeamCTCStream", frame_seconds)
+        self.frame_seconds = positive_seconds("BeamCTCStream", "frame_seconds", frame_seconds)
         self.commit = _commit_args("BeamCTCStream", max_frames, max_pending, max_chunk_frames, commit_log) is not None
         self.decoder = decoder
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)

@@ -20,6 +20,7 @@ from typing import List, NamedTuple, Optional, Sequence, Tuple
 import torch
 
 from . import _lib, ops
+from ._slot_state import SlotFollower, frame_chunks, positive_seconds
 
 STATE_COLS = 8             # int32 per slot: frames, trailing, speech, rule, end_frame, end_trailing, 0, 0
 RULE_COLS = 4              # int32 per rule: min_trailing, min_frames, min_speech, 0
@@ -89,12 +90,6 @@ class Endpoint(NamedTuple):
     trailing_frames: int
 
 
-def _frame_seconds(who: str, value) -> float:
-    if isinstance(value, bool) or not isinstance(value, (int, float)) or not math.isfinite(value) or value <= 0:
-        raise ValueError(f"{who}: frame_seconds must be a positive finite number, got {value!r}")
-    return float(value)
-
-
 def silence_ids(blank_id: int, config: EndpointConfig, vocab: Optional[int] = None) -> List[int]:
     """[blank, then config.silence_ids without repeats]; with `vocab` every id is checked against [0, V)."""
     if isinstance(blank_id, bool) or not isinstance(blank_id, int) or blank_id < 0:
@@ -116,59 +111,38 @@ def endpoint_of(row: Sequence[int], frame_seconds: float) -> Optional[Endpoint]:
     return Endpoint(int(row[3]), int(row[4]), (int(row[4]) + 1) * frame_seconds, int(row[5]))
 
 
-class StreamingEndpointer:
+class StreamingEndpointer(SlotFollower):
     """Endpoint detection for `slots` independent streams (or the utterances of a lockstep batch).
 
         ep = StreamingEndpointer(S, blank_id); ep.step(logits, k); ...; ep.read(); ep.reset_slots([s])
 
     Every slot starts armed.  `state` is the (S, 8) int32 device tensor {frames, trailing, speech, rule, end_frame,
-    end_trailing, 0, 0}."""
+    end_trailing, 0, 0}.  reset_slots arms the slots again: counters 0, nothing latched."""
+
+    _what = "endpointing only exists as a gfx950 kernel"
 
     def __init__(self, slots: int, blank_id: int, config: EndpointConfig = EndpointConfig(), frame_seconds: float = 0.04,
                  device=None) -> None:
-        self.frame_seconds = _frame_seconds("StreamingEndpointer", frame_seconds)
+        self.frame_seconds = positive_seconds("StreamingEndpointer", "frame_seconds", frame_seconds)
         if not isinstance(config, EndpointConfig):
             raise ValueError(f"StreamingEndpointer: config must be an EndpointConfig, got {type(config).__name__}")
         self.rule_rows = config.check(self.frame_seconds)
         self.ids = silence_ids(blank_id, config)
-        self.S = int(slots)
-        if self.S < 1:
-            raise ValueError(f"StreamingEndpointer: slots must be >= 1, got {slots}")
+        self._init_slots("StreamingEndpointer", slots, strict=False)
         self.config = config
         self.log_threshold = math.log(float(config.blank_threshold))
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        if self.device.type != "cuda":
-            raise _lib.ConformerHipError(f"StreamingEndpointer: device {self.device}; endpointing only exists as a gfx950 kernel "
-                                         "(no CPU fallback)")
+        self._init_device("StreamingEndpointer", device)
         self.rules = torch.tensor(self.rule_rows, dtype=torch.int32).to(self.device)
         self.ids_dev = torch.tensor(self.ids, dtype=torch.int32).to(self.device)
         self._armed = torch.tensor([_ARMED], dtype=torch.int32).to(self.device)
         self.state = self._armed.repeat(self.S, 1)
-        self._all: dict = {}               # k=None: the (S) int64 tensor of a k_max, made once per k_max
-
-    def _k(self, k, k_max: int) -> torch.Tensor:
-        if k is None:
-            if k_max not in self._all:
-                self._all[k_max] = torch.full((self.S,), k_max, dtype=torch.int64, device=self.device)
-            return self._all[k_max]
-        if isinstance(k, torch.Tensor) and k.is_cuda:
-            k = ops._req(k, "k", torch.int64)
-        else:
-            host = torch.as_tensor(k, dtype=torch.int64).reshape(-1)
-            k = host.pin_memory().to(self.device, non_blocking=True)
-        if k.dim() != 1 or k.numel() != self.S:
-            raise ValueError(f"k: expected {self.S} frame counts, got shape {tuple(k.shape)}")
-        return k
+        self._armed_state = [(self.state, self._armed)]
 
     @torch.no_grad()
     def step(self, logits: torch.Tensor, k=None) -> None:
         """logits (S, k_max, V) fp32 on the device: slot b's next frames are rows 0 .. k[b]-1 (the rest is never read).  k: a
         device int64 tensor (a slot step's own), a host sequence, or None: every row of every slot.  Enqueues only."""
-        if not isinstance(logits, torch.Tensor) or not logits.is_cuda:
-            raise _lib.ConformerHipError(f"logits: expected a tensor on a HIP device, got {getattr(logits, 'device', type(logits))}; "
-                                         "endpointing only exists as a gfx950 kernel (no CPU fallback)")
-        if logits.dtype != torch.float32:
-            raise _lib.ConformerHipError(f"logits: expected dtype torch.float32, got {logits.dtype}")
+        logits = self._device_input(logits, "logits")
         if logits.dim() != 3 or logits.shape[0] != self.S:
             raise ValueError(f"logits: expected ({self.S}, k_max, V), got {tuple(logits.shape)}")
         _, k_max, V = logits.shape
@@ -177,29 +151,12 @@ class StreamingEndpointer:
         silence_ids(self.ids[0], self.config, V)
         if k_max == 0:
             return
-        k = self._k(k, k_max)
-        for t0 in range(0, k_max, K_MAX):                                  # (a launch takes 4096 frames per slot)
-            n = min(K_MAX, k_max - t0)
-            x = logits[:, t0:t0 + n]
-            if x.stride(2) != 1 or x.stride(1) < V or x.stride(0) < n * x.stride(1):
-                x = x.contiguous()
-            kk = k if k_max <= K_MAX else (k - t0).clamp_(0, n)
-            _lib.call("cfm_endpoint_step_f32", x.data_ptr(), x.stride(0), x.stride(1), kk.data_ptr(), n, V,
+        k = self._frame_counts(k, k_max)
+        for t0, n, kk in frame_chunks(k, k_max, K_MAX):                    # (a launch takes 4096 frames per slot)
+            x, ld_slot, ld_row = self._pitches(logits[:, t0:t0 + n], n, V)
+            _lib.call("cfm_endpoint_step_f32", x.data_ptr(), ld_slot, ld_row, kk.data_ptr(), n, V,
                       self.ids_dev.data_ptr(), len(self.ids), self.log_threshold, self.rules.data_ptr(), len(self.rule_rows),
                       self.state.data_ptr(), self.S, ops._stream())
-
-    def reset_slots(self, slots: Sequence[int]) -> None:
-        """Arm the slots again: counters 0, nothing latched.  Enqueues only."""
-        slots = [int(s) for s in slots]
-        if any(not 0 <= s < self.S for s in slots):
-            raise ValueError(f"slots {slots} outside [0, {self.S})")
-        if not slots:
-            return
-        idx = torch.tensor(slots, dtype=torch.int64).pin_memory().to(self.device, non_blocking=True)
-        self.state.index_copy_(0, idx, self._armed.expand(len(slots), STATE_COLS))
-
-    def reset(self) -> None:
-        self.state.copy_(self._armed.expand(self.S, STATE_COLS))
 
     def read(self, only: Optional[Sequence[int]] = None) -> List[Optional[Endpoint]]:
         """Per slot its Endpoint, or None while its utterance goes on (and for the slots not in `only`).  The one call that

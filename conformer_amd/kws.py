@@ -25,6 +25,7 @@ import numpy as np
 import torch
 
 from . import _lib, ops
+from ._slot_state import SlotFollower, positive_seconds
 
 _C = _lib.OPEN_CONSTANTS["conformer_hip3_kws.h"]
 STATE_ROWS = _C["CFM3_KWS_STATE_ROWS"]         # words per lane: a, start, held, held_start, held_end, held_score, frames, 0
@@ -160,13 +161,7 @@ def suppress_overlaps(detections: Sequence[Detection]) -> List[Detection]:
     return sorted(kept, key=lambda d: (d.end_frame, d.keyword))
 
 
-def _frame_seconds(who: str, value) -> float:
-    if isinstance(value, bool) or not isinstance(value, (int, float)) or not math.isfinite(value) or value <= 0:
-        raise ValueError(f"{who}: frame_seconds must be a positive finite number, got {value!r}")
-    return float(value)
-
-
-class StreamingKeywordSpotter:
+class StreamingKeywordSpotter(SlotFollower):
     """Keyword spotting for `slots` independent streams.
 
         sp = StreamingKeywordSpotter(S, keywords); sp.step(logits, k); ...; sp.pop(); sp.flush(s)
@@ -176,25 +171,25 @@ class StreamingKeywordSpotter:
     `detections` (S, G, max_detections, 4) int32 {keyword, start, end, score bits}, `counts` (S, G) int32 and, of the last
     step, `rowmax` (S, k_max) fp32 (columns at or beyond a slot's frames are not written).  max_chunk_frames: allocate the
     row-maximum workspace up front (steps of up to that many frames then allocate nothing); otherwise it is made once per
-    k_max.  `lost[s]`: the detections of slot s that did not fit max_detections between two pops, so far."""
+    k_max.  `lost[s]`: the detections of slot s that did not fit max_detections between two pops, so far.
+    reset_slots arms the slots again: frame 0, every state at -inf, nothing held, no detection waiting (what was not popped is
+    dropped)."""
+
+    _what = "keyword spotting only exists as gfx950 kernels"
 
     def __init__(self, slots: int, keywords: Keywords, frame_seconds: float = 0.04, max_detections: int = 64,
                  max_chunk_frames: Optional[int] = None, device=None) -> None:
         if not isinstance(keywords, Keywords):
             raise ValueError(f"StreamingKeywordSpotter: keywords must be a Keywords, got {type(keywords).__name__}")
-        self.frame_seconds = _frame_seconds("StreamingKeywordSpotter", frame_seconds)
-        if isinstance(slots, bool) or not isinstance(slots, int) or not 1 <= slots <= 65535:
-            raise ValueError(f"StreamingKeywordSpotter: slots must be 1 to 65535, got {slots!r}")
+        self.frame_seconds = positive_seconds("StreamingKeywordSpotter", "frame_seconds", frame_seconds)
+        self._init_slots("StreamingKeywordSpotter", slots, strict=True, max_slots=65535)
         if isinstance(max_detections, bool) or not isinstance(max_detections, int) or not 1 <= max_detections <= DETECTIONS_MAX:
             raise ValueError(f"StreamingKeywordSpotter: max_detections must be 1 to {DETECTIONS_MAX}, got {max_detections!r}")
         if max_chunk_frames is not None and (isinstance(max_chunk_frames, bool) or not isinstance(max_chunk_frames, int)
                                              or max_chunk_frames < 1):
             raise ValueError(f"StreamingKeywordSpotter: max_chunk_frames must be a number of frames >= 1, got {max_chunk_frames!r}")
-        self.keywords, self.S, self.G, self.max_detections = keywords, slots, keywords.G, max_detections
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        if self.device.type != "cuda":
-            raise _lib.ConformerHipError(f"StreamingKeywordSpotter: device {self.device}; keyword spotting only exists as gfx950 "
-                                         "kernels (no CPU fallback)")
+        self.keywords, self.G, self.max_detections = keywords, keywords.G, max_detections
+        self._init_device("StreamingKeywordSpotter", device)
         self.lanes = torch.from_numpy(keywords.lanes).to(self.device)
         self.thresholds = torch.from_numpy(keywords.thresholds).to(self.device)
         armed = torch.zeros(1, self.G, STATE_ROWS, GROUP_LANES, dtype=torch.int32)
@@ -209,32 +204,14 @@ class StreamingKeywordSpotter:
         self._work = None if max_chunk_frames is None else torch.zeros(self.S, max_chunk_frames, dtype=torch.float32,
                                                                        device=self.device)
         self._buffers: dict = {}           # k_max -> rowmax, made once per k_max (beyond max_chunk_frames)
-        self._all: dict = {}               # k=None: the (S) int64 tensor of a k_max, made once per k_max
-
-    def _k(self, k, k_max: int) -> torch.Tensor:
-        if k is None:
-            if k_max not in self._all:
-                self._all[k_max] = torch.full((self.S,), k_max, dtype=torch.int64, device=self.device)
-            return self._all[k_max]
-        if isinstance(k, torch.Tensor) and k.is_cuda:
-            k = ops._req(k, "k", torch.int64)
-        else:
-            host = torch.as_tensor(k, dtype=torch.int64).reshape(-1)
-            k = host.pin_memory().to(self.device, non_blocking=True)
-        if k.dim() != 1 or k.numel() != self.S:
-            raise ValueError(f"k: expected {self.S} frame counts, got shape {tuple(k.shape)}")
-        return k
+        self._armed_state = [(self.state, self._armed), (self.counts, 0)]
 
     @torch.no_grad()
     def step(self, logits: torch.Tensor, k=None) -> None:
         """logits (S, k_max, V) fp32 on the device: slot b's next frames are rows 0 .. k[b]-1 (the rest is never read).  k: a
         device int64 tensor (a slot step's own), a host sequence, or None: every row of every slot.  Enqueues only: two
         launches."""
-        if not isinstance(logits, torch.Tensor) or not logits.is_cuda:
-            raise _lib.ConformerHipError(f"logits: expected a tensor on a HIP device, got {getattr(logits, 'device', type(logits))}; "
-                                         "keyword spotting only exists as gfx950 kernels (no CPU fallback)")
-        if logits.dtype != torch.float32:
-            raise _lib.ConformerHipError(f"logits: expected dtype torch.float32, got {logits.dtype}")
+        logits = self._device_input(logits, "logits")
         if logits.dim() != 3 or logits.shape[0] != self.S:
             raise ValueError(f"logits: expected ({self.S}, k_max, V), got {tuple(logits.shape)}")
         _, k_max, V = logits.shape
@@ -242,12 +219,8 @@ class StreamingKeywordSpotter:
             raise ValueError(f"logits: V = {V}, the keywords were made for a vocabulary of {self.keywords.vocab_size}")
         if k_max == 0:
             return
-        k = self._k(k, k_max)
-        x = logits
-        if x.stride(2) != 1 or x.stride(1) < V or (self.S > 1 and x.stride(0) < k_max * x.stride(1)):
-            x = x.contiguous()
-        ld_row = x.stride(1) if k_max > 1 else V                           # (the stride of a dimension of 1 says nothing)
-        ld_slot = x.stride(0) if self.S > 1 else k_max * ld_row
+        k = self._frame_counts(k, k_max)
+        x, ld_slot, ld_row = self._pitches(logits, k_max, V)
         if self._chunk is not None and k_max <= self._chunk:
             self.rowmax = self._work
         else:
@@ -261,29 +234,6 @@ class StreamingKeywordSpotter:
                   self.lanes.data_ptr(), self.thresholds.data_ptr(), self.G, len(self.keywords), self.state.data_ptr(),
                   self.detections.data_ptr(), self.max_detections, self.counts.data_ptr(), self.S, stream)
 
-    def _slots(self, slots) -> List[int]:
-        slots = list(range(self.S)) if slots is None else [int(s) for s in slots]
-        if any(not 0 <= s < self.S for s in slots):
-            raise ValueError(f"slots {slots} outside [0, {self.S})")
-        return slots
-
-    def _index(self, slots: Sequence[int]) -> torch.Tensor:
-        return torch.tensor(list(slots), dtype=torch.int64).pin_memory().to(self.device, non_blocking=True)
-
-    def reset_slots(self, slots: Sequence[int]) -> None:
-        """Arm the slots again: frame 0, every state at -inf, nothing held, no detection waiting (what was not popped is
-        dropped).  Enqueues only."""
-        slots = self._slots(slots)
-        if not slots:
-            return
-        idx = self._index(slots)
-        self.state.index_copy_(0, idx, self._armed.expand(len(slots), -1, -1, -1))
-        self.counts.index_fill_(0, idx, 0)
-
-    def reset(self) -> None:
-        self.state.copy_(self._armed.expand(self.S, -1, -1, -1))
-        self.counts.zero_()
-
     def _detection(self, q: int, start: int, end: int, score: float) -> Detection:
         fs = self.frame_seconds
         return Detection(q, self.keywords.phrases[q], start * fs, (end + 1) * fs, score, start, end + 1)
@@ -293,11 +243,11 @@ class StreamingKeywordSpotter:
         for the slots not in `only`); the slots' counts are then cleared, on the stream.  The one call of a running stream that
         synchronises: a copy of the counts and of the detections.  What did not fit max_detections in a group is lost and
         counted in `lost[s]`: pop more often or raise max_detections."""
-        want = self._slots(only)
+        want = self._slot_list(only)
         out: List[Optional[List[Detection]]] = [None] * self.S
         if not want:
             return out
-        idx = self._index(want)
+        idx = self._slot_index(want)
         counts = self.counts.index_select(0, idx).cpu().numpy()
         rows = self.detections.index_select(0, idx).cpu().numpy()
         for i, s in enumerate(want):
@@ -315,7 +265,7 @@ class StreamingKeywordSpotter:
     def held(self, s: int) -> List[Detection]:
         """The detections slot s holds back: per keyword the best qualifying hypothesis that no later frame has closed yet.
         Synchronises; changes nothing."""
-        (s,) = self._slots([s])
+        (s,) = self._slot_list([s])
         words = self.state[s].cpu()
         scores = words[:, 5].contiguous().view(torch.float32)
         out = []

@@ -371,6 +371,16 @@ class Transcriber:
         order = sorted(range(len(frames)), key=lambda i: -frames[i])
         return [order[k:k + self.batch_windows] for k in range(0, len(order), self.batch_windows)]
 
+    def _padded_groups(self, hs: Sequence[torch.Tensor]):
+        """The encoder frames hs (one (T', d) tensor per recording) in `groups`: per group (group, frames of each, their frames
+        zero-padded to the longest (len(group), T', d), the frames as `lengths` (len(group)) int64 on the device)."""
+        for group in self.groups([h.shape[0] for h in hs]):
+            n = [hs[i].shape[0] for i in group]
+            h = hs[group[0]].new_zeros(len(group), n[0], hs[group[0]].shape[1])
+            for k, i in enumerate(group):
+                h[k, :n[k]] = hs[i]
+            yield group, n, h, torch.tensor(n, dtype=torch.int64).to(self.device, non_blocking=True)
+
     @torch.no_grad()
     def transcribe(self, audios: Sequence[torch.Tensor], sample_rates: Optional[Sequence[int]] = None, hotwords=None,
                    hotword_weight=None) -> List[Transcript]:
@@ -395,12 +405,7 @@ class Transcriber:
         groups; one Transcript per recording, in the order given.  rows: None or (hotwords, weights), one entry per recording
         (the same order as hs), which follow their recordings into the groups."""
         out: List[Optional[Transcript]] = [None] * len(hs)
-        for group in self.groups([h.shape[0] for h in hs]):
-            n = [hs[i].shape[0] for i in group]
-            h = hs[group[0]].new_zeros(len(group), n[0], hs[group[0]].shape[1])
-            for k, i in enumerate(group):
-                h[k, :n[k]] = hs[i]
-            lengths = torch.tensor(n, dtype=torch.int64).to(self.device, non_blocking=True)
+        for group, n, h, lengths in self._padded_groups(hs):
             logits = self.decoder_head(h, lengths)
             kw = {} if rows is None else dict(hotwords=[rows[0][i] for i in group], hotword_weight=[rows[1][i] for i in group])
             texts = self.decoder(logits, lengths, **kw)
@@ -462,13 +467,7 @@ class Transcriber:
     def _group_logits(self, audios: Sequence[torch.Tensor], sample_rates: Optional[Sequence[int]]):
         """transcribe's pipeline up to the logits: per group of recordings (group, frames of each, their seconds, logits, lengths)"""
         mels = self.features(audios, sample_rates)
-        hs = self.encoder.encode(mels)
-        for group in self.groups([h.shape[0] for h in hs]):
-            n = [hs[i].shape[0] for i in group]
-            h = hs[group[0]].new_zeros(len(group), n[0], hs[group[0]].shape[1])
-            for k, i in enumerate(group):
-                h[k, :n[k]] = hs[i]
-            lengths = torch.tensor(n, dtype=torch.int64).to(self.device, non_blocking=True)
+        for group, n, h, lengths in self._padded_groups(self.encoder.encode(mels)):
             yield group, n, [mels[i].shape[1] * self.mel_seconds for i in group], self.decoder_head(h, lengths), lengths
 
     @torch.no_grad()

@@ -28,6 +28,7 @@ import numpy as np
 import torch
 
 from . import _lib, ops
+from ._slot_state import OpenSlots
 
 TAIL_LD = 1024             # floats per row of a tail buffer (include/conformer_hip_resample.h)
 TABLE_COLS = 8             # int32 per slot: tail_len, n_new, lead, n_out, flush, keep, new_tail_len, 0
@@ -185,7 +186,7 @@ class ResampleStep(NamedTuple):
     out_counts: List[int]
 
 
-class StreamingResampler:
+class StreamingResampler(OpenSlots):
     """`slots` independent streams through `resampler`, at most max_chunk_samples new (input-rate) samples per slot and step.
 
         rs.open(s); y, out_counts = rs.step(samples, counts, flush=()); rs.close(s)
@@ -201,30 +202,22 @@ class StreamingResampler:
         self.out_cap = (step_output_cap(self.max_chunk, r.width, r.o, r.n) + 3) // 4 * 4     # (the kernel's pitch: 16 bytes)
         self.tails = [torch.zeros(self.S, TAIL_LD, device=self.device, dtype=torch.float32) for _ in range(2)]
         self.table = torch.zeros(self.S, TABLE_COLS, device=self.device, dtype=torch.int32)
-        self.is_open = [False] * self.S
+        self._free_all()
         self.received = [0] * self.S                                       # input samples per slot since open
-
-    def _check_slot(self, s: int, want_open: bool) -> int:
-        s = int(s)
-        if not 0 <= s < self.S:
-            raise ValueError(f"slot {s} out of range [0, {self.S})")
-        if self.is_open[s] != want_open:
-            raise RuntimeError(f"slot {s} is {'free' if want_open else 'already open'}")
-        return s
 
     def open(self, s: int) -> None:
         """Start a new stream in free slot s (host bookkeeping only: an empty tail is a tail length of 0)."""
         s = self._check_slot(s, want_open=False)
         self.received[s] = 0
-        self.is_open[s] = True
+        self._mark_open(s)
 
     def close(self, s: int) -> None:
         """Drop slot s's stream without a flush."""
-        self.is_open[self._check_slot(s, want_open=True)] = False
+        self._mark_closed(self._check_slot(s, want_open=True))
 
     def reset(self) -> None:
         """Every slot free."""
-        self.is_open = [False] * self.S
+        self._free_all()
 
     def plan(self, samples: torch.Tensor, counts: Sequence[int], flush: Iterable[int] = ()) -> ResampleStep:
         """Check a step's arguments against the slots (raises before anything is enqueued, changes nothing)."""
@@ -283,5 +276,5 @@ class StreamingResampler:
         for b in range(S):
             self.received[b] += p.counts[b]
             if p.flush[b]:
-                self.is_open[b] = False
+                self._mark_closed(b)
         return y, p.out_counts

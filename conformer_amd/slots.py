@@ -35,6 +35,7 @@ import numpy as np
 import torch
 
 from . import ops
+from ._slot_state import OpenSlots
 from .align import Word
 from .confidence import ConfidenceConfig, StreamingConfidence, transcriber_confidence
 from .decode import BeamCTCDecoder
@@ -166,7 +167,7 @@ class _SlotStream:
         return s[:, half:].contiguous()
 
 
-class SlotStreamingEncoder(ChunkedEncoder):
+class SlotStreamingEncoder(ChunkedEncoder, OpenSlots):
     """The chunked encoder of StreamingEncoder over `slots` independent streams of at most max_mel_frames mel frames each.
     open(s) starts a stream in a free slot, step(mel, frames) feeds every slot its own number of new frames, close(s) frees the
     slot.  Returns compact rows: step -> ((S, k_max, d), k) with slot b's new encoder frames in rows 0 .. k[b]-1.
@@ -186,19 +187,11 @@ class SlotStreamingEncoder(ChunkedEncoder):
                          left_context=left_context, max_chunk_mel_frames=max_chunk_mel_frames)
         self.S = self.B
         self.max_mel = None if max_mel_frames is None else int(max_mel_frames)
-        self.is_open = [False] * self.S
+        self._free_all()
         self.n0 = [0] * self.S                                             # encoder frames per slot so far
         self.tails = [0] * self.S                                          # buffered mel frames per slot (0..6)
         self.mel_seen = [0] * self.S                                       # mel frames received per slot
         self.last_step: Optional[_Step] = None                            # the latest step's device offsets (k: SlotTranscriber)
-
-    def _check_slot(self, s: int, want_open: bool) -> int:
-        s = int(s)
-        if not 0 <= s < self.S:
-            raise ValueError(f"slot {s} out of range [0, {self.S})")
-        if self.is_open[s] != want_open:
-            raise RuntimeError(f"slot {s} is {'free' if want_open else 'already open'}")
-        return s
 
     def open(self, s: int) -> None:
         """Start a new stream in free slot s: K/V length, depthwise state and mel tail back to empty (enqueues only)."""
@@ -207,15 +200,14 @@ class SlotStreamingEncoder(ChunkedEncoder):
         for t in self.conv_state:
             t[s].zero_()
         self.n0[s] = self.tails[s] = self.mel_seen[s] = 0
-        self.is_open[s] = True
+        self._mark_open(s)
 
     def close(self, s: int) -> None:
-        s = self._check_slot(s, want_open=True)
-        self.is_open[s] = False
+        self._mark_closed(self._check_slot(s, want_open=True))
 
     def reset(self) -> None:
         """Every slot free."""
-        self.is_open = [False] * self.S
+        self._free_all()
 
     def plan(self, mel_chunk: torch.Tensor, frames: Sequence[int]) -> Tuple[torch.Tensor, List[int], List[int]]:
         """Check a step's arguments against the slots (raises before anything is enqueued): (mel, k, new tails)."""

@@ -28,6 +28,7 @@ from typing import Iterable, List, NamedTuple, Optional, Sequence, Tuple
 import torch
 
 from . import _lib, ops
+from ._slot_state import OpenSlots
 from .frontend import ConformerAudioFrontend
 from .resample import Resampler, ResampleStep, StreamingResampler
 
@@ -89,7 +90,7 @@ class StepPlan(NamedTuple):
     resample: Optional[ResampleStep] = None    # with input=: the resampler's checked step; `samples` is then the buffer it fills
 
 
-class StreamingAudioFrontend:
+class StreamingAudioFrontend(OpenSlots):
     """`slots` independent streams through `frontend`'s log-mel configuration, at most max_chunk_samples new samples per slot
     and step.
 
@@ -130,36 +131,27 @@ class StreamingAudioFrontend:
         self.table = self.tables[0]
         if self.input is not None:
             self.input.table = self.tables[1]
-        self.is_open = [False] * S
+        self._free_all()
         self.received = [0] * S                                            # samples per slot since open
         self.emitted = [0] * S                                             # frames per slot since open
-
-    def _check_slot(self, s: int, want_open: bool) -> int:
-        s = int(s)
-        if not 0 <= s < self.S:
-            raise ValueError(f"slot {s} out of range [0, {self.S})")
-        if self.is_open[s] != want_open:
-            raise RuntimeError(f"slot {s} is {'free' if want_open else 'already open'}")
-        return s
 
     def open(self, s: int) -> None:
         """Start a new stream in free slot s (host bookkeeping only: an empty tail is a tail length of 0)."""
         s = self._check_slot(s, want_open=False)
         self.received[s] = self.emitted[s] = 0
-        self.is_open[s] = True
+        self._mark_open(s)
         if self.input is not None:
             self.input.open(s)
 
     def close(self, s: int) -> None:
         """Drop slot s's stream without a flush."""
-        s = self._check_slot(s, want_open=True)
-        self.is_open[s] = False
+        self._mark_closed(self._check_slot(s, want_open=True))
         if self.input is not None:
             self.input.close(s)
 
     def reset(self) -> None:
         """Every slot free."""
-        self.is_open = [False] * self.S
+        self._free_all()
         if self.input is not None:
             self.input.reset()
 
@@ -242,7 +234,7 @@ class StreamingAudioFrontend:
             self.received[b] += p.counts[b]
             self.emitted[b] += p.frames[b]
             if p.flush[b]:
-                self.is_open[b] = False
+                self._mark_closed(b)
         out = torch.empty(S, fe.n_mels, f_max, device=self.device, dtype=torch.float32)
         if f_max == 0:
             return out, p.frames

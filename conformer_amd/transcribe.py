@@ -17,7 +17,8 @@ import torch
 from . import ops
 from .align import Word
 from .confidence import ConfidenceConfig, StreamingConfidence, transcriber_confidence
-from .decode import BeamCTCDecoder, BeamCTCStream, _flag, _frame_seconds
+from ._slot_state import positive_seconds
+from .decode import BeamCTCDecoder, BeamCTCStream, _flag
 from .stream_frontend import StreamingAudioFrontend
 from .streaming import StreamingEncoder, encoder_frames, ring_plan
 
@@ -59,7 +60,7 @@ def search_plan(who: str, max_mel_frames, left_context, max_chunk_mel_frames, ma
 
 def times_plan(who: str, times, frame_seconds) -> Tuple[bool, float]:
     """The transcribers' timestamp options, checked on the host before anything else."""
-    return _flag(who, "times", times), _frame_seconds(who, frame_seconds)
+    return _flag(who, "times", times), positive_seconds(who, "frame_seconds", frame_seconds)
 
 
 def search_stream(decoder: BeamCTCDecoder, plan, batch: int, t_max: Optional[int], device, commit_log: int,

@@ -24,6 +24,7 @@ from typing import List, NamedTuple, Optional, Sequence, Tuple
 import torch
 
 from . import _lib, ops
+from ._slot_state import SlotFollower, frame_chunks, positive_seconds
 
 _C = _lib.OPEN_CONSTANTS["conformer_hip3_vad.h"]
 STATE_COLS = _C["CFM3_VAD_STATE_COLS"]         # int32 per slot: frames, run_speech, run_silence, in_speech, start, count, 0, 0
@@ -38,12 +39,6 @@ def _seconds(who: str, name: str, v, least: float = 0.0) -> float:
     if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v < least:
         raise ValueError(f"{who}: {name} must be a finite time >= {least} in seconds, got {v!r}")
     return float(v)
-
-
-def _mel_seconds(who: str, value) -> float:
-    if isinstance(value, bool) or not isinstance(value, (int, float)) or not math.isfinite(value) or value <= 0:
-        raise ValueError(f"{who}: mel_seconds must be a positive finite number, got {value!r}")
-    return float(value)
 
 
 class VadFrames(NamedTuple):
@@ -82,7 +77,7 @@ class VadConfig(NamedTuple):
 
     def check(self, mel_seconds: float, n_mel: int) -> VadFrames:
         """Refuse a bad configuration (ValueError, on the host); the configuration in frames."""
-        mel_seconds = _mel_seconds("VadConfig", mel_seconds)
+        mel_seconds = positive_seconds("VadConfig", "mel_seconds", mel_seconds)
         if isinstance(n_mel, bool) or not isinstance(n_mel, int) or n_mel < 1:
             raise ValueError(f"VadConfig: n_mel must be a number of mel bins >= 1, got {n_mel!r}")
         v = self.snr_db
@@ -172,7 +167,7 @@ class VadRead(NamedTuple):
     seconds: List[Tuple[float, float]]
 
 
-class StreamingVad:
+class StreamingVad(SlotFollower):
     """Voice activity detection for `slots` independent streams.
 
         vad = StreamingVad(S, 80, VadConfig(snr_db=9.0)); vad.step(mel, frames); ...; vad.read(); vad.finish([s])
@@ -180,63 +175,44 @@ class StreamingVad:
     It takes what StreamingAudioFrontend.step returns and runs beside a SlotTranscriber on the same chunks; what to do with the
     answer is the caller's.  Every slot starts armed.  Device tensors: `state` (S, 8) int32 {frames, run_speech, run_silence,
     in_speech, start, count, 0, 0}, `ring` (S, noise_window + smooth - 1) fp32, `segments` (S, max_segments, 2) int32, and of
-    the last step `energy` (S, k_max) fp32 and `flags` (S, k_max) uint8 (columns at or beyond a slot's frames are not written)."""
+    the last step `energy` (S, k_max) fp32 and `flags` (S, k_max) uint8 (columns at or beyond a slot's frames are not written).
+    reset_slots arms the slots again: frame 0, no floor, not in speech, no segments."""
+
+    _what = "voice activity detection only exists as gfx950 kernels"
 
     def __init__(self, slots: int, n_mel: int, config: VadConfig, mel_seconds: float = 0.01, max_segments: int = 64,
                  device=None) -> None:
         if not isinstance(config, VadConfig):
             raise ValueError(f"StreamingVad: config must be a VadConfig, got {type(config).__name__}")
-        self.mel_seconds = _mel_seconds("StreamingVad", mel_seconds)
+        self.mel_seconds = positive_seconds("StreamingVad", "mel_seconds", mel_seconds)
         self.p = config.check(self.mel_seconds, n_mel)
         self.config, self.n_mel = config, n_mel
-        if isinstance(slots, bool) or not isinstance(slots, int) or not 1 <= slots <= 65535:
-            raise ValueError(f"StreamingVad: slots must be 1 to 65535, got {slots!r}")
+        self._init_slots("StreamingVad", slots, strict=True, max_slots=65535)
         if isinstance(max_segments, bool) or not isinstance(max_segments, int) or not 1 <= max_segments <= COUNT_MAX:
             raise ValueError(f"StreamingVad: max_segments must be 1 to {COUNT_MAX}, got {max_segments!r}")
-        self.S, self.max_segments = slots, max_segments
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        if self.device.type != "cuda":
-            raise _lib.ConformerHipError(f"StreamingVad: device {self.device}; voice activity detection only exists as gfx950 "
-                                         "kernels (no CPU fallback)")
+        self.max_segments = max_segments
+        self._init_device("StreamingVad", device)
         self.state = torch.zeros(self.S, STATE_COLS, dtype=torch.int32, device=self.device)
+        self._armed_state = [(self.state, 0)]
         self.ring = torch.zeros(self.S, self.p.noise_window + self.p.smooth - 1, dtype=torch.float32, device=self.device)
         self.segments = torch.zeros(self.S, max_segments, 2, dtype=torch.int32, device=self.device)
         self.energy = torch.zeros(self.S, 0, dtype=torch.float32, device=self.device)
         self.flags = torch.zeros(self.S, 0, dtype=torch.uint8, device=self.device)
         self._buffers: dict = {}           # k_max -> (energy, flags), made once per k_max
 
-    def _k(self, k, k_max: int) -> torch.Tensor:
-        if isinstance(k, torch.Tensor) and k.is_cuda:
-            k = ops._req(k, "frames", torch.int64)
-        else:
-            host = torch.as_tensor(k, dtype=torch.int64).reshape(-1)
-            k = host.pin_memory().to(self.device, non_blocking=True)
-        if k.dim() != 1 or k.numel() != self.S:
-            raise ValueError(f"frames: expected {self.S} frame counts, got shape {tuple(k.shape)}")
-        return k
-
     @torch.no_grad()
     def step(self, mel_chunk: torch.Tensor, frames) -> None:
         """mel_chunk (S, n_mel, k_max) fp32 log-mel on the device: slot b's next frames are the columns 0 .. frames[b]-1 (the
         rest is never read).  frames: a device int64 tensor or a host sequence.  Enqueues only: one energy launch, and one scan
         launch per 4096 columns."""
-        if not isinstance(mel_chunk, torch.Tensor) or not mel_chunk.is_cuda:
-            raise _lib.ConformerHipError(f"mel_chunk: expected a tensor on a HIP device, got "
-                                         f"{getattr(mel_chunk, 'device', type(mel_chunk))}; voice activity detection only exists "
-                                         "as gfx950 kernels (no CPU fallback)")
-        if mel_chunk.dtype != torch.float32:
-            raise _lib.ConformerHipError(f"mel_chunk: expected dtype torch.float32, got {mel_chunk.dtype}")
+        mel_chunk = self._device_input(mel_chunk, "mel_chunk")
         if mel_chunk.dim() != 3 or mel_chunk.shape[0] != self.S or mel_chunk.shape[1] != self.n_mel:
             raise ValueError(f"mel_chunk: expected ({self.S}, {self.n_mel}, k_max), got {tuple(mel_chunk.shape)}")
         k_max = mel_chunk.shape[2]
         if k_max == 0:
             return
-        k = self._k(frames, k_max)
-        x = mel_chunk
-        ld_mel = x.stride(1) if self.n_mel > 1 else k_max                 # (the stride of a dimension of 1 says nothing)
-        if x.stride(2) != 1 or ld_mel < k_max or (self.S > 1 and x.stride(0) < self.n_mel * ld_mel):
-            x, ld_mel = x.contiguous(), k_max
-        ld_slot = x.stride(0) if self.S > 1 else self.n_mel * ld_mel
+        k = self._frame_counts(frames, k_max, name="frames", allow_all=False)
+        x, ld_slot, ld_mel = self._pitches(mel_chunk, self.n_mel, k_max)
         if k_max not in self._buffers:
             self._buffers[k_max] = (torch.zeros(self.S, k_max, dtype=torch.float32, device=self.device),
                                     torch.zeros(self.S, k_max, dtype=torch.uint8, device=self.device))
@@ -244,36 +220,17 @@ class StreamingVad:
         p, stream = self.p, ops._stream()
         _lib.call("cfm3_vad_energy_f32", x.data_ptr(), ld_slot, ld_mel, k.data_ptr(), k_max, self.n_mel, p.m_lo, p.m_hi,
                   self.energy.data_ptr(), k_max, self.S, stream)
-        for t0 in range(0, k_max, SCAN_FRAMES):                            # (a scan launch takes 4096 frames per slot)
-            n = min(SCAN_FRAMES, k_max - t0)
-            kk = k if k_max <= SCAN_FRAMES else (k - t0).clamp_(0, n)
+        for t0, n, kk in frame_chunks(k, k_max, SCAN_FRAMES):              # (a scan launch takes 4096 frames per slot)
             _lib.call("cfm3_vad_scan_f32", self.energy.data_ptr() + 4 * t0, k_max, kk.data_ptr(), n, p.smooth, p.noise_window,
                       p.snr, p.min_energy, p.onset, p.hangover, self.state.data_ptr(), self.ring.data_ptr(),
                       self.flags.data_ptr() + t0, k_max, self.segments.data_ptr(), self.max_segments, self.S, stream)
-
-    def _slots(self, slots) -> List[int]:
-        slots = list(range(self.S)) if slots is None else [int(s) for s in slots]
-        if any(not 0 <= s < self.S for s in slots):
-            raise ValueError(f"slots {slots} outside [0, {self.S})")
-        return slots
-
-    def reset_slots(self, slots: Sequence[int]) -> None:
-        """Arm the slots again: frame 0, no floor, not in speech, no segments.  Enqueues only."""
-        slots = self._slots(slots)
-        if not slots:
-            return
-        idx = torch.tensor(slots, dtype=torch.int64).pin_memory().to(self.device, non_blocking=True)
-        self.state.index_fill_(0, idx, 0)
-
-    def reset(self) -> None:
-        self.state.zero_()
 
     def read(self, only: Optional[Sequence[int]] = None) -> List[Optional[VadRead]]:
         """Per slot a VadRead (None for the slots not in `only`): whether it is in speech, and the segments that closed since
         the last read; the slot's segment count is then cleared.  The one call that synchronises: a copy of the state and of
         the segments.  RuntimeError when more than max_segments closed in a slot since its last read (nothing was written
         beyond the buffer; the later ones are lost): read more often or raise max_segments."""
-        want = self._slots(only)
+        want = self._slot_list(only)
         rows, segs = self.state.cpu().tolist(), self.segments.cpu().tolist()
         out: List[Optional[VadRead]] = [None] * self.S
         over = [(s, rows[s][5]) for s in want if rows[s][5] > self.max_segments]
@@ -281,8 +238,7 @@ class StreamingVad:
             closed = [(a, b) for a, b in segs[s][:min(rows[s][5], self.max_segments)]]
             out[s] = VadRead(bool(rows[s][3]), closed, [(a * self.mel_seconds, b * self.mel_seconds) for a, b in closed])
         if want:
-            idx = torch.tensor(want, dtype=torch.int64).pin_memory().to(self.device, non_blocking=True)
-            self.state[:, 5].index_fill_(0, idx, 0)
+            self.state[:, 5].index_fill_(0, self._slot_index(want), 0)
         if over:
             raise RuntimeError(f"StreamingVad.read: (slot, segments closed since its last read) {over} beyond max_segments = "
                                f"{self.max_segments}; the later segments are lost: call read more often or raise max_segments")
@@ -291,7 +247,7 @@ class StreamingVad:
     def finish(self, slots: Optional[Sequence[int]] = None) -> List[Optional[VadRead]]:
         """End the streams of `slots` (None: all): `read` them, close a segment that is still open at frames - run_silence
         (the last raw frame + 1), and arm the slots again.  Synchronises."""
-        want = self._slots(slots)
+        want = self._slot_list(slots)
         rows = self.state.cpu().tolist()
         out = self.read(want)
         for s in want:

@@ -1,13 +1,15 @@
 """Dropout on the training path: the counter-based mask is (a) statistically a Bernoulli(1-p) keep mask scaled by 1/(1-p),
 (b) identical in the fused GEMM epilogues, the stand-alone kernel and the backward, so gradients equal those of an
-fp64 torch model that uses the SAME (extracted) masks.  (The stream is not torch's Philox stream; reference parity runs
-use p = 0.)"""
+fp64 torch model that uses the SAME masks: extracted from the device and checked, bit for bit, against the integer restatement
+of the contract (tests/dropout_restatement.py; every site on its own: tests/test_dropout_sites_gpu.py).  (The stream is not
+torch's Philox stream; reference parity runs use p = 0.)"""
 import math
 
 import pytest
 import torch
 
 from oracle import conformer_oracle as O
+from tests.dropout_restatement import mask
 from tests.util import rel_l2
 
 pytestmark = pytest.mark.gpu
@@ -26,8 +28,12 @@ def rnd(*shape, seed=0):
 
 
 def mask_of(shape, p, seed, dev):
+    """The device's mask -- which must be the restated one (tests/dropout_restatement.py), bit for bit: the tests below then
+    compare against the contract and not against whatever the stand-alone kernel computes."""
     from conformer_amd import ops
-    return ops.dropout_apply(torch.ones(*shape, device=dev), p, seed).cpu().double()
+    m = ops.dropout_apply(torch.ones(*shape, device=dev), p, seed).cpu()
+    assert torch.equal(m, torch.from_numpy(mask(shape, p, seed))), f"the device mask {shape} p {p} seed {seed} is not the restated one"
+    return m.double()
 
 
 def test_mask_statistics_and_determinism(dev):

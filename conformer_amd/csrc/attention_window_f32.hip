@@ -11,7 +11,7 @@
 //   * A workgroup (query rows q0 .. q0+127) walks the key tiles from max(q0, cmin) / 32 to cend / 32: <= (left + 128)/32 + 2.
 //     A wave joins at ITS first visible tile, max(i0, cmin) / 32 (it computes that tile's band tile 1 explicitly, as the first
 //     tile of the full-context kernel does); every row of the wave has a visible key in that tile.  Rows past the slot's count
-//     (il >= q_count) may see no key at all: the running-max update takes 0 for an all-masked maximum, so it stays NaN-free.
+//     (il >= q_count) may see no key at all: the running-max update takes 0 for an all-masked maximum, so it yields no NaN.
 //   * Ring rows outside [cmin, cend) hold an older part of the stream or another stream: they are never loaded -- the staging
 //     selects zeros for them -- and masked keys inside the range are selected away before the exponential, so no bit pattern of a
 //     masked row reaches a result.

@@ -1,5 +1,6 @@
 // "Next" rows of the scope table: N2 fused multi-tensor Adam step, N4 greedy CTC decode on device.
 #include "cfm_common.h"
+#include "conformer_hip3_adam.h"
 
 namespace {
 
@@ -15,8 +16,8 @@ struct AdamBatch {
     int count;
 };
 
-__global__ __launch_bounds__(256) void adam_kernel(const AdamBatch batch, float lr, float beta1, float beta2, float eps,
-                                                   float bias_c1, float sqrt_bias_c2) {
+__global__ __launch_bounds__(256) void adam_kernel(const AdamBatch batch, float lr, float omb1, float beta2, float omb2,
+                                                   float eps, float bias_c1, float sqrt_bias_c2) {
     int ti = 0;
     while (ti + 1 < batch.count && batch.first_block[ti + 1] <= blockIdx.x) ++ti;     // uniform: scalar kernarg loads
     const AdamTensor t = batch.t[ti];
@@ -33,8 +34,8 @@ __global__ __launch_bounds__(256) void adam_kernel(const AdamBatch batch, float 
             const f32x4 g = *reinterpret_cast<const f32x4*>(t.g + e);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                m[j] = m[j] + (g[j] - m[j]) * (1.0f - beta1);                   // lerp form, as torch's foreach/fused Adam
-                v[j] = beta2 * v[j] + (1.0f - beta2) * g[j] * g[j];
+                m[j] = m[j] + (g[j] - m[j]) * omb1;                             // lerp form, as torch's foreach/fused Adam
+                v[j] = beta2 * v[j] + omb2 * g[j] * g[j];
                 p[j] -= step_size * m[j] / (sqrtf(v[j]) / sqrt_bias_c2 + eps);
             }
             *reinterpret_cast<f32x4*>(t.p + e) = p;
@@ -43,8 +44,8 @@ __global__ __launch_bounds__(256) void adam_kernel(const AdamBatch batch, float 
         } else {
             for (int64_t k = e; k < t.n && k < e + 4; ++k) {
                 const float g = t.g[k];
-                const float m = t.m[k] + (g - t.m[k]) * (1.0f - beta1);
-                const float v = beta2 * t.v[k] + (1.0f - beta2) * g * g;
+                const float m = t.m[k] + (g - t.m[k]) * omb1;
+                const float v = beta2 * t.v[k] + omb2 * g * g;
                 t.m[k] = m; t.v[k] = v;
                 t.p[k] -= step_size * m / (sqrtf(v) / sqrt_bias_c2 + eps);
             }
@@ -54,9 +55,17 @@ __global__ __launch_bounds__(256) void adam_kernel(const AdamBatch batch, float 
 
 // ---- N4: greedy CTC decode (processor.py:301-328): per-frame argmax, drop pad/unk, collapse repeats ---------------------------
 // NOTE the reference's collapse does NOT reset on a skipped pad/unk frame ("a <pad> a" -> "a"): reproduced as is.
-// Two launches: (1) one wave per frame, lanes over the vocabulary, shuffle arg-max (ties -> lowest index);
+// Two launches: (1) one wave per frame, lanes over the vocabulary, shuffle arg-max (ties -> lowest index, NaN greatest: argmax_beats);
 // (2) one wave per utterance compacts 64 frames at a time with ballots -- "previous kept-or-skipped id" is the id of
 // the nearest earlier non-pad/unk frame, found from the ballot mask, so the collapse needs no serial loop over frames.
+// torch.argmax's order: "value x at column c beats the held (best, bi)".  A NaN is the greatest value, and among equals
+// (NaNs among themselves included) the lowest column wins, so every row of V >= 1 columns yields an id in [0, V).
+__device__ __forceinline__ bool argmax_beats(float x, int c, float best, int bi) {
+    const bool xn = x != x, bn = best != best;
+    if (xn || bn) return xn && (!bn || c < bi);
+    return x > best || (x == best && c < bi);
+}
+
 __global__ __launch_bounds__(256) void frame_argmax_kernel(const float* __restrict__ logits, int64_t* __restrict__ frame_ids,
                                                            int64_t rows, int V) {
     const int lane = threadIdx.x & 63;
@@ -67,13 +76,13 @@ __global__ __launch_bounds__(256) void frame_argmax_kernel(const float* __restri
     int bi = 0x7fffffff;
     for (int c = lane; c < V; c += 64) {
         const float x = r[c];
-        if (x > best || (x == best && c < bi)) { best = x; bi = c; }       // NaN-free logits assumed
+        if (argmax_beats(x, c, best, bi)) { best = x; bi = c; }            // (a lane without a column keeps bi = INT_MAX and loses)
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         const float ob = __shfl_xor(best, o, 64);
         const int oi = __shfl_xor(bi, o, 64);
-        if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
+        if (argmax_beats(ob, oi, best, bi)) { best = ob; bi = oi; }
     }
     if (lane == 0) frame_ids[row] = bi;
 }
@@ -109,10 +118,10 @@ __global__ __launch_bounds__(64) void ctc_collapse_kernel(const int64_t* __restr
 }  // namespace
 
 // One Adam step over n_tensors tensors described by a HOST array of {param, grad, exp_avg, exp_avg_sq, numel} (all device
-// fp32 pointers).  bias_c1 = 1 - beta1^t, sqrt_bias_c2 = sqrt(1 - beta2^t) for the step count t AFTER the increment
-// (torch semantics).  ceil(n_tensors / 48) launches; the table rides in the kernel arguments.
-extern "C" int cfm_adam_step_f32(const cfm_adam_tensor* tensors, int n_tensors, float lr, float beta1, float beta2, float eps,
-                                 float bias_c1, float sqrt_bias_c2, cfm_stream_t stream) {
+// fp32 pointers), from the scalars as the kernel takes them: omb = "1 - beta".  ceil(n_tensors / 48) launches; the table rides
+// in the kernel arguments.  Every refusal returns before the first launch.
+static int adam_step(const cfm_adam_tensor* tensors, int n_tensors, float lr, float omb1, float beta2, float omb2, float eps,
+                     float bias_c1, float sqrt_bias_c2, cfm_stream_t stream) {
     CFM_REQUIRE(tensors, CFM_ERR_NULL);
     CFM_REQUIRE(n_tensors > 0 && bias_c1 > 0.f && sqrt_bias_c2 > 0.f, CFM_ERR_BAD_SHAPE);
     static_assert(sizeof(cfm_adam_tensor) == sizeof(AdamTensor), "ABI struct and kernel struct must agree");
@@ -131,12 +140,28 @@ extern "C" int cfm_adam_step_f32(const cfm_adam_tensor* tensors, int n_tensors, 
             blocks += (unsigned)((s.numel + ADAM_CHUNK - 1) / ADAM_CHUNK);
         }
         batch.first_block[batch.count] = blocks;
-        hipLaunchKernelGGL(adam_kernel, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), batch, lr, beta1, beta2,
-                           eps, bias_c1, sqrt_bias_c2);
+        hipLaunchKernelGGL(adam_kernel, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), batch, lr, omb1, beta2,
+                           omb2, eps, bias_c1, sqrt_bias_c2);
         const int st = cfm_launch_status();
         if (st != CFM_OK) return st;
     }
     return CFM_OK;
+}
+
+// The fp32 entry: bias_c1 = 1 - beta1^t, sqrt_bias_c2 = sqrt(1 - beta2^t) for the step count t AFTER the increment (torch
+// semantics).  "1 - beta" is the fp32 difference from the fp32 beta: exact for THAT beta, but 1 - (float)0.999 is 1.3e-5 off
+// 1 - 0.999, and exp_avg_sq with it.  cfm3_adam_step_f32 takes the scalars in double and does not lose that.
+extern "C" int cfm_adam_step_f32(const cfm_adam_tensor* tensors, int n_tensors, float lr, float beta1, float beta2, float eps,
+                                 float bias_c1, float sqrt_bias_c2, cfm_stream_t stream) {
+    return adam_step(tensors, n_tensors, lr, 1.0f - beta1, beta2, 1.0f - beta2, eps, bias_c1, sqrt_bias_c2, stream);
+}
+
+// The same step from double scalars (conformer_hip3_adam.h): "1 - beta" is formed in double and every scalar rounded to fp32
+// once, so exp_avg and exp_avg_sq follow torch.optim.Adam's to fp32 rounding for any beta.
+extern "C" int cfm3_adam_step_f32(const cfm_adam_tensor* tensors, int n_tensors, double lr, double beta1, double beta2,
+                                  double eps, double bias_c1, double sqrt_bias_c2, cfm_stream_t stream) {
+    return adam_step(tensors, n_tensors, (float)lr, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps,
+                     (float)bias_c1, (float)sqrt_bias_c2, stream);
 }
 
 // logits (B,T,V) fp32 -> frame_ids (B,T) int64 per-frame argmax (the "CTC alignment indices"); tokens (B,T) int64 decoded ids

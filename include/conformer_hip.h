@@ -493,7 +493,9 @@ int cfm_subsample_conv1_bwd_f32(const float* x, const float* w1, const float* b1
  *      `tensors` is a HOST array of n_tensors descriptors holding DEVICE pointers; ceil(n/48) launches, the table rides
  *      in the kernel arguments.  bias_c1 = 1-beta1^t, sqrt_bias_c2 = sqrt(1-beta2^t) (t = step count after increment).
  *      N4: greedy CTC decode (processor.py:301-328): per-frame argmax (B,T) int64, decoded ids (B,T) padded with -1,
- *      counts (B); pad/unk frames are skipped WITHOUT resetting the repeat filter (reference behaviour). */
+ *      counts (B); pad/unk frames are skipped WITHOUT resetting the repeat filter (reference behaviour).  The argmax is
+ *      torch.argmax's: the lowest index among equal maxima, and a NaN is the greatest value (the first NaN of a row wins),
+ *      so every id lies in [0, V) whatever the logits hold. */
 typedef struct cfm_adam_tensor {
     float* param;
     const float* grad;

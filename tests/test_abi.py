@@ -109,6 +109,43 @@ def test_round3_entries_validate_their_arguments_without_gpu(lib):
     assert lib.cfm_relpos_attention_rows_mfma16_f32(1, a, a, a, 1536, a, 512, a, a, a, a, 512, 1, 16, 8, 64, 8, 16, None) < OK      # rows past T
 
 
+@pytest.mark.parametrize("entry", ["cfm_adam_step_f32", "cfm3_adam_step_f32"])
+def test_adam_step_refusals_without_gpu(lib, entry):
+    """Both Adam entries (float scalars; double scalars, csrc/conformer_hip3_adam.h) refuse, before any launch: a null table or
+    a null pointer in ANY descriptor (CFM_ERR_NULL); n_tensors <= 0, a numel <= 0, bias_c1 or sqrt_bias_c2 not above 0
+    (CFM_ERR_BAD_SHAPE)."""
+    from conformer_amd import _lib
+    from conformer_amd.optim import _AdamTensor
+    NULL, SHAPE = _lib.CONSTANTS["CFM_ERR_NULL"], _lib.CONSTANTS["CFM_ERR_BAD_SHAPE"]
+    fn = getattr(lib, entry)
+    buf = (ctypes.c_float * 64)()
+    a = ctypes.addressof(buf)
+
+    def table(n=50, **bad):                                      # 50 descriptors: the bad one sits in the second launch
+        arr = (_AdamTensor * n)()
+        for i in range(n):
+            arr[i] = _AdamTensor(a, a, a, a, 8)
+        for k, v in bad.items():
+            setattr(arr[n - 1], k, v)
+        return arr
+
+    good = (1e-3, 0.9, 0.999, 1e-8, 0.1, 0.03, None)
+    assert fn(None, 1, *good) == NULL
+    for field in ("param", "grad", "exp_avg", "exp_avg_sq"):
+        arr = table(**{field: None})
+        assert fn(ctypes.addressof(arr), 50, *good) == NULL, field
+    for numel in (0, -4):
+        arr = table(numel=numel)
+        assert fn(ctypes.addressof(arr), 50, *good) == SHAPE
+    arr = table()
+    for n in (0, -1):
+        assert fn(ctypes.addressof(arr), n, *good) == SHAPE
+    for c1 in (0.0, -0.1, float("nan")):
+        assert fn(ctypes.addressof(arr), 50, 1e-3, 0.9, 0.999, 1e-8, c1, 0.03, None) == SHAPE
+        assert fn(ctypes.addressof(arr), 50, 1e-3, 0.9, 0.999, 1e-8, 0.1, c1, None) == SHAPE
+    assert not any(buf)                                          # (nothing ran)
+
+
 def test_no_cpu_fallback():
     from conformer_amd import ops
     from conformer_amd._lib import ConformerHipError

@@ -302,3 +302,36 @@ class CtcLossFn(Function):
     @staticmethod
     def backward(ctx, grad_out):
         return ops.ctc_loss_backward(ctx.state, grad_out.float().contiguous()), None, None, None, None
+
+
+class CtcNbestScoreFn(Function):
+    """ll (B,N) float64 = log p(hyps[b, n] | logits[b]) for every row of an n-best list, against the one logits block of its
+    utterance (csrc/ctc_nbest.hip).  Forward: one log-sum-exp per frame and one alpha chain per row; backward: the beta chains
+    and ONE pass over the frames that folds the N occupancies, weighted by grad (B,N), into the (B,T,V) logits gradient.  The
+    logits are never repeated N times; the workspace is allocated once in forward and kept in ctx."""
+
+    @staticmethod
+    def forward(ctx, logits, hyps, hyp_len, in_len, blank, max_len=None):
+        ll, state = ops.ctc_nbest_forward(logits, hyps, hyp_len, in_len, blank, max_len)
+        ctx.state = state
+        return ll
+
+    @staticmethod
+    def backward(ctx, grad):
+        return ops.ctc_nbest_backward(ctx.state, grad.float().contiguous()), None, None, None, None, None
+
+
+class MwerRiskFn(Function):
+    """The MWER risk over n-best lists (cfm3_mwer_risk_f32): the mean over the batch of sum_n P_n W_n - mean_n W_n, P the softmax
+    of ll (B,N) over the live rows, W = errors (B,N) int32.  The kernel leaves d loss / d ll beside the loss; backward scales it."""
+
+    @staticmethod
+    def forward(ctx, ll, errors, hyp_len):
+        loss, weight, _ = ops.mwer_risk(ll, errors, hyp_len)
+        ctx.save_for_backward(weight)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        (weight,) = ctx.saved_tensors
+        return (weight * grad_out.float()).double(), None, None

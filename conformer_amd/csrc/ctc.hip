@@ -16,6 +16,7 @@
 //             (deterministic, no atomics).
 // HBM-bound on the logits (B*T*V read twice, written once); the chains are latency-bound (T sequential steps).
 #include "cfm_common.h"
+#include "ctc_chain.h"
 
 namespace {
 
@@ -28,17 +29,8 @@ struct CtcArgs {
     int B, T, V, Lmax, blank, P;
 };
 
-constexpr float NEG_INF = -__builtin_inff();
-
-__device__ __forceinline__ float log_fast(float x) { return __builtin_amdgcn_logf(x) * 0.69314718055994530942f; }
-__device__ __forceinline__ float lse2(float a, float b) {
-    const float m = fmaxf(a, b);
-    return m == NEG_INF ? NEG_INF : m + log_fast(exp_fast(a - m) + exp_fast(b - m));
-}
-__device__ __forceinline__ float lse3(float a, float b, float c) {
-    const float m = fmaxf(fmaxf(a, b), c);
-    return m == NEG_INF ? NEG_INF : m + log_fast(exp_fast(a - m) + exp_fast(b - m) + exp_fast(c - m));
-}
+using ctc_chain::NEG_INF;
+using ctc_chain::pairs_per_lane;
 
 // utterance geometry, clamped so that no index derived from it can leave a buffer
 __device__ __forceinline__ void ctc_geometry(const CtcArgs& a, int b, int& Tb, int& Lb, int64_t& off) {
@@ -53,8 +45,7 @@ __device__ __forceinline__ void ctc_geometry(const CtcArgs& a, int b, int& Tb, i
     Tb = (int)(t < 0 ? 0 : (t > a.T ? a.T : t));
 }
 __device__ __forceinline__ int ctc_label(const CtcArgs& a, int64_t off, int i) {
-    const int64_t v = a.targets[off + i];
-    return (int)(v < 0 ? 0 : (v >= a.V ? a.V - 1 : v));
+    return ctc_chain::clamp_label(a.targets[off + i], a.V);
 }
 
 __global__ __launch_bounds__(256) void ctc_prepare_kernel(const CtcArgs a) {
@@ -78,11 +69,9 @@ __global__ __launch_bounds__(256) void ctc_prepare_kernel(const CtcArgs a) {
     for (int i = lane; i < Lb; i += 64) out[i] = row[ctc_label(a, off, i)] - lse;
 }
 
-// One wave per utterance.  Lane l owns the pairs i = l*P .. l*P+P-1: blank state 2i (exists for i <= L) and label state
-// 2i+1 (exists for i < L).  Rows of alpha / beta: [t][2*64*P], element 2i (+1).
+// One wave per utterance: the chain of ctc_chain.h.  Rows of alpha / beta: [t][2*64*P], element 2i (+1).
 template <int P, bool BETA>
 __global__ __launch_bounds__(64) void ctc_chain_kernel(const CtcArgs a) {
-    constexpr int U = P >= 16 ? 1 : 16 / P;                   // time steps per prefetch block
     constexpr int NP = 64 * P;
     const int b = blockIdx.x, lane = threadIdx.x;
     int Tb, Lb; int64_t off;
@@ -91,134 +80,17 @@ __global__ __launch_bounds__(64) void ctc_chain_kernel(const CtcArgs a) {
         if (!BETA && lane == 0) { a.nll[b] = Lb == 0 ? 0.f : -NEG_INF; a.ll[b] = Lb == 0 ? 0.0 : (double)NEG_INF; }
         return;
     }
-    double* coff = (BETA ? a.cb : a.ca) + (int64_t)b * a.T;
-    double C = 0.0;                                           // stored value + C = true log alpha (beta)
-    float* out = (BETA ? a.beta : a.alpha) + (int64_t)b * a.T * 2 * NP;
-    const float* lplb = a.lpl + (int64_t)b * a.T * a.Lmax;
-    const float* lpbb = a.lpb + (int64_t)b * a.T;
-
-    int lab[P];
-    bool hop[P];                  // alpha: state 2i+1 may be entered from 2i-1; beta: 2i+1 may go to 2i+3
-#pragma unroll
-    for (int p = 0; p < P; ++p) {
-        const int i = lane * P + p;
-        lab[p] = i < Lb ? ctc_label(a, off, i) : -1 - i;     // distinct negatives: never equal to a neighbour
-    }
-    const int nb_lab = BETA ? __shfl_down(lab[0], 1, 64) : __shfl_up(lab[P - 1], 1, 64);
-#pragma unroll
-    for (int p = 0; p < P; ++p) {
-        const int i = lane * P + p;
-        if (BETA) {
-            const int nxt = p == P - 1 ? nb_lab : lab[p + 1];
-            hop[p] = (i + 1 < Lb) && lab[p] != nxt;
-        } else {
-            const int prv = p == 0 ? nb_lab : lab[p - 1];
-            hop[p] = (i >= 1) && (i < Lb) && lab[p] != prv;
-        }
-    }
-    int idx[P];
-#pragma unroll
-    for (int p = 0; p < P; ++p) idx[p] = min(lane * P + p, a.Lmax - 1);
-
-    float sb[P], sl[P];          // current alpha (beta) of the lane's blank / label states
-    float cb[U], cl[U][P], nb[U], nl[U][P];
-    auto load_block = [&](int t_first, float (&vb)[U], float (&vl)[U][P]) {      // clamped: always in range
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int t = min(max(BETA ? t_first - u : t_first + u, 0), Tb - 1);
-            vb[u] = lpbb[t];
-#pragma unroll
-            for (int p = 0; p < P; ++p) vl[u][p] = lplb[(int64_t)t * a.Lmax + idx[p]];
-        }
-    };
-    const int t_begin = BETA ? Tb - 1 : 0;
-    load_block(t_begin, cb, cl);
-    for (int done = 0; done < Tb; done += U) {
-        const int t0 = BETA ? t_begin - done : done;
-        load_block(BETA ? t0 - U : t0 + U, nb, nl);
-        __builtin_amdgcn_sched_barrier(0);
-        if (done > 0) {                                                      // re-centre the lattice on its maximum
-            float m = NEG_INF;
-#pragma unroll
-            for (int p = 0; p < P; ++p) m = fmaxf(m, fmaxf(sb[p], sl[p]));
-            m = wave_max(m);
-            if (m > NEG_INF) {
-#pragma unroll
-                for (int p = 0; p < P; ++p) { sb[p] -= m; sl[p] -= m; }
-                C += (double)m;
-            }
-        }
-        if (lane < U && done + lane < Tb) coff[BETA ? t0 - lane : t0 + lane] = C;
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            if (done + u >= Tb) break;                                       // uniform
-            const int t = BETA ? t0 - u : t0 + u;
-            if (done + u == 0) {
-#pragma unroll
-                for (int p = 0; p < P; ++p) {
-                    const int i = lane * P + p;
-                    if (BETA) {
-                        sb[p] = i == Lb ? cb[u] : NEG_INF;                       // state S-1
-                        sl[p] = i == Lb - 1 ? cl[u][p] : NEG_INF;                // state S-2
-                    } else {
-                        sb[p] = i == 0 ? cb[u] : NEG_INF;                        // state 0
-                        sl[p] = (i == 0 && Lb > 0) ? cl[u][p] : NEG_INF;         // state 1
-                    }
-                }
-            } else if (BETA) {
-                float right_b = __shfl_down(sb[0], 1, 64), right_l = __shfl_down(sl[0], 1, 64);
-                if (lane == 63) { right_b = NEG_INF; right_l = NEG_INF; }
-                float nsb[P], nsl[P];
-#pragma unroll
-                for (int p = 0; p < P; ++p) {
-                    const int i = lane * P + p;
-                    const float rb = p == P - 1 ? right_b : sb[p + 1], rl = p == P - 1 ? right_l : sl[p + 1];
-                    const float vb = lse2(sb[p], sl[p]) + cb[u];
-                    const float vl = lse3(sl[p], rb, hop[p] ? rl : NEG_INF) + cl[u][p];
-                    nsb[p] = i <= Lb ? vb : NEG_INF;
-                    nsl[p] = i < Lb ? vl : NEG_INF;
-                }
-#pragma unroll
-                for (int p = 0; p < P; ++p) { sb[p] = nsb[p]; sl[p] = nsl[p]; }
-            } else {
-                float left = __shfl_up(sl[P - 1], 1, 64);
-                if (lane == 0) left = NEG_INF;
-#pragma unroll
-                for (int p = 0; p < P; ++p) {
-                    const int i = lane * P + p;
-                    const float ob = sb[p], ol = sl[p];
-                    const float vb = lse2(ob, left) + cb[u];
-                    const float vl = lse3(ol, ob, hop[p] ? left : NEG_INF) + cl[u][p];
-                    sb[p] = i <= Lb ? vb : NEG_INF;
-                    sl[p] = i < Lb ? vl : NEG_INF;
-                    left = ol;
-                }
-            }
-            float* orow = out + (int64_t)t * 2 * NP + (int64_t)lane * 2 * P;
-#pragma unroll
-            for (int p = 0; p < P; ++p) { orow[2 * p] = sb[p]; orow[2 * p + 1] = sl[p]; }
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            cb[u] = nb[u];
-#pragma unroll
-            for (int p = 0; p < P; ++p) cl[u][p] = nl[u][p];
-        }
-    }
-    if (!BETA) {
-        float fb = NEG_INF, fl = NEG_INF;
-#pragma unroll
-        for (int p = 0; p < P; ++p) {
-            const int i = lane * P + p;
-            if (i == Lb) fb = sb[p];
-            if (i == Lb - 1) fl = sl[p];
-        }
-        fb = wave_max(fb); fl = wave_max(fl);
-        if (lane == 0) {
-            const double ll = C + (double)lse2(fb, fl);
-            a.ll[b] = ll;
-            a.nll[b] = (float)(-ll);
-        }
+    ctc_chain::Row r;
+    r.labels = a.targets + off;
+    r.lpl = a.lpl + (int64_t)b * a.T * a.Lmax;
+    r.lpb = a.lpb + (int64_t)b * a.T;
+    r.out = (BETA ? a.beta : a.alpha) + (int64_t)b * a.T * 2 * NP;
+    r.coff = (BETA ? a.cb : a.ca) + (int64_t)b * a.T;
+    r.Tb = Tb; r.Lb = Lb; r.Lmax = a.Lmax; r.V = a.V;
+    const double ll = ctc_chain::run<P, BETA>(r, lane);
+    if (!BETA && lane == 0) {
+        a.ll[b] = ll;
+        a.nll[b] = (float)(-ll);
     }
 }
 
@@ -291,12 +163,6 @@ __global__ __launch_bounds__(256) void ctc_grad_kernel(const CtcArgs a, int wave
     } else {
         for (int v = lane; v < a.V; v += 64) drow[v] = 0.f;
     }
-}
-
-int pairs_per_lane(int Lmax) {                       // 64*P >= Lmax + 1
-    int P = 1;
-    while (64 * P < Lmax + 1) P *= 2;
-    return P;
 }
 
 template <bool BETA>

@@ -370,6 +370,61 @@ class BeamCTCDecoder:
 
 # ---- streaming (resumable) search: INTEGRATION.md "Streaming (resumable) search" ------------------------------------------
 
+def nbest_rows(tokens: torch.Tensor, counts: torch.Tensor, num_hyps: Optional[torch.Tensor], max_len: Optional[int],
+               who: str = "ctc_nbest_scores") -> Tuple[torch.Tensor, int]:
+    """(hyp_len (B,N) int64 with -1 in the rows n >= num_hyps[b], the lattice width) of an n-best list as the search returns
+    it.  max_len=None reads counts.max() on the host: the ONE synchronisation of the n-best scores."""
+    if not (isinstance(tokens, torch.Tensor) and tokens.dim() == 3 and isinstance(counts, torch.Tensor)
+            and tuple(counts.shape) == tuple(tokens.shape[:2])):
+        raise ValueError(f"{who}: tokens must be (B,N,L) with counts (B,N)")
+    hyp_len = counts.to(torch.int64)
+    if num_hyps is not None:
+        if tuple(num_hyps.shape) != (tokens.shape[0],):
+            raise ValueError(f"{who}: num_hyps must be (B), got {tuple(num_hyps.shape)}")
+        n = torch.arange(tokens.shape[1], device=counts.device)
+        hyp_len = hyp_len.masked_fill(n[None, :] >= num_hyps.to(counts.device)[:, None], -1)
+    if max_len is None:
+        max_len = int(hyp_len.max()) if hyp_len.numel() else 0
+    elif not isinstance(max_len, int) or isinstance(max_len, bool) or max_len < 0:
+        raise ValueError(f"{who}: max_len must be a non-negative int or None, got {max_len!r}")
+    return hyp_len, max_len
+
+
+def ctc_nbest_scores(logits: torch.Tensor, tokens: torch.Tensor, counts: torch.Tensor, blank_id: int,
+                     lengths: Optional[torch.Tensor] = None, num_hyps: Optional[torch.Tensor] = None,
+                     max_len: Optional[int] = None) -> torch.Tensor:
+    """The exact CTC log-likelihood log p(tokens[b, n] | logits[b]) of every hypothesis of an n-best list: ll (B,N) float64.
+    The beam search's scores are pruned sums; these run over the full lattice, all N rows of an utterance against its one
+    logits block (INTEGRATION.md "MWER training and n-best scores").  logits (B,T,V) on the HIP device (fp32, or bf16 / fp16
+    cast to fp32); tokens (B,N,L) int64 and counts (B,N) int64 as the search returns them (positions at or behind a count are
+    never read); lengths (B) int64: frames per utterance (None: all).  num_hyps (B), as the search returns it, marks the rows
+    n >= num_hyps[b] UNUSED; without it a row of count 0 is the empty hypothesis.  ll is -inf for an unused row and for a row
+    without an alignment (more labels plus repeats than frames).
+    max_len=None reads counts.max() once on the host -- the one synchronisation; an int avoids it and bounds the lattice width
+    (a longer row is cut to it).  Differentiable with respect to the logits when they require grad."""
+    from . import autograd as ag
+    x = logits.float() if isinstance(logits, torch.Tensor) and logits.dtype in (torch.bfloat16, torch.float16) else logits
+    x = ops._req(x, "logits")
+    hyp_len, max_len = nbest_rows(tokens, counts, num_hyps, max_len)
+    if lengths is None:
+        lengths = torch.full((x.shape[0],), x.shape[1], dtype=torch.int64, device=x.device)
+    return ag.CtcNbestScoreFn.apply(x, tokens, hyp_len, lengths, int(blank_id), max_len)
+
+
+def nbest_posterior(logits: torch.Tensor, tokens: torch.Tensor, counts: torch.Tensor, blank_id: int,
+                    lengths: Optional[torch.Tensor] = None, num_hyps: Optional[torch.Tensor] = None,
+                    max_len: Optional[int] = None) -> torch.Tensor:
+    """The posterior of every hypothesis within its n-best list, (B,N) fp32: the softmax of ctc_nbest_scores over the live rows
+    (used, with an alignment), formed in float64; unused and infeasible rows get 0, and so does a list without a live row.  Row
+    0's value is an utterance-level confidence, and the filter for pseudo-labels.  Arguments as ctc_nbest_scores."""
+    ll = ctc_nbest_scores(logits, tokens, counts, blank_id, lengths, num_hyps, max_len)
+    live = torch.isfinite(ll)
+    ll = ll.masked_fill(~live, -math.inf)
+    top = ll.amax(dim=1, keepdim=True).masked_fill(~live.any(dim=1, keepdim=True), 0.0)
+    e = (ll - top).exp()                                     # 0 for a dead row
+    return (e / e.sum(dim=1, keepdim=True).clamp_min(1e-300)).float()
+
+
 class _StreamState:
     """The device buffer of one resumable search and the mode it was initialised for (what beam_ctc_stream_* pass back)."""
 

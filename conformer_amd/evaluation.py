@@ -4,7 +4,7 @@ torchmetrics' WordErrorRate / CharErrorRate: total edit distance / total referen
 cer_tokens take token ids on the device instead of strings and score them there (conformer_amd.error_rate)."""
 from __future__ import annotations
 
-from typing import List, Sequence, Union
+from typing import List, Optional, Sequence, Union
 
 import torch
 
@@ -23,6 +23,65 @@ class ConformerCriterion:
         if not outputs.is_cuda:
             raise RuntimeError("ConformerCriterion.ctc_loss: logits must be on the HIP device (no CPU fallback)")
         return ag.CtcLossFn.apply(outputs.float(), targets.long(), input_lengths, target_lengths, self.blank_id)
+
+    def mwer_loss(self, outputs: torch.Tensor, targets: torch.Tensor, input_lengths: torch.Tensor,
+                  target_lengths: torch.Tensor, tables, *, unit: str = "word", n_best: int = 4, beam_width: int = 100,
+                  hyp_tokens: Optional[torch.Tensor] = None, hyp_counts: Optional[torch.Tensor] = None,
+                  num_hyps: Optional[torch.Tensor] = None, add_reference: bool = False, ctc_weight: float = 0.0,
+                  decoder=None) -> torch.Tensor:
+        """Minimum-word-error-rate loss over the n-best list (INTEGRATION.md "MWER training and n-best scores"): the mean over
+        the batch of sum_n P_n W_n - mean_n W_n, where W_n is the edit distance of hypothesis n to the reference in `unit`s
+        ("word", "char" or "token", error_rate.error_counts with `tables`, an ErrorRateTables) and P_n the softmax, over the
+        list, of the exact CTC log-likelihoods of the hypotheses given `outputs` (autograd.CtcNbestScoreFn).  The subtracted
+        mean centres the number and has no gradient.  An utterance with fewer than two live hypotheses contributes 0.
+
+        outputs: logits (B,T',V) on the HIP device (no CPU fallback); targets (B,Lr) padded int64; lengths (B).  The list is
+        hyp_tokens (B,N,L), hyp_counts (B,N) and optionally num_hyps (B), as the beam search returns them; when none is handed
+        in, the device beam search runs on outputs.detach() with n_best and beam_width -- or `decoder` (a BeamCTCDecoder) runs
+        its own, with its beam, language model and hotwords.  add_reference appends the reference as one more row unless a
+        hypothesis already equals it (token distance 0).  ctc_weight adds ctc_weight * ctc_loss(...), the usual interpolation.
+        One host read: the longest hypothesis (and, with add_reference, reference) sets the lattice width."""
+        from . import decode, error_rate
+        if not isinstance(outputs, torch.Tensor) or not outputs.is_cuda:
+            raise RuntimeError("ConformerCriterion.mwer_loss: logits must be on the HIP device (no CPU fallback)")
+        if targets.dim() != 2:
+            raise ValueError(f"ConformerCriterion.mwer_loss: targets must be (B,Lr) padded, got {tuple(targets.shape)}")
+        x = outputs.float()
+        B, dev = x.shape[0], x.device
+        refs = targets.long().to(dev).contiguous()
+        in_len = torch.as_tensor(input_lengths).to(dev).long().contiguous()
+        ref_len = torch.as_tensor(target_lengths).to(dev).long().contiguous()
+        if hyp_tokens is None:
+            if hyp_counts is not None or num_hyps is not None:
+                raise ValueError("ConformerCriterion.mwer_loss: hyp_counts / num_hyps without hyp_tokens")
+            if decoder is None:
+                hyp_tokens, hyp_counts, _, num_hyps = decode.beam_ctc_decode(x.detach(), self.blank_id, in_len, beam_width,
+                                                                             n_best)
+            else:
+                out = decode._beam_search(x.detach(), decoder.blank_id, in_len, n_best, decoder.beam_width,
+                                          decoder.token_min_logp, decoder.beam_prune_logp, decoder.max_candidates, decoder.vocab,
+                                          decoder._call_fusion(B, None, None))
+                hyp_tokens, hyp_counts, num_hyps = out[0], out[1], out[-1]
+        elif hyp_counts is None:
+            raise ValueError("ConformerCriterion.mwer_loss: hyp_tokens without hyp_counts")
+        hyp_tokens, hyp_counts = hyp_tokens.to(dev), hyp_counts.to(dev)
+        hyp_len, _ = decode.nbest_rows(hyp_tokens, hyp_counts, num_hyps, 0, "ConformerCriterion.mwer_loss")
+        if add_reference:
+            N, width = hyp_tokens.shape[1], max(hyp_tokens.shape[2], refs.shape[1])
+            rows = torch.full((B, N + 1, width), -1, dtype=torch.int64, device=dev)
+            rows[:, :N, :hyp_tokens.shape[2]] = hyp_tokens
+            rows[:, N, :refs.shape[1]] = refs
+            same, _, _ = error_rate.error_counts(hyp_tokens.contiguous(), hyp_len.clamp_min(0), refs, ref_len, tables, "token")
+            found = ((same == 0) & (hyp_len >= 0)).any(dim=1)
+            last = ref_len.clamp(0, refs.shape[1]).masked_fill(found, -1)
+            hyp_tokens, hyp_len = rows, torch.cat([hyp_len, last[:, None]], dim=1)
+        max_len = int(hyp_len.max())                                   # the one host read
+        errors, _, _ = error_rate.error_counts(hyp_tokens.contiguous(), hyp_len.clamp_min(0), refs, ref_len, tables, unit)
+        ll = ag.CtcNbestScoreFn.apply(x, hyp_tokens, hyp_len, in_len, self.blank_id, max_len)
+        loss = ag.MwerRiskFn.apply(ll, errors, hyp_len)
+        if ctc_weight:
+            loss = loss + float(ctc_weight) * self.ctc_loss(outputs, targets, input_lengths, target_lengths)
+        return loss
 
 
 def _edit_distance(ref: Sequence, hyp: Sequence) -> int:

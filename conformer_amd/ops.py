@@ -1581,3 +1581,72 @@ def ctc_loss_backward(ctx, grad_out):
 def ctc_nll(ctx) -> torch.Tensor:
     """Per-utterance negative log-likelihood (B,) left in the workspace by ctc_loss_forward (inf = no valid alignment)."""
     return ctx[-1][-ctx[0].shape[0]:]
+
+
+# ---- n-best CTC scores over shared logits (conformer_hip3_ctc_nbest.h): MWER training, n-best posteriors -----------------------
+CTC_NBEST_MAX = _lib.OPEN_CONSTANTS["conformer_hip3_ctc_nbest.h"]["CFM3_CTC_NBEST_MAX"]
+
+
+def ctc_nbest_forward(logits, hyps, hyp_len, in_len, blank: int = 0, max_len: Optional[int] = None):
+    """log p(hyps[b, n] | logits[b]) of every row of an n-best list: logits (B,T,V) fp32, hyps (B,N,L) int64 (positions at or
+    behind a count are never read), hyp_len (B,N) int64 (< 0: the row is unused), in_len (B) int64.  Returns (ll (B,N) float64,
+    ctx); ctx carries the lattice workspace for ctc_nbest_backward.  max_len: the lattice width (rows longer than it are cut to
+    it); None takes the width of `hyps`."""
+    logits = _req(logits, "logits")
+    if logits.dim() != 3:
+        raise _lib.ConformerHipError(f"ctc_nbest: logits must be (B,T,V), got {tuple(logits.shape)}")
+    B, T, V = logits.shape
+    hyps = _req(hyps, "hyps", torch.int64)
+    hyp_len = _req(hyp_len, "hyp_len", torch.int64)
+    in_len = _req(torch.as_tensor(in_len).to(logits.device), "in_len", torch.int64)
+    if hyps.dim() != 3 or hyps.shape[0] != B or tuple(hyp_len.shape) != tuple(hyps.shape[:2]) or in_len.numel() != B:
+        raise _lib.ConformerHipError(f"ctc_nbest: hyps must be (B,N,L) with hyp_len (B,N) and in_len (B) for B = {B}, got "
+                                     f"{tuple(hyps.shape)}, {tuple(hyp_len.shape)}, {tuple(in_len.shape)}")
+    N = hyps.shape[1]
+    if not 1 <= N <= CTC_NBEST_MAX:
+        raise NotImplementedError(f"ctc_nbest: lists of {N} hypotheses are not built (1 to {CTC_NBEST_MAX})")
+    lmax = max(1, hyps.shape[2] if max_len is None else min(int(max_len), hyps.shape[2]))
+    if lmax > CTC_MAX_TARGET:
+        raise NotImplementedError(f"ctc_nbest: hypotheses longer than {CTC_MAX_TARGET} labels are not built")
+    if hyps.shape[2] != lmax:             # the entry takes rows of exactly Lmax labels: B N Lmax ids, not a logits-sized copy
+        rows = torch.full((B, N, lmax), -1, dtype=torch.int64, device=logits.device)
+        rows[:, :, :min(lmax, hyps.shape[2])] = hyps[:, :, :lmax]
+        hyps = rows
+    lib = _lib.load()
+    ws = torch.empty(int(lib.cfm3_ctc_nbest_workspace_floats(B, N, T, lmax)), device=logits.device, dtype=torch.float32)
+    ll = torch.empty((B, N), device=logits.device, dtype=torch.float64)
+    _lib.call("cfm3_ctc_nbest_score_f32", logits.data_ptr(), hyps.data_ptr(), hyp_len.data_ptr(), in_len.data_ptr(), B, N, T, V,
+              lmax, int(blank), ws.data_ptr(), ll.data_ptr(), _stream())
+    return ll, (logits, hyps, hyp_len, in_len, lmax, int(blank), ws)
+
+
+def ctc_nbest_backward(ctx, weight):
+    """sum_n weight[b, n] * d ll[b, n] / d logits, (B,T,V) fp32, from the ctx of ctc_nbest_forward: weight (B,N) fp32."""
+    logits, hyps, hyp_len, in_len, lmax, blank, ws = ctx
+    B, T, V = logits.shape
+    N = hyps.shape[1]
+    weight = _req(weight, "weight")
+    if tuple(weight.shape) != (B, N):
+        raise _lib.ConformerHipError(f"ctc_nbest: weight must be {(B, N)}, got {tuple(weight.shape)}")
+    dlogits = torch.empty((B, T, V), device=logits.device, dtype=torch.float32)
+    _lib.call("cfm3_ctc_nbest_grad_f32", logits.data_ptr(), hyps.data_ptr(), hyp_len.data_ptr(), in_len.data_ptr(), B, N, T, V,
+              lmax, blank, ws.data_ptr(), weight.data_ptr(), dlogits.data_ptr(), _stream())
+    return dlogits
+
+
+def mwer_risk(ll, errors, hyp_len, grad_scale: float = 1.0):
+    """The MWER risk of B lists (cfm3_mwer_risk_f32): ll (B,N) float64, errors (B,N) int32, hyp_len (B,N) int64 (< 0: unused).
+    Returns (loss () fp32, weight (B,N) fp32 = grad_scale * d loss / d ll, risk (B) fp32)."""
+    ll = _req(ll, "ll", torch.float64)
+    errors = _req(errors, "errors", torch.int32)
+    hyp_len = _req(hyp_len, "hyp_len", torch.int64)
+    if ll.dim() != 2 or tuple(errors.shape) != tuple(ll.shape) or tuple(hyp_len.shape) != tuple(ll.shape):
+        raise _lib.ConformerHipError(f"mwer_risk: ll, errors and hyp_len must share one (B,N) shape, got {tuple(ll.shape)}, "
+                                     f"{tuple(errors.shape)}, {tuple(hyp_len.shape)}")
+    B, N = ll.shape
+    risk = torch.empty((B,), device=ll.device, dtype=torch.float32)
+    loss = torch.empty((), device=ll.device, dtype=torch.float32)
+    weight = torch.empty((B, N), device=ll.device, dtype=torch.float32)
+    _lib.call("cfm3_mwer_risk_f32", ll.data_ptr(), errors.data_ptr(), hyp_len.data_ptr(), B, N, float(grad_scale),
+              risk.data_ptr(), loss.data_ptr(), weight.data_ptr(), _stream())
+    return loss, weight, risk

@@ -126,15 +126,19 @@ class ConformerAudioFrontend:
         return audios
 
     def __call__(self, audios: Sequence[torch.Tensor], augment: Optional["ConformerAugment"] = None,
-                 sample_rates: Optional[Sequence[int]] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+                 sample_rates: Optional[Sequence[int]] = None, wave_augment=None) -> Tuple[torch.Tensor, torch.Tensor]:
         """processor.py:373-394: zero-pad to the longest, log-mel, lengths = samples // hop + 1.  sample_rates: the rate of every
-        audio; those at another rate than self.sample_rate are resampled first (the default: all at self.sample_rate)."""
+        audio; those at another rate than self.sample_rate are resampled first (the default: all at self.sample_rate).
+        wave_augment: a wave_augment.WaveAugment, run on the padded batch (at this front end's rate) before the log-mel; the
+        frame lengths then come from the lengths it returns."""
         if sample_rates is not None:
             audios = self._to_own_rate(audios, sample_rates)
         lengths = [int(a.numel()) for a in audios]
         batch = torch.zeros(len(audios), max(lengths), device=self.device, dtype=torch.float32)
         for i, a in enumerate(audios):
             batch[i, :lengths[i]] = a.to(self.device)
+        if wave_augment is not None:
+            batch, lengths = wave_augment(batch, lengths)
         mels = self.mel_spectrogram(batch)
         if augment is not None:
             mels = augment(mels)

@@ -21,10 +21,11 @@ class FrontendPipeline:
     """
 
     def __init__(self, source: Iterable[Sequence[torch.Tensor]], frontend: ConformerAudioFrontend,
-                 augment: Optional[ConformerAugment] = None, depth: int = 2) -> None:
+                 augment: Optional[ConformerAugment] = None, depth: int = 2, wave_augment=None) -> None:
         if depth < 1:
             raise ValueError("depth must be >= 1")
         self.source, self.frontend, self.augment, self.depth = source, frontend, augment, depth
+        self.wave_augment = wave_augment          # a wave_augment.WaveAugment: runs on the side stream between the copy and the mel
         self.stream = torch.cuda.Stream(device=frontend.device)
         self.timeline: Optional[List[Tuple[torch.cuda.Event, torch.cuda.Event]]] = None   # set to [] to record (start, done) events per batch
 
@@ -34,12 +35,14 @@ class FrontendPipeline:
         host = torch.zeros(len(audios), max(lengths), dtype=torch.float32).pin_memory()
         for i, a in enumerate(audios):
             host[i, :lengths[i]] = a
-        host_len = torch.tensor(lengths, dtype=torch.int64).pin_memory()
         with torch.cuda.stream(self.stream):
             if self.timeline is not None:
                 ev0 = torch.cuda.Event(enable_timing=True)
                 ev0.record(self.stream)
             wave = host.to(fe.device, non_blocking=True)
+            if self.wave_augment is not None:                                # the plan is drawn on the host from the host lengths
+                wave, lengths = self.wave_augment(wave, lengths)
+            host_len = torch.tensor(lengths, dtype=torch.int64).pin_memory()
             n = host_len.to(fe.device, non_blocking=True)
             mels = fe.mel_spectrogram(wave)
             if self.augment is not None:

@@ -335,3 +335,41 @@ class MwerRiskFn(Function):
     def backward(ctx, grad_out):
         (weight,) = ctx.saved_tensors
         return (weight * grad_out.float()).double(), None, None
+
+
+class GumbelQuantizeFn(Function):
+    """(out (N,G*dg), codes (N,G) int32, perplexity ()) of the Gumbel quantizer (csrc/pretrain.hip): the code is the argmax of
+    logits + noise, out the code's row of codevectors, perplexity the exponentiated entropy of the marginal of the noise-free
+    softmax over the rows of row_mask.  Backward: the straight-through gradient through softmax((logits + noise) / tau) plus
+    the perplexity's gradient into logits, and the rows of dout summed per code into codevectors."""
+
+    @staticmethod
+    def forward(ctx, logits, codevectors, tau, noise, row_mask):
+        out, codes, perplexity, _, state = ops.quantize_forward(logits, codevectors, tau, noise, row_mask)
+        ctx.state = state
+        ctx.mark_non_differentiable(codes)
+        return out, codes, perplexity
+
+    @staticmethod
+    def backward(ctx, dout, _dcodes, dperplexity):
+        dlogits, dcv = ops.quantize_backward(ctx.state, dout.float().contiguous(), dperplexity.float().contiguous())
+        return dlogits, dcv, None, None, None
+
+
+class ContrastiveLossFn(Function):
+    """(loss (), frame_loss (B,T), n_correct () int32) of the contrastive loss (csrc/pretrain.hip): per masked frame the
+    cross-entropy of the positive among itself and K negatives drawn from the same utterance, over cosine / temperature.
+    Backward: dcontext per frame, dtargets through the transposed list of the draws; nothing of B*T*K*D elements exists."""
+
+    @staticmethod
+    def forward(ctx, context, targets, mask, negatives, ids, temperature):
+        loss, frame_loss, n_correct, _, state = ops.contrastive_forward(context, targets, mask, negatives, ids, temperature)
+        ctx.state = state
+        ctx.mark_non_differentiable(n_correct)
+        return loss, frame_loss, n_correct
+
+    @staticmethod
+    def backward(ctx, dloss, dframe, _dn):
+        gframe = (dframe.float() + dloss.float()).contiguous()
+        dcontext, dtargets = ops.contrastive_backward(ctx.state, gframe)
+        return dcontext, dtargets, None, None, None, None

@@ -83,6 +83,40 @@ class ConformerCriterion:
             loss = loss + float(ctc_weight) * self.ctc_loss(outputs, targets, input_lengths, target_lengths)
         return loss
 
+    def pretrain_loss(self, context: torch.Tensor, target: torch.Tensor, perplexity: torch.Tensor, mask_indexes: torch.Tensor,
+                      codes: Optional[torch.Tensor] = None, num_negatives: int = 100, temperature: float = 0.1,
+                      diversity_weight: float = 0.1, generator: Optional[torch.Generator] = None, *,
+                      num_codevectors: int = 640, negatives: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The wav2vec 2.0 objective on what Wav2Vec2.forward returns (INTEGRATION.md "Self-supervised pretraining"):
+
+            contrastive + diversity_weight * (G V - perplexity) / (G V) * n_masked
+
+        contrastive: pretrain.contrastive_loss of context against target (both (B,T',P)) over the frames of mask_indexes (B,T')
+        with num_negatives draws per frame from the other masked frames of the same utterance (pretrain.sample_negatives with
+        `generator`, or `negatives` (B,T',K) handed in).  codes (B,T',G), the quantizer's (Quantization.last_codes): a negative
+        with the positive's codes is excluded.  num_codevectors is G V (640: the reference's 2 x 320).  Everything stays on the
+        device; the parts are left in self.last_pretrain: contrastive, perplexity, n_masked and accuracy = n_correct / n_masked."""
+        from . import pretrain
+        if not isinstance(context, torch.Tensor) or not context.is_cuda:
+            raise RuntimeError("ConformerCriterion.pretrain_loss: context must be on the HIP device (no CPU fallback)")
+        mask = mask_indexes.to(context.device)
+        if negatives is None:
+            negatives = pretrain.sample_negatives(mask, int(num_negatives), generator)
+        ids = None
+        if codes is not None:
+            c = codes.to(torch.int64)
+            if c.shape[-1] <= 6:              # fold the G codes (each below 2^10) into one id: no collision, no host read
+                ids = (c << (10 * torch.arange(c.shape[-1], device=c.device))).sum(dim=-1)
+            else:                             # a dense id per distinct row (torch.unique synchronises)
+                ids = torch.unique(c.reshape(-1, c.shape[-1]), dim=0, return_inverse=True)[1].view(c.shape[:-1])
+        loss, _, n_correct = pretrain.contrastive_loss(context.float(), target.float(), mask, negatives, ids, temperature)
+        n_masked = mask.sum()
+        gv = float(num_codevectors)
+        total = loss + float(diversity_weight) * (gv - perplexity) / gv * n_masked
+        self.last_pretrain = {"contrastive": loss.detach(), "perplexity": perplexity.detach(), "n_masked": n_masked,
+                              "accuracy": n_correct / n_masked.clamp_min(1)}
+        return total
+
 
 def _edit_distance(ref: Sequence, hyp: Sequence) -> int:
     prev = list(range(len(hyp) + 1))

@@ -1650,3 +1650,136 @@ def mwer_risk(ll, errors, hyp_len, grad_scale: float = 1.0):
     _lib.call("cfm3_mwer_risk_f32", ll.data_ptr(), errors.data_ptr(), hyp_len.data_ptr(), B, N, float(grad_scale),
               risk.data_ptr(), loss.data_ptr(), weight.data_ptr(), _stream())
     return loss, weight, risk
+
+
+# ---- self-supervised pretraining (conformer_hip3_pretrain.h): the Gumbel quantizer and the contrastive loss ---------------------
+PRETRAIN_LIMITS = {k[len("CFM3_PRETRAIN_MAX_"):]: v for k, v in _lib.OPEN_CONSTANTS["conformer_hip3_pretrain.h"].items()
+                   if k.startswith("CFM3_PRETRAIN_MAX_")}          # V, G, DG, D, K
+
+
+def _u8(t, name: str, shape) -> torch.Tensor:
+    """a bool / uint8 mask on the device as contiguous uint8 of `shape`"""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise _lib.ConformerHipError(f"{name}: expected a tensor on a HIP device, got {getattr(t, 'device', type(t))}; the "
+                                     "pretraining objective only exists as gfx950 kernels (no CPU fallback)")
+    if t.dtype not in (torch.bool, torch.uint8) or tuple(t.shape) != tuple(shape):
+        raise _lib.ConformerHipError(f"{name}: expected bool or uint8 of shape {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
+    return t.contiguous().view(torch.uint8)
+
+
+def quantize_forward(logits, codevectors, tau: float, noise=None, row_mask=None):
+    """The Gumbel quantizer (cfm3_quantize_fwd_f32): logits (N,G,V) fp32, codevectors (G*V,dg) fp32, noise (N,G,V) fp32 or None
+    (the eval path: plain argmax, one-hot marginal), row_mask (N) bool / uint8 or None.  Returns (out (N,G*dg), codes (N,G) int32,
+    perplexity (), marginal (G,V), ctx); ctx carries the workspace for quantize_backward."""
+    logits = _req(logits, "logits")
+    cv = _req(codevectors, "codevectors")
+    if logits.dim() != 3 or cv.dim() != 2 or cv.shape[0] != logits.shape[1] * logits.shape[2]:
+        raise _lib.ConformerHipError(f"quantize: logits must be (N,G,V) and codevectors (G*V,dg), got {tuple(logits.shape)}, "
+                                     f"{tuple(cv.shape)}")
+    N, G, V = logits.shape
+    dg = cv.shape[1]
+    if noise is not None:
+        noise = _req(noise, "noise")
+        if noise.shape != logits.shape:
+            raise _lib.ConformerHipError(f"quantize: noise must be {tuple(logits.shape)}, got {tuple(noise.shape)}")
+    if row_mask is not None:
+        row_mask = _u8(row_mask, "row_mask", (N,))
+    lib = _lib.load()
+    floats = int(lib.cfm3_quantize_workspace_floats(N, G, V))
+    if floats < 0:
+        raise _lib.ConformerHipError(f"quantize: (N,G,V) = {(N, G, V)} is not built (N >= 1, G <= {PRETRAIN_LIMITS['G']}, "
+                                     f"V <= {PRETRAIN_LIMITS['V']}, N*G < 2^31)")
+    ws = torch.empty(floats, device=logits.device, dtype=torch.float32)
+    codes = torch.empty((N, G), device=logits.device, dtype=torch.int32)
+    out = torch.empty((N, G * dg), device=logits.device, dtype=torch.float32)
+    marginal = torch.empty((G, V), device=logits.device, dtype=torch.float32)
+    perplexity = torch.empty((), device=logits.device, dtype=torch.float32)
+    _lib.call("cfm3_quantize_fwd_f32", logits.data_ptr(), _p(noise), cv.data_ptr(), _p(row_mask), N, G, V, dg, float(tau),
+              ws.data_ptr(), codes.data_ptr(), out.data_ptr(), marginal.data_ptr(), perplexity.data_ptr(), _stream())
+    return out, codes, perplexity, marginal, (logits, noise, cv, row_mask, codes, float(tau), ws)
+
+
+def quantize_backward(ctx, dout, dperplexity):
+    """(dlogits (N,G,V), dcodevectors (G*V,dg)) from the ctx of quantize_forward, dout (N,G*dg) and dperplexity () fp32."""
+    logits, noise, cv, row_mask, codes, tau, ws = ctx
+    if noise is None:
+        raise _lib.ConformerHipError("quantize: the eval path (noise=None) is not differentiable")
+    N, G, V = logits.shape
+    dg = cv.shape[1]
+    dout = _req(dout, "dout")
+    dperplexity = _req(dperplexity, "dperplexity")
+    if tuple(dout.shape) != (N, G * dg) or dperplexity.numel() != 1:
+        raise _lib.ConformerHipError(f"quantize: dout must be {(N, G * dg)} and dperplexity one element, got "
+                                     f"{tuple(dout.shape)}, {tuple(dperplexity.shape)}")
+    dlogits = torch.empty((N, G, V), device=logits.device, dtype=torch.float32)
+    dcv = torch.empty((G * V, dg), device=logits.device, dtype=torch.float32)
+    _lib.call("cfm3_quantize_bwd_f32", logits.data_ptr(), noise.data_ptr(), cv.data_ptr(), _p(row_mask), codes.data_ptr(),
+              dout.data_ptr(), dperplexity.data_ptr(), N, G, V, dg, tau, ws.data_ptr(), dlogits.data_ptr(), dcv.data_ptr(),
+              _stream())
+    return dlogits, dcv
+
+
+def _aligned16(t: torch.Tensor) -> torch.Tensor:
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+def contrastive_forward(context, targets, mask, negatives, ids=None, temperature: float = 0.1):
+    """The contrastive loss (cfm3_contrastive_fwd_f32): context, targets (B,T,D) fp32, mask (B,T) bool / uint8, negatives (B,T,K)
+    int32 frame indices inside the utterance (outside [0,T): absent), ids (B,T) int64 or None.  Returns (loss (), frame_loss
+    (B,T), n_correct () int32, correct (B,T) uint8, ctx); ctx carries p, the cosines and the norms for contrastive_backward."""
+    context = _aligned16(_req(context, "context"))
+    targets = _aligned16(_req(targets, "targets"))
+    negatives = _req(negatives, "negatives", torch.int32)
+    if context.dim() != 3 or targets.shape != context.shape or negatives.dim() != 3 or negatives.shape[:2] != context.shape[:2]:
+        raise _lib.ConformerHipError(f"contrastive: context and targets must be (B,T,D) and negatives (B,T,K), got "
+                                     f"{tuple(context.shape)}, {tuple(targets.shape)}, {tuple(negatives.shape)}")
+    B, T, D = context.shape
+    K = negatives.shape[2]
+    mask = _u8(mask, "mask", (B, T))
+    if ids is not None:
+        ids = _req(ids, "ids", torch.int64)
+        if tuple(ids.shape) != (B, T):
+            raise _lib.ConformerHipError(f"contrastive: ids must be {(B, T)}, got {tuple(ids.shape)}")
+    lib = _lib.load()
+    floats = int(lib.cfm3_contrastive_workspace_floats(B, T, K))
+    if floats < 0:
+        raise _lib.ConformerHipError(f"contrastive: (B,T,K) = {(B, T, K)} is not built (K from 1 to {PRETRAIN_LIMITS['K']}, "
+                                     "B*T*K < 2^31)")
+    ws = torch.empty(floats, device=context.device, dtype=torch.float32)
+    frame_loss = torch.empty((B, T), device=context.device, dtype=torch.float32)
+    correct = torch.empty((B, T), device=context.device, dtype=torch.uint8)
+    loss = torch.empty((), device=context.device, dtype=torch.float32)
+    n_correct = torch.empty((), device=context.device, dtype=torch.int32)
+    _lib.call("cfm3_contrastive_fwd_f32", context.data_ptr(), targets.data_ptr(), mask.data_ptr(), negatives.data_ptr(), _p(ids),
+              B, T, D, K, float(temperature), ws.data_ptr(), frame_loss.data_ptr(), correct.data_ptr(), loss.data_ptr(),
+              n_correct.data_ptr(), _stream())
+    return loss, frame_loss, n_correct, correct, (context, targets, mask, negatives, float(temperature), ws)
+
+
+def transposed_draws(negatives: torch.Tensor):
+    """The CSR list of the draws per frame drawn: (order (B*T*K) int64, start (B*T+1) int64).  A stable sort of the flat
+    negatives on the device, absent entries last; nothing is read back."""
+    B, T, K = negatives.shape
+    neg = negatives.long()
+    base = torch.arange(B, device=negatives.device, dtype=torch.int64)[:, None, None] * T
+    key = torch.where((neg >= 0) & (neg < T), base + neg, torch.full_like(neg, B * T)).reshape(-1)
+    skey, order = torch.sort(key, stable=True)
+    start = torch.searchsorted(skey, torch.arange(B * T + 1, device=negatives.device, dtype=torch.int64))
+    return order.contiguous(), start.contiguous()
+
+
+def contrastive_backward(ctx, gframe):
+    """(dcontext, dtargets), both (B,T,D), from the ctx of contrastive_forward and gframe (B,T) fp32 = d L / d frame_loss."""
+    context, targets, mask, negatives, temperature, ws = ctx
+    B, T, D = context.shape
+    K = negatives.shape[2]
+    gframe = _req(gframe, "gframe")
+    if tuple(gframe.shape) != (B, T):
+        raise _lib.ConformerHipError(f"contrastive: gframe must be {(B, T)}, got {tuple(gframe.shape)}")
+    order, start = transposed_draws(negatives)
+    dcontext = torch.empty((B, T, D), device=context.device, dtype=torch.float32)
+    dtargets = torch.empty((B, T, D), device=context.device, dtype=torch.float32)
+    _lib.call("cfm3_contrastive_bwd_f32", context.data_ptr(), targets.data_ptr(), mask.data_ptr(), negatives.data_ptr(),
+              order.data_ptr(), start.data_ptr(), gframe.data_ptr(), B, T, D, K, temperature, ws.data_ptr(), dcontext.data_ptr(),
+              dtargets.data_ptr(), _stream())
+    return dcontext, dtargets

@@ -21,8 +21,7 @@
 // batches, all key blocks) straight from the accumulators once a band tile is complete for its wave (a register carry
 // joins the two query tiles that touch the same 32 table rows; 134 MB per layer at cfg-2, issued behind the MFMAs).
 // D_i = dO_i.O_i is computed while the query tile is staged (no separate row-dot kernel, no qbias kernel).
-#include "cfm_common.h"
-#include <math.h>
+#include "attention_tile_f32.h"             // for_head_dim: the head-dimension ladder shared with the forward kernels
 
 namespace {
 
@@ -574,13 +573,9 @@ extern "C" int cfm_relpos_attention_bwd_f32(const float* q, const float* k, cons
                   B, T, H, dh, 1.0f / sqrtf((float)dh), drop_p, drop_seed, prec, g_atb_trace};
     const dim3 grid((unsigned)((T + 127) / 128), (unsigned)(B * H)), block(256);
     hipStream_t s = static_cast<hipStream_t>(stream);
-#define ATB_LAUNCH(NC, ND) hipLaunchKernelGGL((relpos_attn_bwd_kernel<NC, ND>), grid, block, 0, s, a)
-    if (dh <= 8) ATB_LAUNCH(1, 1);
-    else if (dh <= 16) ATB_LAUNCH(2, 1);
-    else if (dh <= 32) ATB_LAUNCH(4, 1);
-    else if (dh <= 40) ATB_LAUNCH(5, 2);
-    else ATB_LAUNCH(8, 2);
-#undef ATB_LAUNCH
+    attn_tile::for_head_dim(dh, [&](auto nc, auto nd) {
+        hipLaunchKernelGGL((relpos_attn_bwd_kernel<decltype(nc)::value, decltype(nd)::value>), grid, block, 0, s, a);
+    });
     return cfm_launch_status();
 }
 

@@ -21,13 +21,11 @@
 // conflict-free ds_read_b128 fragment reads.
 // Key-padding mask: keys >= lengths[b] are skipped entirely (identical to the reference's finfo.min fill because exp
 // underflows to exactly 0; lengths[b] <= 0 reproduces its uniform-softmax degenerate case).
-#include "cfm_common.h"
-#include <math.h>
-#include <type_traits>
+#include "attention_tile_f32.h"
 
 namespace {
 
-constexpr int KROW = 68;                 // padded LDS row (floats) of the K tile
+using namespace attn_tile;
 
 struct AttnArgs {
     const float* q; const float* k; const float* v; int64_t ld;
@@ -93,23 +91,16 @@ __global__ __launch_bounds__(64 * NW, 2) void relpos_attn_fwd_kernel(const AttnA
     const int i0 = q0 + wave * 32;
     const bool active = i0 < q_end;                                      // wave-uniform; idle waves still stage + barrier
     // SLOTS: compact row il = i (query) - q_begin of slot b; rows [q_end - q_begin, q_max) are zeros
-    [[maybe_unused]] auto zero_row = [&]() {
+    [[maybe_unused]] auto zero_fill = [&]() {
         if constexpr (SLOTS) {
             const int il = i0 + li - q_begin;
             if (il >= a.q_max) return;
-            float* orow = a.ctx + ((int64_t)b * a.q_max + il) * a.ldo + h * dh;
-#pragma unroll
-            for (int n = 0; n < ND; ++n)
-#pragma unroll
-                for (int gq = 0; gq < 4; ++gq) {
-                    const int dd = 32 * n + 8 * gq + 4 * hf;
-                    if (dd < dh) *reinterpret_cast<f32x4*>(orow + dd) = f32x4{0.f, 0.f, 0.f, 0.f};
-                }
+            zero_row<ND>(a.ctx + ((int64_t)b * a.q_max + il) * a.ldo + h * dh, dh, hf);
         }
     };
     if constexpr (SLOTS) {
         if (q0 >= q_end) {                                               // no query row of this slot here: Q / K / V unread
-            if (a.nsplit == 1) zero_row();
+            if (a.nsplit == 1) zero_fill();
             return;
         }
     }
@@ -150,14 +141,6 @@ __global__ __launch_bounds__(64 * NW, 2) void relpos_attn_fwd_kernel(const AttnA
             pv[p] = sok ? *reinterpret_cast<const f32x4*>(vbase + (int64_t)key * a.ld + sch * 4) : z;
         }
     };
-    auto commit = [&](int buf) {                                   // registers -> LDS buffer `buf`
-#pragma unroll
-        for (int p = 0; p < SP; ++p) {
-            const int r = srow + RPP * p;
-            *reinterpret_cast<f32x4*>(Ksb + buf * 32 * KROW + r * KROW + sch * 4) = pk[p];
-            *reinterpret_cast<f32x4*>(Vsb + buf * 32 * 64 + r * 64 + sch * 4) = pv[p];
-        }
-    };
     // NW = 8: the positional band as a RING of 32-row table blocks in LDS.  Wave w (queries q0 + 32w ..) needs, for key tile t,
     // table rows R0 + 32 (t - w) + (31 - li), R0 = T - 1 - q0: "block" t - w.  The 8 waves of a workgroup therefore read 8
     // CONSECUTIVE blocks, and a key tile brings in exactly ONE new block (32 rows x 256 B, one coalesced 16-byte load per thread,
@@ -180,7 +163,7 @@ __global__ __launch_bounds__(64 * NW, 2) void relpos_attn_fwd_kernel(const AttnA
         *reinterpret_cast<f32x4*>(ring + (ring_slot(blk) * 32 + srow) * KROW + sch * 4) = pr;
     };
     prefetch(kt_begin);
-    commit(0);
+    commit<RPP>(Ksb, Vsb, 0, srow, sch, pk, pv);
     if constexpr (NW == 8) {
         for (int blk = -8; blk <= 0; ++blk) { ring_load(blk); ring_commit(blk); }
     }
@@ -211,9 +194,7 @@ __global__ __launch_bounds__(64 * NW, 2) void relpos_attn_fwd_kernel(const AttnA
 
     f32x16 o[ND];
 #pragma unroll
-    for (int n = 0; n < ND; ++n)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) o[n][r] = 0.f;
+    for (int n = 0; n < ND; ++n) o[n] = zero_tile();
     float mrow = -INFINITY, lrow = 0.f;                              // running maximum in the log2 domain (scores * scale2), row sum
     const float scale2 = a.inv_sqrt_dh * 1.44269504088896340736f;
 
@@ -230,24 +211,8 @@ __global__ __launch_bounds__(64 * NW, 2) void relpos_attn_fwd_kernel(const AttnA
     // band tile mt of the key tile with base row jbase: table rows j = jbase - (32 mt + li), straight from global memory into the
     // A-operand layout (lane (row li, half hf) holds dims 8c + 4hf + e); rows outside the table belong to (query, key) pairs
     // that do not exist and read a clamped row
-    auto band_load = [&](int jbase, int mt, f32x4 (&pf)[NC]) {
-        const int j = max(0, min(jbase - (32 * mt + li), jmax));
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {                               // unconditional (clamped) loads + select: no branches, no drained waits
-            const f32x4 v = *reinterpret_cast<const f32x4*>(pbase + (int64_t)j * a.ldp + min(8 * c + 4 * hf, dh - 4));
-            pf[c] = 8 * c + 4 * hf < dh ? v : f32x4{0.f, 0.f, 0.f, 0.f};
-        }
-    };
-    auto band_mma = [&](const f32x4 (&pf)[NC]) {
-        f32x16 ga;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) ga[r] = 0.f;
-#pragma unroll
-        for (int c = 0; c < NC; ++c)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) ga = __builtin_amdgcn_mfma_f32_32x32x2f32(pf[c][e], qv[4 * c + e], ga, 0, 0, 0);
-        return ga;
-    };
+    auto band_load = [&](int jbase, int mt, f32x4 (&pf)[NC]) { attn_tile::band_load(pbase, a.ldp, jmax, dh, jbase, mt, li, hf, pf); };
+    auto band_mma = [&](const f32x4 (&pf)[NC]) { return attn_tile::band_mma(pf, qv); };
     // NW = 8: band tile of ring block `blk`: A-operand row li <-> block row 31 - li, fragments by ds_read_b128 (272-byte rows)
     [[maybe_unused]] auto band_mma_ring = [&](int blk) {
         const float* rp = ring + (ring_slot(blk) * 32 + (31 - li)) * KROW + 4 * hf;
@@ -267,20 +232,8 @@ __global__ __launch_bounds__(64 * NW, 2) void relpos_attn_fwd_kernel(const AttnA
         for (int r = 0; r < 16; ++r) ga[r] += gb[r];
         return ga;
     };
-    auto spill_band = [&](const f32x16& ga) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) gs[((r & 3) + 8 * (r >> 2) + 4 * hf) * 32 + li] = ga[r];
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    };
-    auto skew_reads = [&](float (&dst)[16]) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int jj = li - ((r & 3) + 8 * (r >> 2) + 4 * hf) + 31;     // 0..62
-            dst[r] = gs[(jj & 31) * 32 + li];
-        }
-    };
+    auto spill_band = [&](const f32x16& ga) { attn_tile::spill_band(gs, li, hf, ga); };
+    auto skew_reads = [&](float (&dst)[16]) { attn_tile::skew_reads(gs, li, hf, dst); };
     float skp[16];                                                   // band tile 1 of the current key tile, skewed (carried)
     f32x4 pf[NC];                                                    // table rows of a band tile in the A-operand layout
     if (active) {                                                    // first key tile: its band tile 1 is computed explicitly
@@ -293,8 +246,7 @@ __global__ __launch_bounds__(64 * NW, 2) void relpos_attn_fwd_kernel(const AttnA
         }
         spill_band(g1);
         skew_reads(skp);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");      // the reads have landed before the tile is rewritten
-        __builtin_amdgcn_wave_barrier();
+        skew_reads_done();
     }
     f32x16 sc;                                                       // content scores of the tile in flight (phase 1 -> phase 2)
 
@@ -306,9 +258,8 @@ __global__ __launch_bounds__(64 * NW, 2) void relpos_attn_fwd_kernel(const AttnA
         // the band tile's table rows land behind the content MFMAs.  (Requesting them a key tile ahead -- before P.V or right
         // after the band product -- was measured: the 32 extra live VGPRs spill at dh = 64 and the kernel is slower, 97 vs 80 us.)
         if constexpr (NW == 4) band_load(jbase, 0, pf);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) sc[r] = 0.f;
         if constexpr (NW == 8) {
+            sc = zero_tile();
             f32x16 sb;                                     // second accumulation chain (odd contraction steps)
 #pragma unroll
             for (int r = 0; r < 16; ++r) sb[r] = 0.f;
@@ -324,12 +275,7 @@ __global__ __launch_bounds__(64 * NW, 2) void relpos_attn_fwd_kernel(const AttnA
 #pragma unroll
             for (int r = 0; r < 16; ++r) sc[r] += sb[r];
         } else {
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            const f32x4 kf = *reinterpret_cast<const f32x4*>(Ks + li * KROW + 8 * c + 4 * hf);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) sc = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[e], qu[4 * c + e], sc, 0, 0, 0);
-        }
+            sc = lds_mma<NC>(Ks + li * KROW + 4 * hf, qu);
         }
         ATT_STAMP(2);
         if constexpr (NW == 8) {
@@ -348,16 +294,16 @@ __global__ __launch_bounds__(64 * NW, 2) void relpos_attn_fwd_kernel(const AttnA
         float skn[16];
         skew_reads(skn);
         ATT_STAMP(4);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();                        // the tile is rewritten by the next key tile
+        skew_reads_done();                                      // the tile is rewritten by the next key tile
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int jj = li - ((r & 3) + 8 * (r >> 2) + 4 * hf) + 31;
+            const int jj = li - acc_row(r, hf) + 31;
             sc[r] += (jj >> 5) ? skp[r] : skn[r];
             skp[r] = skn[r];
         }
         ATT_STAMP(5);
-        // scale + mask, online softmax (query = lane column; keys = registers x 2 halves)
+        // scale + mask, online softmax (query = lane column; keys = registers x 2 halves).  mnew is finite (key k0 < klen is always
+        // valid) and is subtracted as it is; the window kernel guards an all-masked row instead (msub): deliberately different.
         // (log2 domain: one multiply by inv_sqrt_dh * log2 e, v_exp_f32 directly; the key-padding selects run only in the tile that
         //  holds the end of the utterance -- the same arithmetic as the pipelined form below: results are bit-identical across forms)
         float p[16];
@@ -365,7 +311,7 @@ __global__ __launch_bounds__(64 * NW, 2) void relpos_attn_fwd_kernel(const AttnA
         if (uniform || k0 + 32 > klen) {                        // (wave-uniform)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int kk = (r & 3) + 8 * (r >> 2) + 4 * hf;
+                const int kk = acc_row(r, hf);
                 float s = sc[r] * scale2;
                 if (uniform) s = 0.f;
                 if (k0 + kk >= klen) s = -INFINITY;
@@ -376,8 +322,7 @@ __global__ __launch_bounds__(64 * NW, 2) void relpos_attn_fwd_kernel(const AttnA
 #pragma unroll
             for (int r = 0; r < 16; ++r) { p[r] = sc[r] * scale2; tmax = fmaxf(tmax, p[r]); }
         }
-        tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
-        const float mnew = fmaxf(mrow, tmax);                   // finite: key k0 (< klen) is always valid
+        const float mnew = running_max(mrow, tmax);                 // finite: key k0 (< klen) is always valid
         const float alpha = __builtin_amdgcn_exp2f(mrow - mnew);
         float psum = 0.f;
 #pragma unroll
@@ -397,10 +342,7 @@ __global__ __launch_bounds__(64 * NW, 2) void relpos_attn_fwd_kernel(const AttnA
                 for (int e = 0; e < 4; ++e) p[4 * q + e] *= keep[e];
             }
         }
-#pragma unroll
-        for (int n = 0; n < ND; ++n)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) o[n][r] *= alpha;
+        rescale(o, alpha);
         // O^T += V^T . P^T ; MFMA step s contracts key (s&3)+8*(s>>2)+4*hf = the key held in register s
 #pragma unroll
         for (int n = 0; n < ND; ++n)
@@ -420,7 +362,7 @@ __global__ __launch_bounds__(64 * NW, 2) void relpos_attn_fwd_kernel(const AttnA
             // stage the NEXT key tile into the other buffer (its last readers passed the barrier that ended tile kt-1), then
             // request the one after it
             if (kt + 1 < ntiles) {
-                commit(buf ^ 1);
+                commit<RPP>(Ksb, Vsb, buf ^ 1, srow, sch, pk, pv);
                 if (kt + 2 < ntiles) prefetch(kt + 2);
             }
             ATT_STAMP(1);
@@ -444,7 +386,7 @@ __global__ __launch_bounds__(64 * NW, 2) void relpos_attn_fwd_kernel(const AttnA
             if (iv & 1) {
                 const int j = (iv + 1) >> 1;                       // tile (relative) to stage now
                 if (j < nt) {
-                    commit(j & 1);
+                    commit<RPP>(Ksb, Vsb, j & 1, srow, sch, pk, pv);
                     ring_commit(j);
                     if (j + 1 < nt) {
                         prefetch(kt_begin + j + 1);
@@ -471,23 +413,14 @@ __global__ __launch_bounds__(64 * NW, 2) void relpos_attn_fwd_kernel(const AttnA
         float* orow = a.nsplit > 1 ? a.part_ctx + (((int64_t)split * a.B + b) * qc + il) * a.ldo + h * dh
                     : SLOTS        ? a.ctx + ((int64_t)b * qc + il) * a.ldo + h * dh
                                    : a.ctx + ((int64_t)b * T + i0 + li) * a.ldo + h * dh;
-#pragma unroll
-        for (int n = 0; n < ND; ++n)
-#pragma unroll
-            for (int gq = 0; gq < 4; ++gq) {
-                const int dd = 32 * n + 8 * gq + 4 * hf;
-                if (dd < dh) {
-                    f32x4 out = {o[n][4 * gq] * inv, o[n][4 * gq + 1] * inv, o[n][4 * gq + 2] * inv, o[n][4 * gq + 3] * inv};
-                    *reinterpret_cast<f32x4*>(orow + dd) = out;
-                }
-            }
+        store_row(orow, dh, hf, o, inv);
         if (a.nsplit > 1) {
             if (hf == 0) a.part_lse[(((int64_t)split * a.B + b) * a.H + h) * qc + il] = mrow * 0.69314718055994530942f + logf(lrow);
         } else if (a.lse && hf == 0) {
             a.lse[((int64_t)b * a.H + h) * T + i0 + li] = mrow * 0.69314718055994530942f + logf(lrow);
         }
     } else if constexpr (SLOTS) {
-        if (a.nsplit == 1) zero_row();
+        if (a.nsplit == 1) zero_fill();
     }
     if (tracer) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -575,43 +508,17 @@ __global__ __launch_bounds__(512, 2) void relpos_attn_fwd8p_kernel(const AttnArg
     }
     f32x16 o[ND];
 #pragma unroll
-    for (int n = 0; n < ND; ++n)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) o[n][r] = 0.f;
+    for (int n = 0; n < ND; ++n) o[n] = zero_tile();
     float mrow = -INFINITY, lrow = 0.f;                              // running maximum in the log2 domain (scores * scale2), row sum
     const float scale2 = a.inv_sqrt_dh * 1.44269504088896340736f;
 
     // products of key tile kt: content scores S^T[key][query] from K buffer kt & 1, band tile of ring block blk (A-operand row li <->
     // block row 31 - li)
-    auto content = [&](int kt) {
-        const float* Ks = Ksb + (kt & 1) * 32 * KROW + li * KROW + 4 * hf;
-        f32x16 acc;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            const f32x4 kf = *reinterpret_cast<const f32x4*>(Ks + 8 * c);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[e], qu[4 * c + e], acc, 0, 0, 0);
-        }
-        return acc;
-    };
-    auto band = [&](int blk) {
-        const float* rp = ring + (ring_slot(blk) * 32 + (31 - li)) * KROW + 4 * hf;
-        f32x16 acc;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            const f32x4 f = *reinterpret_cast<const f32x4*>(rp + 8 * c);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(f[e], qv[4 * c + e], acc, 0, 0, 0);
-        }
-        return acc;
-    };
+    auto content = [&](int kt) { return lds_mma<NC>(Ksb + (kt & 1) * 32 * KROW + li * KROW + 4 * hf, qu); };
+    auto band = [&](int blk) { return lds_mma<NC>(ring + (ring_slot(blk) * 32 + (31 - li)) * KROW + 4 * hf, qv); };
     auto spill_band = [&](const f32x16& ga) {
 #pragma unroll
-        for (int r = 0; r < 16; ++r) gs[((r & 3) + 8 * (r >> 2) + 4 * hf) * 32 + li] = ga[r];
+        for (int r = 0; r < 16; ++r) gs[acc_row(r, hf) * 32 + li] = ga[r];
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -619,7 +526,7 @@ __global__ __launch_bounds__(512, 2) void relpos_attn_fwd8p_kernel(const AttnArg
     auto skew_reads = [&](float (&dst)[16]) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int jj = li - ((r & 3) + 8 * (r >> 2) + 4 * hf) + 31;     // 0..62
+            const int jj = li - acc_row(r, hf) + 31;     // 0..62
             dst[r] = gs[(jj & 31) * 32 + li];
         }
     };
@@ -627,7 +534,7 @@ __global__ __launch_bounds__(512, 2) void relpos_attn_fwd8p_kernel(const AttnArg
     auto shift_add = [&](f32x16& sn, float (&skp)[16], const float (&skn)[16]) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int jj = li - ((r & 3) + 8 * (r >> 2) + 4 * hf) + 31;
+            const int jj = li - acc_row(r, hf) + 31;
             sn[r] += (jj >> 5) ? skp[r] : skn[r];
             skp[r] = skn[r];
         }
@@ -641,16 +548,14 @@ __global__ __launch_bounds__(512, 2) void relpos_attn_fwd8p_kernel(const AttnArg
             const f32x16 g1 = band(-wave - 1);
             spill_band(g1);
             skew_reads(skp);
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
+            skew_reads_done();
         }
         sc = content(0);
         const f32x16 g0 = band(-wave);
         spill_band(g0);
         float skn[16];
         skew_reads(skn);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
+        skew_reads_done();
         shift_add(sc, skp, skn);
     }
     __syncthreads();                   // iteration 0 overwrites K buffer 0 (K(0)) and ring slot 2 (block -8), both read just above
@@ -675,7 +580,7 @@ __global__ __launch_bounds__(512, 2) void relpos_attn_fwd8p_kernel(const AttnArg
             if (uniform || k0 + 32 > klen) {                        // (wave-uniform) the last key tile, or an all-masked utterance
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int kk = (r & 3) + 8 * (r >> 2) + 4 * hf;
+                    const int kk = acc_row(r, hf);
                     float sv = sc[r] * scale2;
                     if (uniform) sv = 0.f;
                     if (k0 + kk >= klen) sv = -INFINITY;
@@ -686,8 +591,7 @@ __global__ __launch_bounds__(512, 2) void relpos_attn_fwd8p_kernel(const AttnArg
 #pragma unroll
                 for (int r = 0; r < 16; ++r) { p[r] = sc[r] * scale2; tmax = fmaxf(tmax, p[r]); }
             }
-            tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
-            const float mnew = fmaxf(mrow, tmax);                   // finite: key k0 (< klen) is always valid
+            const float mnew = running_max(mrow, tmax);                 // finite: key k0 (< klen) is always valid
             const float alpha = __builtin_amdgcn_exp2f(mrow - mnew);
             float psum = 0.f;
 #pragma unroll
@@ -711,8 +615,7 @@ __global__ __launch_bounds__(512, 2) void relpos_attn_fwd8p_kernel(const AttnArg
                     const float vv = Vs[((s & 3) + 8 * (s >> 2) + 4 * hf) * 64 + ((32 * n + li) & 63)];
                     o[n] = __builtin_amdgcn_mfma_f32_32x32x2f32(vv, p[s], o[n], 0, 0, 0);
                 }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // the skew reads have landed before the tile is rewritten
-            __builtin_amdgcn_wave_barrier();
+            skew_reads_done();                                      // before the tile is rewritten
             shift_add(sn, skp, skn);
             sc = sn;
         }
@@ -723,16 +626,7 @@ __global__ __launch_bounds__(512, 2) void relpos_attn_fwd8p_kernel(const AttnArg
     if (active && i0 + li < a.q_end) {
         const float inv = 1.0f / lrow;
         float* orow = a.ctx + ((int64_t)b * T + i0 + li) * a.ldo + h * dh;
-#pragma unroll
-        for (int n = 0; n < ND; ++n)
-#pragma unroll
-            for (int gq = 0; gq < 4; ++gq) {
-                const int dd = 32 * n + 8 * gq + 4 * hf;
-                if (dd < dh) {
-                    f32x4 out = {o[n][4 * gq] * inv, o[n][4 * gq + 1] * inv, o[n][4 * gq + 2] * inv, o[n][4 * gq + 3] * inv};
-                    *reinterpret_cast<f32x4*>(orow + dd) = out;
-                }
-            }
+        store_row(orow, dh, hf, o, inv);
         if (a.lse && hf == 0) a.lse[((int64_t)b * a.H + h) * T + i0 + li] = mrow * 0.69314718055994530942f + logf(lrow);
     }
 }
@@ -872,24 +766,17 @@ static int attention_launch(const float* q, const float* k, const float* v, int6
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (nw == 9) {
         const dim3 grid9((unsigned)((q_count + 255) / 256), (unsigned)(B * H)), block9(512);
-#define ATT_LAUNCH9(NC, ND) hipLaunchKernelGGL((relpos_attn_fwd8p_kernel<NC, ND>), grid9, block9, 0, s, a)
-        if (dh <= 8) ATT_LAUNCH9(1, 1);
-        else if (dh <= 16) ATT_LAUNCH9(2, 1);
-        else if (dh <= 32) ATT_LAUNCH9(4, 1);
-        else if (dh <= 40) ATT_LAUNCH9(5, 2);
-        else ATT_LAUNCH9(8, 2);
-#undef ATT_LAUNCH9
+        for_head_dim(dh, [&](auto nc, auto nd) {
+            hipLaunchKernelGGL((relpos_attn_fwd8p_kernel<decltype(nc)::value, decltype(nd)::value>), grid9, block9, 0, s, a);
+        });
         return cfm_launch_status();
     }
     const dim3 grid((unsigned)((q_count + 32 * nw - 1) / (32 * nw)) * nsplit, (unsigned)(B * H)), block(64 * nw);
-#define ATT_LAUNCH(NC, ND) do { if (nw == 8) hipLaunchKernelGGL((relpos_attn_fwd_kernel<NC, ND, 8>), grid, block, 0, s, a); \
-                                else hipLaunchKernelGGL((relpos_attn_fwd_kernel<NC, ND, 4>), grid, block, 0, s, a); } while (0)
-    if (dh <= 8) ATT_LAUNCH(1, 1);
-    else if (dh <= 16) ATT_LAUNCH(2, 1);
-    else if (dh <= 32) ATT_LAUNCH(4, 1);
-    else if (dh <= 40) ATT_LAUNCH(5, 2);
-    else ATT_LAUNCH(8, 2);
-#undef ATT_LAUNCH
+    for_head_dim(dh, [&](auto nc, auto nd) {
+        constexpr int NC = decltype(nc)::value, ND = decltype(nd)::value;
+        if (nw == 8) hipLaunchKernelGGL((relpos_attn_fwd_kernel<NC, ND, 8>), grid, block, 0, s, a);
+        else hipLaunchKernelGGL((relpos_attn_fwd_kernel<NC, ND, 4>), grid, block, 0, s, a);
+    });
     if (nsplit > 1) {
         const int64_t total = (int64_t)B * q_count * H * (dh / 4);
         hipLaunchKernelGGL(attn_merge_splits_kernel<false>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, a);
@@ -929,14 +816,11 @@ extern "C" int cfm_relpos_attention_slots_f32(const float* q, const float* k, co
              : ((q_max > 128 && nsplit == 1) ? 8 : 4);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const dim3 grid((unsigned)((q_max + 32 * nw - 1) / (32 * nw)) * nsplit, (unsigned)(B * H)), block(64 * nw);
-#define ATT_LAUNCH(NC, ND) do { if (nw == 8) hipLaunchKernelGGL((relpos_attn_fwd_kernel<NC, ND, 8, true>), grid, block, 0, s, a); \
-                                else hipLaunchKernelGGL((relpos_attn_fwd_kernel<NC, ND, 4, true>), grid, block, 0, s, a); } while (0)
-    if (dh <= 8) ATT_LAUNCH(1, 1);
-    else if (dh <= 16) ATT_LAUNCH(2, 1);
-    else if (dh <= 32) ATT_LAUNCH(4, 1);
-    else if (dh <= 40) ATT_LAUNCH(5, 2);
-    else ATT_LAUNCH(8, 2);
-#undef ATT_LAUNCH
+    for_head_dim(dh, [&](auto nc, auto nd) {
+        constexpr int NC = decltype(nc)::value, ND = decltype(nd)::value;
+        if (nw == 8) hipLaunchKernelGGL((relpos_attn_fwd_kernel<NC, ND, 8, true>), grid, block, 0, s, a);
+        else hipLaunchKernelGGL((relpos_attn_fwd_kernel<NC, ND, 4, true>), grid, block, 0, s, a);
+    });
     if (nsplit > 1) {
         const int64_t total = (int64_t)B * q_max * H * (dh / 4);
         hipLaunchKernelGGL(attn_merge_splits_kernel<true>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, a);

@@ -15,13 +15,12 @@
 //   * Ring rows outside [cmin, cend) hold an older part of the stream or another stream: they are never loaded -- the staging
 //     selects zeros for them -- and masked keys inside the range are selected away before the exponential, so no bit pattern of a
 //     masked row reaches a result.
-#include "cfm_common.h"
+#include "attention_tile_f32.h"
 #include "../../include/conformer_hip_window.h"
-#include <math.h>
 
 namespace {
 
-constexpr int KROW = 68;                 // padded LDS row (floats) of the K tile: conflict-free ds_read_b128 fragment reads
+using namespace attn_tile;
 
 struct WinArgs {
     const float* q; const float* k; const float* v; int64_t ld;
@@ -48,20 +47,13 @@ __global__ __launch_bounds__(256, 2) void relpos_attn_window_kernel(const WinArg
     const int q0 = (int)blockIdx.x * 32 * NW;
     const int i0 = q0 + wave * 32;
     const bool active = i0 < qn;                                         // wave-uniform; idle waves still stage + barrier
-    auto zero_row = [&]() {                                              // compact rows [qn, q_max) are zeros
+    auto zero_fill = [&]() {                                             // compact rows [qn, q_max) are zeros
         const int il = i0 + li;
         if (il >= a.q_max) return;
-        float* orow = a.ctx + ((int64_t)b * a.q_max + il) * a.ldo + h * dh;
-#pragma unroll
-        for (int n = 0; n < ND; ++n)
-#pragma unroll
-            for (int gq = 0; gq < 4; ++gq) {
-                const int dd = 32 * n + 8 * gq + 4 * hf;
-                if (dd < dh) *reinterpret_cast<f32x4*>(orow + dd) = f32x4{0.f, 0.f, 0.f, 0.f};
-            }
+        zero_row<ND>(a.ctx + ((int64_t)b * a.q_max + il) * a.ldo + h * dh, dh, hf);
     };
     if (q0 >= qn) {                                                      // no query row of this slot here: Q / K / V unread
-        zero_row();
+        zero_fill();
         return;
     }
     const int cmin = (int)max((int64_t)0, (int64_t)left - qb);           // local index of frame 0, or 0: <= left
@@ -96,16 +88,8 @@ __global__ __launch_bounds__(256, 2) void relpos_attn_window_kernel(const WinArg
             pv[p] = ok ? *reinterpret_cast<const f32x4*>(vbase + row * a.ld + sch * 4) : z;
         }
     };
-    auto commit = [&](int buf) {                                   // registers -> LDS buffer `buf`
-#pragma unroll
-        for (int p = 0; p < SP; ++p) {
-            const int r = srow + RPP * p;
-            *reinterpret_cast<f32x4*>(Ksb + buf * 32 * KROW + r * KROW + sch * 4) = pk[p];
-            *reinterpret_cast<f32x4*>(Vsb + buf * 32 * 64 + r * 64 + sch * 4) = pv[p];
-        }
-    };
     prefetch(kt_begin);
-    commit(0);
+    commit<RPP>(Ksb, Vsb, 0, srow, sch, pk, pv);
     if (kt_begin + 1 < ntiles) prefetch(kt_begin + 1);
     __syncthreads();
 
@@ -130,9 +114,7 @@ __global__ __launch_bounds__(256, 2) void relpos_attn_window_kernel(const WinArg
 
     f32x16 o[ND];
 #pragma unroll
-    for (int n = 0; n < ND; ++n)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) o[n][r] = 0.f;
+    for (int n = 0; n < ND; ++n) o[n] = zero_tile();
     float mrow = -INFINITY, lrow = 0.f;                              // running maximum in the log2 domain (scores * scale2), row sum
     const float scale2 = a.inv_sqrt_dh * 1.44269504088896340736f;
 
@@ -140,48 +122,14 @@ __global__ __launch_bounds__(256, 2) void relpos_attn_window_kernel(const WinArg
     // relative shift as a per-lane column skew through the per-wave LDS tile; band tile 1 of key tile kt+1 is band tile 0 of key
     // tile kt, carried in registers (skp) -- see attention_f32.hip.  Table rows outside [0, 2P-2] belong to pairs outside every
     // window (r > left or r <= -q_max) and read a clamped row.
-    auto band_load = [&](int jbase, int mt, f32x4 (&pf)[NC]) {
-        const int j = max(0, min(jbase - (32 * mt + li), jmax));
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            const f32x4 v = *reinterpret_cast<const f32x4*>(pbase + (int64_t)j * a.ldp + min(8 * c + 4 * hf, dh - 4));
-            pf[c] = 8 * c + 4 * hf < dh ? v : f32x4{0.f, 0.f, 0.f, 0.f};
-        }
-    };
-    auto band_mma = [&](const f32x4 (&pf)[NC]) {
-        f32x16 ga;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) ga[r] = 0.f;
-#pragma unroll
-        for (int c = 0; c < NC; ++c)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) ga = __builtin_amdgcn_mfma_f32_32x32x2f32(pf[c][e], qv[4 * c + e], ga, 0, 0, 0);
-        return ga;
-    };
-    auto spill_band = [&](const f32x16& ga) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) gs[((r & 3) + 8 * (r >> 2) + 4 * hf) * 32 + li] = ga[r];
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    };
-    auto skew_reads = [&](float (&dst)[16]) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int jj = li - ((r & 3) + 8 * (r >> 2) + 4 * hf) + 31;     // 0..62
-            dst[r] = gs[(jj & 31) * 32 + li];
-        }
-    };
     const int jq = P - 1 - (i0 + left) + 31;                         // jbase of key tile kt: jq + 32 kt
     float skp[16];                                                   // band tile 1 of the current key tile, skewed (carried)
     f32x4 pf[NC];                                                    // table rows of a band tile in the A-operand layout
     if (active) {                                                    // the wave's first key tile: its band tile 1, explicitly
-        band_load(jq + 32 * kt_w, 1, pf);
-        const f32x16 g1 = band_mma(pf);
-        spill_band(g1);
-        skew_reads(skp);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");      // the reads have landed before the tile is rewritten
-        __builtin_amdgcn_wave_barrier();
+        band_load(pbase, a.ldp, jmax, dh, jq + 32 * kt_w, 1, li, hf, pf);
+        spill_band(gs, li, hf, band_mma(pf, qv));
+        skew_reads(gs, li, hf, skp);
+        skew_reads_done();
     }
     const int lo = max(i0 + li, cmin);                               // this lane's query sees the local keys [lo, cend)
     const int lo_wave = max(i0 + 31, cmin);                          // the largest lower bound in the wave
@@ -191,36 +139,24 @@ __global__ __launch_bounds__(256, 2) void relpos_attn_window_kernel(const WinArg
         // stage the NEXT key tile into the other buffer (its last readers passed the barrier that ended tile kt-1), then
         // request the one after it
         if (kt + 1 < ntiles) {
-            commit(buf ^ 1);
+            commit<RPP>(Ksb, Vsb, buf ^ 1, srow, sch, pk, pv);
             if (kt + 2 < ntiles) prefetch(kt + 2);
         }
         if (active && kt >= kt_w) {
             const int k0 = kt * 32;
             // ---- phase 1: content scores S^T[key][query] and band tile 0, spilled to the wave's skew tile
             const float* Ks = Ksb + buf * 32 * KROW;
-            band_load(jq + k0, 0, pf);
-            f32x16 sc;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) sc[r] = 0.f;
-#pragma unroll
-            for (int c = 0; c < NC; ++c) {
-                const f32x4 kf = *reinterpret_cast<const f32x4*>(Ks + li * KROW + 8 * c + 4 * hf);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) sc = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[e], qu[4 * c + e], sc, 0, 0, 0);
-            }
-            {
-                const f32x16 g0 = band_mma(pf);
-                spill_band(g0);
-            }
+            band_load(pbase, a.ldp, jmax, dh, jq + k0, 0, li, hf, pf);
+            f32x16 sc = lds_mma<NC>(Ks + li * KROW + 4 * hf, qu);
+            spill_band(gs, li, hf, band_mma(pf, qv));
             // ---- phase 2: relative shift, scale + window mask, online softmax, O^T += V^T . P^T
             const float* Vs = Vsb + buf * 32 * 64;
             float skn[16];
-            skew_reads(skn);
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();                        // the tile is rewritten by the next key tile
+            skew_reads(gs, li, hf, skn);
+            skew_reads_done();                                      // the tile is rewritten by the next key tile
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int jj = li - ((r & 3) + 8 * (r >> 2) + 4 * hf) + 31;
+                const int jj = li - acc_row(r, hf) + 31;
                 sc[r] += (jj >> 5) ? skp[r] : skn[r];
                 skp[r] = skn[r];
             }
@@ -229,7 +165,7 @@ __global__ __launch_bounds__(256, 2) void relpos_attn_window_kernel(const WinArg
             if (k0 < lo_wave || k0 + 32 > cend) {                   // (wave-uniform) a tile that holds an edge of some row's window
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int c = k0 + (r & 3) + 8 * (r >> 2) + 4 * hf;
+                    const int c = k0 + acc_row(r, hf);
                     const float s = (c >= lo && c < cend) ? sc[r] * scale2 : -INFINITY;     // a select: masked scores are never used
                     p[r] = s;
                     tmax = fmaxf(tmax, s);
@@ -238,9 +174,10 @@ __global__ __launch_bounds__(256, 2) void relpos_attn_window_kernel(const WinArg
 #pragma unroll
                 for (int r = 0; r < 16; ++r) { p[r] = sc[r] * scale2; tmax = fmaxf(tmax, p[r]); }
             }
-            tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
-            const float mnew = fmaxf(mrow, tmax);
+            const float mnew = running_max(mrow, tmax);
             // a row that has seen no key yet (only rows past the slot's count) keeps m = -inf: subtract 0, so alpha = p = 0, no NaN
+            // (deliberately not the full-context kernels' arithmetic: they subtract mnew itself, their first key tile always holds a
+            //  valid key.  The update below is otherwise theirs, written out here: see attention_tile_f32.h for why)
             const float msub = mnew == -INFINITY ? 0.f : mnew;
             const float alpha = __builtin_amdgcn_exp2f(mrow - msub);
             float psum = 0.f;
@@ -249,10 +186,7 @@ __global__ __launch_bounds__(256, 2) void relpos_attn_window_kernel(const WinArg
             psum += __shfl_xor(psum, 32, 64);
             lrow = lrow * alpha + psum;
             mrow = mnew;
-#pragma unroll
-            for (int n = 0; n < ND; ++n)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) o[n][r] *= alpha;
+            rescale(o, alpha);
             // O^T += V^T . P^T ; MFMA step s contracts key (s&3)+8*(s>>2)+4*hf = the key held in register s
 #pragma unroll
             for (int n = 0; n < ND; ++n)
@@ -281,7 +215,7 @@ __global__ __launch_bounds__(256, 2) void relpos_attn_window_kernel(const WinArg
                 }
             }
     } else {
-        zero_row();
+        zero_fill();
     }
 }
 
@@ -305,12 +239,8 @@ extern "C" int cfm_relpos_attention_window_f32(const float* q, const float* k, c
                     1.0f / sqrtf((float)dh)};
     hipStream_t s = static_cast<hipStream_t>(stream);
     const dim3 grid((unsigned)((q_max + 127) / 128), (unsigned)(B * H)), block(256);
-#define WIN_LAUNCH(NC, ND) hipLaunchKernelGGL((relpos_attn_window_kernel<NC, ND>), grid, block, 0, s, a)
-    if (dh <= 8) WIN_LAUNCH(1, 1);
-    else if (dh <= 16) WIN_LAUNCH(2, 1);
-    else if (dh <= 32) WIN_LAUNCH(4, 1);
-    else if (dh <= 40) WIN_LAUNCH(5, 2);
-    else WIN_LAUNCH(8, 2);
-#undef WIN_LAUNCH
+    for_head_dim(dh, [&](auto nc, auto nd) {
+        hipLaunchKernelGGL((relpos_attn_window_kernel<decltype(nc)::value, decltype(nd)::value>), grid, block, 0, s, a);
+    });
     return cfm_launch_status();
 }

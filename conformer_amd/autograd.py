@@ -373,3 +373,36 @@ class ContrastiveLossFn(Function):
         gframe = (dframe.float() + dloss.float()).contiguous()
         dcontext, dtargets = ops.contrastive_backward(ctx.state, gframe)
         return dcontext, dtargets, None, None, None, None
+
+
+class RnntLossFn(Function):
+    """nll (B) float64 of the transducer loss over the joint's logits (B,T,U1,V) (csrc/rnnt.hip).  Forward: one pass over the
+    logits (log-sum-exp, blank and label log-probabilities per lattice cell) and the alpha and beta lattices in float64;
+    backward: one pass that writes the logits gradient, weighted per utterance by grad (B).  The workspace is allocated once in
+    forward and kept in ctx."""
+
+    @staticmethod
+    def forward(ctx, logits, targets, in_len, tg_len, blank):
+        nll, state = ops.rnnt_loss_forward(logits, targets, in_len, tg_len, blank)
+        ctx.state = state
+        return nll
+
+    @staticmethod
+    def backward(ctx, grad):
+        return ops.rnnt_loss_backward(ctx.state, grad.float().contiguous()), None, None, None, None
+
+
+class RnntJointFn(Function):
+    """h (B,T,U1,J) = tanh(e[:, :, None] + p[:, None]) of the transducer's joint network (csrc/rnnt.hip); backward: de and dp as
+    fixed-order sums of dh (1 - h^2) over u and over t."""
+
+    @staticmethod
+    def forward(ctx, e, p):
+        h = ops.rnnt_joint_forward(e, p)
+        ctx.save_for_backward(h)
+        return h
+
+    @staticmethod
+    def backward(ctx, dh):
+        (h,) = ctx.saved_tensors
+        return ops.rnnt_joint_backward(h, dh.contiguous())

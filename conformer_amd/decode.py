@@ -59,6 +59,58 @@ def tokens_to_text(tokens: torch.Tensor, counts: torch.Tensor, vocab: Sequence[s
     return ["".join(vocab[i] for i in row[:n]).replace(delim_token, " ") for row, n in zip(tk, ct)]
 
 
+RNNT_SYNC_EVERY = 64      # iterations between two host reads of the device's `active` counter: the fastest of 4 / 16 / 64 in
+                          # profiles/rnnt_bench.json
+
+
+@torch.no_grad()
+def rnnt_greedy_decode(predictor, joiner, enc: torch.Tensor, enc_len: Optional[torch.Tensor] = None, max_symbols: int = 10,
+                       sync_every: int = RNNT_SYNC_EVERY) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Time-synchronous greedy transducer decode (INTEGRATION.md "Transducer (RNN-T)") of the encoder output enc (B,T,d) with
+    lengths enc_len (B) through a Predictor and a Joiner (model/modules/transducer.py).  Returns (tokens (B, T * max_symbols)
+    int64 padded with -1, counts (B) int64, frames (B, T * max_symbols) int64: the frame each token was emitted at).
+
+    At most max_symbols tokens are emitted per frame.  The loop runs on the device: per iteration one decision per utterance
+    (joint at the utterance's frame, argmax, emit or advance) and one predictor step whose state is kept where a token was
+    emitted.  The host reads the device's count of unfinished utterances once per sync_every iterations and stops
+    unconditionally after T * (max_symbols + 1), the most any utterance can need."""
+    if int(max_symbols) < 1 or int(sync_every) < 1:
+        raise ValueError(f"rnnt_greedy_decode: max_symbols and sync_every must be at least 1, got {max_symbols}, {sync_every}")
+    enc = ops._req(enc if enc.dtype == torch.float32 else enc.float(), "enc")
+    B, T, _ = enc.shape
+    dev = enc.device
+    if enc_len is None:
+        in_len = torch.full((B,), T, dtype=torch.int64, device=dev)
+    else:
+        in_len = ops._req(torch.as_tensor(enc_len).to(dev), "enc_len", torch.int64)
+    blank, cap = predictor.blank_id, T * int(max_symbols)
+    tokens = torch.full((B, cap), -1, dtype=torch.int64, device=dev)
+    frames = torch.full((B, cap), -1, dtype=torch.int64, device=dev)
+    count = torch.zeros((B,), dtype=torch.int64, device=dev)
+    t = torch.zeros((B,), dtype=torch.int64, device=dev)
+    nsym = torch.zeros((B,), dtype=torch.int64, device=dev)
+    last = torch.full((B,), blank, dtype=torch.int64, device=dev)
+    emit = torch.zeros((B,), dtype=torch.int32, device=dev)
+    active = torch.zeros((1,), dtype=torch.int32, device=dev)
+    e = ops.linear(enc, joiner.enc_proj.weight.detach(), joiner.enc_proj.bias.detach())       # once, before the loop
+    w_p, b_p = joiner.pred_proj.weight.detach(), joiner.pred_proj.bias.detach()
+    biases = predictor.fused_biases()
+    state = predictor.init_state(B)
+    predictor.step(last, state, biases)                                     # the state after consuming blank
+    cand = torch.empty(tuple(state.shape), dtype=torch.float32, device=dev)
+    top = state[state.shape[0] - 2]                                         # the top layer's hidden plane (B,H), a view
+    for it in range(T * (int(max_symbols) + 1)):
+        p = ops.linear(top[:, None, :], w_p, b_p)                           # (B,1,J)
+        logits = joiner.combine(e, p, frames=t)                             # (B,1,1,V) at each utterance's own frame
+        ops.rnnt_greedy_decide(logits.view(B, -1), in_len, T, blank, max_symbols, tokens, frames, count, last, t, nsym, emit)
+        cand.copy_(state)
+        predictor.step(last, cand, biases)                                  # the candidate: one step on `last`
+        ops.rnnt_greedy_commit(cand, state, emit, t, in_len, T, active)     # kept where a token was emitted
+        if (it + 1) % int(sync_every) == 0 and int(active) == 0:
+            break
+    return tokens, count, frames
+
+
 class _Fusion:
     """The fusion group of a search: the device tables of the language model and of the hotwords (None: not used) and the
     knobs.  `args` is the group as the C entries take it (lm_tables, alpha, beta, unk_score_offset, score_boundary, hw_tables,

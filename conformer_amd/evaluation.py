@@ -83,6 +83,23 @@ class ConformerCriterion:
             loss = loss + float(ctc_weight) * self.ctc_loss(outputs, targets, input_lengths, target_lengths)
         return loss
 
+    def rnnt_loss(self, outputs: torch.Tensor, targets: Optional[torch.Tensor], input_lengths: torch.Tensor,
+                  target_lengths: torch.Tensor, reduction: str = "mean") -> torch.Tensor:
+        """The transducer loss (INTEGRATION.md "Transducer (RNN-T)"): outputs are the joint's logits (B,T',U1,V) as
+        ConformerTransducer.forward returns them (any float dtype; computed in fp32) on the HIP device (no CPU fallback); targets
+        (B,U1-1) padded (None when U1 == 1); lengths (B).  blank_id is the blank.  "none": nll (B) float64, +inf for an utterance
+        without a frame; "sum": the sum of the finite nll; "mean": that sum divided by B."""
+        if not isinstance(outputs, torch.Tensor) or not outputs.is_cuda:
+            raise RuntimeError("ConformerCriterion.rnnt_loss: logits must be on the HIP device (no CPU fallback)")
+        if reduction not in ("mean", "sum", "none"):
+            raise ValueError(f"ConformerCriterion.rnnt_loss: reduction must be 'mean', 'sum' or 'none', got {reduction!r}")
+        tg = None if targets is None else targets.long().to(outputs.device)
+        nll = ag.RnntLossFn.apply(outputs.float(), tg, input_lengths, target_lengths, self.blank_id)
+        if reduction == "none":
+            return nll
+        total = nll.masked_fill(~torch.isfinite(nll), 0.0).sum()
+        return total / nll.shape[0] if reduction == "mean" else total
+
     def pretrain_loss(self, context: torch.Tensor, target: torch.Tensor, perplexity: torch.Tensor, mask_indexes: torch.Tensor,
                       codes: Optional[torch.Tensor] = None, num_negatives: int = 100, temperature: float = 0.1,
                       diversity_weight: float = 0.1, generator: Optional[torch.Generator] = None, *,

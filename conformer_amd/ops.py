@@ -1783,3 +1783,112 @@ def contrastive_backward(ctx, gframe):
               order.data_ptr(), start.data_ptr(), gframe.data_ptr(), B, T, D, K, temperature, ws.data_ptr(), dcontext.data_ptr(),
               dtargets.data_ptr(), _stream())
     return dcontext, dtargets
+
+
+# ---- the transducer (conformer_hip3_rnnt.h): RNN-T loss, the joint's combine, the greedy decode's bookkeeping -------------------
+RNNT_MAX_U1 = _lib.OPEN_CONSTANTS["conformer_hip3_rnnt.h"]["CFM3_RNNT_MAX_U1"]
+
+
+def rnnt_loss_forward(logits, targets, in_len, tg_len, blank: int = 0):
+    """The transducer negative log-likelihood of every utterance: logits (B,T,U1,V) fp32 (the joint's output), targets (B,U1-1)
+    int64 padded (None when U1 == 1), in_len and tg_len (B) int64.  Returns (nll (B) float64, +inf for an utterance without a
+    frame; ctx); ctx carries the lattice workspace for rnnt_loss_backward."""
+    logits = _req(logits, "logits")
+    if logits.dim() != 4:
+        raise _lib.ConformerHipError(f"rnnt_loss: logits must be (B,T,U1,V), got {tuple(logits.shape)}")
+    B, T, U1, V = logits.shape
+    if not 1 <= U1 <= RNNT_MAX_U1:
+        raise NotImplementedError(f"rnnt_loss: a lattice of {U1} label positions is not built (1 to {RNNT_MAX_U1})")
+    if targets is None and U1 != 1:
+        raise _lib.ConformerHipError(f"rnnt_loss: targets may be None only when U1 == 1, got U1 = {U1}")
+    if targets is not None:
+        targets = _req(targets, "targets", torch.int64)
+        if tuple(targets.shape) != (B, U1 - 1):
+            raise _lib.ConformerHipError(f"rnnt_loss: targets must be {(B, U1 - 1)}, got {tuple(targets.shape)}")
+    in_len = _req(torch.as_tensor(in_len).to(logits.device), "in_len", torch.int64)
+    tg_len = _req(torch.as_tensor(tg_len).to(logits.device), "tg_len", torch.int64)
+    if in_len.numel() != B or tg_len.numel() != B:
+        raise _lib.ConformerHipError("rnnt_loss: in_len / tg_len must hold one entry per utterance")
+    size = int(_lib.load().cfm3_rnnt_workspace_floats(B, T, U1))
+    if size < 0:
+        raise NotImplementedError(f"rnnt_loss: a lattice of {B} x {T} x {U1} cells is not built (at most 2^31 - 1)")
+    ws = torch.empty(size, device=logits.device, dtype=torch.float32)
+    nll = torch.empty((B,), device=logits.device, dtype=torch.float64)
+    _lib.call("cfm3_rnnt_loss_fwd_f32", logits.data_ptr(), _p(targets), in_len.data_ptr(), tg_len.data_ptr(), B, T, U1, V,
+              int(blank), ws.data_ptr(), nll.data_ptr(), _stream())
+    return nll, (logits, targets, in_len, tg_len, int(blank), ws)
+
+
+def rnnt_loss_backward(ctx, weight):
+    """sum_b weight[b] * d nll[b] / d logits, (B,T,U1,V) fp32, from the ctx of rnnt_loss_forward: weight (B) fp32."""
+    logits, targets, in_len, tg_len, blank, ws = ctx
+    B, T, U1, V = logits.shape
+    weight = _req(weight, "weight")
+    if tuple(weight.shape) != (B,):
+        raise _lib.ConformerHipError(f"rnnt_loss: weight must be {(B,)}, got {tuple(weight.shape)}")
+    dlogits = torch.empty((B, T, U1, V), device=logits.device, dtype=torch.float32)
+    _lib.call("cfm3_rnnt_loss_bwd_f32", logits.data_ptr(), _p(targets), in_len.data_ptr(), tg_len.data_ptr(), B, T, U1, V, blank,
+              ws.data_ptr(), weight.data_ptr(), dlogits.data_ptr(), _stream())
+    return dlogits
+
+
+def rnnt_joint_forward(e, p, frames=None):
+    """h (B,T,U1,J) = tanh(e[:, :, None] + p[:, None]): e (B,Te,J), p (B,U1,J) fp32.  frames (B) int64: one row per utterance,
+    h (B,1,U1,J) from e[b, clamp(frames[b], 0, Te - 1)] (the greedy decode's frame pointer)."""
+    e = _req(e, "e"); p = _req(p, "p")
+    if e.dim() != 3 or p.dim() != 3 or e.shape[0] != p.shape[0] or e.shape[2] != p.shape[2]:
+        raise _lib.ConformerHipError(f"rnnt_joint: e must be (B,T,J) and p (B,U1,J), got {tuple(e.shape)}, {tuple(p.shape)}")
+    B, Te, J = e.shape
+    U1 = p.shape[1]
+    T = Te
+    if frames is not None:
+        frames = _req(frames, "frames", torch.int64)
+        if frames.numel() != B:
+            raise _lib.ConformerHipError(f"rnnt_joint: frames must hold one entry per utterance, got {tuple(frames.shape)}")
+        T = 1
+    h = torch.empty((B, T, U1, J), device=e.device, dtype=torch.float32)
+    _lib.call("cfm3_rnnt_joint_fwd_f32", e.data_ptr(), p.data_ptr(), _p(frames), h.data_ptr(), B, Te, T, U1, J, _stream())
+    return h
+
+
+def rnnt_joint_backward(h, dh):
+    """(de (B,T,J), dp (B,U1,J)) from the joint's output h and its gradient dh, both (B,T,U1,J) fp32."""
+    h = _req(h, "h"); dh = _req(dh, "dh")
+    if h.dim() != 4 or tuple(dh.shape) != tuple(h.shape):
+        raise _lib.ConformerHipError(f"rnnt_joint: h and dh must share one (B,T,U1,J) shape, got {tuple(h.shape)}, {tuple(dh.shape)}")
+    B, T, U1, J = h.shape
+    de = torch.empty((B, T, J), device=h.device, dtype=torch.float32)
+    dp = torch.empty((B, U1, J), device=h.device, dtype=torch.float32)
+    _lib.call("cfm3_rnnt_joint_bwd_f32", h.data_ptr(), dh.data_ptr(), de.data_ptr(), dp.data_ptr(), B, T, U1, J, _stream())
+    return de, dp
+
+
+def rnnt_greedy_decide(logits, in_len, T: int, blank: int, max_symbols: int, tokens, frames, count, last, t, nsym, emit):
+    """One decision of the greedy transducer decode per utterance from logits (B,V) fp32: the argmax (lowest index among equals),
+    then emit (tokens / frames / count / last / nsym move, emit = 1) or advance (t += 1, nsym = 0, emit = 0); finished rows do
+    nothing.  tokens and frames (B, T * max_symbols) int64; count, last, t, nsym (B) int64; emit (B) int32; all updated in place."""
+    logits = _req(logits, "logits")
+    B, V = logits.shape
+    cap = int(T) * int(max_symbols)
+    for name, x, shape, dt in (("tokens", tokens, (B, cap), torch.int64), ("frames", frames, (B, cap), torch.int64),
+                               ("count", count, (B,), torch.int64), ("last", last, (B,), torch.int64), ("t", t, (B,), torch.int64),
+                               ("nsym", nsym, (B,), torch.int64), ("emit", emit, (B,), torch.int32),
+                               ("in_len", in_len, (B,), torch.int64)):
+        if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == dt and x.is_contiguous() and tuple(x.shape) == shape):
+            raise _lib.ConformerHipError(f"rnnt_greedy_decide: {name} must be a contiguous {dt} {shape} tensor on the HIP device")
+    _lib.call("cfm3_rnnt_greedy_decide", logits.data_ptr(), in_len.data_ptr(), B, V, int(T), int(blank), int(max_symbols),
+              tokens.data_ptr(), frames.data_ptr(), count.data_ptr(), last.data_ptr(), t.data_ptr(), nsym.data_ptr(),
+              emit.data_ptr(), _stream())
+
+
+def rnnt_greedy_commit(state_new, state_cur, emit, t, in_len, T: int, active):
+    """state_cur[:, b] = state_new[:, b] where emit[b] is set (planes (2 * n_layers, B, H) fp32), and active[0] = the utterances
+    with t < clamp(in_len, 0, T) (int32, on the device)."""
+    state_new = _req(state_new, "state_new"); state_cur = _req(state_cur, "state_cur")
+    if state_new.dim() != 3 or tuple(state_new.shape) != tuple(state_cur.shape):
+        raise _lib.ConformerHipError(f"rnnt_greedy_commit: the states must share one (planes,B,H) shape, got "
+                                     f"{tuple(state_new.shape)}, {tuple(state_cur.shape)}")
+    planes, B, H = state_new.shape
+    _lib.call("cfm3_rnnt_greedy_commit", state_new.data_ptr(), state_cur.data_ptr(), _req(emit, "emit", torch.int32).data_ptr(),
+              _req(t, "t", torch.int64).data_ptr(), _req(in_len, "in_len", torch.int64).data_ptr(), planes, B, H, int(T),
+              _req(active, "active", torch.int32).data_ptr(), _stream())
